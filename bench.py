@@ -1,26 +1,35 @@
 #!/usr/bin/env python3
 """Headline benchmark: molecules/sec of 1000-step DDPM sampling at batch 256 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one reverse-diffusion step (one score evaluation + posterior update) of one batch of
 256 synthetic MOSES-sized molecules per GPU; value = molecules finished per second for 1000-step
 chains = (batch * n_gpus) / (1000 * seconds_per_step).  With the default K = 1000 the timed region
-IS one complete chain per GPU (plus, for N > 1, the RCCL gather of the generated molecules).
+IS one complete chain per GPU (plus, for N > 1, the RCCL gather of the generated molecules); a K
+above 1000 is timed as back-to-back chains of at most 1000 steps (a chain has 1000 time steps).
 Inputs are resident in HBM before the timed region; noise is generated on the device (Philox)
 inside it; per-step trajectories are written to HBM inside it (their D2H copy is reported
-separately as `traj_d2h_ms`, never part of `value`).
+separately as `traj_d2h_ms` under `--full`, never part of `value`).
 
 Before the W warm-up steps the flags ask for, an untimed chain of `--clock-warmup` steps (default 200, ~0.1 s; reported as
 `clock_warmup_steps`) brings the device to its loaded clocks: measured on MI355X, the first ~40 reverse steps after an idle
 period run 7-9 % slower (0.54 -> 0.50 ms/step at B = 256), which a 5-step warm-up in front of a 20-step
 timed region would otherwise charge to every step of the metric's 1000-step chain.  `--clock-warmup 0` switches it off.
 
-Also on the JSON line: `roofline` of the dominant kernel -- per-launch time from the begin/end
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step as
+float32 `DIR/<name>.npy` (rank 0): `pos` and `v`, the final coordinates and atom types (for N > 1 the
+gathered molecules of all ranks), and, unless `--no-traj`, the last step's rows of the trajectories
+(`pos_traj`, `v_traj`, `v0_traj`, `vt_traj`, `pos_cond_traj`, `v_cond_traj`).  Inputs, weights and
+noise are seeded, so the same arguments give the same inputs in every run.  Above DUMP_BYTES every
+array is cut to the same seeded sample of rows.
+
+A plain run only sets up, warms up, times, dumps and prints the headline line.  `--full` adds, on
+rank 0 after the timed region: `roofline` of the dominant kernel -- per-launch time from the begin/end
 timestamps of the kernel dispatches themselves (hipExtLaunchKernelGGL start/stop events on the launch
-stream, the quantity rocprofv3's kernel trace reports), measured live in a short pass after the timed
-region -- and `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample; rank 0,
-N = 1 only).
+stream, the quantity rocprofv3's kernel trace reports), measured live in a short pass --,
+`concurrent_chains`, the optional precision modes `f16x2_mode` / `f16_features_mode`, `traj_d2h_ms`
+and `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample; N = 1 only).
 """
 import argparse
 import json
@@ -104,6 +113,29 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def run_steps(runner, n, seed, use_graph):
+    """Enqueue `n` reverse steps as back-to-back chains of at most runner.max_steps steps (chain j keyed by seed + j)."""
+    for j, first in enumerate(range(0, n, runner.max_steps)):
+        runner.run(min(runner.max_steps, n - first), seed=seed + j, use_graph=use_graph)
+
+
+DUMP_BYTES = 64 << 20              # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, arrays):
+    """Save each (rows, ...) tensor as float32 DIR/<name>.npy.  Above DUMP_BYTES in all, every array keeps the same number of
+    rows, chosen by a fixed seed from its row count (arrays with equal row counts keep the same rows)."""
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    row_bytes = sum(a.nbytes // max(1, len(a)) for a in arrays.values())
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        keep = DUMP_BYTES // row_bytes
+        arrays = {k: (a[np.sort(np.random.RandomState(0).choice(len(a), keep, replace=False))] if len(a) > keep else a)
+                  for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -118,6 +150,12 @@ def main():
     ap.add_argument("--force-collective", action="store_true",
                     help="with --gpus 1: still initialise a 1-rank process group of --backend and run the final gather of the molecules "
                          "through its packing / all_gather_into_tensor / unpacking path (exercises the RCCL branch on a one-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what their last step computed as float32 DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline pass, concurrent chains, the optional precision modes, "
+                         "the trajectory D2H copy and the CPU baseline (the --profile-steps / --concurrent / --exact-steps / "
+                         "--cpu-* options below apply only with --full)")
     ap.add_argument("--profile-steps", type=int, default=10)
     ap.add_argument("--cpu-steps", type=int, default=20, help="reverse steps of the CPU oracle to time (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU oracle (0 = the measured best, see CPU_THREADS_DEFAULT)")
@@ -131,6 +169,8 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="context option for kernel experiments (shapemol_set_option), e.g. --opt x2h_chain=0; recorded in config")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -166,14 +206,14 @@ def main():
     for kv in args.opt:
         name, val = kv.split("=")
         model.set_option(name, int(val))
-    steps, warm = min(args.steps, CHAIN_STEPS), max(0, min(args.warmup, CHAIN_STEPS))
+    steps, warm = args.steps, max(0, args.warmup)
     clock_warm = max(0, min(args.clock_warmup, CHAIN_STEPS))
     if args.exact_steps < 0:
         args.exact_steps = steps
 
     bb = synth.synthetic_batch(args.batch, seed=2021 + rank, atoms_range=atoms_range)     # every rank owns a different batch
     n_atoms = len(bb["batch"])
-    runner = ChainRunner(model, n_atoms, args.batch, max(steps, warm, clock_warm, 1), keep_traj=not args.no_traj, device=dev)
+    runner = ChainRunner(model, n_atoms, args.batch, min(max(steps, warm, clock_warm), CHAIN_STEPS), keep_traj=not args.no_traj, device=dev)
     runner.load_batch(bb["init_pos"], bb["init_v"], bb["batch"], bb["shape"])
     counts = torch.from_numpy(bb["counts"]).to(dev)
     # job set-up: the ranks exchange their (atoms, molecules) sizes once -- atom counts are drawn before a sampling job's chains
@@ -188,7 +228,7 @@ def main():
     use_graph = not args.eager
     log(f"rank {rank}/{world}: {args.batch} molecules, {n_atoms} atoms; warmup {warm} steps")
     if warm:
-        runner.run(warm, seed=11, use_graph=use_graph)
+        run_steps(runner, warm, 11, use_graph)
         runner.synchronize()
         if dist is not None:
             gather_molecules(runner.out_pos, runner.out_v, counts, _single_rank_too=True, plan=plan)
@@ -204,7 +244,7 @@ def main():
     log(f"timing {steps} steps")
     barrier()
     t0 = time.perf_counter()
-    runner.run(steps, seed=12, use_graph=use_graph)
+    run_steps(runner, steps, 12, use_graph)
     t_enq = time.perf_counter() - t0
     runner.synchronize()
     t_chain = time.perf_counter() - t0
@@ -256,7 +296,12 @@ def main():
     }
 
     log(f"timed region done: {elapsed:.3f} s, {value:.2f} molecules/s")
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        last = (steps - 1) % runner.max_steps         # the last chain's last step: its row of the trajectory buffers
+        final = {"pos": g_pos, "v": g_v} if dist is not None else {"pos": runner.out_pos, "v": runner.out_v}
+        dump_outputs(args.dump_outputs, {**final, **{k: b[last] for k, b in runner.bufs.items()}})
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel, from a short event-timed eager pass -------------
         prof = runner.profile(max(1, args.profile_steps), seed=13)
         runner.synchronize()
@@ -329,17 +374,17 @@ def main():
                 mj.load_state_dict({k: torch.from_numpy(v) for k, v in sdn.items()}, strict=True)
                 mj = mj.to(dev)
                 bj = synth.synthetic_batch(args.batch, seed=3021 + j, atoms_range=atoms_range)
-                rj = ChainRunner(mj, len(bj["batch"]), args.batch, max(steps, warm, 1), keep_traj=not args.no_traj, device=dev)
+                rj = ChainRunner(mj, len(bj["batch"]), args.batch, min(max(steps, warm), CHAIN_STEPS), keep_traj=not args.no_traj, device=dev)
                 rj.load_batch(bj["init_pos"], bj["init_v"], bj["batch"], bj["shape"])
                 runners.append(rj)
             for r_ in runners:
-                r_.run(max(warm, 5, min(clock_warm, r_.max_steps)), seed=21, use_graph=True)
+                run_steps(r_, max(warm, 5, min(clock_warm, r_.max_steps)), 21, True)
             for r_ in runners:
                 r_.synchronize()
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             for r_ in runners:
-                r_.run(steps, seed=22, use_graph=True)
+                run_steps(r_, steps, 22, True)
             for r_ in runners:
                 r_.synchronize()
             dtc = time.perf_counter() - t1
@@ -392,6 +437,7 @@ def main():
                                    "os_cpu_count": os.cpu_count(), "cpu_affinity": len(os.sched_getaffinity(0)),
                                    "kind": "port", "sample": f"{args.cpu_steps} reverse steps of the same B={args.batch} batch "
                                    f"({dt:.3f} s/step, torch-CPU oracle), extrapolated to 1000 steps"}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

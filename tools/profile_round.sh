@@ -7,14 +7,14 @@ set -eo pipefail
 OUT=${1:-gpurun_out/prof_round}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-SHORT="--steps 20 --warmup 5 --clock-warmup 0 --cpu-steps 0 --profile-steps 2 --eager --concurrent 0 --exact-steps 0"
+SHORT="--full --steps 20 --warmup 5 --clock-warmup 0 --cpu-steps 0 --profile-steps 2 --eager --concurrent 0 --exact-steps 0"
 find_csv() { find "$1" -name "*$2" | head -1; }
 LIBSHA=$(sha1sum shapemol_amd/libshapemol_hip.so | cut -c1-16)
 
 for B in 256 1024; do
   tag=$([ $B = 256 ] && echo "" || echo "_b$B")
   steps=$([ $B = 256 ] && echo 300 || echo 100)
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace$tag" -- python3 bench.py --batch $B --steps $steps --warmup 20 --cpu-steps 0 --concurrent 0 --exact-steps 0 \
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace$tag" -- python3 bench.py --full --batch $B --steps $steps --warmup 20 --cpu-steps 0 --concurrent 0 --exact-steps 0 \
       > "$OUT/bench_line${tag}_profiled.json" 2> "$OUT/trace$tag.err"
   cp "$(find_csv "$OUT/trace$tag" _kernel_stats.csv)" "$OUT/kernel_stats$tag.csv"
   [ $B = 256 ] && python3 tools/trace_gaps.py "$(find_csv "$OUT/trace$tag" _kernel_trace.csv)" > "$OUT/per_step_breakdown.txt"
@@ -41,10 +41,10 @@ done
 echo "sq done" >&2
 
 mkdir -p profiles/r04 && cp "$OUT"/pmc_traffic*.json profiles/r04/      # bench.py reads its `traffic` field from the committed summaries (keyed to the library's SHA-1)
-python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_line_20steps.json" 2> "$OUT/bench_line_20steps.err"
-python3 bench.py --batch 1024 --steps 100 --cpu-steps 0 > "$OUT/bench_line_b1024.json" 2> "$OUT/bench_line_b1024.err"
-python3 bench.py --batch 512 --atoms 40,80 --knn 32 --steps 60 --cpu-steps 0 --concurrent 0 > "$OUT/bench_line_k32_b512.json" 2> "$OUT/bench_line_k32_b512.err"
+python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_line_20steps.json" 2> "$OUT/bench_line_20steps.err"
+python3 bench.py --full --batch 1024 --steps 100 --cpu-steps 0 > "$OUT/bench_line_b1024.json" 2> "$OUT/bench_line_b1024.err"
+python3 bench.py --full --batch 512 --atoms 40,80 --knn 32 --steps 60 --cpu-steps 0 --concurrent 0 > "$OUT/bench_line_k32_b512.json" 2> "$OUT/bench_line_k32_b512.err"
 # keep only the summaries (the raw traces are large)
 rm -rf "$OUT"/trace* "$OUT"/pmc_FETCH* "$OUT"/pmc_WRITE* "$OUT"/sq[0-9]
 ls -la "$OUT" >&2

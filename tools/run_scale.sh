@@ -9,8 +9,8 @@ PORT=${MASTER_PORT:-29511}
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 run() {   # run <gpus> <bench args...>
   local n=$1; shift
-  if [[ $n == 1 ]]; then python bench.py --gpus 1 "$@"
-  else python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port "$PORT" bench.py --gpus "$n" "$@"
+  if [[ $n == 1 ]]; then python bench.py --gpus 1 --full "$@"
+  else python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port "$PORT" bench.py --gpus "$n" --full "$@"
   fi
 }
 # configs[1]: batch 256 per GPU, 1000 steps (the headline metric at 1/2/4/8 GPUs)
