@@ -126,13 +126,40 @@ int shapemol_guide_points(shapemol_ctx *ctx, float *d_pos, int64_t n_points, con
 int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_cloud, double radius, double ratio, float *d_pos,
                                  int64_t n_atoms, const double *d_draws, uint64_t seed, void *stream);
 
+/* Mesh shape guidance of the following _sample calls (mesh_shape_guidance, models/molopt_score_model.py:742-775; applied to the
+ * predicted x0 of every step with t > grad_step, :571-580; takes precedence over the point cloud of shapemol_set_guidance).
+ * The "within" atoms (inside the mesh, > 0.4 from the nearest cloud point) of the whole batch anchor the pull; every "outmesh"
+ * atom (outside the mesh, or < 0.2 from the cloud) moves away from the mean of its 3 nearest within-atoms by u * 0.8 + 0.2 and
+ * is accepted once inside the mesh and > 0.2 from the cloud, up to five times; atoms never accepted keep their position.
+ * h_verts: HOST (n_verts,3) float64; h_faces: HOST (n_faces,3) int32 vertex indices of a closed, consistently oriented
+ * triangle mesh (checked: every index in [0, n_verts), no repeated index within a face); containment is the parity of a fixed
+ * ray (sm_mesh.h), not trimesh's code.  h_cloud: HOST (n_cloud,3) float64, 3 .. 2048 points.  All three are copied;
+ * n_faces = 0 switches guidance off.  d_draws: DEVICE (S,5,N) float64 uniforms as for shapemol_set_guidance, or NULL
+ * (Philox(seed of the chain), a counter domain of its own).  Fewer than 3 within-atoms (none at all, or fewer than 3 while
+ * some atom is to be pulled) raises status flag 6 (the reference's KD-tree raises ValueError there); the step is left unguided. */
+int shapemol_set_mesh_guidance(shapemol_ctx *ctx, const double *h_verts, int64_t n_verts, const int32_t *h_faces,
+                               int64_t n_faces, const double *h_cloud, int64_t n_cloud, int32_t grad_step, const double *d_draws);
+
+/* mesh_shape_guidance on its own: guide d_pos (N,3) f32 DEVICE in place against the mesh of shapemol_set_mesh_guidance;
+ * d_draws DEVICE (5,N) float64 or NULL (Philox(seed)).  Asynchronous on `stream`; the status flag as above (clear before). */
+int shapemol_guide_points_mesh(shapemol_ctx *ctx, float *d_pos, int64_t n_atoms, const double *d_draws, uint64_t seed,
+                               void *stream);
+
+/* The reference's MODULE-level function mesh_shape_guidance(use_mesh_data, pred_ligand_pos) without a context: mesh and cloud
+ * come with the call (as for shapemol_set_mesh_guidance) on the CURRENT device, d_pos (n_atoms,3) f32 DEVICE is guided in
+ * place; d_draws / seed as above.  Synchronises `stream` before it returns, like shapemol_pointcloud_guidance.  Fewer than 3
+ * within-atoms: returns non-zero and sets *flag_out (may be NULL) to 1, the positions untouched. */
+int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces,
+                           const double *h_cloud, int64_t n_cloud, float *d_pos, int64_t n_atoms, const double *d_draws,
+                           uint64_t seed, int32_t *flag_out, void *stream);
+
 /* Input validation happens on the device (no host synchronisation in _score/_sample): an unsorted or
  * out-of-range d_batch, an atom type outside [0, num_classes) or a time step outside [0, num_timesteps)
  * sets a sticky flag (the offending index is clamped, so nothing is read or written out of bounds).
  * shapemol_status synchronises the device and returns non-zero (message in shapemol_last_error) if the
  * last _score/_sample on this context saw such an input, an activation beyond the fp16 range of the two-piece f16 node
- * kernels (option node_f16) or a timed-out grid barrier (vn_fuse = 1);
- * flags_out (may be NULL) receives the eight raw flags {barrier, batch, atom type, time step, fp16 range, 0...}.
+ * kernels (option node_f16), a timed-out grid barrier (vn_fuse = 1) or too few within-atoms for mesh guidance;
+ * flags_out (may be NULL) receives the eight raw flags {barrier, batch, atom type, time step, fp16 range, span, mesh, 0}.
  * The reference raises from the corresponding torch indexing ops (models/molopt_score_model.py:292-301). */
 int shapemol_status(shapemol_ctx *ctx, int32_t *flags_out);
 /* The same, synchronising only `stream` (the one the last _score/_sample of this context was enqueued on) instead of the whole

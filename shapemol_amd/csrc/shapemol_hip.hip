@@ -11,6 +11,7 @@
 #include "sm_node16.h"
 #include "sm_edge_stream.h"
 #include "sm_misc.h"
+#include "sm_mesh.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -571,6 +572,10 @@ struct shapemol_ctx {
     int num_cu = 256;
     // point-cloud shape guidance (shapemol_set_guidance)
     double *g_cloud = nullptr; int64_t g_points = 0; double g_radius = 0.0; int g_grad_step = 0; const double *g_draws = nullptr;
+    // mesh shape guidance (shapemol_set_mesh_guidance); takes precedence over the point cloud when both are set
+    MeshFace *m_faces = nullptr; double4 *m_fbox = nullptr; double *m_cloud = nullptr;     // one device block
+    int64_t m_nfaces = 0, m_points = 0; int m_grad_step = 0; const double *m_draws = nullptr; double m_bounds[5] = {};
+    float4 *m_within = nullptr; int *m_out = nullptr, *m_cnt = nullptr; int64_t m_cap = 0;  // per-step lists (one block)
     int first_step = 0;         // option "first_step": the next chains start at reverse step first_step (t = T-1-first_step)
     // diagnostic: neighbour lists pinned at given (reverse step, atom) pairs (shapemol_set_knn_pins)
     int *pin_off = nullptr, *pin_atom = nullptr, *pin_nbr = nullptr; int64_t n_pins = 0; int pin_steps = 0, pin_k = 0;
@@ -584,7 +589,7 @@ struct shapemol_ctx {
     // the captured step depends on the batch geometry only: seed, noise and trajectory pointers live in chain_params
     // what a captured step depends on besides the options (which drop the graphs when set): sizes, guidance, and the two
     // launch decisions taken from the max_mol_atoms hint (folded coordinate update, fused graph kernel)
-    struct GraphKey { int64_t N = 0, B = 0; int guided = 0, fold = 0, gfuse = 0;
+    struct GraphKey { int64_t N = 0, B = 0; int guided = 0 /* 0 none, 1 point cloud, 2 mesh */, fold = 0, gfuse = 0;
                       bool operator==(const GraphKey &o) const { return N == o.N && B == o.B && guided == o.guided && fold == o.fold && gfuse == o.gfuse; } } gkey{};
     hipStream_t gstream = nullptr; bool gstream_set = false;     // the stream the executables were last launched on
     void drop_graphs() {      // a replay may still be in flight: drain it before destroying the executables (only the stream the
@@ -1143,7 +1148,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                     pending = VnFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, x_next,
                                      c->mol_span, c->status + ST_SPAN, 1};
                     vn_done = true;
-                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && C <= 16 && hd <= 16) {
+                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->m_nfaces == 0 && C <= 16 && hd <= 16) {
                     // ... or, for the last layer of a chain step, the DDPM kernel
                     ea.xsum = c->xsum;
                     c->ddpm_vf = DdpmFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, out_pos, hd, 1};
@@ -1169,7 +1174,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                     pending = VnFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, x_next,
                                      c->mol_span, c->status + ST_SPAN, 1};
                     vn_done = true;
-                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && C <= 16 && hd <= 16) {
+                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->m_nfaces == 0 && C <= 16 && hd <= 16) {
                     sa.xsum = c->xsum;
                     c->ddpm_vf = DdpmFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, out_pos, hd, 1};
                     vn_done = true;
@@ -1346,6 +1351,8 @@ void shapemol_destroy(shapemol_ctx *c) {
     hipFree(c->etab);
     hipFree(c->d_img);
     if (c->g_cloud) hipFree(c->g_cloud);
+    if (c->m_faces) hipFree(c->m_faces);
+    if (c->m_within) hipFree(c->m_within);
     if (c->bn_run) hipFree(c->bn_run);
     if (c->bn_eval_acc) hipFree(c->bn_eval_acc);
     if (c->pin_off) { hipFree(c->pin_off); hipFree(c->pin_atom); hipFree(c->pin_nbr); }
@@ -1366,6 +1373,75 @@ int shapemol_set_bn_running(shapemol_ctx *c, const float *h_mean, const float *h
     }
     HIPCHK(hipMemcpy(c->bn_run, h_mean, count * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->bn_run + count, h_var, count * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ---- mesh shape guidance: host side
+// Validates the mesh and the cloud and builds the device image [faces F | face boxes F | cloud P] (vertices projected once,
+// in the same operations as the device's mesh_project); bounds = (umin, umax, vmin, vmax, wmax) of the projected mesh.
+static int mesh_image(const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces, const double *h_cloud,
+                      int64_t n_cloud, const char *who, std::vector<unsigned char> &img, double (&bounds)[5]) {
+    if (!h_verts || !h_faces || !h_cloud) return fail(std::string(who) + ": vertices, faces and cloud are required");
+    if (n_verts < 3 || n_verts > (1 << 26)) return fail(std::string(who) + ": the mesh needs 3 .. 2^26 vertices");
+    if (n_faces < 1 || n_faces > (1 << 24)) return fail(std::string(who) + ": the mesh needs 1 .. 2^24 faces");
+    if (n_cloud < 3 || n_cloud > 2048) return fail(std::string(who) + ": the cloud needs 3 .. 2048 points (it is staged in LDS)");
+    std::vector<double> pu(n_verts), pv(n_verts), pw(n_verts);
+    for (int64_t i = 0; i < n_verts; ++i) {
+        const double x = h_verts[i * 3], y = h_verts[i * 3 + 1], z = h_verts[i * 3 + 2];
+        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) return fail(std::string(who) + ": a vertex is not finite");
+        mesh_project(x, y, z, pu[i], pv[i], pw[i]);
+    }
+    for (int64_t i = 0; i < n_cloud * 3; ++i)
+        if (!std::isfinite(h_cloud[i])) return fail(std::string(who) + ": a cloud point is not finite");
+    const size_t fb = (size_t)n_faces * sizeof(MeshFace), bb = (size_t)n_faces * sizeof(double4), cb = (size_t)n_cloud * 24;
+    img.assign(fb + bb + cb, 0);
+    MeshFace *faces = reinterpret_cast<MeshFace *>(img.data());
+    double4 *box = reinterpret_cast<double4 *>(img.data() + fb);
+    std::memcpy(img.data() + fb + bb, h_cloud, cb);
+    bounds[0] = bounds[2] = INFINITY; bounds[1] = bounds[3] = bounds[4] = -INFINITY;
+    for (int64_t f = 0; f < n_faces; ++f) {
+        const int32_t *ix = h_faces + f * 3;
+        for (int k = 0; k < 3; ++k)
+            if (ix[k] < 0 || ix[k] >= n_verts) return fail(std::string(who) + ": face " + std::to_string(f) + " names a vertex outside [0, n_verts)");
+        if (ix[0] == ix[1] || ix[1] == ix[2] || ix[2] == ix[0]) return fail(std::string(who) + ": face " + std::to_string(f) + " repeats a vertex");
+        MeshFace &m = faces[f];
+        double4 &b = box[f];
+        b = make_double4(INFINITY, -INFINITY, INFINITY, -INFINITY);
+        m.canon = 0;
+        for (int k = 0; k < 3; ++k) {
+            m.u[k] = pu[ix[k]]; m.v[k] = pv[ix[k]]; m.w[k] = pw[ix[k]];
+            if (ix[k] < ix[k == 2 ? 0 : k + 1]) m.canon |= 1 << k;
+            b.x = std::min(b.x, m.u[k]); b.y = std::max(b.y, m.u[k]); b.z = std::min(b.z, m.v[k]); b.w = std::max(b.w, m.v[k]);
+            bounds[4] = std::max(bounds[4], m.w[k]);
+        }
+        bounds[0] = std::min(bounds[0], b.x); bounds[1] = std::max(bounds[1], b.y);
+        bounds[2] = std::min(bounds[2], b.z); bounds[3] = std::max(bounds[3], b.w);
+    }
+    return 0;
+}
+
+static MeshGuideArgs mesh_args(const shapemol_ctx *c, float *pos, int64_t N, const int *step_cur, int t_first) {
+    MeshGuideArgs a{};
+    a.pred_pos = pos; a.cloud = c->m_cloud; a.faces = c->m_faces; a.fbox = c->m_fbox;
+    a.within = c->m_within; a.out_list = c->m_out; a.cnt = c->m_cnt; a.status = c->status; a.cp = c->chain_params;
+    a.step_cur = step_cur; a.n_atoms = (int)N; a.n_points = (int)c->m_points; a.n_faces = (int)c->m_nfaces;
+    a.t_first = t_first; a.grad_step = c->m_grad_step;
+    a.umin = c->m_bounds[0]; a.umax = c->m_bounds[1]; a.vmin = c->m_bounds[2]; a.vmax = c->m_bounds[3]; a.wmax = c->m_bounds[4];
+    return a;
+}
+
+// the per-step lists of mesh guidance for N atoms: [within N | outmesh N | counters 4]
+static int mesh_workspace(shapemol_ctx *c, int64_t N) {
+    if (N <= c->m_cap) return 0;
+    c->drop_graphs();                            // the captured steps point into the old block
+    HIPCHK(hipDeviceSynchronize());
+    if (c->m_within) { hipFree(c->m_within); c->m_within = nullptr; c->m_out = c->m_cnt = nullptr; c->m_cap = 0; }
+    unsigned char *blk = nullptr;
+    HIPCHK(hipMalloc((void **)&blk, (size_t)N * 20 + 16));
+    c->m_within = reinterpret_cast<float4 *>(blk);
+    c->m_out = reinterpret_cast<int *>(blk + (size_t)N * 16);
+    c->m_cnt = reinterpret_cast<int *>(blk + (size_t)N * 20);
+    c->m_cap = N;
     return 0;
 }
 
@@ -1403,12 +1479,15 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     hipStream_t s = (hipStream_t)stream;
     c->lastN = N; c->lastB = B;
     const int t_first = c->cfg.num_timesteps - 1;
+    const bool mesh = c->m_nfaces > 0;          // mesh guidance takes precedence over the point cloud (molopt_score_model.py:571)
+    if (mesh && mesh_workspace(c, N)) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
+    if (mesh) HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
     if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_init_v, (int)N, c->cfg.num_classes, c->status));
     {
         ChainParams cp{};
-        cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = c->g_draws;
+        cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->m_draws : c->g_draws;
         if (traj) { cp.tr_pos = traj->pos_traj; cp.tr_v = traj->v_traj; cp.tr_v0 = traj->v0_traj; cp.tr_vt = traj->vt_traj;
                     cp.tr_pos_cond = traj->pos_cond_traj; cp.tr_v_cond = traj->v_cond_traj; }
         LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, cp, c->steps));
@@ -1418,7 +1497,12 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     auto one_step = [&]() -> int {
         if (DISPATCH_H(c, run_score<128>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v),
                        run_score<32>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v))) return 1;
-        if (c->g_points > 0) {     // point-cloud shape guidance of the predicted x0 (steps with t > grad_step)
+        if (mesh) {                // mesh shape guidance of the predicted x0 (steps with t > grad_step)
+            const MeshGuideArgs ma = mesh_args(c, c->pred_pos, N, c->steps + 1, t_first);
+            const dim3 grid((unsigned)((N * 16 + 255) / 256));
+            LAUNCH("mesh_classify", SMK(mesh_classify_kernel, grid, dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
+            LAUNCH("mesh_pull", SMK(mesh_pull_kernel, grid, dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
+        } else if (c->g_points > 0) {     // point-cloud shape guidance of the predicted x0 (steps with t > grad_step)
             PcGuideArgs ga{c->pred_pos, c->g_cloud, c->chain_params, c->steps + 1, (int)N, (int)c->g_points, t_first, c->g_grad_step, c->g_radius, 0.2};
             LAUNCH("pc_guidance", SMK(pc_guidance_kernel, dim3((N * 16 + 255) / 256), dim3(256), (size_t)c->g_points * 24, s, ga));
         }
@@ -1426,7 +1510,7 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     };
     if (use_graph && !c->prof_on) {
         shapemol_ctx::GraphKey key{};
-        key.N = N; key.B = B; key.guided = c->g_points > 0; key.fold = vn_fold_ok(c, (int)N);
+        key.N = N; key.B = B; key.guided = mesh ? 2 : (c->g_points > 0 ? 1 : 0); key.fold = vn_fold_ok(c, (int)N);
         key.gfuse = c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && c->n_pins == 0;
         // two executables: one reverse step, and kGraphUnroll steps back to back (the gap between two graph launches,
         // ~8 us, is then paid once per kGraphUnroll steps); every step reads its index from the device-side counter
@@ -1633,6 +1717,96 @@ int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_points, double
     return 0;
 }
 
+int shapemol_set_mesh_guidance(shapemol_ctx *c, const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces,
+                               const double *h_cloud, int64_t n_cloud, int32_t grad_step, const double *d_draws) {
+    if (!c) return fail("shapemol_set_mesh_guidance: null ctx");
+    if (n_faces < 0) return fail("shapemol_set_mesh_guidance: n_faces < 0");
+    std::vector<unsigned char> img;
+    double bounds[5];
+    if (n_faces > 0 && mesh_image(h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, "shapemol_set_mesh_guidance", img, bounds)) return 1;
+    HIPCHK(hipSetDevice(c->device));
+    c->drop_graphs();                            // also drains the device: the old mesh may still be in use
+    if (c->m_faces) { hipFree(c->m_faces); c->m_faces = nullptr; c->m_fbox = nullptr; c->m_cloud = nullptr; }
+    c->m_nfaces = 0; c->m_points = 0; c->m_draws = nullptr;
+    if (n_faces == 0) return 0;
+    unsigned char *blk = nullptr;
+    HIPCHK(hipMalloc((void **)&blk, img.size()));
+    HIPCHK(hipMemcpy(blk, img.data(), img.size(), hipMemcpyHostToDevice));
+    c->m_faces = reinterpret_cast<MeshFace *>(blk);
+    c->m_fbox = reinterpret_cast<double4 *>(blk + (size_t)n_faces * sizeof(MeshFace));
+    c->m_cloud = reinterpret_cast<double *>(blk + (size_t)n_faces * (sizeof(MeshFace) + sizeof(double4)));
+    std::memcpy(c->m_bounds, bounds, sizeof(bounds));
+    c->m_nfaces = n_faces; c->m_points = n_cloud; c->m_grad_step = grad_step; c->m_draws = d_draws;
+    return 0;
+}
+
+int shapemol_guide_points_mesh(shapemol_ctx *c, float *d_pos, int64_t N, const double *d_draws, uint64_t seed, void *stream) {
+    if (!c || !d_pos || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_mesh: bad argument");
+    if (c->m_nfaces <= 0) return fail("shapemol_guide_points_mesh: no mesh set (shapemol_set_mesh_guidance)");
+    HIPCHK(hipSetDevice(c->device));
+    if (ensure_workspace(c, std::max<int64_t>(N, 1), 1) || mesh_workspace(c, N)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
+    HIPCHK(hipMemsetAsync(c->status + ST_MESH, 0, sizeof(int), s));
+    ChainParams cp{};
+    cp.seed = seed; cp.guide_draws = d_draws; cp.step_base = 0;
+    LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, cp, c->steps));
+    const MeshGuideArgs ma = mesh_args(c, d_pos, N, nullptr, c->m_grad_step + 1);
+    const dim3 grid((unsigned)((N * 16 + 255) / 256));
+    LAUNCH("mesh_classify", SMK(mesh_classify_kernel, grid, dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
+    LAUNCH("mesh_pull", SMK(mesh_pull_kernel, grid, dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
+    return 0;
+}
+
+int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces, const double *h_cloud,
+                           int64_t n_cloud, float *d_pos, int64_t N, const double *d_draws, uint64_t seed, int32_t *flag_out,
+                           void *stream) {
+    if (flag_out) *flag_out = 0;
+    if (!d_pos || N < 1 || N > (1 << 27)) return fail("shapemol_mesh_guidance: bad argument");
+    std::vector<unsigned char> img;
+    double bounds[5];
+    if (mesh_image(h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, "shapemol_mesh_guidance", img, bounds)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    // [mesh image | ChainParams | step counter, status [8], counters [4] | within N | outmesh N]
+    const size_t o_cp = (img.size() + 255) / 256 * 256, o_st = o_cp + (sizeof(ChainParams) + 255) / 256 * 256;
+    const size_t o_in = o_st + 256, o_out = o_in + (size_t)N * 16, total = o_out + (size_t)N * 4;
+    unsigned char *blk = nullptr;
+    HIPCHK(hipMalloc((void **)&blk, total));
+    int *d_misc = reinterpret_cast<int *>(blk + o_st);        // [0] step counter, [4 .. 11] status, [16 .. 19] counters
+    hipError_t e = hipMemcpyAsync(blk, img.data(), img.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_misc, 0, 256, s);
+    int32_t flag = 0;
+    if (e == hipSuccess) {
+        ChainParams cp{};
+        cp.seed = seed; cp.guide_draws = d_draws; cp.step_base = 0;
+        ChainParams *d_cp = reinterpret_cast<ChainParams *>(blk + o_cp);
+        hipLaunchKernelGGL(set_chain_params_kernel, dim3(1), dim3(1), 0, s, d_cp, cp, d_misc);
+        MeshGuideArgs a{};
+        a.pred_pos = d_pos; a.faces = reinterpret_cast<const MeshFace *>(blk);
+        a.fbox = reinterpret_cast<const double4 *>(blk + (size_t)n_faces * sizeof(MeshFace));
+        a.cloud = reinterpret_cast<const double *>(blk + (size_t)n_faces * (sizeof(MeshFace) + sizeof(double4)));
+        a.within = reinterpret_cast<float4 *>(blk + o_in); a.out_list = reinterpret_cast<int *>(blk + o_out);
+        a.cnt = d_misc + 16; a.status = d_misc + 4; a.cp = d_cp; a.step_cur = nullptr;
+        a.n_atoms = (int)N; a.n_points = (int)n_cloud; a.n_faces = (int)n_faces; a.t_first = 1; a.grad_step = 0;   // always guided
+        a.umin = bounds[0]; a.umax = bounds[1]; a.vmin = bounds[2]; a.vmax = bounds[3]; a.wmax = bounds[4];
+        const dim3 grid((unsigned)((N * 16 + 255) / 256));
+        hipLaunchKernelGGL(mesh_classify_kernel, grid, dim3(256), mesh_lds_bytes((int)n_cloud), s, a);
+        hipLaunchKernelGGL(mesh_pull_kernel, grid, dim3(256), mesh_lds_bytes((int)n_cloud), s, a);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_misc + 4 + ST_MESH, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);       // the block is freed below; the reference's function is synchronous too
+    hipFree(blk);
+    if (e != hipSuccess) return fail(std::string("shapemol_mesh_guidance: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(std::string("shapemol_mesh_guidance: ") + hipGetErrorString(e2));
+    if (flag) {
+        if (flag_out) *flag_out = 1;
+        return fail("mesh shape guidance: fewer than 3 atoms lie inside the mesh and > 0.4 from the cloud (none at all, or fewer "
+                    "than 3 while atoms are to be pulled); the reference raises ValueError from its KD-tree here");
+    }
+    return 0;
+}
+
 static int status_message(const int32_t (&f)[8]) {
     if (f[ST_BATCH]) return fail("batch vector is not sorted ascending or names a molecule >= n_mols; results are invalid");
     if (f[ST_ATOM_TYPE]) return fail("an atom type is outside [0, num_classes); results are invalid");
@@ -1640,6 +1814,8 @@ static int status_message(const int32_t (&f)[8]) {
     if (f[ST_SPAN]) return fail("a molecule is larger than the max_mol_atoms hint says (folded coordinate update / fused graph kernel); results are invalid");
     if (f[ST_RANGE]) return fail("an activation left the fp16 range of the two-piece f16 node kernels (|x| >= 6e4 or NaN); results are invalid: set option node_f16 = 0 (exactly split bf16 kernels)");
     if (f[ST_VN_BARRIER]) return fail("grid barrier of the fused coordinate update timed out (workgroups not co-resident); results are invalid");
+    if (f[ST_MESH]) return fail("mesh shape guidance: fewer than 3 atoms lie inside the mesh and > 0.4 from the cloud (none at all, or "
+                                "fewer than 3 while atoms are to be pulled); the reference raises ValueError from its KD-tree here");
     return 0;
 }
 

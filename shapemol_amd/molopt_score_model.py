@@ -9,6 +9,7 @@ Same call surface as the reference (paths relative to the reference repository):
   * ``.sample_diffusion(init_ligand_pos, init_ligand_v, batch_ligand, ligand_shape, ...)``
                                                               models/molopt_score_model.py:533-697
   * ``log_sample_categorical(logits)``                        models/molopt_score_model.py:98-104
+  * ``pointcloud_shape_guidance`` / ``mesh_shape_guidance``   models/molopt_score_model.py:699-775
 
 All arithmetic runs in libshapemol_hip.so (hand-written HIP for gfx950) through the C ABI of
 ``include/shapemol_hip.h``; torch only owns device memory and streams here.  The module's
@@ -29,7 +30,7 @@ from .diffusion import build_schedule_tables
 from .packing import pack_state_dict
 from .spec import ModelDims, state_dict_spec, RBF_CENTRES
 
-__all__ = ["ScorePosNet3D", "log_sample_categorical", "pointcloud_shape_guidance"]
+__all__ = ["ScorePosNet3D", "log_sample_categorical", "pointcloud_shape_guidance", "mesh_shape_guidance"]
 
 
 class _Params(nn.Module):
@@ -398,13 +399,17 @@ class ScorePosNet3D(nn.Module):
         ``use_pointcloud_data=(point_clouds, kdtree, radius)`` with ``grad_step`` is the reference's point-cloud shape
         guidance (``:583-586,699-740``) as a device kernel inside the step (the KD-tree is not used: brute-force float64
         3-nearest search); ``guide_draws`` (S,5,N) float64 feeds the recorded ``np.random.random`` draws (parity mode).
+        ``use_mesh_data=(mesh, point_clouds, kdtree)`` is the reference's mesh shape guidance (``:571-580,742-775``), two
+        device kernels inside the step, and takes precedence over ``use_pointcloud_data`` as there; the mesh is anything with
+        ``.vertices`` (V,3) and ``.faces`` (F,3) (a ``trimesh.Trimesh``) or a ``(vertices, faces)`` pair, the KD-tree is not
+        used.  Too few atoms inside the mesh raise ``ValueError`` (``_lib.MeshGuidanceError``), as the reference's KD-tree does.
         Private to shapemol_amd.sampling: ``_slot`` picks one of the model's library contexts (own workspace and captured
         graphs), ``_async=True`` returns a handle right after the chain has been enqueued; its ``.result()`` waits and
         builds the dict (chains on different slots then run side by side, and a finished chain's trajectories are
         unbatched and copied while the next one runs).
         """
-        if use_mesh_data is not None or use_grad:
-            raise NotImplementedError("mesh / gradient shape guidance is outside the accelerated path")
+        if use_grad:
+            raise NotImplementedError("gradient shape guidance is outside the accelerated path (commented out in the reference)")
         if self.cond_mask_prob == 0:
             assert guide_stren == 0
         if guide_stren:
@@ -436,7 +441,8 @@ class ScorePosNet3D(nn.Module):
             u = _check_device_tensor("noise[1]", noise[1], torch.float32)
             if tuple(eps.shape) != (num_steps, n, 3) or tuple(u.shape) != (num_steps, n, cc):
                 raise ValueError("noise must be (eps (S,N,3), u (S,N,C))")
-        guided = use_pointcloud_data is not None
+        guided = "mesh" if use_mesh_data is not None else ("cloud" if use_pointcloud_data is not None else None)
+        mesh = _mesh_arrays(use_mesh_data) if guided == "mesh" else None
         if seed is None:
             if noise is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -451,12 +457,18 @@ class ScorePosNet3D(nn.Module):
         # kernel (one tiny synchronising reduction per chain; the reference synchronises at every step)
         _lib.check(lib.shapemol_set_option(ctx, b"max_mol_atoms", int(torch.bincount(batch).max().item()) if n else 0), "shapemol_set_option")
         gd = None
-        if guided:
+        if guided and guide_draws is not None:
+            gd = _check_device_tensor("guide_draws", guide_draws, torch.float64)
+            if tuple(gd.shape) != (num_steps, 5, n):
+                raise ValueError("guide_draws must be (S, 5, N) float64")
+        if guided == "mesh":
+            verts, faces, cloud = mesh
+            _lib.check(lib.shapemol_set_mesh_guidance(ctx, verts.ctypes.data_as(C.c_void_p), verts.shape[0],
+                                                      faces.ctypes.data_as(C.c_void_p), faces.shape[0],
+                                                      cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], int(grad_step), _ptr(gd)),
+                       "shapemol_set_mesh_guidance")
+        elif guided:
             cloud = np.ascontiguousarray(np.asarray(use_pointcloud_data[0], dtype=np.float64).reshape(-1, 3))
-            if guide_draws is not None:
-                gd = _check_device_tensor("guide_draws", guide_draws, torch.float64)
-                if tuple(gd.shape) != (num_steps, 5, n):
-                    raise ValueError("guide_draws must be (S, 5, N) float64")
             _lib.check(lib.shapemol_set_guidance(ctx, cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], float(use_pointcloud_data[2]),
                                                  int(grad_step), _ptr(gd)), "shapemol_set_guidance")
         tr = _lib.Traj()
@@ -498,6 +510,10 @@ class ScorePosNet3D(nn.Module):
         """Method form of the module-level :func:`pointcloud_shape_guidance` (kept for callers that hold a model)."""
         return pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=k, ratio=ratio, draws=draws, seed=seed)
 
+    def mesh_shape_guidance(self, use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws=None, seed=None):
+        """Method form of the module-level :func:`mesh_shape_guidance`."""
+        return mesh_shape_guidance(use_mesh_data, pred_ligand_pos, k=k, ratio=ratio, draws=draws, seed=seed)
+
     def check_status(self):
         """Synchronise and raise if the last forward / sample_diffusion saw an invalid input (batch vector not sorted
         or >= the number of shapes, atom type or time step out of range).  forward() stays asynchronous, so its flags
@@ -535,6 +551,7 @@ class _PendingChain:
     result() waits for it, reads the status flags and builds the reference's result dict."""
 
     def __init__(self, model, ctx, dev, guided, bufs, out_pos, out_v, return_traj, reuse, keep, offset=None):
+        # guided: None, "cloud" or "mesh" (what _drop_guidance removes from the context)
         self.offset = offset                 # (N, 3) per-atom centre of its molecule (center_pos_mode='center') or None
         self.model, self.ctx, self.dev, self.guided, self.bufs = model, ctx, dev, guided, bufs
         self.out_pos, self.out_v, self.return_traj, self.reuse, self.keep = out_pos, out_v, return_traj, reuse, keep
@@ -542,10 +559,13 @@ class _PendingChain:
         self.done = False
 
     def _drop_guidance(self):
-        if self.guided:      # whatever happened, the context must not keep the cloud (and the caller-owned draws pointer) installed
-            self.guided = False
+        if self.guided:      # whatever happened, the context must not keep the cloud / mesh (and the caller-owned draws pointer) installed
+            kind, self.guided = self.guided, None
             torch.cuda.synchronize(self.dev)
-            _lib.check(_lib.load().shapemol_set_guidance(self.ctx, None, 0, 0.0, 0, None), "shapemol_set_guidance")
+            if kind == "mesh":
+                _lib.check(_lib.load().shapemol_set_mesh_guidance(self.ctx, None, 0, None, 0, None, 0, 0, None), "shapemol_set_mesh_guidance")
+            else:
+                _lib.check(_lib.load().shapemol_set_guidance(self.ctx, None, 0, 0.0, 0, None), "shapemol_set_guidance")
 
     def abandon(self):
         self.done = True
@@ -557,7 +577,11 @@ class _PendingChain:
         try:
             # the reference returns finished results; also the point where the input flags are read (only this chain's stream
             # is waited for: another slot's chain may be running beside it)
-            _lib.check(_lib.load().shapemol_status_stream(self.ctx, None, _stream_ptr(self.side)), "input check")
+            flags = (C.c_int32 * 8)()
+            rc = _lib.load().shapemol_status_stream(self.ctx, flags, _stream_ptr(self.side))
+            if rc and flags[_lib.ST_MESH] and not any(flags[i] for i in range(8) if i != _lib.ST_MESH):
+                raise _lib.MeshGuidanceError(f"mesh shape guidance: {_lib.load().shapemol_last_error().decode()}")
+            _lib.check(rc, "input check")
         finally:
             self._drop_guidance()
         self.cur.wait_stream(self.side)
@@ -617,6 +641,65 @@ def pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=3, ratio=0
                                                       float(ratio), _ptr(pos), pos.shape[0], _ptr(gd), C.c_uint64(seed),
                                                       _stream_ptr(torch.cuda.current_stream(pos.device)))
     _lib.check(rc, "shapemol_pointcloud_guidance")
+    return pred_ligand_pos
+
+
+def _mesh_arrays(use_mesh_data):
+    """(mesh, point_clouds, kdtree) -> contiguous (V,3) float64 vertices, (F,3) int32 faces, (P,3) float64 cloud.  The mesh is
+    duck-typed: ``.vertices`` / ``.faces`` (a ``trimesh.Trimesh``) or a ``(vertices, faces)`` pair."""
+    if not isinstance(use_mesh_data, (tuple, list)) or len(use_mesh_data) != 3:
+        raise NotImplementedError("use_mesh_data must be (mesh, point_clouds, kdtree), as the reference's sampling script builds it")
+    mesh, cloud = use_mesh_data[0], use_mesh_data[1]
+    if hasattr(mesh, "vertices") and hasattr(mesh, "faces"):
+        verts, faces = mesh.vertices, mesh.faces
+    elif isinstance(mesh, (tuple, list)) and len(mesh) == 2:
+        verts, faces = mesh
+    else:
+        raise NotImplementedError(f"a mesh of type {type(mesh).__name__}: give one with .vertices / .faces or a (vertices, faces) pair")
+    verts = np.ascontiguousarray(np.asarray(verts, dtype=np.float64))
+    faces = np.asarray(faces)
+    if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3 or len(faces) == 0:
+        raise ValueError("the mesh must have (V, 3) vertices and (F >= 1, 3) faces")
+    if faces.min() < 0 or faces.max() >= len(verts):
+        raise ValueError("a face names a vertex outside [0, V)")
+    faces = np.ascontiguousarray(faces.astype(np.int32))
+    cloud = cloud.detach().cpu().numpy() if isinstance(cloud, torch.Tensor) else cloud
+    cloud = np.ascontiguousarray(np.asarray(cloud, dtype=np.float64).reshape(-1, 3))
+    return verts, faces, cloud
+
+
+def mesh_shape_guidance(use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws=None, seed=None):
+    """``mesh_shape_guidance`` of the reference (``models/molopt_score_model.py:742-775``) as two device kernels: the atoms of
+    ``pred_ligand_pos`` (N,3) inside the mesh and > 0.4 from the cloud anchor the pull; every atom outside the mesh or < 0.2
+    from the cloud moves away from the mean of its 3 nearest anchors by ``u * 0.8 + 0.2`` and is accepted once inside the mesh
+    and > 0.2 from the cloud, up to five times; atoms never accepted keep their position.  The tensor is updated in place and
+    returned.  ``use_mesh_data = (mesh, point_clouds, kdtree)`` as there; the mesh is anything with ``.vertices`` / ``.faces``
+    or a ``(vertices, faces)`` pair, the KD-tree is not used (brute-force float64 searches on the device), and ``k`` / ``ratio``
+    are ignored, as the reference ignores them.  Containment is the parity of a fixed ray (``csrc/sm_mesh.h``), not trimesh's
+    code.  Raises ``ValueError`` (``_lib.MeshGuidanceError``) when fewer than 3 atoms are inside, as the reference's KD-tree.
+    Extensions (keyword-only): ``draws`` (5,N) float64 device tensor = the uniform of every (iteration, atom) (parity mode);
+    otherwise device Philox keyed by ``seed`` (default: drawn from numpy's global generator)."""
+    del k, ratio                 # the reference hard-codes 3 neighbours and the fraction u * 0.8 + 0.2
+    pos = _check_device_tensor("pred_ligand_pos", pred_ligand_pos, torch.float32)
+    if pos.data_ptr() != pred_ligand_pos.data_ptr() or pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pred_ligand_pos must be a contiguous (N, 3) tensor (it is updated in place)")
+    verts, faces, cloud = _mesh_arrays(use_mesh_data)
+    gd = None if draws is None else _check_device_tensor("draws", draws, torch.float64)
+    if gd is not None and tuple(gd.shape) != (5, pos.shape[0]):
+        raise ValueError("draws must be (5, N) float64")
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64)) if gd is None else 0
+    if pos.shape[0] == 0:
+        raise _lib.MeshGuidanceError("mesh shape guidance: no atoms inside the mesh (the reference's KDTree of none raises)")
+    flag = C.c_int32(0)
+    with torch.cuda.device(pos.device):
+        rc = _lib.load().shapemol_mesh_guidance(verts.ctypes.data_as(C.c_void_p), verts.shape[0], faces.ctypes.data_as(C.c_void_p),
+                                                faces.shape[0], cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], _ptr(pos),
+                                                pos.shape[0], _ptr(gd), C.c_uint64(seed), C.byref(flag),
+                                                _stream_ptr(torch.cuda.current_stream(pos.device)))
+    if rc and flag.value:
+        raise _lib.MeshGuidanceError(_lib.load().shapemol_last_error().decode())
+    _lib.check(rc, "shapemol_mesh_guidance")
     return pred_ligand_pos
 
 

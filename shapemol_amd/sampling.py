@@ -104,7 +104,8 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
                             pos_only=False, center_pos_mode="none", sample_func=None, threshold_type=None,
                             threshold_args=None, sample_num_atoms="prior", bounds=None, ref_num_atoms=None,
                             ref_atom_feature=None, guide_stren=0, seed=None, use_graph=True, host_rng=False,
-                            use_pointcloud_data=None, grad_step=1000, pipeline=2, _batches=None, _batch_seed=None):
+                            use_pointcloud_data=None, grad_step=1000, pipeline=2, use_mesh_data=None, use_mesh_gap=None,
+                            _batches=None, _batch_seed=None):
     """``sample_diffusion_ligand`` of the reference for one shape condition.
 
     shape_emb        (32, 3) latent of the condition (``data.shape_emb``); repeated per molecule of a batch.
@@ -122,6 +123,11 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
     use_pointcloud_data, grad_step   ``(point_clouds, kdtree, radius)`` and the time step below which guidance stops
                      (``config.sample.use_pointcloud*`` / ``grad_step``, ``scripts/sample_diffusion.py:237-243``): the point-cloud
                      shape guidance runs as a device kernel inside every step with t > grad_step.
+    use_mesh_data    ``(mesh, point_clouds, kdtree)`` as ``scripts/sample_diffusion.py:227-235`` builds it (a ``trimesh.Trimesh``,
+                     or anything with ``.vertices`` / ``.faces``, or a ``(vertices, faces)`` pair; the KD-tree is not used): the
+                     mesh shape guidance runs as two device kernels inside every step with t > grad_step, and takes precedence
+                     over ``use_pointcloud_data``, as in the reference.
+    use_mesh_gap     accepted and ignored: the reference passes ``config.sample.use_mesh_gap`` here and never reads it.
     shape_emb        may also be (n_data, 32, 3), one condition per molecule of a single batch (fixtures).
     pipeline         batches in flight on the device (accelerated model only; 1 = one after the other, as the reference).  With 2
                      (default) two library contexts alternate: while the chain of batch i runs, the trajectories of batch i - 1
@@ -154,8 +160,8 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
     num_batch = int(np.ceil(num_samples / batch_size))
     accelerated = getattr(model, "_accelerated", False)
     depth = max(1, int(pipeline)) if accelerated else 1
-    if accelerated and depth > 1 and use_pointcloud_data is not None:
-        depth = 1          # installing / removing the guidance cloud drains the device: nothing to overlap
+    if accelerated and depth > 1 and (use_pointcloud_data is not None or use_mesh_data is not None):
+        depth = 1          # installing / removing the guidance cloud or mesh drains the device: nothing to overlap
     pending = collections.deque()
 
     def deliver(job):
@@ -233,7 +239,7 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
                 ligand_shape=(shape_emb if per_mol_shapes else shape_emb.repeat(n_data, 1, 1)).to(dev).reshape(n_data, -1),
                 threshold_type=threshold_type, threshold_args=threshold_args, num_steps=num_steps,
                 center_pos_mode=center_pos_mode, guide_stren=guide_stren, bounds=bounds,
-                use_pointcloud_data=use_pointcloud_data, grad_step=grad_step,
+                use_pointcloud_data=use_pointcloud_data, use_mesh_data=use_mesh_data, grad_step=grad_step,
                 seed=None if seed is None else int(seed) + i, use_graph=use_graph, **noise_kw,
                 **({"_reuse_host_buffers": "device", "_slot": slot_i % depth, "_async": True} if accelerated else {}))
             pending.append((handle, ligand_num_atoms, n_data, t1))
