@@ -58,8 +58,22 @@ class Dims:
 # ------------------------------------------------------------------------------------------
 # building blocks
 # ------------------------------------------------------------------------------------------
+class _Precision(dict):
+    """The state dict of a score evaluation in another precision: every floating tensor cast to `dtype`; `operands`, if
+    given, rounds both matrix operands of every Linear (input rows and weight) before the product, to emulate the operand
+    formats of the kernels (tests/precision.py)."""
+
+    def __init__(self, sd, dtype, operands=None):
+        super().__init__({k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()})
+        self.operands = operands
+
+
 def _lin(sd, p, x):
-    return F.linear(x, sd[p + ".weight"], sd.get(p + ".bias"))
+    w = sd[p + ".weight"]
+    rnd = getattr(sd, "operands", None)
+    if rnd is not None:
+        x, w = rnd(x), rnd(w)
+    return F.linear(x, w, sd.get(p + ".bias"))
 
 
 def _mlp(sd, p, x):
@@ -71,7 +85,7 @@ def _mlp(sd, p, x):
 
 def _rbf(d):
     """exp(-0.5 (d - mu_g)^2 / (mu_1 - mu_0)^2) over the 20 fixed centres; d: (E,1) or (E,)."""
-    mu = torch.tensor(RBF_CENTRES, dtype=torch.float32)
+    mu = torch.tensor(RBF_CENTRES, dtype=d.dtype)
     coeff = -0.5 / float(mu[1] - mu[0]) ** 2
     return torch.exp(coeff * (d.reshape(-1, 1) - mu.view(1, -1)) ** 2)
 
@@ -103,21 +117,23 @@ def knn_edges(x, batch, k):
 def _segment_softmax(logit, dst, n):
     """softmax over the incoming edges of each centre, independently per trailing column."""
     idx = dst.view(-1, 1).expand_as(logit)
-    mx = torch.full((n, logit.shape[1]), float("-inf")).scatter_reduce(0, idx, logit, "amax", include_self=True)
+    mx = torch.full((n, logit.shape[1]), float("-inf"), dtype=logit.dtype).scatter_reduce(0, idx, logit, "amax", include_self=True)
     ex = torch.exp(logit - mx[dst])
-    den = torch.zeros(n, logit.shape[1]).index_add_(0, dst, ex)
+    den = torch.zeros(n, logit.shape[1], dtype=logit.dtype).index_add_(0, dst, ex)
     return ex / den[dst]
 
 
 def _segment_sum(val, dst, n):
-    return torch.zeros((n,) + tuple(val.shape[1:])).index_add_(0, dst, val)
+    return torch.zeros((n,) + tuple(val.shape[1:]), dtype=val.dtype).index_add_(0, dst, val)
 
 
 def _time_embedding(sd, dm, t):
+    """The sinusoidal features are float32 whatever the precision of the rest (like the kNN graph, an input of the network):
+    their argument t * f rounds at ulp(t) ~ 6e-5 near t = 1000, an input error every float32 implementation shares."""
     half = dm.temb // 2
     freq = torch.exp(torch.arange(half) * -(math.log(10000) / (half - 1)))
     arg = t[:, None] * freq[None, :]
-    e = torch.cat((arg.sin(), arg.cos()), dim=-1)
+    e = torch.cat((arg.sin(), arg.cos()), dim=-1).to(sd["time_emb.1.weight"].dtype)
     return _lin(sd, "time_emb.3", F.silu(_lin(sd, "time_emb.1", e)))
 
 
@@ -170,7 +186,7 @@ def _vn_linear_lrelu(sd, p, z, taps=None, bn_eval=False):
     pf = pf / nrm.unsqueeze(2) * nbn.unsqueeze(2)
     d = torch.einsum("oc,ncd->nod", wd, z)
     dot = (pf * d).sum(2, keepdim=True)
-    mask = (dot >= 0).float()
+    mask = (dot >= 0).to(dot.dtype)
     dsq = (d * d).sum(2, keepdim=True)
     return LEAK * pf + (1 - LEAK) * (mask * pf + (1 - mask) * (pf - (dot / (dsq + VN_EPS)) * d))
 
@@ -192,7 +208,7 @@ def _h2x(sd, p, dm, h, x, rel_x, rfeat, src, dst, inv_atom, shape_atom, e_w, tap
 def _refine(sd, dm, h, x, batch, shape, taps=None, bn_eval=False):
     inv_atom = _invariant_shape(sd, shape)[batch]
     shape_atom = shape[batch]
-    src, dst = knn_edges(x, batch, dm.k)
+    src, dst = knn_edges(x.float(), batch, dm.k)        # float32 distances in every precision: one graph for all
     e_w = _edge_weight(sd, x, src, dst)
     if taps is not None:
         taps["edge_index"] = torch.stack([src, dst])
@@ -206,16 +222,22 @@ def _refine(sd, dm, h, x, batch, shape, taps=None, bn_eval=False):
         dx = _h2x(sd, p + ".h2x_layers.0", dm, h, x, rel_x, rfeat, src, dst, inv_atom, shape_atom, e_w, lt, bn_eval)
         x = x + dx
         if taps is not None:
-            taps[f"h_{l}"], taps[f"dx_{l}"] = h, dx
+            taps[f"h_{l}"], taps[f"dx_{l}"], taps[f"x_{l}"] = h, dx, x
             taps[f"bn_in_{l}"] = lt["bn_in"]
     return h, x
 
 
-def score_with_grad(sd, dm, pos, v, batch, shape, t, taps=None, bn_eval=False):
+def score_with_grad(sd, dm, pos, v, batch, shape, t, taps=None, bn_eval=False, dtype=torch.float32, operands=None):
     """One score evaluation, recorded by autograd (the training step's forward; score() is the same under no_grad).  pos (N,3) f32, v (N,) i64, batch (N,) i64 sorted, shape (B,S,3)
     f32, t (B,) i64 -> dict(pred_ligand_pos (N,3), pred_ligand_h (N,H), pred_ligand_v (N,C)).
-    bn_eval: the module after .eval() (running batch-norm statistics)."""
-    onehot = F.one_hot(v, dm.C).float()
+    bn_eval: the module after .eval() (running batch-norm statistics).
+    dtype: the precision of the arithmetic (torch.float64: the high-precision reference of the precision gates); weights, positions
+    and shapes are cast from their float32 values, the kNN graph and the time features stay float32 (the same inputs in every
+    precision).  operands: see _Precision."""
+    if dtype != torch.float32 or operands is not None:
+        sd = _Precision(sd, dtype, operands)
+        pos, shape = pos.to(dtype), shape.to(dtype)
+    onehot = F.one_hot(v, dm.C).to(pos.dtype)
     feat = torch.cat([onehot, _time_embedding(sd, dm, t)[batch]], -1)
     h = _lin(sd, "ligand_atom_emb", feat)
     h, x = _refine(sd, dm, h, pos, batch, shape, taps, bn_eval)
@@ -223,10 +245,10 @@ def score_with_grad(sd, dm, pos, v, batch, shape, t, taps=None, bn_eval=False):
     return {"pred_ligand_pos": x, "pred_ligand_h": h, "pred_ligand_v": _lin(sd, "v_inference.2", hv)}
 
 
-def score(sd, dm, pos, v, batch, shape, t, taps=None, bn_eval=False):
+def score(sd, dm, pos, v, batch, shape, t, taps=None, bn_eval=False, dtype=torch.float32, operands=None):
     """score_with_grad without autograd (sampling, validation)."""
     with torch.no_grad():
-        return score_with_grad(sd, dm, pos, v, batch, shape, t, taps, bn_eval)
+        return score_with_grad(sd, dm, pos, v, batch, shape, t, taps, bn_eval, dtype, operands)
 
 
 # ------------------------------------------------------------------------------------------
