@@ -153,6 +153,18 @@ int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t
                            const double *h_cloud, int64_t n_cloud, float *d_pos, int64_t n_atoms, const double *d_draws,
                            uint64_t seed, int32_t *flag_out, void *stream);
 
+/* Classifier-free guidance of the following _sample calls (models/molopt_score_model.py:616-642).  Every step then evaluates
+ * the score with the shape and with a zeroed shape (same positions, kNN graph and edge weights), combines the predictions as
+ * (1 + guide_stren) * cond - guide_stren * uncond and applies threshold_CFG (:136-151) to positions and logits:
+ * threshold_type 0 none, 1 reference_threshold (s = max|cond| * p), 2 dynamic_threshold (s = torch.quantile(x, p)),
+ * 3 rescale (p * x * std(cond) / std(x) + (1 - p) * x); each statistic is over the whole batch tensor.  h_bounds: HOST
+ * (3,2) float64 box [lo, hi] per coordinate that clamps every predicted position (the reference's bounds[0]), or NULL.
+ * d_pos_uncond_traj (S,N,3) / d_v_uncond_traj (S,N,C) f32 DEVICE receive the raw unconditional predictions, or NULL; the
+ * pos_cond / v_cond trajectories of shapemol_traj keep the raw conditional ones, v0_traj the thresholded logits.
+ * guide_stren = 0 switches guidance off.  Mesh or point-cloud guidance, when set, take precedence (the reference's elif). */
+int shapemol_set_cfg(shapemol_ctx *ctx, double guide_stren, int32_t threshold_type, double p, const double *h_bounds,
+                     float *d_pos_uncond_traj, float *d_v_uncond_traj);
+
 /* Input validation happens on the device (no host synchronisation in _score/_sample): an unsorted or
  * out-of-range d_batch, an atom type outside [0, num_classes) or a time step outside [0, num_timesteps)
  * sets a sticky flag (the offending index is clamped, so nothing is read or written out of bounds).

@@ -19,7 +19,7 @@ EXPORTS = (
     "shapemol_log_sample_categorical", "shapemol_set_option", "shapemol_debug_read",
     "shapemol_profile_begin", "shapemol_profile_end", "shapemol_status", "shapemol_status_stream", "shapemol_set_guidance", "shapemol_guide_points",
     "shapemol_pointcloud_guidance", "shapemol_set_mesh_guidance", "shapemol_guide_points_mesh", "shapemol_mesh_guidance",
-    "shapemol_set_knn_pins", "shapemol_debug_split_exact",
+    "shapemol_set_cfg", "shapemol_set_knn_pins", "shapemol_debug_split_exact",
     "shapemol_mlp_backward_workspace", "shapemol_mlp_forward", "shapemol_mlp_backward",
     "shapemol_seg_attention_forward", "shapemol_seg_attention_backward",
     "shapemol_vn_backward_workspace", "shapemol_vn_forward", "shapemol_vn_backward",
@@ -48,6 +48,10 @@ class MeshGuidanceError(ShapeMolLibraryError, ValueError):
     """Mesh shape guidance found fewer than 3 atoms inside the mesh (and > 0.4 from the cloud) to pull towards: the
     reference's sklearn KD-tree raises ValueError there."""
 
+
+# threshold_CFG's threshold_type -> the library's code (shapemol_set_cfg)
+CFG_THRESHOLDS = {None: 0, "reference_threshold": 1, "dynamic_threshold": 2, "rescale": 3}
+CFG_DEFAULT_P = {None: 0.0, "reference_threshold": 1.1, "dynamic_threshold": 0.995, "rescale": 0.7}
 
 ST_MESH = 6     # index of the mesh-guidance flag among the eight status flags (shapemol_status)
 
@@ -106,6 +110,7 @@ def load():
     lib.shapemol_set_mesh_guidance.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp]
     lib.shapemol_guide_points_mesh.argtypes = [vp, vp, i64, vp, u64, vp]
     lib.shapemol_mesh_guidance.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, u64, vp, vp]
+    lib.shapemol_set_cfg.argtypes = [vp, C.c_double, i32, C.c_double, vp, vp, vp]
     lib.shapemol_mlp_backward_workspace.restype = C.c_size_t
     lib.shapemol_mlp_backward_workspace.argtypes = [i64, i32, i32, i32]
     lib.shapemol_mlp_forward.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]

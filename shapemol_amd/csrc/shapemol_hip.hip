@@ -12,6 +12,7 @@
 #include "sm_edge_stream.h"
 #include "sm_misc.h"
 #include "sm_mesh.h"
+#include "sm_cfg.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -576,6 +577,14 @@ struct shapemol_ctx {
     MeshFace *m_faces = nullptr; double4 *m_fbox = nullptr; double *m_cloud = nullptr;     // one device block
     int64_t m_nfaces = 0, m_points = 0; int m_grad_step = 0; const double *m_draws = nullptr; double m_bounds[5] = {};
     float4 *m_within = nullptr; int *m_out = nullptr, *m_cnt = nullptr; int64_t m_cap = 0;  // per-step lists (one block)
+    // classifier-free guidance (shapemol_set_cfg): a second score evaluation per step on a zeroed shape, whose prepared shape
+    // data (invariant embedding, shape terms, VN shape part) lives in the parallel *_u buffers; swap_uncond() exchanges the sets
+    double cfg_w = 0.0, cfg_p = 0.0; int cfg_type = 0, cfg_has_bounds = 0; float cfg_lo[3] = {}, cfg_hi[3] = {};
+    float *cfg_tr_pos_u = nullptr, *cfg_tr_v_u = nullptr;      // caller's uncond trajectories (or nullptr)
+    float *inv_u = nullptr, *add0_u = nullptr, *addp_u = nullptr, *ps_u = nullptr, *pred_pos_u = nullptr, *pred_v_u = nullptr;
+    float *shape_zero = nullptr;      // [B][S][3] zeros (never written)
+    ShapeTermArgs *prep_terms_u = nullptr; VnShapeArgs *prep_vn_u = nullptr;
+    float *cfg_stat = nullptr; double *cfg_part = nullptr; unsigned *cfg_hist = nullptr;
     int first_step = 0;         // option "first_step": the next chains start at reverse step first_step (t = T-1-first_step)
     // diagnostic: neighbour lists pinned at given (reverse step, atom) pairs (shapemol_set_knn_pins)
     int *pin_off = nullptr, *pin_atom = nullptr, *pin_nbr = nullptr; int64_t n_pins = 0; int pin_steps = 0, pin_k = 0;
@@ -589,8 +598,14 @@ struct shapemol_ctx {
     // the captured step depends on the batch geometry only: seed, noise and trajectory pointers live in chain_params
     // what a captured step depends on besides the options (which drop the graphs when set): sizes, guidance, and the two
     // launch decisions taken from the max_mol_atoms hint (folded coordinate update, fused graph kernel)
+    // (classifier-free guidance: its type and scalars are kernel arguments of the captured step)
     struct GraphKey { int64_t N = 0, B = 0; int guided = 0 /* 0 none, 1 point cloud, 2 mesh */, fold = 0, gfuse = 0;
-                      bool operator==(const GraphKey &o) const { return N == o.N && B == o.B && guided == o.guided && fold == o.fold && gfuse == o.gfuse; } } gkey{};
+                      int cfg = 0 /* 0 off, else 1 + CfgType */; double cfgv[9] = {};   // w, p, has_bounds, box
+                      bool operator==(const GraphKey &o) const {
+                          if (!(N == o.N && B == o.B && guided == o.guided && fold == o.fold && gfuse == o.gfuse && cfg == o.cfg)) return false;
+                          for (int i = 0; i < 9; ++i) if (cfgv[i] != o.cfgv[i]) return false;
+                          return true;
+                      } } gkey{};
     hipStream_t gstream = nullptr; bool gstream_set = false;     // the stream the executables were last launched on
     void drop_graphs() {      // a replay may still be in flight: drain it before destroying the executables (only the stream the
         if (!gexec && !gexec_u) return;       // graphs ran on: another context's chain may be running beside, and must not be waited for)
@@ -655,29 +670,38 @@ int ensure_workspace(shapemol_ctx *c, int64_t N, int64_t B) {
         A(&c->x_b, capN * 3) || A(&c->x_state, capN * 3) || A(&c->pred_pos, capN * 3) ||
         A(&c->pred_v, capN * g.num_classes) || A(&c->v_state, capN) || A(&c->stamps, 2048) || A(&c->kstamps, 8 * 16 * 4096) || A(&c->bn_acc, (size_t)L * kBnReplicas * 2 * hd + L + 1) ||
         (c->KP > 16 && (A(&c->part_rows, (size_t)2 * capN * H) || A(&c->part_ms, (size_t)2 * capN * hd * 2))) ||
-        A(&c->status, 8) || A(&c->chain_params, 1) || A(&c->prep_terms, 2 * L + 1) || A(&c->prep_vn, L))
+        A(&c->status, 8) || A(&c->chain_params, 1) || A(&c->prep_terms, 2 * L + 1) || A(&c->prep_vn, L) ||
+        A(&c->inv_u, capB * g.shape_latent_dim) || A(&c->add0_u, (size_t)capB * 4 * H) || A(&c->addp_u, (size_t)L * capB * 8 * H) ||
+        A(&c->ps_u, (size_t)L * capB * 2 * hd * 3) || A(&c->pred_pos_u, capN * 3) || A(&c->pred_v_u, capN * g.num_classes) ||
+        A(&c->shape_zero, (size_t)capB * g.shape_dim * 3) || A(&c->prep_terms_u, 2 * L + 1) || A(&c->prep_vn_u, L) ||
+        A(&c->cfg_stat, 4) || A(&c->cfg_part, (size_t)2 * kCfgMaxBlocks * 4) || A(&c->cfg_hist, (size_t)2 * kCfgHistWords))
         return 1;
     c->capN = capN; c->capB = capB;
-    {   // argument blocks of the batched prep launches (they point into the workspace just allocated)
+    // argument blocks of the batched prep launches (they point into the workspace just allocated): the conditional set and
+    // the unconditional one of classifier-free guidance
+    auto prep_blocks = [&](float *inv, float *add0, float *addp_all, float *ps, ShapeTermArgs *d_terms, VnShapeArgs *d_vn) -> int {
         const int SL = g.shape_latent_dim, S = g.shape_dim;
         std::vector<ShapeTermArgs> terms;
         std::vector<VnShapeArgs> vns;
         const DevLayer &D0 = c->dm.layer[0];
-        terms.push_back(ShapeTermArgs{c->inv, c->P(D0.sk_x2h), c->P(D0.bk_x2h), c->P(D0.sv_x2h), c->P(D0.bv_x2h), c->add0, SL, H, SL, 4 * H});
+        terms.push_back(ShapeTermArgs{inv, c->P(D0.sk_x2h), c->P(D0.bk_x2h), c->P(D0.sv_x2h), c->P(D0.bv_x2h), add0, SL, H, SL, 4 * H});
         for (int l = 0; l < L; ++l) {
             const DevLayer &D = c->dm.layer[l];
-            float *addp = c->addp + (size_t)l * c->capB * 8 * H;      // [B][8H]: this layer's h2x | the next layer's x2h
-            terms.push_back(ShapeTermArgs{c->inv, c->P(D.sk_h2x), c->P(D.bk_h2x), c->P(D.sv_h2x), c->P(D.bv_h2x), addp, SL, H, SL, 8 * H});
+            float *addp = addp_all + (size_t)l * c->capB * 8 * H;      // [B][8H]: this layer's h2x | the next layer's x2h
+            terms.push_back(ShapeTermArgs{inv, c->P(D.sk_h2x), c->P(D.bk_h2x), c->P(D.sv_h2x), c->P(D.bv_h2x), addp, SL, H, SL, 8 * H});
             if (l + 1 < L) {
                 const DevLayer &Dn = c->dm.layer[l + 1];
-                terms.push_back(ShapeTermArgs{c->inv, c->P(Dn.sk_x2h), c->P(Dn.bk_x2h), c->P(Dn.sv_x2h), c->P(Dn.bv_x2h), addp + 4 * H, SL, H, SL, 8 * H});
+                terms.push_back(ShapeTermArgs{inv, c->P(Dn.sk_x2h), c->P(Dn.bk_x2h), c->P(Dn.sv_x2h), c->P(Dn.bv_x2h), addp + 4 * H, SL, H, SL, 8 * H});
             }
-            vns.push_back(VnShapeArgs{nullptr, c->P(D.vn_f), c->P(D.vn_d), c->ps + (size_t)l * c->capB * 2 * hd * 3, S, hd});
+            vns.push_back(VnShapeArgs{nullptr, c->P(D.vn_f), c->P(D.vn_d), ps + (size_t)l * c->capB * 2 * hd * 3, S, hd});
         }
         c->n_prep_terms = (int)terms.size();
-        HIPCHK(hipMemcpy(c->prep_terms, terms.data(), terms.size() * sizeof(ShapeTermArgs), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->prep_vn, vns.data(), vns.size() * sizeof(VnShapeArgs), hipMemcpyHostToDevice));
-    }
+        HIPCHK(hipMemcpy(d_terms, terms.data(), terms.size() * sizeof(ShapeTermArgs), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_vn, vns.data(), vns.size() * sizeof(VnShapeArgs), hipMemcpyHostToDevice));
+        return 0;
+    };
+    if (prep_blocks(c->inv, c->add0, c->addp, c->ps, c->prep_terms, c->prep_vn) ||
+        prep_blocks(c->inv_u, c->add0_u, c->addp_u, c->ps_u, c->prep_terms_u, c->prep_vn_u)) return 1;
     return 0;
 }
 
@@ -977,11 +1001,72 @@ __global__ void knn_pin_kernel(const int *off, int n_steps, const int *atom, con
 }
 
 template <int H>
+int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape);
+
+// classifier-free guidance applies to this chain (the reference's if / elif: mesh or point-cloud guidance come first)
+bool cfg_on(const shapemol_ctx *c) { return c->cfg_w != 0.0 && c->m_nfaces == 0 && c->g_points == 0; }
+
+// exchange the conditional and the unconditional sets of prepared shape data and score outputs
+void swap_uncond(shapemol_ctx *c) {
+    std::swap(c->inv, c->inv_u); std::swap(c->add0, c->add0_u); std::swap(c->addp, c->addp_u); std::swap(c->ps, c->ps_u);
+    std::swap(c->prep_terms, c->prep_terms_u); std::swap(c->prep_vn, c->prep_vn_u);
+}
+
+CfgArgs cfg_args(const shapemol_ctx *c, int64_t N) {
+    CfgArgs a{};
+    a.on = cfg_on(c) ? 1 : 0;
+    if (!a.on) return a;
+    const int C = c->cfg.num_classes;
+    a.pos_c = c->pred_pos; a.pos_u = c->pred_pos_u; a.v_c = c->pred_v; a.v_u = c->pred_v_u;
+    a.w1 = (float)(1.0 + c->cfg_w); a.w = (float)c->cfg_w; a.pf = (float)c->cfg_p; a.qf = (float)(1.0 - c->cfg_p);
+    for (int k = 0; k < 3; ++k) { a.lo[k] = c->cfg_lo[k]; a.hi[k] = c->cfg_hi[k]; }
+    a.has_bounds = c->cfg_has_bounds; a.type = c->cfg_type; a.n_atoms = (int)N; a.C = C;
+    a.stat = c->cfg_stat; a.part = c->cfg_part; a.hist = c->cfg_hist;
+    for (int w = 0; w < 2; ++w) {
+        const int64_t n = N * (w ? C : 3);
+        a.blocks[w] = (int)std::min<int64_t>(kCfgMaxBlocks, std::max<int64_t>(1, (n + 2047) / 2048));
+        // torch.quantile: q rounded to float32, rank = q * (n - 1) in float32, the two ranks around it, weight rank - below
+        volatile float q = (float)c->cfg_p, last = (float)(n - 1);
+        volatile float rank = q * last;
+        a.k_lo[w] = (long long)rank;
+        a.k_hi[w] = (long long)std::ceil(rank);
+        a.weight[w] = rank - (float)a.k_lo[w];
+        a.k_lo[w] = std::min<long long>(std::max<long long>(a.k_lo[w], 0), n - 1);
+        a.k_hi[w] = std::min<long long>(std::max<long long>(a.k_hi[w], 0), n - 1);
+    }
+    return a;
+}
+
+// classifier-free guidance, after both score evaluations: the batch statistic of each tensor (threshold_CFG's s or r)
+int run_cfg_stats(shapemol_ctx *c, hipStream_t s, const CfgArgs &a) {
+    const dim3 grid((unsigned)std::max(a.blocks[0], a.blocks[1]), 2);
+    if (a.type == CFG_REFERENCE || a.type == CFG_RESCALE) {
+        LAUNCH("cfg_stat", SMK(cfg_partial_kernel, grid, dim3(256), 0, s, a));
+    } else if (a.type == CFG_DYNAMIC) {
+        LAUNCH("cfg_stat", SMK(cfg_hist_kernel<0>, grid, dim3(256), 0, s, a));
+        LAUNCH("cfg_stat", SMK(cfg_hist_kernel<1>, grid, dim3(256), 0, s, a));
+        LAUNCH("cfg_stat", SMK(cfg_hist_kernel<2>, grid, dim3(256), 0, s, a));
+    } else {
+        return 0;        // no threshold: the combine and the clamp need no statistic
+    }
+    LAUNCH("cfg_stat", SMK(cfg_finalize_kernel, dim3(2), dim3(256), 0, s, a));
+    return 0;
+}
+
+template <int H>
 int run_prep(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int64_t B, const float *d_shape) {
     const shapemol_config &g = c->cfg;
     const int L = g.num_layers, hd = g.n_heads, SL = g.shape_latent_dim, S = g.shape_dim;
     LAUNCH("prep", SMK(mol_index_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_batch, (int)N, (int)B, c->mol_of, c->mol_off, c->status));
     LAUNCH("prep", SMK(mol_span_kernel, dim3((N + 255) / 256), dim3(256), 0, s, c->mol_of, c->mol_off, (int)N, c->mol_span));
+    return run_prep_shape<H>(c, s, B, d_shape);
+}
+
+// the shape-dependent part of run_prep (into the buffer set in use: swap_uncond)
+template <int H>
+int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape) {
+    const shapemol_config &g = c->cfg;
+    const int L = g.num_layers, hd = g.n_heads, SL = g.shape_latent_dim, S = g.shape_dim;
     ShapeInvArgs si{d_shape, c->P(c->dm.inv.w1), c->P(c->dm.inv.b1), c->P(c->dm.inv.g), c->P(c->dm.inv.be),
                     c->P(c->dm.inv.w2), c->P(c->dm.inv.b2), c->inv, S, SL};
     LAUNCH("prep", SMK(shape_invariant_kernel, dim3(B), dim3(64), 0, s, si));
@@ -996,7 +1081,9 @@ int run_prep(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, 
 // One score evaluation on prepared batch data.  x_in/v_in: current state; outputs as given.
 template <int H>
 int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *v_in, int64_t N, int64_t B,
-              bool sampling, int t_first, float *out_pos, float *out_h, float *out_v) {
+              bool sampling, int t_first, float *out_pos, float *out_h, float *out_v, bool reuse_graph = false) {
+    // reuse_graph: the second (unconditional) evaluation of a guided step on the same positions keeps the step's kNN graph
+    // and edge weights (nbr, ew)
     const shapemol_config &g = c->cfg;
     const int L = g.num_layers, hd = g.n_heads, C = g.num_classes, D = g.time_emb_dim, KP = c->KP;
     const int n = (int)N;
@@ -1026,7 +1113,8 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
     }
     // (chains only: the hint is set for the batch of a chain; a score evaluation on other data must not trust a stale one)
     const bool graph_fused = sampling && c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && KP <= 32 && c->n_pins == 0;
-    if (graph_fused) {
+    if (reuse_graph) {
+    } else if (graph_fused) {
         GraphArgs ga{x_in, c->mol_span, n, g.knn, KP, c->nbr, c->P(c->dm.ew.w1), c->P(c->dm.ew.b1), c->P(c->dm.ew.g), c->P(c->dm.ew.be),
                      c->P(c->dm.ew.w2), c->P(c->dm.ew.b2), c->ew, c->status + ST_SPAN, c->kstamp_sel == 4 ? c->kstamps : nullptr};
         const int apb = kGraphWaves * (KP >= 16 ? 1 : 16 / KP);      // atoms per workgroup
@@ -1034,11 +1122,11 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
         else if (KP == 16) LAUNCH("graph", SMK((graph_kernel<H, 16>), dim3((n + apb - 1) / apb), dim3(kGraphWaves * 64), 0, s, ga));
         else LAUNCH("graph", SMK((graph_kernel<H, 32>), dim3((n + apb - 1) / apb), dim3(kGraphWaves * 64), 0, s, ga));
     } else LAUNCH("knn", SMK(knn_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x_in, c->mol_of, c->mol_off, n, g.knn, KP, c->nbr));
-    if (sampling && c->n_pins > 0)      // diagnostic: the pinned atoms of this reverse step take the given neighbour lists
+    if (sampling && c->n_pins > 0 && !reuse_graph)      // diagnostic: the pinned atoms of this reverse step take the given neighbour lists
         LAUNCH("knn", SMK(knn_pin_kernel, dim3(32), dim3(256), 0, s, c->pin_off, c->pin_steps, c->pin_atom, c->pin_nbr, c->pin_k, KP, c->steps + 1, n, c->nbr));
     EdgeWeightArgs ea{x_in, c->nbr, c->P(c->dm.ew.w1), c->P(c->dm.ew.b1), c->P(c->dm.ew.g), c->P(c->dm.ew.be),
                       c->P(c->dm.ew.w2), c->P(c->dm.ew.b2), c->ew, n * KP, KP};
-    if (!graph_fused) {
+    if (!graph_fused && !reuse_graph) {
         const int tiles = (n * KP + 15) / 16;
         LAUNCH("edge_weight", SMK(edge_weight_kernel<H>, dim3((tiles + 3) / 4), dim3(256), 0, s, ea));
     }
@@ -1148,7 +1236,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                     pending = VnFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, x_next,
                                      c->mol_span, c->status + ST_SPAN, 1};
                     vn_done = true;
-                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->m_nfaces == 0 && C <= 16 && hd <= 16) {
+                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->m_nfaces == 0 && !cfg_on(c) && C <= 16 && hd <= 16) {
                     // ... or, for the last layer of a chain step, the DDPM kernel
                     ea.xsum = c->xsum;
                     c->ddpm_vf = DdpmFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, out_pos, hd, 1};
@@ -1174,7 +1262,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                     pending = VnFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, x_next,
                                      c->mol_span, c->status + ST_SPAN, 1};
                     vn_done = true;
-                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->m_nfaces == 0 && C <= 16 && hd <= 16) {
+                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->m_nfaces == 0 && !cfg_on(c) && C <= 16 && hd <= 16) {
                     sa.xsum = c->xsum;
                     c->ddpm_vf = DdpmFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, out_pos, hd, 1};
                     vn_done = true;
@@ -1228,9 +1316,10 @@ int run_ddpm(shapemol_ctx *c, hipStream_t s, int64_t N) {
     a.x_next = c->x_state; a.v_next = c->v_state;
     a.n_atoms = (int)N; a.C = g.num_classes;
     a.vf = c->ddpm_vf; c->ddpm_vf = DdpmFold{};
+    const CfgArgs cfg = cfg_args(c, N);
     if (c->stamp_on) LAUNCH("stamp", SMK(clock_stamp_kernel, dim3(1), dim3(64), 0, s, c->stamps, c->steps + 1, 1024));
-    if (g.num_classes <= 16) LAUNCH("ddpm", SMK(ddpm_step16_kernel, dim3((N * 16 + 255) / 256), dim3(256), 0, s, a));
-    else LAUNCH("ddpm", SMK(ddpm_step_kernel<32>, dim3((N + 127) / 128), dim3(128), 0, s, a));
+    if (g.num_classes <= 16) LAUNCH("ddpm", SMK(ddpm_step16_kernel, dim3((N * 16 + 255) / 256), dim3(256), 0, s, a, cfg));
+    else LAUNCH("ddpm", SMK(ddpm_step_kernel<32>, dim3((N + 127) / 128), dim3(128), 0, s, a, cfg));
     return 0;
 }
 
@@ -1484,12 +1573,21 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
     if (mesh) HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
     if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
+    const bool cfg = cfg_on(c);
+    if (cfg) {      // classifier-free guidance: the unconditional evaluation's shape data, from a zeroed shape, once per chain
+        swap_uncond(c);
+        const int rc = DISPATCH_H(c, run_prep_shape<128>(c, s, B, c->shape_zero), run_prep_shape<32>(c, s, B, c->shape_zero));
+        swap_uncond(c);
+        if (rc) return 1;
+        HIPCHK(hipMemsetAsync(c->cfg_hist, 0, (size_t)2 * kCfgHistWords * sizeof(unsigned), s));
+    }
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_init_v, (int)N, c->cfg.num_classes, c->status));
     {
         ChainParams cp{};
         cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->m_draws : c->g_draws;
         if (traj) { cp.tr_pos = traj->pos_traj; cp.tr_v = traj->v_traj; cp.tr_v0 = traj->v0_traj; cp.tr_vt = traj->vt_traj;
                     cp.tr_pos_cond = traj->pos_cond_traj; cp.tr_v_cond = traj->v_cond_traj; }
+        if (cfg) { cp.tr_pos_uncond = c->cfg_tr_pos_u; cp.tr_v_uncond = c->cfg_tr_v_u; }
         LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, cp, c->steps));
     }
     HIPCHK(hipMemcpyAsync(c->x_state, d_init_pos, N * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1497,6 +1595,13 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     auto one_step = [&]() -> int {
         if (DISPATCH_H(c, run_score<128>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v),
                        run_score<32>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v))) return 1;
+        if (cfg) {        // the same step on a zeroed shape: same positions, graph and step index; own batch statistics and outputs
+            swap_uncond(c);
+            const int rc = DISPATCH_H(c, run_score<128>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true),
+                                      run_score<32>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true));
+            swap_uncond(c);
+            if (rc || run_cfg_stats(c, s, cfg_args(c, N))) return 1;
+        }
         if (mesh) {                // mesh shape guidance of the predicted x0 (steps with t > grad_step)
             const MeshGuideArgs ma = mesh_args(c, c->pred_pos, N, c->steps + 1, t_first);
             const dim3 grid((unsigned)((N * 16 + 255) / 256));
@@ -1512,6 +1617,11 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
         shapemol_ctx::GraphKey key{};
         key.N = N; key.B = B; key.guided = mesh ? 2 : (c->g_points > 0 ? 1 : 0); key.fold = vn_fold_ok(c, (int)N);
         key.gfuse = c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && c->n_pins == 0;
+        if (cfg) {
+            key.cfg = 1 + c->cfg_type;
+            const double v[9] = {c->cfg_w, c->cfg_p, (double)c->cfg_has_bounds, c->cfg_lo[0], c->cfg_lo[1], c->cfg_lo[2], c->cfg_hi[0], c->cfg_hi[1], c->cfg_hi[2]};
+            std::copy(v, v + 9, key.cfgv);
+        }
         // two executables: one reverse step, and kGraphUnroll steps back to back (the gap between two graph launches,
         // ~8 us, is then paid once per kGraphUnroll steps); every step reads its index from the device-side counter
         auto capture = [&](int n_steps, hipGraphExec_t *exec) -> int {
@@ -1625,6 +1735,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     else if (k == "stamps") { src = c->stamps; bytes = 2048 * 8; }
     else if (k == "kstamps") { src = c->kstamps; bytes = (size_t)8 * 16 * 4096 * 8; }
     else if (k == "vn_err") { src = c->status + ST_VN_BARRIER; bytes = 4; }
+    else if (k == "cfg_stat") { src = c->cfg_stat; bytes = 2 * 4; }
     else if (k == "bnstat") { src = c->bn_acc; bytes = (size_t)g.num_layers * kBnReplicas * 2 * g.n_heads * 8; }
     else { fail("shapemol_debug_read: unknown buffer " + k); return -1; }
     if (!src || bytes > max_bytes) { fail("shapemol_debug_read: buffer unavailable or destination too small"); return -1; }
@@ -1672,6 +1783,22 @@ int shapemol_set_guidance(shapemol_ctx *c, const double *h_cloud, int64_t n_poin
     HIPCHK(hipMalloc((void **)&c->g_cloud, (size_t)n_points * 3 * sizeof(double)));
     HIPCHK(hipMemcpy(c->g_cloud, h_cloud, (size_t)n_points * 3 * sizeof(double), hipMemcpyHostToDevice));
     c->g_points = n_points; c->g_radius = radius; c->g_grad_step = grad_step; c->g_draws = d_draws;
+    return 0;
+}
+
+int shapemol_set_cfg(shapemol_ctx *c, double guide_stren, int32_t threshold_type, double p, const double *h_bounds,
+                     float *d_pos_uncond_traj, float *d_v_uncond_traj) {
+    if (!c) return fail("shapemol_set_cfg: null ctx");
+    if (!(guide_stren == guide_stren) || threshold_type < CFG_NONE || threshold_type > CFG_RESCALE || !(p == p))
+        return fail("shapemol_set_cfg: bad arguments");
+    c->cfg_w = guide_stren; c->cfg_type = guide_stren != 0.0 ? threshold_type : 0; c->cfg_p = guide_stren != 0.0 ? p : 0.0;
+    c->cfg_has_bounds = guide_stren != 0.0 && h_bounds != nullptr;
+    for (int k = 0; k < 3; ++k) {
+        c->cfg_lo[k] = c->cfg_has_bounds ? (float)h_bounds[2 * k] : 0.f;
+        c->cfg_hi[k] = c->cfg_has_bounds ? (float)h_bounds[2 * k + 1] : 0.f;
+    }
+    c->cfg_tr_pos_u = guide_stren != 0.0 ? d_pos_uncond_traj : nullptr;
+    c->cfg_tr_v_u = guide_stren != 0.0 ? d_v_uncond_traj : nullptr;
     return 0;
 }
 

@@ -3,6 +3,7 @@
 // train-mode batch statistics, and the DDPM posterior step.
 #pragma once
 #include "sm_device.h"
+#include "sm_cfg.h"
 
 // ---------------------------------------------------------------------------------------------
 // batch (N,) i64 sorted -> mol_of (N,) i32 and mol_off (B+1,) i32
@@ -665,6 +666,7 @@ struct ChainParams {
     unsigned long long seed;
     const float *eps, *u;    // host-fed noise of ALL steps ([S][N][3], [S][N][C]) or nullptr
     float *tr_pos; int64_t *tr_v; float *tr_v0; float *tr_vt; float *tr_pos_cond; float *tr_v_cond;  // trajectories or nullptr
+    float *tr_pos_uncond; float *tr_v_uncond;   // classifier-free guidance: unconditional predictions, or nullptr
     const double *guide_draws;   // point-cloud guidance: host-fed uniforms [S][5][N] (parity mode) or nullptr (device Philox)
     int step_base;           // index of the chain's first reverse step (0 unless a chain is resumed mid-way): noise and
                              // trajectory rows are indexed by step - step_base
@@ -699,8 +701,10 @@ struct DdpmArgs {
     int n_atoms, C;
     DdpmFold vf;             // ddpm_step16_kernel only
 };
+// (both kernels take a second argument block, CfgArgs (sm_cfg.h): classifier-free guidance, pred_pos / pred_v are then the
+// conditional predictions; cfg.on = 0 leaves the step as it was)
 template <int MAXC>
-__global__ void ddpm_step_kernel(DdpmArgs aa) {
+__global__ void ddpm_step_kernel(DdpmArgs aa, CfgArgs cfg) {
     struct : DdpmArgs, ChainParams {} a;
     static_cast<DdpmArgs &>(a) = aa;
     static_cast<ChainParams &>(a) = *aa.cp;
@@ -733,16 +737,31 @@ __global__ void ddpm_step_kernel(DdpmArgs aa) {
         const float sig = t != 0 ? expf(0.5f * a.logvar[t]) : 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float pp = a.pred_pos[i * 3 + k];
+            float pp = a.pred_pos[i * 3 + k];
+            if (cfg.on) {      // combine, threshold, clamp; the trajectories keep the raw predictions
+                const float pu = cfg.pos_u[i * 3 + k];
+                if (a.tr_pos_cond) a.tr_pos_cond[so * 3 + k] = pp;
+                if (a.tr_pos_uncond) a.tr_pos_uncond[so * 3 + k] = pu;
+                pp = cfg_apply(cfg, cfg_combine(cfg, pp, pu), cfg.stat[0], k);
+            }
             const float xn = (c0 * pp + ct * a.x_t[i * 3 + k]) + sig * e3[k];
             a.x_next[i * 3 + k] = xn;
             if (a.tr_pos) a.tr_pos[so * 3 + k] = xn;
-            if (a.tr_pos_cond) a.tr_pos_cond[so * 3 + k] = pp;
+            if (a.tr_pos_cond && !cfg.on) a.tr_pos_cond[so * 3 + k] = pp;
         }
         // ---- atom types
         float lg[MAXC];
         float mx = -INFINITY;
-        for (int c = 0; c < C; ++c) { lg[c] = a.pred_v[(size_t)i * C + c]; mx = fmaxf(mx, lg[c]); }
+        for (int c = 0; c < C; ++c) {
+            lg[c] = a.pred_v[(size_t)i * C + c];
+            if (cfg.on) {
+                const float lu = cfg.v_u[(size_t)i * C + c];
+                if (a.tr_v_cond) a.tr_v_cond[so * C + c] = lg[c];
+                if (a.tr_v_uncond) a.tr_v_uncond[so * C + c] = lu;
+                lg[c] = cfg_apply(cfg, cfg_combine(cfg, lg[c], lu), cfg.stat[1], -1);
+            }
+            mx = fmaxf(mx, lg[c]);
+        }
         float se = 0.f;
         for (int c = 0; c < C; ++c) se += expf(lg[c] - mx);
         const float lse = mx + logf(se);
@@ -755,7 +774,7 @@ __global__ void ddpm_step_kernel(DdpmArgs aa) {
         float umx = -INFINITY;
         for (int c = 0; c < C; ++c) {
             const float lv0 = lg[c] - lse;
-            if (a.tr_v_cond) a.tr_v_cond[so * C + c] = lg[c];
+            if (a.tr_v_cond && !cfg.on) a.tr_v_cond[so * C + c] = lg[c];
             if (a.tr_v0) a.tr_v0[so * C + c] = lv0;
             const float A1 = lv0 + la_prev;
             const float m1 = fmaxf(A1, l1_prev);
@@ -786,7 +805,7 @@ __global__ void ddpm_step_kernel(DdpmArgs aa) {
 
 // Same step with 16 lanes per atom (one class per lane, C <= 16): the per-class transcendental chains
 // run in parallel and the reductions are DPP row operations.
-__global__ void __launch_bounds__(256) ddpm_step16_kernel(DdpmArgs aa) {
+__global__ void __launch_bounds__(256) ddpm_step16_kernel(DdpmArgs aa, CfgArgs cfg) {
     struct : DdpmArgs, ChainParams {} a;
     static_cast<DdpmArgs &>(a) = aa;
     static_cast<ChainParams &>(a) = *aa.cp;
@@ -859,17 +878,29 @@ __global__ void __launch_bounds__(256) ddpm_step16_kernel(DdpmArgs aa) {
     }
     // ---- positions (lanes 0..2)
     if (c < 3) {
-        const float pp = a.vf.enable ? pp_fold : a.pred_pos[i * 3 + c];
+        float pp = a.vf.enable ? pp_fold : a.pred_pos[i * 3 + c];
+        if (cfg.on) {      // combine, threshold, clamp; the trajectories keep the raw predictions
+            const float pu = cfg.pos_u[i * 3 + c];
+            if (atom_ok && a.tr_pos_cond) a.tr_pos_cond[so * 3 + c] = pp;
+            if (atom_ok && a.tr_pos_uncond) a.tr_pos_uncond[so * 3 + c] = pu;
+            pp = cfg_apply(cfg, cfg_combine(cfg, pp, pu), cfg.stat[0], c);
+        }
         const float sig = t != 0 ? expf(0.5f * a.logvar[t]) : 0.f;
         const float xn = (a.c0[t] * pp + a.ct[t] * a.x_t[i * 3 + c]) + sig * eps;
         if (atom_ok) {
             a.x_next[i * 3 + c] = xn;
             if (a.tr_pos) a.tr_pos[so * 3 + c] = xn;
-            if (a.tr_pos_cond) a.tr_pos_cond[so * 3 + c] = pp;
+            if (a.tr_pos_cond && !cfg.on) a.tr_pos_cond[so * 3 + c] = pp;
         }
     }
     // ---- atom types (one class per lane)
-    const float lg = cls ? a.pred_v[(size_t)i * C + c] : -INFINITY;
+    float lg = cls ? a.pred_v[(size_t)i * C + c] : -INFINITY;
+    if (cfg.on && cls) {
+        const float lu = cfg.v_u[(size_t)i * C + c];
+        if (atom_ok && a.tr_v_cond) a.tr_v_cond[so * C + c] = lg;
+        if (atom_ok && a.tr_v_uncond) a.tr_v_uncond[so * C + c] = lu;
+        lg = cfg_apply(cfg, cfg_combine(cfg, lg, lu), cfg.stat[1], -1);
+    }
     const float mx = seg_max<16>(lg);
     const float se = seg_sum<16>(cls ? expf(lg - mx) : 0.f);
     const float lv0 = lg - (mx + logf(se));
@@ -894,7 +925,7 @@ __global__ void __launch_bounds__(256) ddpm_step16_kernel(DdpmArgs aa) {
     const float cand = (sc == best) ? (float)c : 99.f;
     const float win = -seg_max<16>(-cand);
     if (atom_ok && cls) {
-        if (a.tr_v_cond) a.tr_v_cond[so * C + c] = lg;
+        if (a.tr_v_cond && !cfg.on) a.tr_v_cond[so * C + c] = lg;
         if (a.tr_v0) a.tr_v0[so * C + c] = lv0;
         if (a.tr_vt) a.tr_vt[so * C + c] = lp;
     }

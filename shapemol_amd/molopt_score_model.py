@@ -403,6 +403,13 @@ class ScorePosNet3D(nn.Module):
         device kernels inside the step, and takes precedence over ``use_pointcloud_data`` as there; the mesh is anything with
         ``.vertices`` (V,3) and ``.faces`` (F,3) (a ``trimesh.Trimesh``) or a ``(vertices, faces)`` pair, the KD-tree is not
         used.  Too few atoms inside the mesh raise ``ValueError`` (``_lib.MeshGuidanceError``), as the reference's KD-tree does.
+        ``guide_stren > 0`` on a model trained with ``cond_mask_prob > 0`` is the reference's classifier-free guidance
+        (``:616-642``): every step also evaluates the score on a zeroed shape, combines ``(1 + w) * cond - w * uncond`` and
+        applies ``threshold_CFG(threshold_type, threshold_args)`` with batch-wide statistics, all as device kernels inside the
+        step; ``pos_uncond_traj`` / ``v_uncond_traj`` then hold the unconditional predictions.  ``bounds`` is the reference's
+        per-batch box: a (B,3,2) tensor or array of which only ``bounds[0]`` clamps every atom, as there, or a single (3,2) box;
+        ``bounds=None`` means no clamp (an extension: the reference's ``bounds[0]`` raises there).  Mesh or point-cloud guidance,
+        when given, take precedence and the chain is not CFG-guided, as in the reference's ``if / elif``.
         Private to shapemol_amd.sampling: ``_slot`` picks one of the model's library contexts (own workspace and captured
         graphs), ``_async=True`` returns a handle right after the chain has been enqueued; its ``.result()`` waits and
         builds the dict (chains on different slots then run side by side, and a finished chain's trajectories are
@@ -412,8 +419,25 @@ class ScorePosNet3D(nn.Module):
             raise NotImplementedError("gradient shape guidance is outside the accelerated path (commented out in the reference)")
         if self.cond_mask_prob == 0:
             assert guide_stren == 0
-        if guide_stren:
-            raise NotImplementedError("classifier-free guidance is unreachable in the reference (SURVEY.md F10)")
+        # classifier-free guidance: the reference's branch order (:561-642) -- mesh, point cloud, then CFG
+        cfg = use_mesh_data is None and use_pointcloud_data is None and (self.cond_mask_prob or 0) > 0 and guide_stren > 0.0
+        cfg_p, cfg_box = 0.0, None
+        if cfg:
+            if threshold_type not in _lib.CFG_THRESHOLDS:
+                raise ValueError("undefined thresholding strategy: expect one of (reference_threshold, dynamic_threshold, rescale, none) "
+                                 + "but get %s" % (threshold_type))
+            if threshold_type is not None:
+                cfg_p = float((threshold_args or {}).get("p", _lib.CFG_DEFAULT_P[threshold_type]))
+            if threshold_type == "dynamic_threshold" and not 0.0 <= cfg_p <= 1.0:
+                raise RuntimeError(f"quantile() q must be in the range [0, 1] but got {cfg_p}")     # torch.quantile's check
+            if bounds is not None:
+                bx = bounds.detach().cpu().numpy() if isinstance(bounds, torch.Tensor) else np.asarray(bounds)
+                bx = np.asarray(bx, dtype=np.float64)
+                if bx.ndim == 3:
+                    bx = bx[0]               # the box of molecule 0 clamps every atom, as the reference's bounds[0]
+                if bx.shape != (3, 2):
+                    raise ValueError("bounds must be a (B, 3, 2) or (3, 2) box")
+                cfg_box = np.ascontiguousarray(bx)
         if center_pos_mode not in (None, "none", "center"):
             raise NotImplementedError(center_pos_mode)       # as center_pos() of the reference (:52-60)
         if num_steps is None:
@@ -480,6 +504,9 @@ class ScorePosNet3D(nn.Module):
                                   ("v_cond_traj", (num_steps, n, cc), torch.float32)):
                 bufs[name] = torch.empty(shp, dtype=dt, device=dev)
                 setattr(tr, name, bufs[name].data_ptr())
+            if cfg:
+                bufs["pos_uncond_traj"] = torch.empty((num_steps, n, 3), dtype=torch.float32, device=dev)
+                bufs["v_uncond_traj"] = torch.empty((num_steps, n, cc), dtype=torch.float32, device=dev)
         out_pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
         out_v = torch.empty((n,), dtype=torch.int64, device=dev)
         pending = _PendingChain(self, ctx, dev, guided, bufs, out_pos, out_v, return_traj, _reuse_host_buffers,
@@ -492,6 +519,11 @@ class ScorePosNet3D(nn.Module):
                 side.wait_stream(cur)
                 if first_step:
                     _lib.check(lib.shapemol_set_option(ctx, b"first_step", int(first_step)), "shapemol_set_option")
+                if cfg:
+                    _lib.check(lib.shapemol_set_cfg(ctx, float(guide_stren), _lib.CFG_THRESHOLDS[threshold_type], cfg_p,
+                                                    None if cfg_box is None else cfg_box.ctypes.data_as(C.c_void_p),
+                                                    _ptr(bufs.get("pos_uncond_traj")), _ptr(bufs.get("v_uncond_traj"))),
+                               "shapemol_set_cfg")
                 try:
                     rc = lib.shapemol_sample(ctx, _ptr(pos), _ptr(v), _ptr(batch), n, b, _ptr(shape), int(num_steps),
                                              _ptr(eps), _ptr(u), C.c_uint64(seed), C.byref(tr), _ptr(out_pos), _ptr(out_v),
@@ -499,6 +531,8 @@ class ScorePosNet3D(nn.Module):
                 finally:
                     if first_step:
                         lib.shapemol_set_option(ctx, b"first_step", 0)
+                    if cfg:      # read when the chain is enqueued: the context goes back to unguided chains at once
+                        lib.shapemol_set_cfg(ctx, 0.0, 0, 0.0, None, None, None)
                 pending.side, pending.cur = side, cur
             _lib.check(rc, "shapemol_sample")
         except BaseException:
@@ -594,6 +628,9 @@ class _PendingChain:
             if "pos_traj" in bufs:
                 bufs["pos_traj"] += self.offset.unsqueeze(0)
         res = {"pos": self.out_pos, "v": self.out_v, "pos_uncond_traj": [], "v_uncond_traj": []}
+        if self.return_traj and "pos_uncond_traj" in bufs and self.reuse != "device":
+            # (device tensors, as the reference appends the predictions without .cpu())
+            res.update(pos_uncond_traj=list(bufs["pos_uncond_traj"].unbind(0)), v_uncond_traj=list(bufs["v_uncond_traj"].unbind(0)))
         if self.return_traj and self.reuse == "device":
             # private to shapemol_amd.sampling: hand out the (S, N, ...) device buffers; the driver reorders them on the
             # device and copies each to the host once
@@ -608,7 +645,8 @@ class _PendingChain:
                        pos_cond_traj=list(bufs["pos_cond_traj"].unbind(0)), v_cond_traj=list(bufs["v_cond_traj"].unbind(0)))
             # not a key of the reference: the same trajectories as whole (S, N, ...) tensors, for callers that unbatch
             # them at once (shapemol_amd.sampling) instead of re-stacking the per-step lists
-            res["_stacked"] = dict(host, pos_cond_traj=bufs["pos_cond_traj"], v_cond_traj=bufs["v_cond_traj"])
+            res["_stacked"] = dict(host, pos_cond_traj=bufs["pos_cond_traj"], v_cond_traj=bufs["v_cond_traj"],
+                                   **{k: bufs[k] for k in ("pos_uncond_traj", "v_uncond_traj") if k in bufs})
         else:
             res.update(pos_traj=[], v_traj=[], v0_traj=[], vt_traj=[], pos_cond_traj=[], v_cond_traj=[])
         return res

@@ -111,7 +111,11 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
     shape_emb        (32, 3) latent of the condition (``data.shape_emb``); repeated per molecule of a batch.
     sample_num_atoms 'size' -> ``sample_func(n)`` gives the atom counts; 'ref' -> ``ref_num_atoms`` for every copy.
     ref_atom_feature (ref_num_atoms,) int64, needed for ``pos_only`` (atom types are then kept, ``:84-86``).
-    bounds           accepted and ignored, like every caller of the reference's ``sample_diffusion`` with guidance off.
+    guide_stren, threshold_type, threshold_args, bounds   classifier-free guidance (``config.sample.guide_stren`` /
+                     ``threshold_CFG``) of a model trained with ``cond_mask_prob > 0``: with ``guide_stren > 0`` every step runs the
+                     score with and without the shape and thresholds the combination on the device.  ``bounds`` is then used as the
+                     reference's per-batch ``batch.bound``: a (B,3,2) box of which ``bounds[0]`` clamps every atom, or one (3,2) box;
+                     None means no clamp.  Ignored while ``guide_stren`` is 0, as in the reference.
     seed             seed of the device noise of the chains (None: drawn from torch's CPU generator per batch).
     host_rng         True: every random number comes from torch's CPU generator (and numpy's, for the atom counts) in the
                      order the reference driver consumes them when it runs on the CPU -- ``np.random.choice`` (``:34``),
