@@ -117,6 +117,23 @@ int shapemol_set_guidance(shapemol_ctx *ctx, const double *h_cloud, int64_t n_po
  * cloud of shapemol_set_guidance; d_draws DEVICE (5,N) float64 or NULL (Philox(seed)). */
 int shapemol_guide_points(shapemol_ctx *ctx, float *d_pos, int64_t n_points, const double *d_draws, uint64_t seed, void *stream);
 
+/* Point-cloud shape guidance with one cloud per GROUP of molecules, for the following _sample calls.  Group g is the contiguous
+ * run of molecules h_mol_off[g] .. h_mol_off[g + 1] - 1 of the batch (so a contiguous run of atoms); its cloud is rows
+ * h_cloud_off[g] .. h_cloud_off[g + 1] - 1 of h_clouds (HOST (sum P_g, 3) float64, copied) and its radius h_radius[g].  A group
+ * with an empty cloud is left unguided.  Per atom the arithmetic is shapemol_set_guidance's; d_draws is the same DEVICE
+ * (S,5,N) float64 table indexed by the batch-global atom, or NULL: Philox(seed of the chain) keyed by the batch-global atom.
+ * Validated on the host (offsets start at 0 and do not decrease, every non-empty cloud has 3 .. 2048 points and a radius > 0);
+ * the error names the offending group.  shapemol_sample then requires n_mols == h_mol_off[n_groups].  n_groups = 0 removes the
+ * groups.  Installing groups removes a single cloud and shapemol_set_guidance removes the groups; a mesh, when set, takes
+ * precedence over both. */
+int shapemol_set_guidance_groups(shapemol_ctx *ctx, int32_t n_groups, const int64_t *h_mol_off, const double *h_clouds,
+                                 const int64_t *h_cloud_off, const double *h_radius, int32_t grad_step, const double *d_draws);
+
+/* One guidance pass on its own against the groups of shapemol_set_guidance_groups: guide d_pos (n_atoms,3) f32 DEVICE in place;
+ * d_batch DEVICE (n_atoms) int64, sorted, gives every atom's molecule; d_draws DEVICE (5,n_atoms) float64 or NULL (Philox(seed)). */
+int shapemol_guide_points_groups(shapemol_ctx *ctx, float *d_pos, const int64_t *d_batch, int64_t n_atoms, const double *d_draws,
+                                 uint64_t seed, void *stream);
+
 /* The same as the reference's MODULE-level function pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=3,
  * ratio=0.2) (models/molopt_score_model.py:699-740), which has no model object at hand: no context, the cloud comes with
  * the call (h_cloud: HOST (n_cloud,3) float64, 3 .. 2048 points) on the CURRENT device; d_pos (n_atoms,3) f32 DEVICE is

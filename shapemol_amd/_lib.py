@@ -18,6 +18,7 @@ EXPORTS = (
     "shapemol_destroy", "shapemol_reserve", "shapemol_score", "shapemol_sample",
     "shapemol_log_sample_categorical", "shapemol_set_option", "shapemol_debug_read",
     "shapemol_profile_begin", "shapemol_profile_end", "shapemol_status", "shapemol_status_stream", "shapemol_set_guidance", "shapemol_guide_points",
+    "shapemol_set_guidance_groups", "shapemol_guide_points_groups",
     "shapemol_pointcloud_guidance", "shapemol_set_mesh_guidance", "shapemol_guide_points_mesh", "shapemol_mesh_guidance",
     "shapemol_set_cfg", "shapemol_set_knn_pins", "shapemol_debug_split_exact",
     "shapemol_mlp_backward_workspace", "shapemol_mlp_forward", "shapemol_mlp_backward",
@@ -103,6 +104,8 @@ def load():
     lib.shapemol_set_bn_running.argtypes = [vp, vp, vp, i64]
     lib.shapemol_set_guidance.argtypes = [vp, vp, i64, C.c_double, i32, vp]
     lib.shapemol_guide_points.argtypes = [vp, vp, i64, vp, u64, vp]
+    lib.shapemol_set_guidance_groups.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp]
+    lib.shapemol_guide_points_groups.argtypes = [vp, vp, vp, i64, vp, u64, vp]
     lib.shapemol_set_knn_pins.argtypes = [vp, vp, i32, vp, vp, i64, i32]
     lib.shapemol_debug_split_exact.argtypes = [C.c_float, vp]
     lib.shapemol_debug_split_exact.restype = None

@@ -12,6 +12,7 @@
 #include "sm_edge_stream.h"
 #include "sm_misc.h"
 #include "sm_mesh.h"
+#include "sm_guide_groups.h"
 #include "sm_cfg.h"
 #include <hip/hip_ext.h>
 
@@ -573,6 +574,10 @@ struct shapemol_ctx {
     int num_cu = 256;
     // point-cloud shape guidance (shapemol_set_guidance)
     double *g_cloud = nullptr; int64_t g_points = 0; double g_radius = 0.0; int g_grad_step = 0; const double *g_draws = nullptr;
+    // point-cloud shape guidance per group of molecules (shapemol_set_guidance_groups); replaces the single cloud and vice versa.
+    // One device block: [clouds | radii | mol_off, cloud_off, atom_off, wg_off (G + 1 ints each)]; the workgroup table is sized by the chain
+    double *gg_clouds = nullptr, *gg_radius = nullptr; int *gg_ints = nullptr; int2 *gg_table = nullptr; int64_t gg_table_cap = 0;
+    int gg_groups = 0, gg_max_points = 0, gg_grad_step = 0; int64_t gg_mols = 0, gg_points = 0; const double *gg_draws = nullptr;
     // mesh shape guidance (shapemol_set_mesh_guidance); takes precedence over the point cloud when both are set
     MeshFace *m_faces = nullptr; double4 *m_fbox = nullptr; double *m_cloud = nullptr;     // one device block
     int64_t m_nfaces = 0, m_points = 0; int m_grad_step = 0; const double *m_draws = nullptr; double m_bounds[5] = {};
@@ -599,7 +604,7 @@ struct shapemol_ctx {
     // what a captured step depends on besides the options (which drop the graphs when set): sizes, guidance, and the two
     // launch decisions taken from the max_mol_atoms hint (folded coordinate update, fused graph kernel)
     // (classifier-free guidance: its type and scalars are kernel arguments of the captured step)
-    struct GraphKey { int64_t N = 0, B = 0; int guided = 0 /* 0 none, 1 point cloud, 2 mesh */, fold = 0, gfuse = 0;
+    struct GraphKey { int64_t N = 0, B = 0; int guided = 0 /* 0 none, 1 point cloud, 2 mesh, 3 clouds per group */, fold = 0, gfuse = 0;
                       int cfg = 0 /* 0 off, else 1 + CfgType */; double cfgv[9] = {};   // w, p, has_bounds, box
                       bool operator==(const GraphKey &o) const {
                           if (!(N == o.N && B == o.B && guided == o.guided && fold == o.fold && gfuse == o.gfuse && cfg == o.cfg)) return false;
@@ -1004,7 +1009,7 @@ template <int H>
 int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape);
 
 // classifier-free guidance applies to this chain (the reference's if / elif: mesh or point-cloud guidance come first)
-bool cfg_on(const shapemol_ctx *c) { return c->cfg_w != 0.0 && c->m_nfaces == 0 && c->g_points == 0; }
+bool cfg_on(const shapemol_ctx *c) { return c->cfg_w != 0.0 && c->m_nfaces == 0 && c->g_points == 0 && c->gg_points == 0; }
 
 // exchange the conditional and the unconditional sets of prepared shape data and score outputs
 void swap_uncond(shapemol_ctx *c) {
@@ -1236,7 +1241,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                     pending = VnFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, x_next,
                                      c->mol_span, c->status + ST_SPAN, 1};
                     vn_done = true;
-                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->m_nfaces == 0 && !cfg_on(c) && C <= 16 && hd <= 16) {
+                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->gg_points == 0 && c->m_nfaces == 0 && !cfg_on(c) && C <= 16 && hd <= 16) {
                     // ... or, for the last layer of a chain step, the DDPM kernel
                     ea.xsum = c->xsum;
                     c->ddpm_vf = DdpmFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, out_pos, hd, 1};
@@ -1262,7 +1267,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                     pending = VnFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, x_next,
                                      c->mol_span, c->status + ST_SPAN, 1};
                     vn_done = true;
-                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->m_nfaces == 0 && !cfg_on(c) && C <= 16 && hd <= 16) {
+                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->gg_points == 0 && c->m_nfaces == 0 && !cfg_on(c) && C <= 16 && hd <= 16) {
                     sa.xsum = c->xsum;
                     c->ddpm_vf = DdpmFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, out_pos, hd, 1};
                     vn_done = true;
@@ -1440,6 +1445,8 @@ void shapemol_destroy(shapemol_ctx *c) {
     hipFree(c->etab);
     hipFree(c->d_img);
     if (c->g_cloud) hipFree(c->g_cloud);
+    if (c->gg_clouds) hipFree(c->gg_clouds);
+    if (c->gg_table) hipFree(c->gg_table);
     if (c->m_faces) hipFree(c->m_faces);
     if (c->m_within) hipFree(c->m_within);
     if (c->bn_run) hipFree(c->bn_run);
@@ -1462,6 +1469,35 @@ int shapemol_set_bn_running(shapemol_ctx *c, const float *h_mean, const float *h
     }
     HIPCHK(hipMemcpy(c->bn_run, h_mean, count * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->bn_run + count, h_var, count * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ---- point-cloud guidance per group of molecules: host side
+// workgroups of pc_guidance_groups_kernel: the sum over the groups of ceil(n_g / 16) is at most floor(N / 16) + G
+static unsigned groups_grid(const shapemol_ctx *c, int64_t N) { return (unsigned)(N / 16 + c->gg_groups); }
+
+static PcGroupsArgs groups_args(const shapemol_ctx *c, float *d_pos, int64_t N, const int *step_cur, int t_first) {
+    const int G1 = c->gg_groups + 1;
+    PcGroupsArgs a{};
+    a.pred_pos = d_pos; a.clouds = c->gg_clouds; a.cloud_off = c->gg_ints + G1; a.radius = c->gg_radius; a.atom_off = c->gg_ints + 2 * G1;
+    a.wg_table = c->gg_table; a.cp = c->chain_params; a.step_cur = step_cur;
+    a.n_atoms = (int)N; a.t_first = t_first; a.grad_step = c->gg_grad_step; a.ratio = 0.2;
+    return a;
+}
+
+// the per-workgroup table of this chain (atom ranges come from the batch vector on the device)
+static int groups_table(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N) {
+    const int64_t n_wg = groups_grid(c, N);
+    if (n_wg > c->gg_table_cap) {
+        c->drop_graphs();                        // a captured step holds the table's address
+        if (c->gg_table) { hipFree(c->gg_table); c->gg_table = nullptr; }
+        c->gg_table_cap = 0;
+        HIPCHK(hipMalloc((void **)&c->gg_table, (size_t)n_wg * sizeof(int2)));
+        c->gg_table_cap = n_wg;
+    }
+    const int G1 = c->gg_groups + 1;
+    LAUNCH("prep", SMK(pc_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, c->gg_ints, c->gg_ints + G1, c->gg_groups,
+                       c->gg_ints + 2 * G1, c->gg_ints + 3 * G1, c->gg_table, (int)n_wg));
     return 0;
 }
 
@@ -1570,6 +1606,10 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     const int t_first = c->cfg.num_timesteps - 1;
     const bool mesh = c->m_nfaces > 0;          // mesh guidance takes precedence over the point cloud (molopt_score_model.py:571)
     if (mesh && mesh_workspace(c, N)) return 1;
+    const bool groups = !mesh && c->gg_groups > 0;
+    if (c->gg_groups > 0 && c->gg_mols != B)
+        return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the guidance groups cover " + std::to_string(c->gg_mols) + " molecules");
+    if (groups && c->gg_points > 0 && groups_table(c, s, d_batch, N)) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
     if (mesh) HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
     if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
@@ -1584,7 +1624,7 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_init_v, (int)N, c->cfg.num_classes, c->status));
     {
         ChainParams cp{};
-        cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->m_draws : c->g_draws;
+        cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->m_draws : (groups ? c->gg_draws : c->g_draws);
         if (traj) { cp.tr_pos = traj->pos_traj; cp.tr_v = traj->v_traj; cp.tr_v0 = traj->v0_traj; cp.tr_vt = traj->vt_traj;
                     cp.tr_pos_cond = traj->pos_cond_traj; cp.tr_v_cond = traj->v_cond_traj; }
         if (cfg) { cp.tr_pos_uncond = c->cfg_tr_pos_u; cp.tr_v_uncond = c->cfg_tr_v_u; }
@@ -1610,12 +1650,15 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
         } else if (c->g_points > 0) {     // point-cloud shape guidance of the predicted x0 (steps with t > grad_step)
             PcGuideArgs ga{c->pred_pos, c->g_cloud, c->chain_params, c->steps + 1, (int)N, (int)c->g_points, t_first, c->g_grad_step, c->g_radius, 0.2};
             LAUNCH("pc_guidance", SMK(pc_guidance_kernel, dim3((N * 16 + 255) / 256), dim3(256), (size_t)c->g_points * 24, s, ga));
+        } else if (groups && c->gg_points > 0) {     // the same per group of molecules, each group towards its own cloud
+            const PcGroupsArgs ga = groups_args(c, c->pred_pos, N, c->steps + 1, t_first);
+            LAUNCH("pc_guidance_groups", SMK(pc_guidance_groups_kernel, dim3(groups_grid(c, N)), dim3(256), (size_t)c->gg_max_points * 24, s, ga));
         }
         return DISPATCH_H(c, run_ddpm<128>(c, s, N), run_ddpm<32>(c, s, N));
     };
     if (use_graph && !c->prof_on) {
         shapemol_ctx::GraphKey key{};
-        key.N = N; key.B = B; key.guided = mesh ? 2 : (c->g_points > 0 ? 1 : 0); key.fold = vn_fold_ok(c, (int)N);
+        key.N = N; key.B = B; key.guided = mesh ? 2 : (groups && c->gg_points > 0 ? 3 : (c->g_points > 0 ? 1 : 0)); key.fold = vn_fold_ok(c, (int)N);
         key.gfuse = c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && c->n_pins == 0;
         if (cfg) {
             key.cfg = 1 + c->cfg_type;
@@ -1771,6 +1814,12 @@ int shapemol_set_knn_pins(shapemol_ctx *c, const int32_t *h_off, int32_t n_steps
     return 0;
 }
 
+static void groups_clear(shapemol_ctx *c) {
+    if (c->gg_clouds) { hipFree(c->gg_clouds); c->gg_clouds = nullptr; }
+    c->gg_radius = nullptr; c->gg_ints = nullptr;
+    c->gg_groups = 0; c->gg_max_points = 0; c->gg_mols = 0; c->gg_points = 0; c->gg_draws = nullptr;
+}
+
 int shapemol_set_guidance(shapemol_ctx *c, const double *h_cloud, int64_t n_points, double radius, int32_t grad_step, const double *d_draws) {
     if (!c) return fail("shapemol_set_guidance: null ctx");
     if (n_points < 0 || n_points > 2048 || (n_points > 0 && n_points < 3)) return fail("shapemol_set_guidance: the cloud needs 3 .. 2048 points (it is staged in LDS)");
@@ -1780,9 +1829,71 @@ int shapemol_set_guidance(shapemol_ctx *c, const double *h_cloud, int64_t n_poin
     if (c->g_cloud) { hipFree(c->g_cloud); c->g_cloud = nullptr; }
     c->g_points = 0; c->g_draws = nullptr;
     if (n_points == 0) return 0;
+    groups_clear(c);                             // a single cloud replaces clouds per group
     HIPCHK(hipMalloc((void **)&c->g_cloud, (size_t)n_points * 3 * sizeof(double)));
     HIPCHK(hipMemcpy(c->g_cloud, h_cloud, (size_t)n_points * 3 * sizeof(double), hipMemcpyHostToDevice));
     c->g_points = n_points; c->g_radius = radius; c->g_grad_step = grad_step; c->g_draws = d_draws;
+    return 0;
+}
+
+int shapemol_set_guidance_groups(shapemol_ctx *c, int32_t n_groups, const int64_t *h_mol_off, const double *h_clouds, const int64_t *h_cloud_off,
+                                 const double *h_radius, int32_t grad_step, const double *d_draws) {
+    const std::string me = "shapemol_set_guidance_groups: ";
+    if (!c) return fail(me + "null ctx");
+    if (n_groups < 0 || n_groups > (1 << 20)) return fail(me + "n_groups out of range");
+    if (n_groups > 0) {
+        if (!h_mol_off || !h_cloud_off || !h_radius) return fail(me + "offsets / radii missing");
+        if (h_mol_off[0] != 0 || h_cloud_off[0] != 0) return fail(me + "group 0: the molecule and cloud offsets must start at 0");
+        for (int g = 0; g < n_groups; ++g) {
+            const std::string grp = me + "group " + std::to_string(g) + ": ";
+            if (h_mol_off[g + 1] < h_mol_off[g]) return fail(grp + "the molecule offsets decrease");
+            if (h_cloud_off[g + 1] < h_cloud_off[g]) return fail(grp + "the cloud offsets decrease");
+            const int64_t p = h_cloud_off[g + 1] - h_cloud_off[g];
+            if (p > 0 && (p < 3 || p > 2048)) return fail(grp + "the cloud needs 3 .. 2048 points (it is staged in LDS), or none");
+            if (p > 0 && !(h_radius[g] > 0.0)) return fail(grp + "the radius must be > 0");
+        }
+        if (h_mol_off[n_groups] > (1 << 27)) return fail(me + "too many molecules");
+        if (h_cloud_off[n_groups] > 0 && !h_clouds) return fail(me + "clouds missing");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    c->drop_graphs();                            // also drains the device: the old clouds may still be in use
+    groups_clear(c);
+    if (n_groups == 0) return 0;
+    if (c->g_cloud) { hipFree(c->g_cloud); c->g_cloud = nullptr; }      // clouds per group replace a single cloud
+    c->g_points = 0; c->g_draws = nullptr;
+    const int G1 = n_groups + 1;
+    const int64_t P = h_cloud_off[n_groups];
+    std::vector<double> hd((size_t)P * 3 + n_groups);
+    if (P) std::copy(h_clouds, h_clouds + P * 3, hd.begin());
+    std::copy(h_radius, h_radius + n_groups, hd.begin() + P * 3);
+    std::vector<int> hi((size_t)4 * G1, 0);       // mol_off | cloud_off | atom_off | wg_off (the last two are written on the device)
+    int max_points = 0;
+    for (int g = 0; g < G1; ++g) { hi[g] = (int)h_mol_off[g]; hi[G1 + g] = (int)h_cloud_off[g]; }
+    for (int g = 0; g < n_groups; ++g) max_points = std::max(max_points, hi[G1 + g + 1] - hi[G1 + g]);
+    const size_t bytes_d = hd.size() * sizeof(double), bytes_i = hi.size() * sizeof(int);
+    HIPCHK(hipMalloc((void **)&c->gg_clouds, bytes_d + bytes_i));
+    HIPCHK(hipMemcpy(c->gg_clouds, hd.data(), bytes_d, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((char *)c->gg_clouds + bytes_d, hi.data(), bytes_i, hipMemcpyHostToDevice));
+    c->gg_radius = c->gg_clouds + P * 3; c->gg_ints = (int *)((char *)c->gg_clouds + bytes_d);
+    c->gg_groups = n_groups; c->gg_max_points = max_points; c->gg_mols = h_mol_off[n_groups]; c->gg_points = P;
+    c->gg_grad_step = grad_step; c->gg_draws = d_draws;
+    return 0;
+}
+
+int shapemol_guide_points_groups(shapemol_ctx *c, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws, uint64_t seed,
+                                 void *stream) {
+    if (!c || !d_pos || !d_batch || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_groups: bad argument");
+    if (c->gg_groups <= 0) return fail("shapemol_guide_points_groups: no groups set (shapemol_set_guidance_groups)");
+    HIPCHK(hipSetDevice(c->device));
+    if (ensure_workspace(c, N, 1)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->gg_points == 0) return 0;             // no group has a cloud: nothing moves
+    if (groups_table(c, s, d_batch, N)) return 1;
+    ChainParams cp{};
+    cp.seed = seed; cp.guide_draws = d_draws; cp.step_base = 0;
+    LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, cp, c->steps));
+    const PcGroupsArgs ga = groups_args(c, d_pos, N, nullptr, c->gg_grad_step + 1);
+    LAUNCH("pc_guidance_groups", SMK(pc_guidance_groups_kernel, dim3(groups_grid(c, N)), dim3(256), (size_t)c->gg_max_points * 24, s, ga));
     return 0;
 }
 

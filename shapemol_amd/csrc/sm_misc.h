@@ -1028,34 +1028,28 @@ SM_DEV Top3 pc_query(const double *cloud, int n_points, const double (&p)[3], in
     return t;
 }
 
-__global__ void __launch_bounds__(256) pc_guidance_kernel(PcGuideArgs a) {
-    extern __shared__ double pc_cloud[];                            // [P][3]
-    const int step = a.step_cur ? *a.step_cur : 0;
-    if (a.t_first - step <= a.grad_step) return;                   // `if i > grad_step` (molopt_score_model.py:585)
-    for (int i = threadIdx.x; i < a.n_points * 3; i += blockDim.x) pc_cloud[i] = a.cloud[i];
-    __syncthreads();
-    const double *cloud = pc_cloud;
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int atom_raw = gid >> 4, l16 = gid & 15;
-    const int atom = atom_raw < a.n_atoms ? atom_raw : a.n_atoms - 1;
-    double p[3] = {(double)a.pred_pos[atom * 3], (double)a.pred_pos[atom * 3 + 1], (double)a.pred_pos[atom * 3 + 2]};
-    Top3 t = pc_query(cloud, a.n_points, p, l16);
-    bool far = (sqrt(t.d[0]) + sqrt(t.d[1]) + sqrt(t.d[2])) / 3.0 > a.radius;
+// One atom's guidance on its 16 lanes (all 16 must call it: the queries shuffle).  `cloud` is the LDS copy of the cloud the atom is
+// pulled towards; `atom` is the batch-global index that keys the draws (fed table [S][5][n_atoms] or Philox (atom, step, 100 + j));
+// `valid` is false for the padding lanes past the last atom, which compute on a clamped atom and write nothing.
+SM_DEV void pc_guide_atom(float *pred_pos, const double *cloud, int n_points, double radius, double ratio, const ChainParams &cp,
+                          int step, int n_atoms, int atom, bool valid, int l16) {
+    double p[3] = {(double)pred_pos[atom * 3], (double)pred_pos[atom * 3 + 1], (double)pred_pos[atom * 3 + 2]};
+    Top3 t = pc_query(cloud, n_points, p, l16);
+    bool far = (sqrt(t.d[0]) + sqrt(t.d[1]) + sqrt(t.d[2])) / 3.0 > radius;
     bool changed = false;
-    const ChainParams cp = *a.cp;
     for (int j = 0; j < 5; ++j) {
         if (!__any(far)) break;
         if (far) {
             double u;
             if (cp.guide_draws) {
-                u = cp.guide_draws[((size_t)(step - cp.step_base) * 5 + j) * a.n_atoms + atom];
+                u = cp.guide_draws[((size_t)(step - cp.step_base) * 5 + j) * n_atoms + atom];
             } else {
                 Philox ph{(uint32_t)cp.seed, (uint32_t)(cp.seed >> 32)};
                 uint32_t r[4];
                 ph((uint32_t)atom, (uint32_t)step, (uint32_t)(100 + j), 0x9c1du, r);
                 u = ((double)(r[0] >> 5) * 67108864.0 + (double)(r[1] >> 6)) * (1.0 / 9007199254740992.0);
             }
-            const double scalar = u * (0.8 - a.ratio) + a.ratio;   // np.random.random() * (0.8 - ratio) + ratio
+            const double scalar = u * (0.8 - ratio) + ratio;   // np.random.random() * (0.8 - ratio) + ratio
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const double nearest = (cloud[t.i[0] * 3 + k] + cloud[t.i[1] * 3 + k] + cloud[t.i[2] * 3 + k]) / 3.0;
@@ -1064,8 +1058,20 @@ __global__ void __launch_bounds__(256) pc_guidance_kernel(PcGuideArgs a) {
             changed = true;
         }
         // the query is wave-uniform control flow (shuffles): lanes of atoms that are done run it on their final point
-        t = pc_query(cloud, a.n_points, p, l16);
-        if (far && (sqrt(t.d[0]) + sqrt(t.d[1]) + sqrt(t.d[2])) / 3.0 < a.radius) far = false;
+        t = pc_query(cloud, n_points, p, l16);
+        if (far && (sqrt(t.d[0]) + sqrt(t.d[1]) + sqrt(t.d[2])) / 3.0 < radius) far = false;
     }
-    if (changed && atom_raw < a.n_atoms && l16 < 3) a.pred_pos[atom * 3 + l16] = (float)(l16 == 0 ? p[0] : (l16 == 1 ? p[1] : p[2]));
+    if (changed && valid && l16 < 3) pred_pos[atom * 3 + l16] = (float)(l16 == 0 ? p[0] : (l16 == 1 ? p[1] : p[2]));
+}
+
+__global__ void __launch_bounds__(256) pc_guidance_kernel(PcGuideArgs a) {
+    extern __shared__ double pc_cloud[];                            // [P][3]
+    const int step = a.step_cur ? *a.step_cur : 0;
+    if (a.t_first - step <= a.grad_step) return;                   // `if i > grad_step` (molopt_score_model.py:585)
+    for (int i = threadIdx.x; i < a.n_points * 3; i += blockDim.x) pc_cloud[i] = a.cloud[i];
+    __syncthreads();
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int atom_raw = gid >> 4, l16 = gid & 15;
+    const int atom = atom_raw < a.n_atoms ? atom_raw : a.n_atoms - 1;
+    pc_guide_atom(a.pred_pos, pc_cloud, a.n_points, a.radius, a.ratio, *a.cp, step, a.n_atoms, atom, atom_raw < a.n_atoms, l16);
 }

@@ -399,6 +399,11 @@ class ScorePosNet3D(nn.Module):
         ``use_pointcloud_data=(point_clouds, kdtree, radius)`` with ``grad_step`` is the reference's point-cloud shape
         guidance (``:583-586,699-740``) as a device kernel inside the step (the KD-tree is not used: brute-force float64
         3-nearest search); ``guide_draws`` (S,5,N) float64 feeds the recorded ``np.random.random`` draws (parity mode).
+        ``use_pointcloud_data`` may also be a LIST with one entry per group of molecules, in batch order:
+        ``[(point_clouds, kdtree, radius, n_mols), ...]`` -- the next ``n_mols`` molecules of the batch are guided towards that
+        cloud, or left unguided where ``point_clouds`` is None; the counts must sum to the number of molecules (``ValueError``
+        otherwise).  ``guide_draws`` and ``grad_step`` work as for one cloud (the draws stay indexed by the batch-global atom).  A
+        list together with ``use_mesh_data`` raises ``NotImplementedError``: mesh guidance takes one mesh per chain.
         ``use_mesh_data=(mesh, point_clouds, kdtree)`` is the reference's mesh shape guidance (``:571-580,742-775``), two
         device kernels inside the step, and takes precedence over ``use_pointcloud_data`` as there; the mesh is anything with
         ``.vertices`` (V,3) and ``.faces`` (F,3) (a ``trimesh.Trimesh``) or a ``(vertices, faces)`` pair, the KD-tree is not
@@ -417,6 +422,11 @@ class ScorePosNet3D(nn.Module):
         """
         if use_grad:
             raise NotImplementedError("gradient shape guidance is outside the accelerated path (commented out in the reference)")
+        groups = None
+        if isinstance(use_pointcloud_data, list):
+            if use_mesh_data is not None:
+                raise NotImplementedError("mesh guidance takes one mesh per chain")
+            groups = _guidance_groups(use_pointcloud_data, int(ligand_shape.shape[0]))
         if self.cond_mask_prob == 0:
             assert guide_stren == 0
         # classifier-free guidance: the reference's branch order (:561-642) -- mesh, point cloud, then CFG
@@ -465,7 +475,8 @@ class ScorePosNet3D(nn.Module):
             u = _check_device_tensor("noise[1]", noise[1], torch.float32)
             if tuple(eps.shape) != (num_steps, n, 3) or tuple(u.shape) != (num_steps, n, cc):
                 raise ValueError("noise must be (eps (S,N,3), u (S,N,C))")
-        guided = "mesh" if use_mesh_data is not None else ("cloud" if use_pointcloud_data is not None else None)
+        guided = "mesh" if use_mesh_data is not None else ("groups" if groups is not None else
+                                                           ("cloud" if use_pointcloud_data is not None else None))
         mesh = _mesh_arrays(use_mesh_data) if guided == "mesh" else None
         if seed is None:
             if noise is None:
@@ -491,6 +502,8 @@ class ScorePosNet3D(nn.Module):
                                                       faces.ctypes.data_as(C.c_void_p), faces.shape[0],
                                                       cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], int(grad_step), _ptr(gd)),
                        "shapemol_set_mesh_guidance")
+        elif guided == "groups":
+            _set_guidance_groups(lib, ctx, groups, int(grad_step), gd)
         elif guided:
             cloud = np.ascontiguousarray(np.asarray(use_pointcloud_data[0], dtype=np.float64).reshape(-1, 3))
             _lib.check(lib.shapemol_set_guidance(ctx, cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], float(use_pointcloud_data[2]),
@@ -544,6 +557,36 @@ class ScorePosNet3D(nn.Module):
         """Method form of the module-level :func:`pointcloud_shape_guidance` (kept for callers that hold a model)."""
         return pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=k, ratio=ratio, draws=draws, seed=seed)
 
+    def pointcloud_shape_guidance_groups(self, use_pointcloud_data, pred_ligand_pos, batch_ligand, *, draws=None, seed=None):
+        """One pass of :func:`pointcloud_shape_guidance` with one cloud per group of molecules: ``use_pointcloud_data`` is the list
+        ``[(point_clouds or None, kdtree, radius, n_mols), ...]`` that :meth:`sample_diffusion` takes, ``batch_ligand`` (N,) gives
+        every atom's molecule.  ``pred_ligand_pos`` (N,3) is updated in place and returned; ``draws`` (5,N) / ``seed`` as there."""
+        pos = _check_device_tensor("pred_ligand_pos", pred_ligand_pos, torch.float32)
+        if pos.data_ptr() != pred_ligand_pos.data_ptr() or pos.dim() != 2 or pos.shape[1] != 3:
+            raise ValueError("pred_ligand_pos must be a contiguous (N, 3) tensor (it is updated in place)")
+        batch = _check_device_tensor("batch_ligand", batch_ligand, torch.int64)
+        if not isinstance(use_pointcloud_data, list):
+            raise TypeError("use_pointcloud_data must be a list of (point_clouds, kdtree, radius, n_mols)")
+        groups = _guidance_groups(use_pointcloud_data, sum(int(e[3]) for e in use_pointcloud_data if len(e) == 4))
+        gd = None if draws is None else _check_device_tensor("draws", draws, torch.float64)
+        if batch.shape != (pos.shape[0],) or (gd is not None and tuple(gd.shape) != (5, pos.shape[0])):
+            raise ValueError("batch_ligand must be (N,) and draws (5, N) float64")
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64)) if gd is None else 0
+        if pos.shape[0] == 0:
+            return pred_ligand_pos
+        ctx, lib = self._context(pos.device), _lib.load()
+        _set_guidance_groups(lib, ctx, groups, 0, None)
+        try:
+            with torch.cuda.device(pos.device):
+                stream = torch.cuda.current_stream(pos.device)
+                _lib.check(lib.shapemol_guide_points_groups(ctx, _ptr(pos), _ptr(batch), pos.shape[0], _ptr(gd), C.c_uint64(seed),
+                                                            _stream_ptr(stream)), "shapemol_guide_points_groups")
+                stream.synchronize()
+        finally:
+            _lib.check(lib.shapemol_set_guidance_groups(ctx, 0, None, None, None, None, 0, None), "shapemol_set_guidance_groups")
+        return pred_ligand_pos
+
     def mesh_shape_guidance(self, use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws=None, seed=None):
         """Method form of the module-level :func:`mesh_shape_guidance`."""
         return mesh_shape_guidance(use_mesh_data, pred_ligand_pos, k=k, ratio=ratio, draws=draws, seed=seed)
@@ -585,7 +628,7 @@ class _PendingChain:
     result() waits for it, reads the status flags and builds the reference's result dict."""
 
     def __init__(self, model, ctx, dev, guided, bufs, out_pos, out_v, return_traj, reuse, keep, offset=None):
-        # guided: None, "cloud" or "mesh" (what _drop_guidance removes from the context)
+        # guided: None, "cloud", "groups" or "mesh" (what _drop_guidance removes from the context)
         self.offset = offset                 # (N, 3) per-atom centre of its molecule (center_pos_mode='center') or None
         self.model, self.ctx, self.dev, self.guided, self.bufs = model, ctx, dev, guided, bufs
         self.out_pos, self.out_v, self.return_traj, self.reuse, self.keep = out_pos, out_v, return_traj, reuse, keep
@@ -598,6 +641,8 @@ class _PendingChain:
             torch.cuda.synchronize(self.dev)
             if kind == "mesh":
                 _lib.check(_lib.load().shapemol_set_mesh_guidance(self.ctx, None, 0, None, 0, None, 0, 0, None), "shapemol_set_mesh_guidance")
+            elif kind == "groups":
+                _lib.check(_lib.load().shapemol_set_guidance_groups(self.ctx, 0, None, None, None, None, 0, None), "shapemol_set_guidance_groups")
             else:
                 _lib.check(_lib.load().shapemol_set_guidance(self.ctx, None, 0, 0.0, 0, None), "shapemol_set_guidance")
 
@@ -680,6 +725,36 @@ def pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=3, ratio=0
                                                       _stream_ptr(torch.cuda.current_stream(pos.device)))
     _lib.check(rc, "shapemol_pointcloud_guidance")
     return pred_ligand_pos
+
+
+def _guidance_groups(entries, n_mols):
+    """``[(point_clouds or None, kdtree, radius, n_mols), ...]`` -> (mol_off (G+1,) int64, clouds (sum P_g, 3) float64, cloud_off
+    (G+1,) int64, radii (G,) float64), host arrays for ``shapemol_set_guidance_groups``.  The groups' molecule counts must sum to
+    ``n_mols``.  Host logic only: the clouds' sizes and the radii are checked by the library, which names the offending group."""
+    if len(entries) == 0:
+        raise ValueError("use_pointcloud_data: the list of groups is empty")
+    counts, clouds, radii = [], [], []
+    for g, e in enumerate(entries):
+        if not isinstance(e, (tuple, list)) or len(e) != 4:
+            raise ValueError(f"use_pointcloud_data[{g}] must be (point_clouds, kdtree, radius, n_mols)")
+        cnt = int(e[3])
+        if cnt < 0:
+            raise ValueError(f"use_pointcloud_data[{g}]: n_mols < 0")
+        counts.append(cnt)
+        clouds.append(np.zeros((0, 3)) if e[0] is None else np.asarray(e[0], dtype=np.float64).reshape(-1, 3))
+        radii.append(1.0 if e[0] is None else float(e[2]))          # an unguided group's radius is not used
+    if sum(counts) != n_mols:
+        raise ValueError(f"use_pointcloud_data: the groups hold {sum(counts)} molecules, the batch has {n_mols}")
+    mol_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    cloud_off = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+    return mol_off, np.ascontiguousarray(np.concatenate(clouds)), cloud_off, np.asarray(radii, dtype=np.float64)
+
+
+def _set_guidance_groups(lib, ctx, groups, grad_step, gd):
+    mol_off, clouds, cloud_off, radii = groups
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)        # noqa: E731
+    _lib.check(lib.shapemol_set_guidance_groups(ctx, len(radii), vp(mol_off), vp(clouds) if len(clouds) else None, vp(cloud_off),
+                                                vp(radii), int(grad_step), _ptr(gd)), "shapemol_set_guidance_groups")
 
 
 def _mesh_arrays(use_mesh_data):

@@ -22,7 +22,8 @@ import torch
 
 from .molopt_score_model import log_sample_categorical
 
-__all__ = ["atom_num_sampler", "sample_atom_nums", "sample_diffusion_ligand", "pack_result", "unbatch"]
+__all__ = ["atom_num_sampler", "sample_atom_nums", "sample_diffusion_ligand", "sample_diffusion_ligand_multi", "plan_batches",
+           "pack_result", "unbatch"]
 
 
 def sample_atom_nums(batch_size, atom_nums, atom_dist):
@@ -100,6 +101,66 @@ def _traj_to_host(r, name):
     return t.cpu().numpy()
 
 
+def _atom_counts(sample_num_atoms, sample_func, ref_num_atoms, n_data):
+    """Atom count of each of `n_data` molecules (``scripts/sample_diffusion.py:66-75``)."""
+    if sample_num_atoms == "size":
+        assert sample_func is not None
+        return [int(x) for x in sample_func(n_data)]
+    if sample_num_atoms == "ref":
+        assert ref_num_atoms is not None
+        return [int(ref_num_atoms)] * n_data
+    raise ValueError
+
+
+def _initial_types(model, n_atoms, dev, host_rng):
+    """Initial atom types: ``log_sample_categorical`` of uniform logits (``scripts/sample_diffusion.py:90-91``)."""
+    if getattr(model, "v_mode", "categorical") == "gaussian":
+        raise NotImplementedError("v_mode 'gaussian' is not part of the accelerated path")
+    uniform_logits = torch.zeros(n_atoms, model.num_classes, device=dev)
+    if host_rng:
+        return log_sample_categorical(uniform_logits, u=torch.rand(n_atoms, model.num_classes).to(dev))
+    return log_sample_categorical(uniform_logits)
+
+
+def _host_noise(model, num_steps, n_atoms, dev, accelerated):
+    """``noise=(eps, u)`` of a chain from torch's CPU generator, in the reference's per-step order (host_rng)."""
+    if not accelerated:
+        raise ValueError("host_rng feeds recorded draws to the device chain: it needs the accelerated model")
+    n_steps = num_steps if num_steps is not None else model.num_timesteps
+    eps = torch.empty(n_steps, n_atoms, 3)
+    uu = torch.empty(n_steps, n_atoms, model.num_classes)
+    for s_ in range(n_steps):                    # one reverse step at a time: the two streams interleave
+        eps[s_] = torch.randn(n_atoms, 3)
+        uu[s_] = torch.rand(n_atoms, model.num_classes)
+    return eps.to(dev), uu.to(dev)
+
+
+def _unbatch_result(r, ligand_num_atoms, pos_only):
+    """A finished chain's result dict -> per-molecule host arrays, keyed like the 9-tuple's entries: final state and the six
+    trajectories (``v0_traj`` / ``vt_traj`` stay empty for ``pos_only``)."""
+    n_data = len(ligand_num_atoms)
+    cum = np.cumsum([0] + list(ligand_num_atoms))
+    out = {}
+    pos = r["pos"].cpu().numpy().astype(np.float64)
+    out["pos"] = [pos[cum[k]:cum[k + 1]] for k in range(n_data)]
+    v = r["v"].cpu().numpy()
+    out["v"] = [v[cum[k]:cum[k + 1]] for k in range(n_data)]
+    st = r.get("_stacked")
+    if st is not None and all(torch.is_tensor(x) and x.is_cuda for x in st.values()):
+        some = next(iter(st.values()))
+        dest = _regroup_index(some.shape[0], ligand_num_atoms, some.device)
+        take = lambda name, dt=None: _unbatch_on_device(st[name], ligand_num_atoms, dt, dest)      # noqa: E731
+    else:
+        take = lambda name, dt=None: unbatch(_traj_to_host(r, name), cum, None if dt is None else np.float64)  # noqa: E731
+    out["pos_traj"] = take("pos_traj", torch.float64)
+    out["pos_cond_traj"] = take("pos_cond_traj", torch.float64)
+    out["v_traj"] = take("v_traj")
+    out["v_cond_traj"] = take("v_cond_traj")
+    out["v0_traj"] = [] if pos_only else take("v0_traj")
+    out["vt_traj"] = [] if pos_only else take("vt_traj")
+    return out
+
+
 def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device="cuda:0", num_steps=None,
                             pos_only=False, center_pos_mode="none", sample_func=None, threshold_type=None,
                             threshold_args=None, sample_num_atoms="prior", bounds=None, ref_num_atoms=None,
@@ -174,25 +235,15 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
         nonlocal all_pred_v0_traj, all_pred_vt_traj
         handle, ligand_num_atoms, n_data, t1 = job
         r = handle.result() if hasattr(handle, "result") else handle
-        cum = np.cumsum([0] + ligand_num_atoms)
-        pos = r["pos"].cpu().numpy().astype(np.float64)
-        all_pred_pos += [pos[cum[k]:cum[k + 1]] for k in range(n_data)]
-        v = r["v"].cpu().numpy()
-        all_pred_v += [v[cum[k]:cum[k + 1]] for k in range(n_data)]
-        st = r.get("_stacked")
-        if st is not None and all(torch.is_tensor(x) and x.is_cuda for x in st.values()):
-            some = next(iter(st.values()))
-            dest = _regroup_index(some.shape[0], ligand_num_atoms, some.device)
-            take = lambda name, dt=None: _unbatch_on_device(st[name], ligand_num_atoms, dt, dest)      # noqa: E731
-        else:
-            take = lambda name, dt=None: unbatch(_traj_to_host(r, name), cum, None if dt is None else np.float64)  # noqa: E731
-        all_pred_pos_traj += take("pos_traj", torch.float64)
-        all_pred_pos_cond_traj += take("pos_cond_traj", torch.float64)
-        all_pred_v_traj += take("v_traj")
-        all_pred_v_cond_traj += take("v_cond_traj")
-        if not pos_only:
-            all_pred_v0_traj += take("v0_traj")
-            all_pred_vt_traj += take("vt_traj")
+        o = _unbatch_result(r, ligand_num_atoms, pos_only)
+        all_pred_pos += o["pos"]
+        all_pred_v += o["v"]
+        all_pred_pos_traj += o["pos_traj"]
+        all_pred_pos_cond_traj += o["pos_cond_traj"]
+        all_pred_v_traj += o["v_traj"]
+        all_pred_v_cond_traj += o["v_cond_traj"]
+        all_pred_v0_traj += o["v0_traj"]
+        all_pred_vt_traj += o["vt_traj"]
         time_list.append(time.time() - t1)
 
     try:
@@ -202,14 +253,7 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
             if _batch_seed is not None:
                 np.random.seed((int(_batch_seed) + i) % (2 ** 32))
                 torch.manual_seed(int(_batch_seed) + i)
-            if sample_num_atoms == "size":
-                assert sample_func is not None
-                ligand_num_atoms = [int(x) for x in sample_func(n_data)]
-            elif sample_num_atoms == "ref":
-                assert ref_num_atoms is not None
-                ligand_num_atoms = [int(ref_num_atoms)] * n_data
-            else:
-                raise ValueError
+            ligand_num_atoms = _atom_counts(sample_num_atoms, sample_func, ref_num_atoms, n_data)
             batch_ligand = torch.repeat_interleave(torch.arange(n_data), torch.tensor(ligand_num_atoms)).to(dev)
             all_ligand_atoms = sum(ligand_num_atoms)
             init_ligand_pos = torch.randn(all_ligand_atoms, 3).to(dev)            # host generator, as the reference
@@ -218,24 +262,10 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
                     raise ValueError("pos_only keeps the reference atom types: needs sample_num_atoms='ref' and ref_atom_feature")
                 init_ligand_v = torch.as_tensor(ref_atom_feature, dtype=torch.int64).repeat(n_data).to(dev)
             else:
-                if getattr(model, "v_mode", "categorical") == "gaussian":
-                    raise NotImplementedError("v_mode 'gaussian' is not part of the accelerated path")
-                uniform_logits = torch.zeros(len(batch_ligand), model.num_classes, device=dev)
-                if host_rng:
-                    init_ligand_v = log_sample_categorical(uniform_logits, u=torch.rand(all_ligand_atoms, model.num_classes).to(dev))
-                else:
-                    init_ligand_v = log_sample_categorical(uniform_logits)
+                init_ligand_v = _initial_types(model, all_ligand_atoms, dev, host_rng)
             noise_kw = {}
             if host_rng:
-                if not accelerated:
-                    raise ValueError("host_rng feeds recorded draws to the device chain: it needs the accelerated model")
-                n_steps = num_steps if num_steps is not None else model.num_timesteps
-                eps = torch.empty(n_steps, all_ligand_atoms, 3)
-                uu = torch.empty(n_steps, all_ligand_atoms, model.num_classes)
-                for s_ in range(n_steps):                    # one reverse step at a time: the two streams interleave
-                    eps[s_] = torch.randn(all_ligand_atoms, 3)
-                    uu[s_] = torch.rand(all_ligand_atoms, model.num_classes)
-                noise_kw["noise"] = (eps.to(dev), uu.to(dev))
+                noise_kw["noise"] = _host_noise(model, num_steps, all_ligand_atoms, dev, accelerated)
             while len(pending) >= depth:                     # the slot this batch will use must be free again
                 deliver(pending.popleft())
             handle = model.sample_diffusion(
@@ -261,6 +291,104 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
                 pass
     return (all_pred_pos, all_pred_v, all_pred_pos_traj, all_pred_v_traj, all_pred_v0_traj, all_pred_vt_traj, time_list,
             all_pred_pos_cond_traj, all_pred_v_cond_traj)
+
+
+def plan_batches(n_conditions, num_samples, batch_size):
+    """Condition-major packing of ``n_conditions * num_samples`` molecules into batches of ``batch_size`` (host logic only).
+    Molecule m of the job is sample ``m % num_samples`` of condition ``m // num_samples``.  Returns one list per batch of
+    ``(condition, first_sample, n)`` segments in batch order: a batch may hold several conditions, and a condition may straddle
+    two (or more) batches."""
+    if n_conditions < 1 or num_samples < 1 or batch_size < 1:
+        raise ValueError("plan_batches: n_conditions, num_samples and batch_size must be >= 1")
+    total, plan = n_conditions * num_samples, []
+    for lo in range(0, total, batch_size):
+        hi, segs, m = min(lo + batch_size, total), [], lo
+        while m < hi:
+            c = m // num_samples
+            n = min(hi, (c + 1) * num_samples) - m
+            segs.append((c, m - c * num_samples, n))
+            m += n
+        plan.append(segs)
+    return plan
+
+
+def _per_condition(value, n_conditions, name):
+    """One value for all conditions, or a sequence with one per condition."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n_conditions:
+            raise ValueError(f"{name}: {len(value)} entries for {n_conditions} conditions")
+        return list(value)
+    return [value] * n_conditions
+
+
+def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256, device="cuda:0", num_steps=None,
+                                  center_pos_mode="none", sample_func=None, sample_num_atoms="prior", ref_num_atoms=None,
+                                  seed=None, use_graph=True, host_rng=False, grad_step=1000):
+    """``sample_diffusion_ligand`` for MANY shape conditions at once: ``num_samples`` molecules for each of ``conditions``, with
+    molecules of different conditions sharing the chains.
+
+    conditions       sequence of ``(shape_emb (32, 3), use_pointcloud_data or None)``; ``use_pointcloud_data`` is the
+                     reference's ``(point_clouds, kdtree, radius)`` of that condition, None leaves its molecules unguided.
+    num_samples      molecules per condition.
+    batch_size       molecules per chain.  The ``len(conditions) * num_samples`` molecules are laid out condition-major and cut
+                     into batches of this size (:func:`plan_batches`); every batch runs as ONE chain, in which each condition's run
+                     of molecules is guided towards its own cloud (``sample_diffusion`` with a list of groups).
+    sample_func, ref_num_atoms   as for :func:`sample_diffusion_ligand`, or a sequence with one entry per condition (the
+                     atom-count prior depends on the condition's voxel size).  ``sample_func`` is called once per condition and
+                     batch, in batch order.
+    seed, host_rng, use_graph, grad_step, num_steps, center_pos_mode   as for :func:`sample_diffusion_ligand`; the initial
+                     coordinates, the initial types and (``host_rng``) the chain's noise are drawn per batch, as there.
+
+    Semantics of a mixed batch.  With the module in train mode -- what the reference's sampling script runs -- the VN batch-norm
+    takes its statistics over the whole batch, so a mixed batch is not the same computation as one batch per condition, exactly as
+    two values of ``batch_size`` are not the same computation in the reference.  After ``model.eval()`` (running statistics)
+    molecules are independent, and a mixed batch reproduces the per-condition chains on the same per-molecule random numbers.
+
+    The chains run one after the other (installing and removing the clouds drains the device, as for one cloud).
+    Not covered: ``pos_only``, classifier-free guidance and mesh guidance (one mesh per chain); use
+    :func:`sample_diffusion_ligand` per condition for those.
+
+    Returns a list with, per condition, the reference's 9-tuple in the layout :func:`sample_diffusion_ligand` returns;
+    ``time_list`` holds the wall time of every batch the condition has molecules in.
+    """
+    if not getattr(model, "_accelerated", False):
+        raise ValueError("sample_diffusion_ligand_multi needs the accelerated model (groups of clouds inside one chain)")
+    dev = torch.device(device)
+    n_cond = len(conditions)
+    shapes = [torch.as_tensor(c[0], dtype=torch.float32).reshape(1, -1) for c in conditions]
+    clouds = [c[1] for c in conditions]
+    funcs = _per_condition(sample_func, n_cond, "sample_func")
+    refs = _per_condition(ref_num_atoms, n_cond, "ref_num_atoms")
+    keys = ("pos", "v", "pos_traj", "v_traj", "v0_traj", "vt_traj", "time", "pos_cond_traj", "v_cond_traj")     # the 9-tuple's order
+    acc = [{k: [] for k in keys} for _ in range(n_cond)]
+    for i, segs in enumerate(plan_batches(n_cond, num_samples, batch_size)):
+        t1 = time.time()
+        ligand_num_atoms = []
+        for c, _first, n in segs:
+            ligand_num_atoms += _atom_counts(sample_num_atoms, funcs[c], refs[c], n)
+        n_data = len(ligand_num_atoms)
+        batch_ligand = torch.repeat_interleave(torch.arange(n_data), torch.tensor(ligand_num_atoms)).to(dev)
+        all_ligand_atoms = sum(ligand_num_atoms)
+        init_ligand_pos = torch.randn(all_ligand_atoms, 3).to(dev)            # host generator, as the reference
+        init_ligand_v = _initial_types(model, all_ligand_atoms, dev, host_rng)
+        noise_kw = {"noise": _host_noise(model, num_steps, all_ligand_atoms, dev, True)} if host_rng else {}
+        groups = None
+        if any(clouds[c] is not None for c, _f, _n in segs):
+            groups = [(None, None, None, n) if clouds[c] is None else (clouds[c][0], None, clouds[c][2], n) for c, _f, n in segs]
+        r = model.sample_diffusion(
+            init_ligand_pos=init_ligand_pos, init_ligand_v=init_ligand_v, batch_ligand=batch_ligand,
+            ligand_shape=torch.cat([shapes[c].repeat(n, 1) for c, _f, n in segs]).to(dev), num_steps=num_steps,
+            center_pos_mode=center_pos_mode, use_pointcloud_data=groups, grad_step=grad_step,
+            seed=None if seed is None else int(seed) + i, use_graph=use_graph, _reuse_host_buffers="device", **noise_kw)
+        o = _unbatch_result(r, ligand_num_atoms, False)
+        dt, m = time.time() - t1, 0
+        for c, _first, n in segs:
+            for k in keys:
+                if k != "time":
+                    acc[c][k] += o[k][m:m + n]
+            acc[c]["time"].append(dt)
+            m += n
+    return [tuple(a[k] for k in keys) for a in acc]
 
 
 def pack_result(data, outputs):
