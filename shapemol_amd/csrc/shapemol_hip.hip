@@ -25,10 +25,9 @@
 #include <string>
 #include <vector>
 
-namespace {
+#include "sm_pack.h"
 
-thread_local std::string g_err;
-int fail(const std::string &m) { g_err = m; return 1; }
+namespace {
 
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
@@ -43,478 +42,9 @@ constexpr int kEdgeThreadsDefault = 768;
 #endif
 constexpr int kGraphUnroll = SM_GRAPH_UNROLL;   // reverse steps per graph launch
 
-// ---- host view of the packed weight array (order documented in shapemol_amd/packing.py) ----
-struct Lin { const float *w = nullptr, *b = nullptr; int out = 0, in = 0; };
-struct Mlp { Lin l1; const float *g = nullptr, *be = nullptr; Lin l2; };
-struct Cursor {
-    const float *p; size_t left;
-    bool ok = true;
-    const float *take(size_t n) {
-        if (n > left) { ok = false; return p; }
-        const float *r = p; p += n; left -= n; return r;
-    }
-    Lin lin(int out, int in, bool bias = true) {
-        Lin l; l.out = out; l.in = in; l.w = take((size_t)out * in); l.b = bias ? take(out) : nullptr; return l;
-    }
-    Mlp mlp(int in, int hid, int out) {
-        Mlp m; m.l1 = lin(hid, in); m.g = take(hid); m.be = take(hid); m.l2 = lin(out, hid); return m;
-    }
-};
-struct HostLayer { Mlp hk, hv, hq, no, xk, xv, xq; const float *vn_f, *bn_g, *bn_b, *vn_d; };
-struct HostModel {
-    const float *tab[7];
-    Lin te1, te2, emb;
-    Mlp ew;
-    std::vector<HostLayer> layer;
-    Mlp inv;
-    Lin v1, v2;
-};
-
-size_t weight_count(const shapemol_config &c) {
-    const size_t H = c.hidden_dim, G = c.num_r_gaussian, S = c.shape_dim, SL = c.shape_latent_dim,
-                 D = c.time_emb_dim, C = c.num_classes, T = c.num_timesteps, hd = c.n_heads;
-    const size_t kv = G + 2 * H + SL, cin = 1 + hd + S;
-    auto mlp = [](size_t in, size_t hid, size_t out) { return hid * in + hid + 2 * hid + out * hid + out; };
-    size_t n = 7 * T;
-    n += 2 * D * D + 2 * D + D * 2 * D + D;
-    n += H * (C + D) + H;
-    n += mlp(G, H, 1);
-    const size_t per_layer = 2 * mlp(kv, H, H) + mlp(H, H, H) + mlp(2 * H, H, H) + mlp(kv, H, H) +
-                             mlp(kv, H, hd) + mlp(H, H, H) + 2 * hd * cin + 2 * hd;
-    n += (size_t)c.num_layers * per_layer;
-    n += mlp(S, S, SL);
-    n += H * H + H + C * H + C;
-    return n;
-}
-
-bool parse_weights(const shapemol_config &c, const float *w, size_t n, HostModel &m) {
-    const int H = c.hidden_dim, G = c.num_r_gaussian, S = c.shape_dim, SL = c.shape_latent_dim,
-              D = c.time_emb_dim, C = c.num_classes, T = c.num_timesteps, hd = c.n_heads;
-    const int kv = G + 2 * H + SL, cin = 1 + hd + S;
-    Cursor cu{w, n};
-    for (int i = 0; i < 7; ++i) m.tab[i] = cu.take(T);
-    m.te1 = cu.lin(2 * D, D);
-    m.te2 = cu.lin(D, 2 * D);
-    m.emb = cu.lin(H, C + D);
-    m.ew = cu.mlp(G, H, 1);
-    m.layer.resize(c.num_layers);
-    for (auto &L : m.layer) {
-        L.hk = cu.mlp(kv, H, H); L.hv = cu.mlp(kv, H, H); L.hq = cu.mlp(H, H, H); L.no = cu.mlp(2 * H, H, H);
-        L.xk = cu.mlp(kv, H, H); L.xv = cu.mlp(kv, H, hd); L.xq = cu.mlp(H, H, H);
-        L.vn_f = cu.take((size_t)hd * cin); L.bn_g = cu.take(hd); L.bn_b = cu.take(hd); L.vn_d = cu.take((size_t)hd * cin);
-    }
-    m.inv = cu.mlp(S, S, SL);
-    m.v1 = cu.lin(H, H);
-    m.v2 = cu.lin(C, H);
-    return cu.ok && cu.left == 0;
-}
-
-// ---- device image builder --------------------------------------------------------------------
-struct Image {
-    std::vector<float> d;
-    size_t alloc(size_t n) {
-        const size_t off = (d.size() + 63) & ~size_t(63);
-        d.resize(off + n, 0.f);
-        return off;
-    }
-    size_t put(const float *src, size_t n) { const size_t o = alloc(n); std::memcpy(&d[o], src, n * sizeof(float)); return o; }
-};
-
-struct DevMlp { size_t w1, b1, g, be, w2, b2; };            // raw row-major (VALU kernels)
-struct DevMlpImg { size_t w1img, b1, g, be, w2img, b2; int nt2; size_t w1img6, w2img6, w1img16, w2img16; };   // MFMA A-fragment images (sm_node.h)
-struct DevLayer {
-    size_t pre_x2h, pre_h2x;          // images of [4H][H]: first-layer node blocks (k_i, k_j, v_i, v_j)
-    size_t lin_img;                   // image of [8H][H]: pre_h2x of this layer followed by pre_x2h of the next
-    size_t lin6_img, pre6_x2h;        // the same (and pre_x2h alone) as split bf16 images (node_linear6_kernel)
-    size_t lin16_img, pre16_x2h;      // ... and as two-piece f16 images (node_linear16_kernel)
-    size_t sk_x2h, sv_x2h, sk_h2x, sv_h2x;   // [H][SL] shape columns of the first layers
-    size_t bk_x2h, bv_x2h, bk_h2x, bv_h2x;   // first-layer biases [H]
-    DevMlpImg q_x2h, q_h2x, no;
-    size_t blob_x2h, blob_h2x;        // fp32 edge kernels (sm_edge.h): both MLPs of a kernel in one LDS image
-    size_t img_kx, img_vx, img_kh, img_vh;   // bf16-split phase kernels (sm_edge_bf16.h): one image per MLP
-    size_t i16_kx, i16_vx, i16_kh, i16_vh;   // two-piece f16 images (sm_edge16.h)
-    size_t st_kx, st_vx, st_kh, st_vh;       // streaming kernels (sm_edge_stream.h): producer parts (LDS images) ...
-    size_t sw2_kx, sw2_vx, sw2_kh;           // ... and the second Linears as three bf16 pieces (consumers' registers)
-    size_t sb2_vx;                           // bias of the x2h value MLP's second Linear [H]
-    size_t vn_f, vn_d;                // original [heads][cin]
-    size_t wf_x, wd_x, wf_o, wd_o, bn_g, bn_b;
-};
-struct DevModel {
-    size_t tab[7];
-    size_t te1w, te1b, te2w, te2b, embw, embb, embwT;
-    DevMlp ew, inv;
-    DevMlpImg vhead;             // Linear -> SSP -> Linear (second image padded to 16 rows)
-    std::vector<DevLayer> layer;
-};
-
-// A-fragment image of W[rows][K] taken from src[r * ld + col0 + c]; rows padded with zeros to rows_pad
-size_t pack_image(Image &im, const float *src, int rows, int rows_pad, int K, int ld, int col0) {
-    const int ntk = K / 16;
-    const size_t o = im.alloc((size_t)rows_pad * K);
-    for (int t2 = 0; t2 < rows_pad / 16; ++t2)
-        for (int t = 0; t < ntk; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int row = 16 * t2 + (lane & 15), col = 16 * t + 4 * (lane >> 4) + r;
-                    im.d[o + ((size_t)(t2 * ntk + t) * 64 + lane) * 4 + r] = row < rows ? src[(size_t)row * ld + col0 + col] : 0.f;
-                }
-    return o;
-}
-size_t put_padded(Image &im, const float *src, int n, int n_pad) {
-    const size_t o = im.alloc(n_pad);
-    std::memcpy(&im.d[o], src, n * sizeof(float));
-    return o;
-}
-void split3_host(float w, uint16_t (&p)[3]);
-size_t pack_linear6_image(Image &im, size_t src, int rows, int K);
-size_t pack_linear16_image(Image &im, size_t src, int rows, int K);
-DevMlpImg put_mlp_img(Image &im, const Mlp &m) {
-    DevMlpImg d;
-    const int r2 = (m.l2.out + 15) / 16 * 16;
-    d.w1img = pack_image(im, m.l1.w, m.l1.out, m.l1.out, m.l1.in, m.l1.in, 0);
-    d.b1 = im.put(m.l1.b, m.l1.out);
-    d.g = m.g ? im.put(m.g, m.l1.out) : 0; d.be = m.be ? im.put(m.be, m.l1.out) : 0;
-    d.w2img = pack_image(im, m.l2.w, m.l2.out, r2, m.l2.in, m.l2.in, 0);
-    d.b2 = put_padded(im, m.l2.b, m.l2.out, r2);
-    d.nt2 = r2 / 16;
-    d.w1img6 = pack_linear6_image(im, d.w1img, m.l1.out, m.l1.in);
-    d.w2img6 = pack_linear6_image(im, d.w2img, r2, m.l2.in);
-    d.w1img16 = pack_linear16_image(im, d.w1img, m.l1.out, m.l1.in);
-    d.w2img16 = pack_linear16_image(im, d.w2img, r2, m.l2.in);
-    return d;
-}
-
-int head_of_row(int m, int nt) {     // value row 4g + r of the h2x edge kernel -> head index, -1 = padding
-    const int g = m >> 2, r = m & 3;
-    if (r >= nt / 2) return -1;
-    return 2 * ((nt / 2) * (g & 1) + r) + (g >> 1);
-}
-
-// pack one edge MLP into the EdgeBlob image (see sm_edge.h)
-void pack_edge_mlp(const Mlp &m, int H, int kv_in, bool perm_heads, float *wr, float *w2, float *gam, float *bet, float *b2) {
-    const int NT = H / 16;
-    const int nt2 = perm_heads ? 1 : NT;
-    for (int t = 0; t < NT; ++t)
-        for (int s = 0; s < 5; ++s)
-            for (int lane = 0; lane < 64; ++lane)
-                wr[(t * 5 + s) * 64 + lane] = m.l1.w[(size_t)(16 * t + (lane & 15)) * kv_in + 4 * s + (lane >> 4)];
-    for (int t2 = 0; t2 < nt2; ++t2)
-        for (int t = 0; t < NT; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    int row = 16 * t2 + (lane & 15);
-                    if (perm_heads) row = head_of_row(lane & 15, NT);
-                    const int col = 16 * t + 4 * (lane >> 4) + r;
-                    w2[((t2 * NT + t) * 64 + lane) * 4 + r] = row < 0 ? 0.f : m.l2.w[(size_t)row * H + col];
-                }
-    std::memcpy(gam, m.g, H * sizeof(float));
-    std::memcpy(bet, m.be, H * sizeof(float));
-    for (int i = 0; i < nt2 * 16; ++i) {
-        int row = i;
-        if (perm_heads) row = head_of_row(i, NT);
-        b2[i] = row < 0 ? 0.f : m.l2.b[row];
-    }
-}
-
-// exact 3-way bf16 split of a float by truncation; returns the three 16-bit patterns
-void split3_host(float w, uint16_t (&p)[3]) {
-    float r = w;
-    for (int i = 0; i < 3; ++i) {
-        uint32_t u; std::memcpy(&u, &r, 4);
-        const uint32_t hi = u & 0xFFFF0000u;
-        p[i] = (uint16_t)(hi >> 16);
-        float h; std::memcpy(&h, &hi, 4);
-        r = r - h;
-    }
-}
-
-// one edge MLP -> EdgePhaseImage (sm_edge_bf16.h)
-template <int H>
-size_t pack_phase_image(Image &im, const Mlp &m, int kv_in, bool perm_heads) {
-    constexpr int NT = H / 16, NB = NT / 2;
-    const int nt2 = perm_heads ? 1 : NT;
-    const int G4 = (NT + 3) / 4;
-    const bool bf1 = nt2 > 1;          // EdgePhaseImage::BF1
-    const int o_wr = 0, o_g = o_wr + (bf1 ? 3 * NT * 256 : 5 * G4 * 256), o_b = o_g + H, o_b2 = o_b + H, o_w2 = o_b2 + nt2 * 16;
-    const int total = o_w2 + 3 * nt2 * NB * 256;
-    const size_t o = im.alloc(total);
-    float *d = &im.d[o];
-    for (int t = 0; t < NT; ++t)
-        for (int s = 0; s < 5; ++s)
-            for (int lane = 0; lane < 64; ++lane)
-                if (!bf1) d[o_wr + ((s * G4 + t / 4) * 64 + lane) * 4 + (t & 3)] = m.l1.w[(size_t)(16 * t + (lane & 15)) * kv_in + 4 * s + (lane >> 4)];
-    if (bf1) {
-        uint32_t *wr = reinterpret_cast<uint32_t *>(d + o_wr);
-        for (int t = 0; t < NT; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int q = 0; q < 4; ++q) {
-                    uint16_t pc[2][3];
-                    for (int e = 0; e < 2; ++e) {
-                        const int j = 2 * q + e;
-                        split3_host(j < 5 ? m.l1.w[(size_t)(16 * t + (lane & 15)) * kv_in + 4 * j + (lane >> 4)] : 0.f, pc[e]);
-                    }
-                    for (int piece = 0; piece < 3; ++piece)
-                        wr[((size_t)(piece * NT + t) * 64 + lane) * 4 + q] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);
-                }
-    }
-    std::memcpy(d + o_g, m.g, H * sizeof(float));
-    std::memcpy(d + o_b, m.be, H * sizeof(float));
-    for (int i = 0; i < nt2 * 16; ++i) {
-        const int row = perm_heads ? head_of_row(i, NT) : i;
-        d[o_b2 + i] = row < 0 ? 0.f : m.l2.b[row];
-    }
-    uint32_t *w2 = reinterpret_cast<uint32_t *>(d + o_w2);
-    for (int t2 = 0; t2 < nt2; ++t2)
-        for (int b = 0; b < NB; ++b)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int mrow = lane & 15, g = lane >> 4;
-                const int row = perm_heads ? head_of_row(mrow, NT) : 16 * t2 + mrow;
-                for (int q = 0; q < 4; ++q) {
-                    uint16_t pc[2][3];
-                    for (int e = 0; e < 2; ++e) {
-                        const int j = 2 * q + e;
-                        const int col = 16 * (2 * b + (j >> 2)) + 4 * g + (j & 3);
-                        split3_host(row < 0 ? 0.f : m.l2.w[(size_t)row * H + col], pc[e]);
-                    }
-                    for (int piece = 0; piece < 3; ++piece)
-                        w2[(((size_t)(piece * nt2 + t2) * NB + b) * 64 + lane) * 4 + q] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);
-                }
-            }
-    return o;
-}
-
-// hi + lo two-piece f16 split (both round-to-nearest): the 16-bit patterns
-void split2_host(float w, uint16_t (&p)[2]) {
-    const _Float16 h = (_Float16)w;
-    const _Float16 l = (_Float16)(w - (float)h);
-    std::memcpy(&p[0], &h, 2);
-    std::memcpy(&p[1], &l, 2);
-}
-
-// one edge MLP -> EdgeImage16 (sm_edge16.h); returns the largest |hidden activation| the LayerNorm of this MLP can
-// produce (the fp16 range check of the caller)
-template <int H>
-float pack_image16(Image &im, const Mlp &m, int kv_in, bool perm_heads, size_t &img) {
-    constexpr int NT = H / 16, NB = NT / 2;
-    const int nt2 = perm_heads ? 1 : NT;
-    const int o_w1 = 0, o_w2 = 2 * NT * 192, o_g = o_w2 + 2 * nt2 * NB * 256, o_b = o_g + H, o_b2 = o_b + H;
-    const int total = (o_b2 + nt2 * 16 + 255) / 256 * 256;
-    img = im.alloc(total);
-    uint32_t *d = reinterpret_cast<uint32_t *>(&im.d[img]);
-    for (int t = 0; t < NT; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int q = 0; q < 3; ++q) {
-                uint16_t pc[2][2];
-                for (int e = 0; e < 2; ++e) {
-                    const int j = 2 * q + e;
-                    split2_host(j < 5 ? m.l1.w[(size_t)(16 * t + (lane & 15)) * kv_in + 4 * j + (lane >> 4)] : 0.f, pc[e]);
-                }
-                for (int piece = 0; piece < 2; ++piece)
-                    d[o_w1 + ((size_t)(piece * NT + t) * 3 + q) * 64 + lane] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);
-            }
-    for (int t2 = 0; t2 < nt2; ++t2)
-        for (int b = 0; b < NB; ++b)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int mrow = lane & 15, g = lane >> 4;
-                const int row = perm_heads ? head_of_row(mrow, NT) : 16 * t2 + mrow;
-                for (int q = 0; q < 4; ++q) {
-                    uint16_t pc[2][2];
-                    for (int e = 0; e < 2; ++e) {
-                        const int j = 2 * q + e;
-                        const int col = 16 * (2 * b + (j >> 2)) + 4 * g + (j & 3);
-                        split2_host(row < 0 ? 0.f : m.l2.w[(size_t)row * H + col], pc[e]);
-                    }
-                    for (int piece = 0; piece < 2; ++piece)
-                        d[o_w2 + (((size_t)(piece * nt2 + t2) * NB + b) * 64 + lane) * 4 + q] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);
-                }
-            }
-    float *pp = &im.d[img];
-    std::memcpy(pp + o_g, m.g, H * sizeof(float));
-    std::memcpy(pp + o_b, m.be, H * sizeof(float));
-    for (int i = 0; i < nt2 * 16; ++i) {
-        const int row = perm_heads ? head_of_row(i, NT) : i;
-        pp[o_b2 + i] = row < 0 ? 0.f : m.l2.b[row];
-    }
-    float gmax = 0.f, bmax = 0.f;
-    for (int i = 0; i < H; ++i) { gmax = std::max(gmax, std::fabs(m.g[i])); bmax = std::max(bmax, std::fabs(m.be[i])); }
-    return gmax * std::sqrt((float)(H - 1)) + bmax;
-}
-
-// fp32 A-fragment image of W[rows][K] (pack_image) -> split bf16 image of node_linear6_kernel:
-//   [(((ot * 3 + piece) * NB + b) * 64 + lane) * 4 + q] u32, element order of gemm_bf16x6
-size_t pack_linear6_image(Image &im, size_t src, int rows, int K) {
-    const int ntk = K / 16, NB = K / 32, nto = rows / 16;
-    const size_t o = im.alloc((size_t)nto * 3 * NB * 256);
-    uint32_t *w = reinterpret_cast<uint32_t *>(&im.d[o]);
-    for (int ot = 0; ot < nto; ++ot)
-        for (int b = 0; b < NB; ++b)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int q = 0; q < 4; ++q) {
-                    uint16_t pc[2][3];
-                    for (int e = 0; e < 2; ++e) {
-                        const int j = 2 * q + e, t = 2 * b + (j >> 2), r = j & 3;
-                        split3_host(im.d[src + ((size_t)(ot * ntk + t) * 64 + lane) * 4 + r], pc[e]);
-                    }
-                    for (int piece = 0; piece < 3; ++piece)
-                        w[(((size_t)(ot * 3 + piece) * NB + b) * 64 + lane) * 4 + q] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);
-                }
-    return o;
-}
-
-// fp32 A-fragment image -> two-piece f16 image of node_linear16_kernel / node_chain16_kernel:
-//   [(((ot * 2 + piece) * NB + b) * 64 + lane) * 4 + q] u32
-size_t pack_linear16_image(Image &im, size_t src, int rows, int K) {
-    const int ntk = K / 16, NB = K / 32, nto = rows / 16;
-    const size_t o = im.alloc((size_t)nto * 2 * NB * 256);
-    uint32_t *w = reinterpret_cast<uint32_t *>(&im.d[o]);
-    for (int ot = 0; ot < nto; ++ot)
-        for (int b = 0; b < NB; ++b)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int q = 0; q < 4; ++q) {
-                    uint16_t pc[2][2];
-                    for (int e = 0; e < 2; ++e) {
-                        const int j = 2 * q + e, t = 2 * b + (j >> 2), r = j & 3;
-                        split2_host(im.d[src + ((size_t)(ot * ntk + t) * 64 + lane) * 4 + r], pc[e]);
-                    }
-                    for (int piece = 0; piece < 2; ++piece)
-                        w[(((size_t)(ot * 2 + piece) * NB + b) * 64 + lane) * 4 + q] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);
-                }
-    return o;
-}
-
-// one edge MLP -> the producer part of the streaming kernels (StreamMap<H, .>::P_*, sm_edge_stream.h): RBF block of the first
-// Linear as three bf16 pieces (whole A fragments of the K = 32 step: centres 0..5 of lane group g in words 0..2, word 3 zero), gamma, beta, b2 and,
-// for the heads-wide value MLP of h2x, the second Linear (rows = heads in natural order, padded to 16)
-template <int H>
-size_t pack_stream_part(Image &im, const Mlp &m, int kv_in, bool h2x_value) {
-    constexpr int NT = H / 16, NB = NT / 2;
-    using MX = StreamMap<H, false>; using MH = StreamMap<H, true>;
-    const int total = h2x_value ? MH::PART_V : MX::PART_K;
-    const size_t o = im.alloc(total);
-    uint32_t *d = reinterpret_cast<uint32_t *>(&im.d[o]);
-    std::memset(d, 0, (size_t)total * 4);
-    for (int t = 0; t < NT; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int q = 0; q < 3; ++q) {
-                uint16_t pc[2][3];
-                for (int e = 0; e < 2; ++e) {
-                    const int j = 2 * q + e;
-                    split3_host(j < 5 ? m.l1.w[(size_t)(16 * t + (lane & 15)) * kv_in + 4 * j + (lane >> 4)] : 0.f, pc[e]);
-                }
-                for (int piece = 0; piece < 3; ++piece)
-                    d[MX::P_W1 + ((size_t)(piece * NT + t) * 64 + lane) * 4 + q] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);      // (word 3 stays zero)
-            }
-    float *pp = &im.d[o];
-    std::memcpy(pp + MX::P_G, m.g, H * sizeof(float));
-    std::memcpy(pp + MX::P_B, m.be, H * sizeof(float));
-    std::memcpy(pp + MX::P_B2, m.l2.b, std::min(m.l2.out, H) * sizeof(float));
-    if (h2x_value) {
-        for (int b = 0; b < NB; ++b)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int row = lane & 15, g = lane >> 4;
-                for (int q = 0; q < 4; ++q) {
-                    uint16_t pc[2][3];
-                    for (int e = 0; e < 2; ++e) {
-                        const int j = 2 * q + e;
-                        const int col = 16 * (2 * b + (j >> 2)) + 4 * g + (j & 3);
-                        split3_host(row < m.l2.out ? m.l2.w[(size_t)row * H + col] : 0.f, pc[e]);
-                    }
-                    for (int piece = 0; piece < 3; ++piece)
-                        d[MH::P_W2 + (((size_t)piece * NB + b) * 64 + lane) * 4 + q] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);
-                }
-            }
-    }
-    return o;
-}
-
-// second Linear [H][H] of an edge MLP as three bf16 pieces [3][NT][NB][64][4] u32, element order of gemm_bf16x6 (rows natural)
-template <int H>
-size_t pack_stream_w2(Image &im, const Mlp &m) {
-    constexpr int NT = H / 16, NB = NT / 2;
-    const size_t o = im.alloc((size_t)3 * NT * NB * 256);
-    uint32_t *w2 = reinterpret_cast<uint32_t *>(&im.d[o]);
-    for (int t2 = 0; t2 < NT; ++t2)
-        for (int b = 0; b < NB; ++b)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int row = 16 * t2 + (lane & 15), g = lane >> 4;
-                for (int q = 0; q < 4; ++q) {
-                    uint16_t pc[2][3];
-                    for (int e = 0; e < 2; ++e) {
-                        const int j = 2 * q + e;
-                        const int col = 16 * (2 * b + (j >> 2)) + 4 * g + (j & 3);
-                        split3_host(m.l2.w[(size_t)row * H + col], pc[e]);
-                    }
-                    for (int piece = 0; piece < 3; ++piece)
-                        w2[(((size_t)(piece * NT + t2) * NB + b) * 64 + lane) * 4 + q] = (uint32_t)pc[0][piece] | ((uint32_t)pc[1][piece] << 16);
-                }
-            }
-    return o;
-}
-
-template <int H>
-int build_layer_image(const shapemol_config &c, const HostLayer &L, Image &im, DevLayer &D, float &hid_max) {
-    const int G = c.num_r_gaussian, SL = c.shape_latent_dim, S = c.shape_dim, hd = c.n_heads;
-    const int kv = G + 2 * H + SL, cin = 1 + hd + S, NT = H / 16;
-    bool contiguous = true;
-    auto put_pre = [&](const Mlp &k, const Mlp &v) {      // 4 images of [H][H]: k_i, k_j, v_i, v_j column blocks
-        const Mlp *src[4] = {&k, &k, &v, &v};
-        size_t first = 0;
-        for (int blk = 0; blk < 4; ++blk) {
-            const size_t o = pack_image(im, src[blk]->l1.w, H, H, H, kv, G + (blk & 1) * H);
-            if (blk == 0) first = o;
-            else if (o != first + (size_t)blk * H * H) contiguous = false;     // images must be contiguous
-        }
-        return first;
-    };
-    auto put_scols = [&](const Mlp &m) {
-        const size_t o = im.alloc((size_t)H * SL);
-        for (int f = 0; f < H; ++f) std::memcpy(&im.d[o + (size_t)f * SL], m.l1.w + (size_t)f * kv + G + 2 * H, SL * sizeof(float));
-        return o;
-    };
-    D.pre_x2h = put_pre(L.hk, L.hv); D.pre_h2x = put_pre(L.xk, L.xv);
-    if (!contiguous) return fail("shapemol_create: packed first-layer images are not contiguous (H * H must be a multiple of 64)");
-    D.sk_x2h = put_scols(L.hk); D.sv_x2h = put_scols(L.hv); D.sk_h2x = put_scols(L.xk); D.sv_h2x = put_scols(L.xv);
-    D.bk_x2h = im.put(L.hk.l1.b, H); D.bv_x2h = im.put(L.hv.l1.b, H);
-    D.bk_h2x = im.put(L.xk.l1.b, H); D.bv_h2x = im.put(L.xv.l1.b, H);
-    D.q_x2h = put_mlp_img(im, L.hq); D.q_h2x = put_mlp_img(im, L.xq); D.no = put_mlp_img(im, L.no);
-    {
-        using B = EdgeBlob<H, false>;
-        const size_t o = im.alloc(B::TOTAL); D.blob_x2h = o; float *b = &im.d[o];
-        pack_edge_mlp(L.hk, H, kv, false, b + B::K_WR, b + B::K_W2, b + B::K_G, b + B::K_B, b + B::K_B2);
-        pack_edge_mlp(L.hv, H, kv, false, b + B::V_WR, b + B::V_W2, b + B::V_G, b + B::V_B, b + B::V_B2);
-    }
-    {
-        using B = EdgeBlob<H, true>;
-        const size_t o = im.alloc(B::TOTAL); D.blob_h2x = o; float *b = &im.d[o];
-        pack_edge_mlp(L.xk, H, kv, false, b + B::K_WR, b + B::K_W2, b + B::K_G, b + B::K_B, b + B::K_B2);
-        pack_edge_mlp(L.xv, H, kv, true, b + B::V_WR, b + B::V_W2, b + B::V_G, b + B::V_B, b + B::V_B2);
-    }
-    D.img_kx = pack_phase_image<H>(im, L.hk, kv, false); D.img_vx = pack_phase_image<H>(im, L.hv, kv, false);
-    D.img_kh = pack_phase_image<H>(im, L.xk, kv, false); D.img_vh = pack_phase_image<H>(im, L.xv, kv, true);
-    hid_max = std::max(hid_max, pack_image16<H>(im, L.hk, kv, false, D.i16_kx));
-    hid_max = std::max(hid_max, pack_image16<H>(im, L.hv, kv, false, D.i16_vx));
-    hid_max = std::max(hid_max, pack_image16<H>(im, L.xk, kv, false, D.i16_kh));
-    hid_max = std::max(hid_max, pack_image16<H>(im, L.xv, kv, true, D.i16_vh));
-    D.st_kx = pack_stream_part<H>(im, L.hk, kv, false); D.st_vx = pack_stream_part<H>(im, L.hv, kv, false);
-    D.st_kh = pack_stream_part<H>(im, L.xk, kv, false); D.st_vh = pack_stream_part<H>(im, L.xv, kv, true);
-    D.sw2_kx = pack_stream_w2<H>(im, L.hk); D.sw2_vx = pack_stream_w2<H>(im, L.hv); D.sw2_kh = pack_stream_w2<H>(im, L.xk);
-    D.sb2_vx = im.put(L.hv.l2.b, H);
-    D.vn_f = im.put(L.vn_f, (size_t)hd * cin); D.vn_d = im.put(L.vn_d, (size_t)hd * cin);
-    D.bn_g = im.put(L.bn_g, hd); D.bn_b = im.put(L.bn_b, hd);
-    D.wf_x = im.alloc(hd); D.wd_x = im.alloc(hd); D.wf_o = im.alloc((size_t)hd * 16); D.wd_o = im.alloc((size_t)hd * 16);
-    for (int ch = 0; ch < hd; ++ch) {
-        im.d[D.wf_x + ch] = L.vn_f[(size_t)ch * cin];
-        im.d[D.wd_x + ch] = L.vn_d[(size_t)ch * cin];
-        for (int m = 0; m < 16; ++m) {
-            const int hh = head_of_row(m, NT);
-            im.d[D.wf_o + ch * 16 + m] = hh < 0 ? 0.f : L.vn_f[(size_t)ch * cin + 1 + hh];
-            im.d[D.wd_o + ch * 16 + m] = hh < 0 ? 0.f : L.vn_d[(size_t)ch * cin + 1 + hh];
-        }
-    }
-    return 0;
-}
-
 struct ProfRec { const char *name; hipEvent_t e0, e1; };
+
+enum class Guide { None, Cloud, Groups, Mesh, Cfg };      // guidance of a chain's predicted x0: chain_guide (sm_guide_host.h)
 
 }  // namespace
 
@@ -604,10 +134,10 @@ struct shapemol_ctx {
     // what a captured step depends on besides the options (which drop the graphs when set): sizes, guidance, and the two
     // launch decisions taken from the max_mol_atoms hint (folded coordinate update, fused graph kernel)
     // (classifier-free guidance: its type and scalars are kernel arguments of the captured step)
-    struct GraphKey { int64_t N = 0, B = 0; int guided = 0 /* 0 none, 1 point cloud, 2 mesh, 3 clouds per group */, fold = 0, gfuse = 0;
+    struct GraphKey { int64_t N = 0, B = 0; Guide guide = Guide::None; int fold = 0, gfuse = 0;
                       int cfg = 0 /* 0 off, else 1 + CfgType */; double cfgv[9] = {};   // w, p, has_bounds, box
                       bool operator==(const GraphKey &o) const {
-                          if (!(N == o.N && B == o.B && guided == o.guided && fold == o.fold && gfuse == o.gfuse && cfg == o.cfg)) return false;
+                          if (!(N == o.N && B == o.B && guide == o.guide && fold == o.fold && gfuse == o.gfuse && cfg == o.cfg)) return false;
                           for (int i = 0; i < 9; ++i) if (cfgv[i] != o.cfgv[i]) return false;
                           return true;
                       } } gkey{};
@@ -710,6 +240,12 @@ int ensure_workspace(shapemol_ctx *c, int64_t N, int64_t B) {
     return 0;
 }
 
+}  // namespace
+
+#include "sm_guide_host.h"
+
+namespace {
+
 static int stream_chunk(const shapemol_ctx *c, int n_atoms);
 constexpr int kVnFoldBytes = kVnFoldCap * 3 * 4 + 32 * 8;      // LDS of the folded coordinate update: table + batch sums
 
@@ -732,57 +268,51 @@ bool vn_fold_ok(const shapemol_ctx *c, int n_atoms) {
     return waves_max * apj + 2 * (c->max_mol_atoms - 1) <= kVnFoldCap;
 }
 
-template <int H>
-int set_edge_attr(int KP) {
-    const int b0 = EdgeBlob<H, false>::TOTAL * 4, b1 = EdgeBlob<H, true>::TOTAL * 4;
-#define SETATTR(K)                                                                                                    \
-    HIPCHK(hipFuncSetAttribute((const void *)edge_attention_kernel<H, K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b0)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge_attention_kernel<H, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b1));
-#define SETATTR3(K)                                                                                                   \
-    HIPCHK(hipFuncSetAttribute((const void *)edge_fused_kernel<H, K, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, EdgePhaseImage<H, H / 16>::TOTAL * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge_fused_kernel<H, K, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, EdgePhaseImage<H, H / 16>::TOTAL * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge_fused_kernel<H, K, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgePhaseImage<H, H / 16>::TOTAL + EdgePhaseImage<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge_fused_kernel<H, K, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgePhaseImage<H, H / 16>::TOTAL + EdgePhaseImage<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4));
-    HIPCHK(hipFuncSetAttribute((const void *)node_prologue6_kernel<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * Chain6Lds<H>::FRAG * 16 + Chain6Lds<H>::PRE * 4)));
-    HIPCHK(hipFuncSetAttribute((const void *)node_chain6_kernel<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Chain6Lds<H>::BYTES));
-    HIPCHK(hipFuncSetAttribute((const void *)node_linear6_kernel<H>, hipFuncAttributeMaxDynamicSharedMemorySize, kLin6Chunk * 3 * H * 32));
-    HIPCHK(hipFuncSetAttribute((const void *)node_prologue16_kernel<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4)));
-    HIPCHK(hipFuncSetAttribute((const void *)node_chain16_kernel<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Chain16Lds<H>::BYTES));
-    HIPCHK(hipFuncSetAttribute((const void *)node_linear16_kernel<H>, hipFuncAttributeMaxDynamicSharedMemorySize, kLin16Chunk * 2 * H * 32));
-    HIPCHK(hipFuncSetAttribute((const void *)node_prologue16_kernel<H, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4)));
-    HIPCHK(hipFuncSetAttribute((const void *)node_chain16_kernel<H, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Chain16Lds<H>::BYTES));
-    HIPCHK(hipFuncSetAttribute((const void *)node_linear16_kernel<H, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLin16Chunk * 2 * H * 32));
-#define SETATTR4(K)                                                                                                   \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_kernel<H, K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4 + kVnFoldBytes)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_kernel<H, K, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4 + kVnFoldBytes)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_loop_kernel<H, K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4 + kVnFoldBytes)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_loop_kernel<H, K, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4 + kVnFoldBytes)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_kernel<H, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_kernel<H, K, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_loop_kernel<H, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_loop_kernel<H, K, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)x2h_chain16_kernel<H, K>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4 + kVnFoldBytes)); \
-    HIPCHK(hipFuncSetAttribute((const void *)x2h_chain16_kernel<H, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4 + kVnFoldBytes));
-#define SETATTR6(K)                                                                                                   \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_kernel<H, K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_kernel<H, K, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_loop_kernel<H, K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_loop_kernel<H, K, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EdgeImage16<H, H / 16>::TOTAL * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_kernel<H, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_kernel<H, K, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_loop_kernel<H, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge16_loop_kernel<H, K, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4));
-#define SETATTR7(K)                                                                                                   \
-    HIPCHK(hipFuncSetAttribute((const void *)edge_stream_kernel<H, K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, StreamMap<H, false>::O_TAIL * 4 + kVnFoldBytes)); \
-    HIPCHK(hipFuncSetAttribute((const void *)edge_stream_kernel<H, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, StreamMap<H, true>::O_TAIL * 4 + (H / 16 + kStreamProducers) * 64 * 2 * 8));
-    if (KP == 8) { SETATTR(8) SETATTR3(8) SETATTR4(8) SETATTR7(8) } else if (KP == 16) { SETATTR(16) SETATTR3(16) SETATTR4(16) SETATTR7(16) } else { SETATTR6(32) SETATTR7(32) }
-#undef SETATTR7
-#undef SETATTR6
-#undef SETATTR4
-#undef SETATTR3
-#undef SETATTR
+// Largest dynamic LDS of every kernel that needs more than the default: one size per kernel family
+#define ATTR(bytes, ...) HIPCHK(hipFuncSetAttribute((const void *)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
+template <int H, int K>
+int set_edge_attr_k() {
+    constexpr int NT = H / 16;
+    constexpr int vn_tail = vn_red_doubles(12, H / 8) * 8 + 12 * 96 * 4;     // h2x, 12 waves: reduction scratch + attention rows of the fused coordinate update
+    constexpr int fold = K <= 16 ? kVnFoldBytes : 0;                         // x2h: table of the folded coordinate update (not for k > 16)
+    constexpr int x16 = 2 * EdgeImage16<H, NT>::TOTAL * 4 + fold, h16 = (EdgeImage16<H, NT>::TOTAL + EdgeImage16<H, 1>::TOTAL) * 4 + vn_tail;
+    ATTR(x16, edge16_kernel<H, K, false>); ATTR(x16, edge16_kernel<H, K, false, true>);
+    ATTR(x16, edge16_loop_kernel<H, K, false>); ATTR(x16, edge16_loop_kernel<H, K, false, true>);
+    ATTR(h16, edge16_kernel<H, K, true>); ATTR(h16, edge16_kernel<H, K, true, true>);
+    ATTR(h16, edge16_loop_kernel<H, K, true>); ATTR(h16, edge16_loop_kernel<H, K, true, true>);
+    ATTR((StreamMap<H, false>::O_TAIL * 4 + kVnFoldBytes), edge_stream_kernel<H, K, false>);
+    ATTR((StreamMap<H, true>::O_TAIL * 4 + (NT + kStreamProducers) * 64 * 2 * 8), edge_stream_kernel<H, K, true>);
+    if constexpr (K <= 16) {      // kernels of single-tile jobs only
+        constexpr int xph = EdgePhaseImage<H, NT>::TOTAL * 4, hph = (EdgePhaseImage<H, NT>::TOTAL + EdgePhaseImage<H, 1>::TOTAL) * 4 + vn_tail;
+        ATTR(x16, x2h_chain16_kernel<H, K>); ATTR(x16, x2h_chain16_kernel<H, K, true>);
+        ATTR((EdgeBlob<H, false>::TOTAL * 4), edge_attention_kernel<H, K, false>); ATTR((EdgeBlob<H, true>::TOTAL * 4), edge_attention_kernel<H, K, true>);
+        ATTR(xph, edge_fused_kernel<H, K, false, false>); ATTR(xph, edge_fused_kernel<H, K, false, true>);
+        ATTR(hph, edge_fused_kernel<H, K, true, false>); ATTR(hph, edge_fused_kernel<H, K, true, true>);
+    }
     return 0;
 }
+
+template <int H>
+int set_edge_attr(int KP) {
+    constexpr size_t pro6 = 2 * Chain6Lds<H>::FRAG * 16 + Chain6Lds<H>::PRE * 4, pro16 = 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4;
+    ATTR(pro6, node_prologue6_kernel<H>); ATTR(Chain6Lds<H>::BYTES, node_chain6_kernel<H>); ATTR(kLin6Chunk * 3 * H * 32, node_linear6_kernel<H>);
+    ATTR(pro16, node_prologue16_kernel<H>); ATTR(Chain16Lds<H>::BYTES, node_chain16_kernel<H>); ATTR(kLin16Chunk * 2 * H * 32, node_linear16_kernel<H>);
+    ATTR(pro16, node_prologue16_kernel<H, true>); ATTR(Chain16Lds<H>::BYTES, node_chain16_kernel<H, true>); ATTR(kLin16Chunk * 2 * H * 32, node_linear16_kernel<H, true>);
+    return KP == 8 ? set_edge_attr_k<H, 8>() : (KP == 16 ? set_edge_attr_k<H, 16>() : set_edge_attr_k<H, 32>());
+}
+#undef ATTR
+
+// One launch of KERNEL<H, KP TAIL> for the context's padded neighbour count: TAIL = (, further template arguments) or ().
+// DISPATCH_KP16: kernels of single-tile jobs, not instantiated for k > 16 (the caller has ruled it out); _F16: kernels with a
+// trailing "f16 features" flag (option feat_f16)
+#define SM_ARGS(...) __VA_ARGS__
+#define LAUNCH_KP(name, K, KERNEL, TAIL, ...) LAUNCH(name, SMK((KERNEL<H, K SM_ARGS TAIL>), __VA_ARGS__))
+#define DISPATCH_KP16(name, KERNEL, TAIL, ...)                                                      \
+    do { if (KP == 8) LAUNCH_KP(name, 8, KERNEL, TAIL, __VA_ARGS__); else LAUNCH_KP(name, 16, KERNEL, TAIL, __VA_ARGS__); } while (0)
+#define DISPATCH_KP(name, KERNEL, TAIL, ...)                                                        \
+    do { if (KP > 16) LAUNCH_KP(name, 32, KERNEL, TAIL, __VA_ARGS__); else DISPATCH_KP16(name, KERNEL, TAIL, __VA_ARGS__); } while (0)
+#define DISPATCH_KP_F16(DISPATCH, name, KERNEL, TAIL, ...)                                          \
+    do { if (c->feat_f16) DISPATCH(name, KERNEL, (SM_ARGS TAIL, true), __VA_ARGS__); else DISPATCH(name, KERNEL, TAIL, __VA_ARGS__); } while (0)
 
 // Waves per workgroup of the single-tile edge kernels: one job per wave while the jobs fit (the launch then lasts
 // one job latency), on as many CUs as possible: ceil(jobs / CUs) waves, at least 4 and at most 12 (the 168-VGPR budget).
@@ -800,9 +330,8 @@ int launch_edge(shapemol_ctx *c, hipStream_t s, const EdgeArgs &a) {     // fp32
     const int grid = std::max(1, std::min(c->num_cu, njobs));
     const size_t shm = EdgeBlob<H, H2X>::TOTAL * sizeof(float);
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
-    if (KP == 8) LAUNCH(nm, SMK((edge_attention_kernel<H, 8, H2X>), dim3(grid), dim3(waves * 64), shm, s, a));
-    else if (KP == 16) LAUNCH(nm, SMK((edge_attention_kernel<H, 16, H2X>), dim3(grid), dim3(waves * 64), shm, s, a));
-    else return fail("k > 16 runs on the two-piece f16 edge kernels only (option edge_bf16 = 3)");
+    if (KP > 16) return fail("k > 16 runs on the two-piece f16 edge kernels only (option edge_bf16 = 3)");
+    DISPATCH_KP16(nm, edge_attention_kernel, (, H2X), dim3(grid), dim3(waves * 64), shm, s, a);
     return 0;
 }
 
@@ -815,13 +344,8 @@ int launch_fused(shapemol_ctx *c, hipStream_t s, const EdgeFusedArgs &a) {
                        + (H2X ? (size_t)vn_red_doubles(waves, H / 8) * 8 + (size_t)waves * apj * 48 * 4 : 0);   // + reduction scratch and attention rows of the fused coordinate update
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
     const bool one = njobs <= grid * waves;      // every wave has at most one job: straight-line instantiation
-    if (KP == 8) {
-        if (one) LAUNCH(nm, SMK((edge_fused_kernel<H, 8, H2X, true>), dim3(grid), dim3(waves * 64), shm, s, a));
-        else LAUNCH(nm, SMK((edge_fused_kernel<H, 8, H2X, false>), dim3(grid), dim3(waves * 64), shm, s, a));
-    } else {
-        if (one) LAUNCH(nm, SMK((edge_fused_kernel<H, 16, H2X, true>), dim3(grid), dim3(waves * 64), shm, s, a));
-        else LAUNCH(nm, SMK((edge_fused_kernel<H, 16, H2X, false>), dim3(grid), dim3(waves * 64), shm, s, a));
-    }
+    if (one) DISPATCH_KP16(nm, edge_fused_kernel, (, H2X, true), dim3(grid), dim3(waves * 64), shm, s, a);
+    else DISPATCH_KP16(nm, edge_fused_kernel, (, H2X, false), dim3(grid), dim3(waves * 64), shm, s, a);
     return 0;
 }
 
@@ -830,16 +354,6 @@ int launch_edge16(shapemol_ctx *c, hipStream_t s, const Edge16Args &a) {
     const int KP = c->KP;
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
     const int tiles_mode = c->edge_tiles >= 0 ? c->edge_tiles : 1;      // -1 = automatic: looping launches
-#define EDGE_DISPATCH(KERNEL, ...)                                                                  \
-    do {                                                                                            \
-        if (c->feat_f16) {                                                                          \
-            if (KP == 8) LAUNCH(nm, SMK((KERNEL<H, 8, H2X, true>), __VA_ARGS__));                   \
-            else if (KP == 16) LAUNCH(nm, SMK((KERNEL<H, 16, H2X, true>), __VA_ARGS__));            \
-            else LAUNCH(nm, SMK((KERNEL<H, 32, H2X, true>), __VA_ARGS__));                          \
-        } else if (KP == 8) LAUNCH(nm, SMK((KERNEL<H, 8, H2X>), __VA_ARGS__));                      \
-        else if (KP == 16) LAUNCH(nm, SMK((KERNEL<H, 16, H2X>), __VA_ARGS__));                      \
-        else LAUNCH(nm, SMK((KERNEL<H, 32, H2X>), __VA_ARGS__));                                    \
-    } while (0)
     {
         // a job = one 16-slot tile: 16 / KP centre atoms (k <= 16) or half an atom (k > 16: two tiles per atom, merged afterwards)
         const int apj = KP >= 16 ? 1 : 16 / KP;
@@ -858,7 +372,7 @@ int launch_edge16(shapemol_ctx *c, hipStream_t s, const Edge16Args &a) {
             Edge16Args b = a;
             b.job_base = 0; b.job_end = njobs; b.nwave = lw; b.chunk = (njobs + lgrid - 1) / lgrid;
             const int g2 = (njobs + b.chunk - 1) / b.chunk;
-            EDGE_DISPATCH(edge16_loop_kernel, dim3(g2), dim3(lw * 64), shm_for(lw), s, b);
+            DISPATCH_KP_F16(DISPATCH_KP, nm, edge16_loop_kernel, (, H2X), dim3(g2), dim3(lw * 64), shm_for(lw), s, b);
             return 0;
         }
         // one launch of the straight-line instantiation, or (larger batches, edge_tiles = 0) several, each over a slice of
@@ -876,10 +390,9 @@ int launch_edge16(shapemol_ctx *c, hipStream_t s, const Edge16Args &a) {
             Edge16Args b = a;
             b.job_base = base; b.job_end = std::min(njobs, base + per); b.nwave = ws;
             const int g2 = std::max(1, std::min(gs, (b.job_end - base + ws - 1) / ws));
-            EDGE_DISPATCH(edge16_kernel, dim3(g2), dim3(ws * 64), shm_for(ws), s, b);
+            DISPATCH_KP_F16(DISPATCH_KP, nm, edge16_kernel, (, H2X), dim3(g2), dim3(ws * 64), shm_for(ws), s, b);
         }
     }
-#undef EDGE_DISPATCH
     return 0;
 }
 
@@ -904,9 +417,7 @@ int launch_stream(shapemol_ctx *c, hipStream_t s, EdgeStreamArgs a) {
     constexpr int NWAVE = H / 16 + kStreamProducers;
     const size_t shm = (size_t)M::O_TAIL * 4 + (H2X ? (size_t)NWAVE * 64 * 2 * 8 : (a.vf.enable ? (size_t)kVnFoldBytes : 0));
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
-    if (KP == 8) LAUNCH(nm, SMK((edge_stream_kernel<H, 8, H2X>), dim3(grid), dim3(NWAVE * 64), shm, s, a));
-    else if (KP == 16) LAUNCH(nm, SMK((edge_stream_kernel<H, 16, H2X>), dim3(grid), dim3(NWAVE * 64), shm, s, a));
-    else LAUNCH(nm, SMK((edge_stream_kernel<H, 32, H2X>), dim3(grid), dim3(NWAVE * 64), shm, s, a));
+    DISPATCH_KP(nm, edge_stream_kernel, (, H2X), dim3(grid), dim3(NWAVE * 64), shm, s, a);
     return 0;
 }
 
@@ -940,11 +451,7 @@ int launch_x2h_chain(shapemol_ctx *c, hipStream_t s, const Edge16Args &a, const 
     const size_t shm = 2 * EdgeImage16<H, H / 16>::TOTAL * sizeof(float) + (a.vf.enable ? kVnFoldBytes : 0);
     Edge16Args b = a;
     b.job_base = 0; b.job_end = njobs; b.nwave = waves;
-    if (c->feat_f16) {
-        if (KP == 8) LAUNCH("edge_x2h_chain", SMK((x2h_chain16_kernel<H, 8, true>), dim3(grid), dim3(waves * 64), shm, s, b, na, c->status + ST_RANGE));
-        else LAUNCH("edge_x2h_chain", SMK((x2h_chain16_kernel<H, 16, true>), dim3(grid), dim3(waves * 64), shm, s, b, na, c->status + ST_RANGE));
-    } else if (KP == 8) LAUNCH("edge_x2h_chain", SMK((x2h_chain16_kernel<H, 8>), dim3(grid), dim3(waves * 64), shm, s, b, na, c->status + ST_RANGE));
-    else LAUNCH("edge_x2h_chain", SMK((x2h_chain16_kernel<H, 16>), dim3(grid), dim3(waves * 64), shm, s, b, na, c->status + ST_RANGE));
+    DISPATCH_KP_F16(DISPATCH_KP16, "edge_x2h_chain", x2h_chain16_kernel, (), dim3(grid), dim3(waves * 64), shm, s, b, na, c->status + ST_RANGE);
     return 0;
 }
 
@@ -1008,9 +515,6 @@ __global__ void knn_pin_kernel(const int *off, int n_steps, const int *atom, con
 template <int H>
 int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape);
 
-// classifier-free guidance applies to this chain (the reference's if / elif: mesh or point-cloud guidance come first)
-bool cfg_on(const shapemol_ctx *c) { return c->cfg_w != 0.0 && c->m_nfaces == 0 && c->g_points == 0 && c->gg_points == 0; }
-
 // exchange the conditional and the unconditional sets of prepared shape data and score outputs
 void swap_uncond(shapemol_ctx *c) {
     std::swap(c->inv, c->inv_u); std::swap(c->add0, c->add0_u); std::swap(c->addp, c->addp_u); std::swap(c->ps, c->ps_u);
@@ -1019,7 +523,7 @@ void swap_uncond(shapemol_ctx *c) {
 
 CfgArgs cfg_args(const shapemol_ctx *c, int64_t N) {
     CfgArgs a{};
-    a.on = cfg_on(c) ? 1 : 0;
+    a.on = chain_guide(c) == Guide::Cfg ? 1 : 0;
     if (!a.on) return a;
     const int C = c->cfg.num_classes;
     a.pos_c = c->pred_pos; a.pos_u = c->pred_pos_u; a.v_c = c->pred_v; a.v_u = c->pred_v_u;
@@ -1060,8 +564,6 @@ int run_cfg_stats(shapemol_ctx *c, hipStream_t s, const CfgArgs &a) {
 
 template <int H>
 int run_prep(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int64_t B, const float *d_shape) {
-    const shapemol_config &g = c->cfg;
-    const int L = g.num_layers, hd = g.n_heads, SL = g.shape_latent_dim, S = g.shape_dim;
     LAUNCH("prep", SMK(mol_index_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_batch, (int)N, (int)B, c->mol_of, c->mol_off, c->status));
     LAUNCH("prep", SMK(mol_span_kernel, dim3((N + 255) / 256), dim3(256), 0, s, c->mol_of, c->mol_off, (int)N, c->mol_span));
     return run_prep_shape<H>(c, s, B, d_shape);
@@ -1071,7 +573,7 @@ int run_prep(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, 
 template <int H>
 int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape) {
     const shapemol_config &g = c->cfg;
-    const int L = g.num_layers, hd = g.n_heads, SL = g.shape_latent_dim, S = g.shape_dim;
+    const int L = g.num_layers, SL = g.shape_latent_dim, S = g.shape_dim;
     ShapeInvArgs si{d_shape, c->P(c->dm.inv.w1), c->P(c->dm.inv.b1), c->P(c->dm.inv.g), c->P(c->dm.inv.be),
                     c->P(c->dm.inv.w2), c->P(c->dm.inv.b2), c->inv, S, SL};
     LAUNCH("prep", SMK(shape_invariant_kernel, dim3(B), dim3(64), 0, s, si));
@@ -1079,8 +581,47 @@ int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_sha
     if (SL == 32) LAUNCH("prep", SMK(shape_term_multi_tiled_kernel<32>, dim3((unsigned)((B + kShapeTermMols - 1) / kShapeTermMols), (unsigned)c->n_prep_terms), dim3(256), 0, s, c->prep_terms, (int)B));
     else LAUNCH("prep", SMK(shape_term_multi_kernel, dim3((unsigned)B, (unsigned)c->n_prep_terms), dim3(256), 0, s, c->prep_terms));
     LAUNCH("prep", SMK(vn_shape_multi_kernel, dim3((unsigned)B, (unsigned)L), dim3(128), 0, s, d_shape, c->prep_vn));
-    (void)SL; (void)S; (void)hd;
     return 0;
+}
+
+// the fields Edge16Args and EdgeStreamArgs share (they use the same member names on purpose)
+template <typename A>
+void fill_edge(A &a, const shapemol_ctx *c, const float *pre, int ld_pre, const float *q, const float *x, float *out, int n_atoms,
+               bool half_tiles, unsigned long long *stamps) {
+    a.pre = pre; a.ld_pre = ld_pre; a.q = q; a.x = x; a.nbr = c->nbr; a.ew = c->ew; a.out = out; a.n_atoms = n_atoms; a.stamps = stamps;
+    if (half_tiles) { a.out = c->part_rows; a.part_ms = c->part_ms; }       // k > 16: per-tile rows, merged by combine32_kernel
+}
+
+// VN-linear + batch statistics (enable = 2) or the whole coordinate update (1) of layer l behind its h2x attention
+EdgeFusedArgs::VnFuse vn_fuse_args(const shapemol_ctx *c, int l, float *x_next, unsigned *arrive, int enable) {
+    const DevLayer &D = c->dm.layer[l];
+    const int hd = c->cfg.n_heads;
+    return {c->ps + (size_t)l * c->capB * 2 * hd * 3, c->P(D.wf_x), c->P(D.wd_x), c->P(D.wf_o), c->P(D.wd_o), c->P(D.bn_g), c->P(D.bn_b),
+            c->mol_of, c->pd, c->bn_acc + (size_t)l * kBnReplicas * 2 * hd, arrive, c->status + ST_VN_BARRIER, x_next, enable};
+}
+
+// What follows the h2x attention of layer l on the f16 / streaming kernels (vn_fuse = 0 or 2): the VN-linear + statistics epilogue
+// (not on half-atom tiles), and who finishes the coordinate update -- the next layer's x2h kernel (`pending`), the DDPM kernel
+// (`ddpm`: the model's last layer in a chain step whose predicted x0 nobody reads before: no guidance, no CFG), or, with neither,
+// the vn_apply launch (vn_done = false; vn_stats too unless stats_done)
+struct H2xPlan { EdgeFusedArgs::VnFuse vn{}; float *xsum = nullptr; VnFold pending{}; DdpmFold ddpm{}; bool stats_done = false, vn_done = false; };
+H2xPlan h2x_plan(const shapemol_ctx *c, int l, bool fold, bool has_next, bool half_tiles, const double *stat_acc, const float *cur_x,
+                 float *x_next, float *out_pos) {
+    H2xPlan p;
+    if (!c->vn_fuse || half_tiles) return p;
+    const DevLayer &D = c->dm.layer[l];
+    const int hd = c->cfg.n_heads;
+    const double *acc = stat_acc + (size_t)l * kBnReplicas * 2 * hd;
+    p.vn = vn_fuse_args(c, l, x_next, nullptr, 2);
+    p.stats_done = true;
+    const bool to_ddpm = !has_next && l == c->cfg.num_layers - 1 && out_pos && c->ddpm_fold && chain_guide(c) == Guide::None &&
+                         c->cfg.num_classes <= 16 && hd <= 16;
+    if (fold && has_next) p.pending = VnFold{c->pd, acc, c->P(D.bn_g), c->P(D.bn_b), c->xsum, cur_x, x_next, c->mol_span, c->status + ST_SPAN, 1};
+    else if (fold && to_ddpm) p.ddpm = DdpmFold{c->pd, acc, c->P(D.bn_g), c->P(D.bn_b), c->xsum, cur_x, out_pos, hd, 1};
+    else return p;
+    p.xsum = c->xsum;
+    p.vn_done = true;
+    return p;
 }
 
 // One score evaluation on prepared batch data.  x_in/v_in: current state; outputs as given.
@@ -1123,9 +664,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
         GraphArgs ga{x_in, c->mol_span, n, g.knn, KP, c->nbr, c->P(c->dm.ew.w1), c->P(c->dm.ew.b1), c->P(c->dm.ew.g), c->P(c->dm.ew.be),
                      c->P(c->dm.ew.w2), c->P(c->dm.ew.b2), c->ew, c->status + ST_SPAN, c->kstamp_sel == 4 ? c->kstamps : nullptr};
         const int apb = kGraphWaves * (KP >= 16 ? 1 : 16 / KP);      // atoms per workgroup
-        if (KP == 8) LAUNCH("graph", SMK((graph_kernel<H, 8>), dim3((n + apb - 1) / apb), dim3(kGraphWaves * 64), 0, s, ga));
-        else if (KP == 16) LAUNCH("graph", SMK((graph_kernel<H, 16>), dim3((n + apb - 1) / apb), dim3(kGraphWaves * 64), 0, s, ga));
-        else LAUNCH("graph", SMK((graph_kernel<H, 32>), dim3((n + apb - 1) / apb), dim3(kGraphWaves * 64), 0, s, ga));
+        DISPATCH_KP("graph", graph_kernel, (), dim3((n + apb - 1) / apb), dim3(kGraphWaves * 64), 0, s, ga);
     } else LAUNCH("knn", SMK(knn_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x_in, c->mol_of, c->mol_off, n, g.knn, KP, c->nbr));
     if (sampling && c->n_pins > 0 && !reuse_graph)      // diagnostic: the pinned atoms of this reverse step take the given neighbour lists
         LAUNCH("knn", SMK(knn_pin_kernel, dim3(32), dim3(256), 0, s, c->pin_off, c->pin_steps, c->pin_atom, c->pin_nbr, c->pin_k, KP, c->steps + 1, n, c->nbr));
@@ -1160,38 +699,37 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
         const DevLayer &Dl = c->dm.layer[l];
         const bool last = (l == nlay - 1), has_next = !last;
         const bool phases = c->edge_bf16 && KP <= 16;
-        const bool f16 = c->edge_bf16 == 3;     // two-piece f16 operands (sm_edge16.h), the default
-        const bool stream = c->edge_bf16 == 2;      // exactly split bf16 operands, streaming kernels (sm_edge_stream.h)
+        const bool f16 = c->edge_bf16 == 3;         // two-piece f16 operands (sm_edge16.h), the fast optional kernels
+        const bool stream = c->edge_bf16 == 2;      // exactly split bf16 operands, streaming kernels (sm_edge_stream.h), the default
         const bool xc_fused = f16 && x2h_chain_ok<H>(c, n);
-        const bool half_tiles = (f16 || c->edge_bf16 == 2) && KP > 16;          // k > 16: two 16-slot tiles per atom + combine
+        const bool half_tiles = (f16 || stream) && KP > 16;          // k > 16: two 16-slot tiles per atom + combine
+        const float *pre_x = l == 0 ? c->pre0 : c->preAB + 4 * H;      // node pre-products of this x2h attention
+        const int ld_pre_x = l == 0 ? 4 * H : 8 * H;
+        unsigned long long *stamps_x = (c->kstamp_sel == 1 && l == 0) ? c->kstamps : nullptr;
         Edge16Args xea{};
-        if (f16) {   // x2h attention: both MLP images resident, one barrier
-            Edge16Args &ea = xea;
-            ea.image_k = c->P(Dl.i16_kx); ea.image_v = c->P(Dl.i16_vx);
-            ea.pre = l == 0 ? c->pre0 : c->preAB + 4 * H; ea.q = c->q_x; ea.x = cur_x; ea.nbr = c->nbr; ea.ew = c->ew; ea.out = c->att;
-            ea.n_atoms = n; ea.ld_pre = l == 0 ? 4 * H : 8 * H; ea.stamps = (c->kstamp_sel == 1 && l == 0) ? c->kstamps : nullptr;
-            ea.vf = pending; pending = VnFold{};
-            if (half_tiles) { ea.out = c->part_rows; ea.part_ms = c->part_ms; }       // k > 16: per-tile rows, merged below
-            if (!xc_fused && launch_edge16<H, false>(c, s, ea)) return 1;     // (fused: launched with the node stage below)
-            if (half_tiles && launch_combine32<false>(c, s, c->att, n)) return 1;
-        } else if (stream) {   // x2h attention, exactly split bf16 operands, producer / consumer waves (sm_edge_stream.h)
-            EdgeStreamArgs sa{};
-            sa.part_k = c->P(Dl.st_kx); sa.part_v = c->P(Dl.st_vx);
-            sa.w2k = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_kx)); sa.w2v = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_vx));
-            sa.b2v = c->P(Dl.sb2_vx);
-            sa.pre = l == 0 ? c->pre0 : c->preAB + 4 * H; sa.q = c->q_x; sa.x = cur_x; sa.nbr = c->nbr; sa.ew = c->ew; sa.out = c->att;
-            sa.n_atoms = n; sa.ld_pre = l == 0 ? 4 * H : 8 * H; sa.stamps = (c->kstamp_sel == 1 && l == 0) ? c->kstamps : nullptr;
-            sa.vf = pending; pending = VnFold{};
-            if (half_tiles) { sa.out = c->part_rows; sa.part_ms = c->part_ms; }       // k > 16: per-tile rows, merged below
-            if (launch_stream<H, false>(c, s, sa)) return 1;
+        if (f16 || stream) {   // x2h attention: two-piece f16 operands, both MLP images resident (sm_edge16.h), or exactly split bf16
+                               // operands, producer / consumer waves (sm_edge_stream.h); `pending`: the previous layer's coordinate update
+            if (f16) {
+                xea.image_k = c->P(Dl.i16_kx); xea.image_v = c->P(Dl.i16_vx);
+                fill_edge(xea, c, pre_x, ld_pre_x, c->q_x, cur_x, c->att, n, half_tiles, stamps_x);
+                xea.vf = pending;
+                if (!xc_fused && launch_edge16<H, false>(c, s, xea)) return 1;     // (fused: launched with the node stage below)
+            } else {
+                EdgeStreamArgs sa{};
+                sa.part_k = c->P(Dl.st_kx); sa.part_v = c->P(Dl.st_vx);
+                sa.w2k = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_kx)); sa.w2v = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_vx));
+                sa.b2v = c->P(Dl.sb2_vx);
+                fill_edge(sa, c, pre_x, ld_pre_x, c->q_x, cur_x, c->att, n, half_tiles, stamps_x);
+                sa.vf = pending;
+                if (launch_stream<H, false>(c, s, sa)) return 1;
+            }
+            pending = VnFold{};
             if (half_tiles && launch_combine32<false>(c, s, c->att, n)) return 1;
         } else if (phases && c->edge_bf16 == 1) {   // x2h attention, key and value phase in one launch
-            EdgeFusedArgs fa{c->P(Dl.img_kx), c->P(Dl.img_vx), l == 0 ? c->pre0 : c->preAB + 4 * H, c->q_x, cur_x, c->nbr, c->ew,
-                             c->alpha, c->att, n, l == 0 ? 4 * H : 8 * H, (c->kstamp_sel == 1 && l == 0) ? c->kstamps : nullptr};
+            EdgeFusedArgs fa{c->P(Dl.img_kx), c->P(Dl.img_vx), pre_x, c->q_x, cur_x, c->nbr, c->ew, c->alpha, c->att, n, ld_pre_x, stamps_x};
             if (launch_fused<H, false>(c, s, fa)) return 1;
         } else {   // x2h attention (fp32 MFMA kernels)
-            EdgeArgs e{c->P(Dl.blob_x2h), l == 0 ? c->pre0 : c->preAB + 4 * H, c->q_x, cur_x, c->nbr, c->ew, c->att, n,
-                       l == 0 ? 4 * H : 8 * H, (c->kstamp_sel == 1 && l == 0) ? c->kstamps : nullptr};
+            EdgeArgs e{c->P(Dl.blob_x2h), pre_x, c->q_x, cur_x, c->nbr, c->ew, c->att, n, ld_pre_x, stamps_x};
             if (launch_edge<H, false>(c, s, e)) return 1;
         }
         {   // node side: h' = h + MLP([att | h]); queries of h2x (this layer) and x2h (next layer) or the v head
@@ -1225,70 +763,36 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
         }
         float *x_next = (last && out_pos) ? out_pos : ((cur_x == c->x_a) ? c->x_b : c->x_a);
         bool vn_done = false, stats_done = false;
-        if (f16 && c->vn_fuse != 1) {   // h2x attention (+ VN-linear and batch statistics when vn_fuse = 2)
-            Edge16Args ea{};
-            ea.image_k = c->P(Dl.i16_kh); ea.image_v = c->P(Dl.i16_vh);
-            ea.pre = c->preAB; ea.q = c->q_h; ea.x = cur_x; ea.nbr = c->nbr; ea.ew = c->ew; ea.out = c->o3;
-            ea.n_atoms = n; ea.ld_pre = 8 * H; ea.stamps = (c->kstamp_sel == 2 && l == 0) ? c->kstamps : nullptr;
-            if (half_tiles) { ea.out = c->part_rows; ea.part_ms = c->part_ms; }       // (no fused VN-linear: vn_stats / vn_apply below)
-            if (c->vn_fuse && !half_tiles) {
-                ea.vn = {c->ps + (size_t)l * c->capB * 2 * hd * 3, c->P(Dl.wf_x), c->P(Dl.wd_x), c->P(Dl.wf_o), c->P(Dl.wd_o),
-                         c->P(Dl.bn_g), c->P(Dl.bn_b), c->mol_of, c->pd, c->bn_acc + (size_t)l * kBnReplicas * 2 * hd,
-                         nullptr, c->status + ST_VN_BARRIER, x_next, 2};
-                stats_done = true;
-                if (fold && has_next) {      // no vn_apply launch: the next x2h kernel finishes the update
-                    ea.xsum = c->xsum;
-                    pending = VnFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, x_next,
-                                     c->mol_span, c->status + ST_SPAN, 1};
-                    vn_done = true;
-                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->gg_points == 0 && c->m_nfaces == 0 && !cfg_on(c) && C <= 16 && hd <= 16) {
-                    // ... or, for the last layer of a chain step, the DDPM kernel
-                    ea.xsum = c->xsum;
-                    c->ddpm_vf = DdpmFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, out_pos, hd, 1};
-                    vn_done = true;
-                }
+        unsigned long long *stamps_h = (c->kstamp_sel == 2 && l == 0) ? c->kstamps : nullptr;
+        if ((f16 || stream) && c->vn_fuse != 1) {   // h2x attention (+ VN-linear and batch statistics when vn_fuse = 2)
+            const H2xPlan plan = h2x_plan(c, l, fold, has_next, half_tiles, stat_acc, cur_x, x_next, out_pos);
+            pending = plan.pending; stats_done = plan.stats_done; vn_done = plan.vn_done;
+            if (plan.ddpm.enable) c->ddpm_vf = plan.ddpm;
+            if (f16) {
+                Edge16Args ea{};
+                ea.image_k = c->P(Dl.i16_kh); ea.image_v = c->P(Dl.i16_vh);
+                fill_edge(ea, c, c->preAB, 8 * H, c->q_h, cur_x, c->o3, n, half_tiles, stamps_h);
+                ea.vn = plan.vn; ea.xsum = plan.xsum;
+                if (launch_edge16<H, true>(c, s, ea)) return 1;
+            } else {
+                EdgeStreamArgs sa{};
+                sa.part_k = c->P(Dl.st_kh); sa.part_v = c->P(Dl.st_vh);
+                sa.w2k = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_kh));
+                fill_edge(sa, c, c->preAB, 8 * H, c->q_h, cur_x, c->o3, n, half_tiles, stamps_h);
+                sa.vn = plan.vn; sa.xsum = plan.xsum;
+                if (launch_stream<H, true>(c, s, sa)) return 1;
             }
-            if (launch_edge16<H, true>(c, s, ea)) return 1;
-            if (half_tiles && launch_combine32<true>(c, s, c->o3, n)) return 1;
-        } else if (stream && c->vn_fuse != 1) {   // h2x attention (+ VN-linear and batch statistics when vn_fuse = 2), streaming kernel
-            EdgeStreamArgs sa{};
-            sa.part_k = c->P(Dl.st_kh); sa.part_v = c->P(Dl.st_vh);
-            sa.w2k = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_kh));
-            sa.pre = c->preAB; sa.q = c->q_h; sa.x = cur_x; sa.nbr = c->nbr; sa.ew = c->ew; sa.out = c->o3;
-            sa.n_atoms = n; sa.ld_pre = 8 * H; sa.stamps = (c->kstamp_sel == 2 && l == 0) ? c->kstamps : nullptr;
-            if (half_tiles) { sa.out = c->part_rows; sa.part_ms = c->part_ms; }       // (no fused VN-linear: vn_stats / vn_apply below)
-            if (c->vn_fuse && !half_tiles) {
-                sa.vn = {c->ps + (size_t)l * c->capB * 2 * hd * 3, c->P(Dl.wf_x), c->P(Dl.wd_x), c->P(Dl.wf_o), c->P(Dl.wd_o),
-                         c->P(Dl.bn_g), c->P(Dl.bn_b), c->mol_of, c->pd, c->bn_acc + (size_t)l * kBnReplicas * 2 * hd,
-                         nullptr, c->status + ST_VN_BARRIER, x_next, 2};
-                stats_done = true;
-                if (fold && has_next) {      // no vn_apply launch: the next x2h kernel finishes the update
-                    sa.xsum = c->xsum;
-                    pending = VnFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, x_next,
-                                     c->mol_span, c->status + ST_SPAN, 1};
-                    vn_done = true;
-                } else if (fold && last && l == L - 1 && out_pos && c->ddpm_fold && c->g_points == 0 && c->gg_points == 0 && c->m_nfaces == 0 && !cfg_on(c) && C <= 16 && hd <= 16) {
-                    sa.xsum = c->xsum;
-                    c->ddpm_vf = DdpmFold{c->pd, stat_acc + (size_t)l * kBnReplicas * 2 * hd, c->P(Dl.bn_g), c->P(Dl.bn_b), c->xsum, cur_x, out_pos, hd, 1};
-                    vn_done = true;
-                }
-            }
-            if (launch_stream<H, true>(c, s, sa)) return 1;
             if (half_tiles && launch_combine32<true>(c, s, c->o3, n)) return 1;
         } else if (phases) {   // h2x attention, both images resident in LDS (exactly split bf16 operands)
-            EdgeFusedArgs fa{c->P(Dl.img_kh), c->P(Dl.img_vh), c->preAB, c->q_h, cur_x, c->nbr, c->ew, c->alpha, c->o3, n, 8 * H,
-                             (c->kstamp_sel == 2 && l == 0) ? c->kstamps : nullptr};
+            EdgeFusedArgs fa{c->P(Dl.img_kh), c->P(Dl.img_vh), c->preAB, c->q_h, cur_x, c->nbr, c->ew, c->alpha, c->o3, n, 8 * H, stamps_h};
             if (c->vn_fuse) {   // VN-linear + batch statistics (2) or the whole coordinate update (1: grid barrier inside) behind the attention
                 double *tail = c->bn_acc + (size_t)L * kBnReplicas * 2 * hd;
-                fa.vn = {c->ps + (size_t)l * c->capB * 2 * hd * 3, c->P(Dl.wf_x), c->P(Dl.wd_x), c->P(Dl.wf_o), c->P(Dl.wd_o),
-                         c->P(Dl.bn_g), c->P(Dl.bn_b), c->mol_of, c->pd, c->bn_acc + (size_t)l * kBnReplicas * 2 * hd,
-                         reinterpret_cast<unsigned *>(tail + l), c->status + ST_VN_BARRIER, x_next, c->vn_fuse == 1 ? 1 : 2};
+                fa.vn = vn_fuse_args(c, l, x_next, reinterpret_cast<unsigned *>(tail + l), c->vn_fuse == 1 ? 1 : 2);
                 if (c->vn_fuse == 1) vn_done = true; else stats_done = true;
             }
             if (launch_fused<H, true>(c, s, fa)) return 1;
         } else {   // h2x attention (fp32 MFMA kernels)
-            EdgeArgs e{c->P(Dl.blob_h2x), c->preAB, c->q_h, cur_x, c->nbr, c->ew, c->o3, n, 8 * H,
-                       (c->kstamp_sel == 2 && l == 0) ? c->kstamps : nullptr};
+            EdgeArgs e{c->P(Dl.blob_h2x), c->preAB, c->q_h, cur_x, c->nbr, c->ew, c->o3, n, 8 * H, stamps_h};
             if (launch_edge<H, true>(c, s, e)) return 1;
         }
         VnArgs va{cur_x, c->o3, c->ps + (size_t)l * c->capB * 2 * hd * 3, c->P(Dl.wf_x), c->P(Dl.wd_x), c->P(Dl.wf_o),
@@ -1371,48 +875,10 @@ int shapemol_create(const shapemol_config *cfg, const float *weights, size_t n_w
     HIPCHK(hipGetDeviceProperties(&prop, device));
     c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 
-    const int H = cfg->hidden_dim, C = cfg->num_classes, T = cfg->num_timesteps;
     Image im;
-    DevModel &dm = c->dm;
-    for (int i = 0; i < 7; ++i) dm.tab[i] = im.put(hm.tab[i], T);
-    dm.te1w = im.put(hm.te1.w, (size_t)hm.te1.out * hm.te1.in); dm.te1b = im.put(hm.te1.b, hm.te1.out);
-    dm.te2w = im.put(hm.te2.w, (size_t)hm.te2.out * hm.te2.in); dm.te2b = im.put(hm.te2.b, hm.te2.out);
-    dm.embw = im.put(hm.emb.w, (size_t)hm.emb.out * hm.emb.in); dm.embb = im.put(hm.emb.b, hm.emb.out);
-    dm.embwT = im.alloc((size_t)hm.emb.in * hm.emb.out);          // [C + D][H]
-    for (int f = 0; f < hm.emb.out; ++f)
-        for (int k = 0; k < hm.emb.in; ++k) im.d[dm.embwT + (size_t)k * hm.emb.out + f] = hm.emb.w[(size_t)f * hm.emb.in + k];
-    auto put_mlp = [&](const Mlp &m) {
-        DevMlp d;
-        d.w1 = im.put(m.l1.w, (size_t)m.l1.out * m.l1.in); d.b1 = im.put(m.l1.b, m.l1.out);
-        d.g = im.put(m.g, m.l1.out); d.be = im.put(m.be, m.l1.out);
-        d.w2 = im.put(m.l2.w, (size_t)m.l2.out * m.l2.in); d.b2 = im.put(m.l2.b, m.l2.out);
-        return d;
-    };
-    dm.ew = put_mlp(hm.ew);
-    dm.inv = put_mlp(hm.inv);
-    {
-        Mlp vh; vh.l1 = hm.v1; vh.l2 = hm.v2; vh.g = nullptr; vh.be = nullptr;
-        dm.vhead = put_mlp_img(im, vh);
-    }
-    dm.layer.resize(cfg->num_layers);
-    for (int l = 0; l < cfg->num_layers; ++l) {
-        if (H == 128 ? build_layer_image<128>(*cfg, hm.layer[l], im, dm.layer[l], c->hid_max)
-                     : build_layer_image<32>(*cfg, hm.layer[l], im, dm.layer[l], c->hid_max)) { delete c; return 1; }
-    }
-    for (int l = 0; l < cfg->num_layers; ++l) {      // paired images: pre_h2x(l) | pre_x2h(l + 1)
-        const size_t blk = (size_t)4 * H * H;
-        const size_t o = im.alloc(2 * blk);
-        std::memcpy(&im.d[o], &im.d[dm.layer[l].pre_h2x], blk * sizeof(float));
-        if (l + 1 < cfg->num_layers) std::memcpy(&im.d[o + blk], &im.d[dm.layer[l + 1].pre_x2h], blk * sizeof(float));
-        dm.layer[l].lin_img = o;
-    }
-    for (int l = 0; l < cfg->num_layers; ++l) {
-        dm.layer[l].lin6_img = pack_linear6_image(im, dm.layer[l].lin_img, 8 * H, H);
-        dm.layer[l].pre6_x2h = l == 0 ? pack_linear6_image(im, dm.layer[l].pre_x2h, 4 * H, H) : 0;
-        dm.layer[l].lin16_img = pack_linear16_image(im, dm.layer[l].lin_img, 8 * H, H);
-        dm.layer[l].pre16_x2h = l == 0 ? pack_linear16_image(im, dm.layer[l].pre_x2h, 4 * H, H) : 0;
-    }
-    im.alloc(64);
+    if (build_model_image(*cfg, hm, im, c->dm, c->hid_max)) { delete c; return 1; }
+    const DevModel &dm = c->dm;
+    const int H = cfg->hidden_dim, T = cfg->num_timesteps;
     if (hipMalloc((void **)&c->d_img, im.d.size() * sizeof(float)) != hipSuccess) { delete c; return fail("hipMalloc(weights) failed"); }
     if (hipMemcpy(c->d_img, im.d.data(), im.d.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { hipFree(c->d_img); delete c; return fail("hipMemcpy(weights) failed"); }
     if (H == 128 ? set_edge_attr<128>(c->KP) : set_edge_attr<32>(c->KP)) { hipFree(c->d_img); delete c; return 1; }
@@ -1472,104 +938,6 @@ int shapemol_set_bn_running(shapemol_ctx *c, const float *h_mean, const float *h
     return 0;
 }
 
-// ---- point-cloud guidance per group of molecules: host side
-// workgroups of pc_guidance_groups_kernel: the sum over the groups of ceil(n_g / 16) is at most floor(N / 16) + G
-static unsigned groups_grid(const shapemol_ctx *c, int64_t N) { return (unsigned)(N / 16 + c->gg_groups); }
-
-static PcGroupsArgs groups_args(const shapemol_ctx *c, float *d_pos, int64_t N, const int *step_cur, int t_first) {
-    const int G1 = c->gg_groups + 1;
-    PcGroupsArgs a{};
-    a.pred_pos = d_pos; a.clouds = c->gg_clouds; a.cloud_off = c->gg_ints + G1; a.radius = c->gg_radius; a.atom_off = c->gg_ints + 2 * G1;
-    a.wg_table = c->gg_table; a.cp = c->chain_params; a.step_cur = step_cur;
-    a.n_atoms = (int)N; a.t_first = t_first; a.grad_step = c->gg_grad_step; a.ratio = 0.2;
-    return a;
-}
-
-// the per-workgroup table of this chain (atom ranges come from the batch vector on the device)
-static int groups_table(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N) {
-    const int64_t n_wg = groups_grid(c, N);
-    if (n_wg > c->gg_table_cap) {
-        c->drop_graphs();                        // a captured step holds the table's address
-        if (c->gg_table) { hipFree(c->gg_table); c->gg_table = nullptr; }
-        c->gg_table_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->gg_table, (size_t)n_wg * sizeof(int2)));
-        c->gg_table_cap = n_wg;
-    }
-    const int G1 = c->gg_groups + 1;
-    LAUNCH("prep", SMK(pc_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, c->gg_ints, c->gg_ints + G1, c->gg_groups,
-                       c->gg_ints + 2 * G1, c->gg_ints + 3 * G1, c->gg_table, (int)n_wg));
-    return 0;
-}
-
-// ---- mesh shape guidance: host side
-// Validates the mesh and the cloud and builds the device image [faces F | face boxes F | cloud P] (vertices projected once,
-// in the same operations as the device's mesh_project); bounds = (umin, umax, vmin, vmax, wmax) of the projected mesh.
-static int mesh_image(const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces, const double *h_cloud,
-                      int64_t n_cloud, const char *who, std::vector<unsigned char> &img, double (&bounds)[5]) {
-    if (!h_verts || !h_faces || !h_cloud) return fail(std::string(who) + ": vertices, faces and cloud are required");
-    if (n_verts < 3 || n_verts > (1 << 26)) return fail(std::string(who) + ": the mesh needs 3 .. 2^26 vertices");
-    if (n_faces < 1 || n_faces > (1 << 24)) return fail(std::string(who) + ": the mesh needs 1 .. 2^24 faces");
-    if (n_cloud < 3 || n_cloud > 2048) return fail(std::string(who) + ": the cloud needs 3 .. 2048 points (it is staged in LDS)");
-    std::vector<double> pu(n_verts), pv(n_verts), pw(n_verts);
-    for (int64_t i = 0; i < n_verts; ++i) {
-        const double x = h_verts[i * 3], y = h_verts[i * 3 + 1], z = h_verts[i * 3 + 2];
-        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) return fail(std::string(who) + ": a vertex is not finite");
-        mesh_project(x, y, z, pu[i], pv[i], pw[i]);
-    }
-    for (int64_t i = 0; i < n_cloud * 3; ++i)
-        if (!std::isfinite(h_cloud[i])) return fail(std::string(who) + ": a cloud point is not finite");
-    const size_t fb = (size_t)n_faces * sizeof(MeshFace), bb = (size_t)n_faces * sizeof(double4), cb = (size_t)n_cloud * 24;
-    img.assign(fb + bb + cb, 0);
-    MeshFace *faces = reinterpret_cast<MeshFace *>(img.data());
-    double4 *box = reinterpret_cast<double4 *>(img.data() + fb);
-    std::memcpy(img.data() + fb + bb, h_cloud, cb);
-    bounds[0] = bounds[2] = INFINITY; bounds[1] = bounds[3] = bounds[4] = -INFINITY;
-    for (int64_t f = 0; f < n_faces; ++f) {
-        const int32_t *ix = h_faces + f * 3;
-        for (int k = 0; k < 3; ++k)
-            if (ix[k] < 0 || ix[k] >= n_verts) return fail(std::string(who) + ": face " + std::to_string(f) + " names a vertex outside [0, n_verts)");
-        if (ix[0] == ix[1] || ix[1] == ix[2] || ix[2] == ix[0]) return fail(std::string(who) + ": face " + std::to_string(f) + " repeats a vertex");
-        MeshFace &m = faces[f];
-        double4 &b = box[f];
-        b = make_double4(INFINITY, -INFINITY, INFINITY, -INFINITY);
-        m.canon = 0;
-        for (int k = 0; k < 3; ++k) {
-            m.u[k] = pu[ix[k]]; m.v[k] = pv[ix[k]]; m.w[k] = pw[ix[k]];
-            if (ix[k] < ix[k == 2 ? 0 : k + 1]) m.canon |= 1 << k;
-            b.x = std::min(b.x, m.u[k]); b.y = std::max(b.y, m.u[k]); b.z = std::min(b.z, m.v[k]); b.w = std::max(b.w, m.v[k]);
-            bounds[4] = std::max(bounds[4], m.w[k]);
-        }
-        bounds[0] = std::min(bounds[0], b.x); bounds[1] = std::max(bounds[1], b.y);
-        bounds[2] = std::min(bounds[2], b.z); bounds[3] = std::max(bounds[3], b.w);
-    }
-    return 0;
-}
-
-static MeshGuideArgs mesh_args(const shapemol_ctx *c, float *pos, int64_t N, const int *step_cur, int t_first) {
-    MeshGuideArgs a{};
-    a.pred_pos = pos; a.cloud = c->m_cloud; a.faces = c->m_faces; a.fbox = c->m_fbox;
-    a.within = c->m_within; a.out_list = c->m_out; a.cnt = c->m_cnt; a.status = c->status; a.cp = c->chain_params;
-    a.step_cur = step_cur; a.n_atoms = (int)N; a.n_points = (int)c->m_points; a.n_faces = (int)c->m_nfaces;
-    a.t_first = t_first; a.grad_step = c->m_grad_step;
-    a.umin = c->m_bounds[0]; a.umax = c->m_bounds[1]; a.vmin = c->m_bounds[2]; a.vmax = c->m_bounds[3]; a.wmax = c->m_bounds[4];
-    return a;
-}
-
-// the per-step lists of mesh guidance for N atoms: [within N | outmesh N | counters 4]
-static int mesh_workspace(shapemol_ctx *c, int64_t N) {
-    if (N <= c->m_cap) return 0;
-    c->drop_graphs();                            // the captured steps point into the old block
-    HIPCHK(hipDeviceSynchronize());
-    if (c->m_within) { hipFree(c->m_within); c->m_within = nullptr; c->m_out = c->m_cnt = nullptr; c->m_cap = 0; }
-    unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, (size_t)N * 20 + 16));
-    c->m_within = reinterpret_cast<float4 *>(blk);
-    c->m_out = reinterpret_cast<int *>(blk + (size_t)N * 16);
-    c->m_cnt = reinterpret_cast<int *>(blk + (size_t)N * 20);
-    c->m_cap = N;
-    return 0;
-}
-
 int shapemol_reserve(shapemol_ctx *c, int64_t max_atoms, int64_t max_mols) {
     if (!c || max_atoms < 1 || max_mols < 1) return fail("shapemol_reserve: bad argument");
     return ensure_workspace(c, max_atoms, max_mols);
@@ -1604,16 +972,15 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     hipStream_t s = (hipStream_t)stream;
     c->lastN = N; c->lastB = B;
     const int t_first = c->cfg.num_timesteps - 1;
-    const bool mesh = c->m_nfaces > 0;          // mesh guidance takes precedence over the point cloud (molopt_score_model.py:571)
+    const Guide kind = chain_guide(c);
+    const bool mesh = kind == Guide::Mesh, cfg = kind == Guide::Cfg;
     if (mesh && mesh_workspace(c, N)) return 1;
-    const bool groups = !mesh && c->gg_groups > 0;
-    if (c->gg_groups > 0 && c->gg_mols != B)
+    if (c->gg_groups > 0 && c->gg_mols != B)        // (groups that are set must fit the batch even where another kind, or none, guides)
         return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the guidance groups cover " + std::to_string(c->gg_mols) + " molecules");
-    if (groups && c->gg_points > 0 && groups_table(c, s, d_batch, N)) return 1;
+    if (kind == Guide::Groups && groups_table(c, s, d_batch, N)) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
     if (mesh) HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
     if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
-    const bool cfg = cfg_on(c);
     if (cfg) {      // classifier-free guidance: the unconditional evaluation's shape data, from a zeroed shape, once per chain
         swap_uncond(c);
         const int rc = DISPATCH_H(c, run_prep_shape<128>(c, s, B, c->shape_zero), run_prep_shape<32>(c, s, B, c->shape_zero));
@@ -1624,7 +991,7 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_init_v, (int)N, c->cfg.num_classes, c->status));
     {
         ChainParams cp{};
-        cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->m_draws : (groups ? c->gg_draws : c->g_draws);
+        cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->m_draws : (c->gg_groups > 0 ? c->gg_draws : c->g_draws);
         if (traj) { cp.tr_pos = traj->pos_traj; cp.tr_v = traj->v_traj; cp.tr_v0 = traj->v0_traj; cp.tr_vt = traj->vt_traj;
                     cp.tr_pos_cond = traj->pos_cond_traj; cp.tr_v_cond = traj->v_cond_traj; }
         if (cfg) { cp.tr_pos_uncond = c->cfg_tr_pos_u; cp.tr_v_uncond = c->cfg_tr_v_u; }
@@ -1642,23 +1009,12 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
             swap_uncond(c);
             if (rc || run_cfg_stats(c, s, cfg_args(c, N))) return 1;
         }
-        if (mesh) {                // mesh shape guidance of the predicted x0 (steps with t > grad_step)
-            const MeshGuideArgs ma = mesh_args(c, c->pred_pos, N, c->steps + 1, t_first);
-            const dim3 grid((unsigned)((N * 16 + 255) / 256));
-            LAUNCH("mesh_classify", SMK(mesh_classify_kernel, grid, dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
-            LAUNCH("mesh_pull", SMK(mesh_pull_kernel, grid, dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
-        } else if (c->g_points > 0) {     // point-cloud shape guidance of the predicted x0 (steps with t > grad_step)
-            PcGuideArgs ga{c->pred_pos, c->g_cloud, c->chain_params, c->steps + 1, (int)N, (int)c->g_points, t_first, c->g_grad_step, c->g_radius, 0.2};
-            LAUNCH("pc_guidance", SMK(pc_guidance_kernel, dim3((N * 16 + 255) / 256), dim3(256), (size_t)c->g_points * 24, s, ga));
-        } else if (groups && c->gg_points > 0) {     // the same per group of molecules, each group towards its own cloud
-            const PcGroupsArgs ga = groups_args(c, c->pred_pos, N, c->steps + 1, t_first);
-            LAUNCH("pc_guidance_groups", SMK(pc_guidance_groups_kernel, dim3(groups_grid(c, N)), dim3(256), (size_t)c->gg_max_points * 24, s, ga));
-        }
+        if (enqueue_guidance(c, s, kind, c->pred_pos, N, c->steps + 1, t_first)) return 1;     // shape guidance of the predicted x0 (steps with t > grad_step)
         return DISPATCH_H(c, run_ddpm<128>(c, s, N), run_ddpm<32>(c, s, N));
     };
     if (use_graph && !c->prof_on) {
         shapemol_ctx::GraphKey key{};
-        key.N = N; key.B = B; key.guided = mesh ? 2 : (groups && c->gg_points > 0 ? 3 : (c->g_points > 0 ? 1 : 0)); key.fold = vn_fold_ok(c, (int)N);
+        key.N = N; key.B = B; key.guide = kind; key.fold = vn_fold_ok(c, (int)N);
         key.gfuse = c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && c->n_pins == 0;
         if (cfg) {
             key.cfg = 1 + c->cfg_type;
@@ -1814,89 +1170,6 @@ int shapemol_set_knn_pins(shapemol_ctx *c, const int32_t *h_off, int32_t n_steps
     return 0;
 }
 
-static void groups_clear(shapemol_ctx *c) {
-    if (c->gg_clouds) { hipFree(c->gg_clouds); c->gg_clouds = nullptr; }
-    c->gg_radius = nullptr; c->gg_ints = nullptr;
-    c->gg_groups = 0; c->gg_max_points = 0; c->gg_mols = 0; c->gg_points = 0; c->gg_draws = nullptr;
-}
-
-int shapemol_set_guidance(shapemol_ctx *c, const double *h_cloud, int64_t n_points, double radius, int32_t grad_step, const double *d_draws) {
-    if (!c) return fail("shapemol_set_guidance: null ctx");
-    if (n_points < 0 || n_points > 2048 || (n_points > 0 && n_points < 3)) return fail("shapemol_set_guidance: the cloud needs 3 .. 2048 points (it is staged in LDS)");
-    if (n_points > 0 && (!h_cloud || !(radius > 0.0))) return fail("shapemol_set_guidance: cloud / radius missing");
-    HIPCHK(hipSetDevice(c->device));
-    c->drop_graphs();                            // also drains the device: the old cloud may still be in use
-    if (c->g_cloud) { hipFree(c->g_cloud); c->g_cloud = nullptr; }
-    c->g_points = 0; c->g_draws = nullptr;
-    if (n_points == 0) return 0;
-    groups_clear(c);                             // a single cloud replaces clouds per group
-    HIPCHK(hipMalloc((void **)&c->g_cloud, (size_t)n_points * 3 * sizeof(double)));
-    HIPCHK(hipMemcpy(c->g_cloud, h_cloud, (size_t)n_points * 3 * sizeof(double), hipMemcpyHostToDevice));
-    c->g_points = n_points; c->g_radius = radius; c->g_grad_step = grad_step; c->g_draws = d_draws;
-    return 0;
-}
-
-int shapemol_set_guidance_groups(shapemol_ctx *c, int32_t n_groups, const int64_t *h_mol_off, const double *h_clouds, const int64_t *h_cloud_off,
-                                 const double *h_radius, int32_t grad_step, const double *d_draws) {
-    const std::string me = "shapemol_set_guidance_groups: ";
-    if (!c) return fail(me + "null ctx");
-    if (n_groups < 0 || n_groups > (1 << 20)) return fail(me + "n_groups out of range");
-    if (n_groups > 0) {
-        if (!h_mol_off || !h_cloud_off || !h_radius) return fail(me + "offsets / radii missing");
-        if (h_mol_off[0] != 0 || h_cloud_off[0] != 0) return fail(me + "group 0: the molecule and cloud offsets must start at 0");
-        for (int g = 0; g < n_groups; ++g) {
-            const std::string grp = me + "group " + std::to_string(g) + ": ";
-            if (h_mol_off[g + 1] < h_mol_off[g]) return fail(grp + "the molecule offsets decrease");
-            if (h_cloud_off[g + 1] < h_cloud_off[g]) return fail(grp + "the cloud offsets decrease");
-            const int64_t p = h_cloud_off[g + 1] - h_cloud_off[g];
-            if (p > 0 && (p < 3 || p > 2048)) return fail(grp + "the cloud needs 3 .. 2048 points (it is staged in LDS), or none");
-            if (p > 0 && !(h_radius[g] > 0.0)) return fail(grp + "the radius must be > 0");
-        }
-        if (h_mol_off[n_groups] > (1 << 27)) return fail(me + "too many molecules");
-        if (h_cloud_off[n_groups] > 0 && !h_clouds) return fail(me + "clouds missing");
-    }
-    HIPCHK(hipSetDevice(c->device));
-    c->drop_graphs();                            // also drains the device: the old clouds may still be in use
-    groups_clear(c);
-    if (n_groups == 0) return 0;
-    if (c->g_cloud) { hipFree(c->g_cloud); c->g_cloud = nullptr; }      // clouds per group replace a single cloud
-    c->g_points = 0; c->g_draws = nullptr;
-    const int G1 = n_groups + 1;
-    const int64_t P = h_cloud_off[n_groups];
-    std::vector<double> hd((size_t)P * 3 + n_groups);
-    if (P) std::copy(h_clouds, h_clouds + P * 3, hd.begin());
-    std::copy(h_radius, h_radius + n_groups, hd.begin() + P * 3);
-    std::vector<int> hi((size_t)4 * G1, 0);       // mol_off | cloud_off | atom_off | wg_off (the last two are written on the device)
-    int max_points = 0;
-    for (int g = 0; g < G1; ++g) { hi[g] = (int)h_mol_off[g]; hi[G1 + g] = (int)h_cloud_off[g]; }
-    for (int g = 0; g < n_groups; ++g) max_points = std::max(max_points, hi[G1 + g + 1] - hi[G1 + g]);
-    const size_t bytes_d = hd.size() * sizeof(double), bytes_i = hi.size() * sizeof(int);
-    HIPCHK(hipMalloc((void **)&c->gg_clouds, bytes_d + bytes_i));
-    HIPCHK(hipMemcpy(c->gg_clouds, hd.data(), bytes_d, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy((char *)c->gg_clouds + bytes_d, hi.data(), bytes_i, hipMemcpyHostToDevice));
-    c->gg_radius = c->gg_clouds + P * 3; c->gg_ints = (int *)((char *)c->gg_clouds + bytes_d);
-    c->gg_groups = n_groups; c->gg_max_points = max_points; c->gg_mols = h_mol_off[n_groups]; c->gg_points = P;
-    c->gg_grad_step = grad_step; c->gg_draws = d_draws;
-    return 0;
-}
-
-int shapemol_guide_points_groups(shapemol_ctx *c, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws, uint64_t seed,
-                                 void *stream) {
-    if (!c || !d_pos || !d_batch || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_groups: bad argument");
-    if (c->gg_groups <= 0) return fail("shapemol_guide_points_groups: no groups set (shapemol_set_guidance_groups)");
-    HIPCHK(hipSetDevice(c->device));
-    if (ensure_workspace(c, N, 1)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (c->gg_points == 0) return 0;             // no group has a cloud: nothing moves
-    if (groups_table(c, s, d_batch, N)) return 1;
-    ChainParams cp{};
-    cp.seed = seed; cp.guide_draws = d_draws; cp.step_base = 0;
-    LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, cp, c->steps));
-    const PcGroupsArgs ga = groups_args(c, d_pos, N, nullptr, c->gg_grad_step + 1);
-    LAUNCH("pc_guidance_groups", SMK(pc_guidance_groups_kernel, dim3(groups_grid(c, N)), dim3(256), (size_t)c->gg_max_points * 24, s, ga));
-    return 0;
-}
-
 int shapemol_set_cfg(shapemol_ctx *c, double guide_stren, int32_t threshold_type, double p, const double *h_bounds,
                      float *d_pos_uncond_traj, float *d_v_uncond_traj) {
     if (!c) return fail("shapemol_set_cfg: null ctx");
@@ -1910,138 +1183,6 @@ int shapemol_set_cfg(shapemol_ctx *c, double guide_stren, int32_t threshold_type
     }
     c->cfg_tr_pos_u = guide_stren != 0.0 ? d_pos_uncond_traj : nullptr;
     c->cfg_tr_v_u = guide_stren != 0.0 ? d_v_uncond_traj : nullptr;
-    return 0;
-}
-
-int shapemol_guide_points(shapemol_ctx *c, float *d_pos, int64_t N, const double *d_draws, uint64_t seed, void *stream) {
-    if (!c || !d_pos || N < 1) return fail("shapemol_guide_points: bad argument");
-    if (c->g_points <= 0) return fail("shapemol_guide_points: no cloud set (shapemol_set_guidance)");
-    HIPCHK(hipSetDevice(c->device));
-    if (ensure_workspace(c, std::max<int64_t>(N, 1), 1)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    ChainParams cp{};
-    cp.seed = seed; cp.guide_draws = d_draws; cp.step_base = 0;
-    LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, cp, c->steps));
-    PcGuideArgs ga{d_pos, c->g_cloud, c->chain_params, nullptr, (int)N, (int)c->g_points, c->g_grad_step + 1, c->g_grad_step, c->g_radius, 0.2};
-    LAUNCH("pc_guidance", SMK(pc_guidance_kernel, dim3((N * 16 + 255) / 256), dim3(256), (size_t)c->g_points * 24, s, ga));
-    return 0;
-}
-
-int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_points, double radius, double ratio, float *d_pos, int64_t N,
-                                 const double *d_draws, uint64_t seed, void *stream) {
-    if (!h_cloud || !d_pos || N < 1) return fail("shapemol_pointcloud_guidance: bad argument");
-    if (n_points < 3 || n_points > 2048) return fail("shapemol_pointcloud_guidance: the cloud needs 3 .. 2048 points (it is staged in LDS)");
-    if (!(radius > 0.0) || !(ratio >= 0.0 && ratio < 0.8)) return fail("shapemol_pointcloud_guidance: radius must be > 0, ratio in [0, 0.8)");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t cloud_bytes = (size_t)n_points * 3 * sizeof(double);
-    unsigned char *blk = nullptr;                       // [cloud | ChainParams | step counter]
-    HIPCHK(hipMalloc((void **)&blk, cloud_bytes + sizeof(ChainParams) + 16));
-    double *d_cloud = reinterpret_cast<double *>(blk);
-    ChainParams *d_cp = reinterpret_cast<ChainParams *>(blk + cloud_bytes);
-    int *d_step = reinterpret_cast<int *>(blk + cloud_bytes + sizeof(ChainParams));
-    hipError_t e = hipMemcpyAsync(d_cloud, h_cloud, cloud_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        ChainParams cp{};
-        cp.seed = seed; cp.guide_draws = d_draws; cp.step_base = 0;
-        hipLaunchKernelGGL(set_chain_params_kernel, dim3(1), dim3(1), 0, s, d_cp, cp, d_step);
-        PcGuideArgs ga{d_pos, d_cloud, d_cp, nullptr, (int)N, (int)n_points, 1, 0, radius, ratio};      // t_first - 0 > grad_step: always guided
-        hipLaunchKernelGGL(pc_guidance_kernel, dim3((N * 16 + 255) / 256), dim3(256), (size_t)n_points * 24, s, ga);
-        e = hipGetLastError();
-    }
-    const hipError_t e2 = hipStreamSynchronize(s);       // the block is freed below; the reference's function is synchronous too
-    hipFree(blk);
-    if (e != hipSuccess) return fail(std::string("shapemol_pointcloud_guidance: ") + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(std::string("shapemol_pointcloud_guidance: ") + hipGetErrorString(e2));
-    return 0;
-}
-
-int shapemol_set_mesh_guidance(shapemol_ctx *c, const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces,
-                               const double *h_cloud, int64_t n_cloud, int32_t grad_step, const double *d_draws) {
-    if (!c) return fail("shapemol_set_mesh_guidance: null ctx");
-    if (n_faces < 0) return fail("shapemol_set_mesh_guidance: n_faces < 0");
-    std::vector<unsigned char> img;
-    double bounds[5];
-    if (n_faces > 0 && mesh_image(h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, "shapemol_set_mesh_guidance", img, bounds)) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    c->drop_graphs();                            // also drains the device: the old mesh may still be in use
-    if (c->m_faces) { hipFree(c->m_faces); c->m_faces = nullptr; c->m_fbox = nullptr; c->m_cloud = nullptr; }
-    c->m_nfaces = 0; c->m_points = 0; c->m_draws = nullptr;
-    if (n_faces == 0) return 0;
-    unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, img.size()));
-    HIPCHK(hipMemcpy(blk, img.data(), img.size(), hipMemcpyHostToDevice));
-    c->m_faces = reinterpret_cast<MeshFace *>(blk);
-    c->m_fbox = reinterpret_cast<double4 *>(blk + (size_t)n_faces * sizeof(MeshFace));
-    c->m_cloud = reinterpret_cast<double *>(blk + (size_t)n_faces * (sizeof(MeshFace) + sizeof(double4)));
-    std::memcpy(c->m_bounds, bounds, sizeof(bounds));
-    c->m_nfaces = n_faces; c->m_points = n_cloud; c->m_grad_step = grad_step; c->m_draws = d_draws;
-    return 0;
-}
-
-int shapemol_guide_points_mesh(shapemol_ctx *c, float *d_pos, int64_t N, const double *d_draws, uint64_t seed, void *stream) {
-    if (!c || !d_pos || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_mesh: bad argument");
-    if (c->m_nfaces <= 0) return fail("shapemol_guide_points_mesh: no mesh set (shapemol_set_mesh_guidance)");
-    HIPCHK(hipSetDevice(c->device));
-    if (ensure_workspace(c, std::max<int64_t>(N, 1), 1) || mesh_workspace(c, N)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
-    HIPCHK(hipMemsetAsync(c->status + ST_MESH, 0, sizeof(int), s));
-    ChainParams cp{};
-    cp.seed = seed; cp.guide_draws = d_draws; cp.step_base = 0;
-    LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, cp, c->steps));
-    const MeshGuideArgs ma = mesh_args(c, d_pos, N, nullptr, c->m_grad_step + 1);
-    const dim3 grid((unsigned)((N * 16 + 255) / 256));
-    LAUNCH("mesh_classify", SMK(mesh_classify_kernel, grid, dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
-    LAUNCH("mesh_pull", SMK(mesh_pull_kernel, grid, dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
-    return 0;
-}
-
-int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces, const double *h_cloud,
-                           int64_t n_cloud, float *d_pos, int64_t N, const double *d_draws, uint64_t seed, int32_t *flag_out,
-                           void *stream) {
-    if (flag_out) *flag_out = 0;
-    if (!d_pos || N < 1 || N > (1 << 27)) return fail("shapemol_mesh_guidance: bad argument");
-    std::vector<unsigned char> img;
-    double bounds[5];
-    if (mesh_image(h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, "shapemol_mesh_guidance", img, bounds)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    // [mesh image | ChainParams | step counter, status [8], counters [4] | within N | outmesh N]
-    const size_t o_cp = (img.size() + 255) / 256 * 256, o_st = o_cp + (sizeof(ChainParams) + 255) / 256 * 256;
-    const size_t o_in = o_st + 256, o_out = o_in + (size_t)N * 16, total = o_out + (size_t)N * 4;
-    unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, total));
-    int *d_misc = reinterpret_cast<int *>(blk + o_st);        // [0] step counter, [4 .. 11] status, [16 .. 19] counters
-    hipError_t e = hipMemcpyAsync(blk, img.data(), img.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_misc, 0, 256, s);
-    int32_t flag = 0;
-    if (e == hipSuccess) {
-        ChainParams cp{};
-        cp.seed = seed; cp.guide_draws = d_draws; cp.step_base = 0;
-        ChainParams *d_cp = reinterpret_cast<ChainParams *>(blk + o_cp);
-        hipLaunchKernelGGL(set_chain_params_kernel, dim3(1), dim3(1), 0, s, d_cp, cp, d_misc);
-        MeshGuideArgs a{};
-        a.pred_pos = d_pos; a.faces = reinterpret_cast<const MeshFace *>(blk);
-        a.fbox = reinterpret_cast<const double4 *>(blk + (size_t)n_faces * sizeof(MeshFace));
-        a.cloud = reinterpret_cast<const double *>(blk + (size_t)n_faces * (sizeof(MeshFace) + sizeof(double4)));
-        a.within = reinterpret_cast<float4 *>(blk + o_in); a.out_list = reinterpret_cast<int *>(blk + o_out);
-        a.cnt = d_misc + 16; a.status = d_misc + 4; a.cp = d_cp; a.step_cur = nullptr;
-        a.n_atoms = (int)N; a.n_points = (int)n_cloud; a.n_faces = (int)n_faces; a.t_first = 1; a.grad_step = 0;   // always guided
-        a.umin = bounds[0]; a.umax = bounds[1]; a.vmin = bounds[2]; a.vmax = bounds[3]; a.wmax = bounds[4];
-        const dim3 grid((unsigned)((N * 16 + 255) / 256));
-        hipLaunchKernelGGL(mesh_classify_kernel, grid, dim3(256), mesh_lds_bytes((int)n_cloud), s, a);
-        hipLaunchKernelGGL(mesh_pull_kernel, grid, dim3(256), mesh_lds_bytes((int)n_cloud), s, a);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_misc + 4 + ST_MESH, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    }
-    const hipError_t e2 = hipStreamSynchronize(s);       // the block is freed below; the reference's function is synchronous too
-    hipFree(blk);
-    if (e != hipSuccess) return fail(std::string("shapemol_mesh_guidance: ") + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(std::string("shapemol_mesh_guidance: ") + hipGetErrorString(e2));
-    if (flag) {
-        if (flag_out) *flag_out = 1;
-        return fail("mesh shape guidance: fewer than 3 atoms lie inside the mesh and > 0.4 from the cloud (none at all, or fewer "
-                    "than 3 while atoms are to be pulled); the reference raises ValueError from its KD-tree here");
-    }
     return 0;
 }
 

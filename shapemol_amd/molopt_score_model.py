@@ -496,18 +496,8 @@ class ScorePosNet3D(nn.Module):
             gd = _check_device_tensor("guide_draws", guide_draws, torch.float64)
             if tuple(gd.shape) != (num_steps, 5, n):
                 raise ValueError("guide_draws must be (S, 5, N) float64")
-        if guided == "mesh":
-            verts, faces, cloud = mesh
-            _lib.check(lib.shapemol_set_mesh_guidance(ctx, verts.ctypes.data_as(C.c_void_p), verts.shape[0],
-                                                      faces.ctypes.data_as(C.c_void_p), faces.shape[0],
-                                                      cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], int(grad_step), _ptr(gd)),
-                       "shapemol_set_mesh_guidance")
-        elif guided == "groups":
-            _set_guidance_groups(lib, ctx, groups, int(grad_step), gd)
-        elif guided:
-            cloud = np.ascontiguousarray(np.asarray(use_pointcloud_data[0], dtype=np.float64).reshape(-1, 3))
-            _lib.check(lib.shapemol_set_guidance(ctx, cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], float(use_pointcloud_data[2]),
-                                                 int(grad_step), _ptr(gd)), "shapemol_set_guidance")
+        if guided:      # (taken out of the context again by _PendingChain._drop_guidance)
+            _install_guidance(lib, ctx, guided, {"mesh": mesh, "groups": groups}.get(guided, use_pointcloud_data), grad_step, gd)
         tr = _lib.Traj()
         bufs = {}
         if return_traj:
@@ -561,22 +551,15 @@ class ScorePosNet3D(nn.Module):
         """One pass of :func:`pointcloud_shape_guidance` with one cloud per group of molecules: ``use_pointcloud_data`` is the list
         ``[(point_clouds or None, kdtree, radius, n_mols), ...]`` that :meth:`sample_diffusion` takes, ``batch_ligand`` (N,) gives
         every atom's molecule.  ``pred_ligand_pos`` (N,3) is updated in place and returned; ``draws`` (5,N) / ``seed`` as there."""
-        pos = _check_device_tensor("pred_ligand_pos", pred_ligand_pos, torch.float32)
-        if pos.data_ptr() != pred_ligand_pos.data_ptr() or pos.dim() != 2 or pos.shape[1] != 3:
-            raise ValueError("pred_ligand_pos must be a contiguous (N, 3) tensor (it is updated in place)")
-        batch = _check_device_tensor("batch_ligand", batch_ligand, torch.int64)
-        if not isinstance(use_pointcloud_data, list):
-            raise TypeError("use_pointcloud_data must be a list of (point_clouds, kdtree, radius, n_mols)")
-        groups = _guidance_groups(use_pointcloud_data, sum(int(e[3]) for e in use_pointcloud_data if len(e) == 4))
-        gd = None if draws is None else _check_device_tensor("draws", draws, torch.float64)
-        if batch.shape != (pos.shape[0],) or (gd is not None and tuple(gd.shape) != (5, pos.shape[0])):
-            raise ValueError("batch_ligand must be (N,) and draws (5, N) float64")
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64)) if gd is None else 0
+        def payload():
+            if not isinstance(use_pointcloud_data, list):
+                raise TypeError("use_pointcloud_data must be a list of (point_clouds, kdtree, radius, n_mols)")
+            return _guidance_groups(use_pointcloud_data, sum(int(e[3]) for e in use_pointcloud_data if len(e) == 4))
+        pos, batch, groups, gd, seed = _standalone_inputs(pred_ligand_pos, draws, seed, payload, batch_ligand)
         if pos.shape[0] == 0:
             return pred_ligand_pos
         ctx, lib = self._context(pos.device), _lib.load()
-        _set_guidance_groups(lib, ctx, groups, 0, None)
+        _install_guidance(lib, ctx, "groups", groups, 0, None)
         try:
             with torch.cuda.device(pos.device):
                 stream = torch.cuda.current_stream(pos.device)
@@ -584,7 +567,7 @@ class ScorePosNet3D(nn.Module):
                                                             _stream_ptr(stream)), "shapemol_guide_points_groups")
                 stream.synchronize()
         finally:
-            _lib.check(lib.shapemol_set_guidance_groups(ctx, 0, None, None, None, None, 0, None), "shapemol_set_guidance_groups")
+            _clear_guidance(lib, ctx, "groups")
         return pred_ligand_pos
 
     def mesh_shape_guidance(self, use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws=None, seed=None):
@@ -628,7 +611,6 @@ class _PendingChain:
     result() waits for it, reads the status flags and builds the reference's result dict."""
 
     def __init__(self, model, ctx, dev, guided, bufs, out_pos, out_v, return_traj, reuse, keep, offset=None):
-        # guided: None, "cloud", "groups" or "mesh" (what _drop_guidance removes from the context)
         self.offset = offset                 # (N, 3) per-atom centre of its molecule (center_pos_mode='center') or None
         self.model, self.ctx, self.dev, self.guided, self.bufs = model, ctx, dev, guided, bufs
         self.out_pos, self.out_v, self.return_traj, self.reuse, self.keep = out_pos, out_v, return_traj, reuse, keep
@@ -639,12 +621,7 @@ class _PendingChain:
         if self.guided:      # whatever happened, the context must not keep the cloud / mesh (and the caller-owned draws pointer) installed
             kind, self.guided = self.guided, None
             torch.cuda.synchronize(self.dev)
-            if kind == "mesh":
-                _lib.check(_lib.load().shapemol_set_mesh_guidance(self.ctx, None, 0, None, 0, None, 0, 0, None), "shapemol_set_mesh_guidance")
-            elif kind == "groups":
-                _lib.check(_lib.load().shapemol_set_guidance_groups(self.ctx, 0, None, None, None, None, 0, None), "shapemol_set_guidance_groups")
-            else:
-                _lib.check(_lib.load().shapemol_set_guidance(self.ctx, None, 0, 0.0, 0, None), "shapemol_set_guidance")
+            _clear_guidance(_lib.load(), self.ctx, kind)
 
     def abandon(self):
         self.done = True
@@ -708,15 +685,7 @@ def pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=3, ratio=0
     function draws its uniforms from)."""
     if k != 3:
         raise NotImplementedError("the device kernel searches the reference's default k = 3 nearest cloud points")
-    pos = _check_device_tensor("pred_ligand_pos", pred_ligand_pos, torch.float32)
-    if pos.data_ptr() != pred_ligand_pos.data_ptr() or pos.dim() != 2 or pos.shape[1] != 3:
-        raise ValueError("pred_ligand_pos must be a contiguous (N, 3) tensor (it is updated in place)")
-    cloud = np.ascontiguousarray(np.asarray(use_pointcloud_data[0], dtype=np.float64).reshape(-1, 3))
-    gd = None if draws is None else _check_device_tensor("draws", draws, torch.float64)
-    if gd is not None and tuple(gd.shape) != (5, pos.shape[0]):
-        raise ValueError("draws must be (5, N) float64")
-    if seed is None:
-        seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64)) if gd is None else 0
+    pos, _, cloud, gd, seed = _standalone_inputs(pred_ligand_pos, draws, seed, lambda: _cloud_array(use_pointcloud_data[0]))
     if pos.shape[0] == 0:
         return pred_ligand_pos
     with torch.cuda.device(pos.device):
@@ -750,11 +719,51 @@ def _guidance_groups(entries, n_mols):
     return mol_off, np.ascontiguousarray(np.concatenate(clouds)), cloud_off, np.asarray(radii, dtype=np.float64)
 
 
-def _set_guidance_groups(lib, ctx, groups, grad_step, gd):
-    mol_off, clouds, cloud_off, radii = groups
+def _cloud_array(points):
+    return np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+
+
+# setter of each kind of guidance, and the arguments that take the guidance out of the context again
+_GUIDANCE = {"mesh": ("shapemol_set_mesh_guidance", (None, 0, None, 0, None, 0, 0, None)),
+             "groups": ("shapemol_set_guidance_groups", (0, None, None, None, None, 0, None)),
+             "cloud": ("shapemol_set_guidance", (None, 0, 0.0, 0, None))}
+
+
+def _install_guidance(lib, ctx, kind, payload, grad_step, gd):
+    """payload -- "mesh": _mesh_arrays' triple; "groups": _guidance_groups' arrays; "cloud": (point_clouds, kdtree, radius)."""
     vp = lambda a: a.ctypes.data_as(C.c_void_p)        # noqa: E731
-    _lib.check(lib.shapemol_set_guidance_groups(ctx, len(radii), vp(mol_off), vp(clouds) if len(clouds) else None, vp(cloud_off),
-                                                vp(radii), int(grad_step), _ptr(gd)), "shapemol_set_guidance_groups")
+    if kind == "mesh":
+        verts, faces, cloud = payload
+        args = (vp(verts), verts.shape[0], vp(faces), faces.shape[0], vp(cloud), cloud.shape[0])
+    elif kind == "groups":
+        mol_off, clouds, cloud_off, radii = payload
+        args = (len(radii), vp(mol_off), vp(clouds) if len(clouds) else None, vp(cloud_off), vp(radii))
+    else:
+        cloud = _cloud_array(payload[0])
+        args = (vp(cloud), cloud.shape[0], float(payload[2]))
+    _lib.check(getattr(lib, _GUIDANCE[kind][0])(ctx, *args, int(grad_step), _ptr(gd)), _GUIDANCE[kind][0])
+
+
+def _clear_guidance(lib, ctx, kind):
+    name, off = _GUIDANCE[kind]
+    _lib.check(getattr(lib, name)(ctx, *off), name)
+
+
+def _standalone_inputs(pred_ligand_pos, draws, seed, payload, batch_ligand=None):
+    """Shared head of the stand-alone guidance functions, in the order their errors are raised: the (N, 3) tensor updated in place,
+    the batch vector (groups only), ``payload()``'s host arrays, the (5, N) draws, the default seed (numpy's global generator)."""
+    pos = _check_device_tensor("pred_ligand_pos", pred_ligand_pos, torch.float32)
+    if pos.data_ptr() != pred_ligand_pos.data_ptr() or pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pred_ligand_pos must be a contiguous (N, 3) tensor (it is updated in place)")
+    batch = None if batch_ligand is None else _check_device_tensor("batch_ligand", batch_ligand, torch.int64)
+    arrays = payload()
+    gd = None if draws is None else _check_device_tensor("draws", draws, torch.float64)
+    bad_draws = gd is not None and tuple(gd.shape) != (5, pos.shape[0])
+    if bad_draws or (batch is not None and batch.shape != (pos.shape[0],)):
+        raise ValueError("draws must be (5, N) float64" if batch is None else "batch_ligand must be (N,) and draws (5, N) float64")
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64)) if gd is None else 0
+    return pos, batch, arrays, gd, seed
 
 
 def _mesh_arrays(use_mesh_data):
@@ -777,8 +786,7 @@ def _mesh_arrays(use_mesh_data):
         raise ValueError("a face names a vertex outside [0, V)")
     faces = np.ascontiguousarray(faces.astype(np.int32))
     cloud = cloud.detach().cpu().numpy() if isinstance(cloud, torch.Tensor) else cloud
-    cloud = np.ascontiguousarray(np.asarray(cloud, dtype=np.float64).reshape(-1, 3))
-    return verts, faces, cloud
+    return verts, faces, _cloud_array(cloud)
 
 
 def mesh_shape_guidance(use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws=None, seed=None):
@@ -793,15 +801,7 @@ def mesh_shape_guidance(use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws
     Extensions (keyword-only): ``draws`` (5,N) float64 device tensor = the uniform of every (iteration, atom) (parity mode);
     otherwise device Philox keyed by ``seed`` (default: drawn from numpy's global generator)."""
     del k, ratio                 # the reference hard-codes 3 neighbours and the fraction u * 0.8 + 0.2
-    pos = _check_device_tensor("pred_ligand_pos", pred_ligand_pos, torch.float32)
-    if pos.data_ptr() != pred_ligand_pos.data_ptr() or pos.dim() != 2 or pos.shape[1] != 3:
-        raise ValueError("pred_ligand_pos must be a contiguous (N, 3) tensor (it is updated in place)")
-    verts, faces, cloud = _mesh_arrays(use_mesh_data)
-    gd = None if draws is None else _check_device_tensor("draws", draws, torch.float64)
-    if gd is not None and tuple(gd.shape) != (5, pos.shape[0]):
-        raise ValueError("draws must be (5, N) float64")
-    if seed is None:
-        seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64)) if gd is None else 0
+    pos, _, (verts, faces, cloud), gd, seed = _standalone_inputs(pred_ligand_pos, draws, seed, lambda: _mesh_arrays(use_mesh_data))
     if pos.shape[0] == 0:
         raise _lib.MeshGuidanceError("mesh shape guidance: no atoms inside the mesh (the reference's KDTree of none raises)")
     flag = C.c_int32(0)

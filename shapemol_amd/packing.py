@@ -1,6 +1,6 @@
 """State dict -> the flat float32 weight array consumed by shapemol_create().
 
-Order (mirrored by parse_weights() in csrc/shapemol_hip.hip); names are reference state-dict keys:
+Order (mirrored by parse_weights() in csrc/sm_pack.h); names are reference state-dict keys:
   7 schedule tables of length T: posterior_mean_c0_coef, posterior_mean_ct_coef, posterior_logvar,
       log_alphas_v, log_one_minus_alphas_v, log_alphas_cumprod_v, log_one_minus_alphas_cumprod_v
   time_emb.1.{weight,bias}, time_emb.3.{weight,bias}, ligand_atom_emb.{weight,bias}
