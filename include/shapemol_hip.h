@@ -162,6 +162,30 @@ int shapemol_set_mesh_guidance(shapemol_ctx *ctx, const double *h_verts, int64_t
 int shapemol_guide_points_mesh(shapemol_ctx *ctx, float *d_pos, int64_t n_atoms, const double *d_draws, uint64_t seed,
                                void *stream);
 
+/* Mesh shape guidance with one mesh per GROUP of molecules, for the following _sample calls.  Group g is the contiguous run of
+ * molecules h_mol_off[g] .. h_mol_off[g + 1] - 1 of the batch (so a contiguous run of atoms); its mesh is vertices
+ * h_vert_off[g] .. h_vert_off[g + 1] - 1 of h_verts (HOST (sum V_g, 3) float64) and faces h_face_off[g] .. h_face_off[g + 1] - 1
+ * of h_faces (HOST (sum F_g, 3) int32, indices RELATIVE to the group's first vertex), its cloud rows h_cloud_off[g] ..
+ * h_cloud_off[g + 1] - 1 of h_clouds (HOST (sum P_g, 3) float64); all are copied.  One guided step is shapemol_set_mesh_guidance's
+ * step applied once per group to the group's atoms: the within-atoms and the 3-nearest search among them are PER GROUP.  A
+ * group with no vertices, faces and cloud is left unguided.  d_draws is the same DEVICE (S,5,N) float64 table indexed by the
+ * batch-global atom, or NULL: Philox(seed of the chain) keyed by the batch-global atom in the single mesh's counter domain.
+ * Validated on the host (all offsets start at 0 and do not decrease; every non-empty group has >= 3 vertices, >= 1 face with
+ * indices inside the group's vertices and none repeated, and a cloud of 3 .. 2048 points); the error names the offending
+ * group.  shapemol_sample then requires n_mols == h_mol_off[n_groups].  n_groups = 0 removes the groups.  Installing groups
+ * removes a single mesh and shapemol_set_mesh_guidance removes the groups; mesh groups take precedence over point clouds.  A
+ * group with fewer than 3 within-atoms (none at all, or fewer than 3 while one of its atoms is to be pulled) raises status
+ * flag 6 and is left unguided in that step; the other groups are guided (shapemol_debug_read "mesh_group_flags" tells which). */
+int shapemol_set_mesh_guidance_groups(shapemol_ctx *ctx, int32_t n_groups, const int64_t *h_mol_off, const double *h_verts,
+                                      const int64_t *h_vert_off, const int32_t *h_faces, const int64_t *h_face_off,
+                                      const double *h_clouds, const int64_t *h_cloud_off, int32_t grad_step, const double *d_draws);
+
+/* One guidance pass on its own against the groups of shapemol_set_mesh_guidance_groups: guide d_pos (n_atoms,3) f32 DEVICE in
+ * place; d_batch DEVICE (n_atoms) int64, sorted, gives every atom's molecule; d_draws DEVICE (5,n_atoms) float64 or NULL
+ * (Philox(seed)).  Asynchronous on `stream`; the status flag as above (cleared before). */
+int shapemol_guide_points_mesh_groups(shapemol_ctx *ctx, float *d_pos, const int64_t *d_batch, int64_t n_atoms,
+                                      const double *d_draws, uint64_t seed, void *stream);
+
 /* The reference's MODULE-level function mesh_shape_guidance(use_mesh_data, pred_ligand_pos) without a context: mesh and cloud
  * come with the call (as for shapemol_set_mesh_guidance) on the CURRENT device, d_pos (n_atoms,3) f32 DEVICE is guided in
  * place; d_draws / seed as above.  Synchronises `stream` before it returns, like shapemol_pointcloud_guidance.  Fewer than 3
@@ -359,7 +383,9 @@ void shapemol_debug_split_exact(float x, uint16_t *pieces);
 /* Copy an internal device buffer of the last _score to HOST memory (synchronises the device).
  * names: "nbr" (N,KP) i32, "ew" (N,KP) f32, "h" (N,H), "x" (N,3), "pre" (N,4H), "q" (N,H),
  *        "att" (N,H), "o3" (N,48), "bnstat" (L,16,2,heads) f64, "dims" (8,) i64,
- *        "captures" (1,) i64 hipGraph captures of this context so far.
+ *        "captures" (1,) i64 hipGraph captures of this context so far,
+ *        "mesh_group_flags" (G,) i32: per group of the last chain / pass with mesh groups, the steps in which the group was
+ *        left unguided for want of within-atoms (status flag 6 says that some group was, this says which and how often).
  * Returns the number of bytes written, or -1. */
 int64_t shapemol_debug_read(shapemol_ctx *ctx, const char *name, void *host_dst, size_t max_bytes);
 /* Per-kernel launch-time accounting with HIP events on the launch stream (bench only).

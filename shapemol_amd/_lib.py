@@ -20,6 +20,7 @@ EXPORTS = (
     "shapemol_profile_begin", "shapemol_profile_end", "shapemol_status", "shapemol_status_stream", "shapemol_set_guidance", "shapemol_guide_points",
     "shapemol_set_guidance_groups", "shapemol_guide_points_groups",
     "shapemol_pointcloud_guidance", "shapemol_set_mesh_guidance", "shapemol_guide_points_mesh", "shapemol_mesh_guidance",
+    "shapemol_set_mesh_guidance_groups", "shapemol_guide_points_mesh_groups",
     "shapemol_set_cfg", "shapemol_set_knn_pins", "shapemol_debug_split_exact",
     "shapemol_mlp_backward_workspace", "shapemol_mlp_forward", "shapemol_mlp_backward",
     "shapemol_seg_attention_forward", "shapemol_seg_attention_backward",
@@ -113,6 +114,8 @@ def load():
     lib.shapemol_set_mesh_guidance.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp]
     lib.shapemol_guide_points_mesh.argtypes = [vp, vp, i64, vp, u64, vp]
     lib.shapemol_mesh_guidance.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, u64, vp, vp]
+    lib.shapemol_set_mesh_guidance_groups.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.shapemol_guide_points_mesh_groups.argtypes = [vp, vp, vp, i64, vp, u64, vp]
     lib.shapemol_set_cfg.argtypes = [vp, C.c_double, i32, C.c_double, vp, vp, vp]
     lib.shapemol_mlp_backward_workspace.restype = C.c_size_t
     lib.shapemol_mlp_backward_workspace.argtypes = [i64, i32, i32, i32]

@@ -5,11 +5,12 @@
 
 namespace {
 
-// The guidance of the chains to come: the reference's if / elif in sample_diffusion -- mesh, else the point cloud (one for the
-// batch, or one per group of molecules: the setters keep at most one of the two), else classifier-free guidance.  Groups
-// without any cloud guide nothing (and leave classifier-free guidance its turn).  The only place that spells this out.
+// The guidance of the chains to come: the reference's if / elif in sample_diffusion -- mesh (one for the batch, or one per group
+// of molecules), else the point cloud (likewise: the setters keep at most one of each two), else classifier-free guidance.
+// Groups without any mesh / cloud guide nothing (and leave the next kind its turn).  The only place that spells this out.
 Guide chain_guide(const shapemol_ctx *c) {
     if (c->m_nfaces > 0) return Guide::Mesh;
+    if (c->mg_groups > 0 && c->mg_nfaces > 0) return Guide::MeshGroups;
     if (c->g_points > 0) return Guide::Cloud;
     if (c->gg_groups > 0 && c->gg_points > 0) return Guide::Groups;
     return c->cfg_w != 0.0 ? Guide::Cfg : Guide::None;
@@ -25,9 +26,9 @@ ChainParams guide_alone_params(uint64_t seed, const double *d_draws) {
     return cp;
 }
 
-// ---- point-cloud guidance per group of molecules: host side
-// workgroups of pc_guidance_groups_kernel: the sum over the groups of ceil(n_g / 16) is at most floor(N / 16) + G
-unsigned groups_grid(const shapemol_ctx *c, int64_t N) { return (unsigned)(N / 16 + c->gg_groups); }
+// ---- guidance per group of molecules (point clouds, meshes): host side
+// workgroups of the kernels that run per group: the sum over the groups of ceil(n_g / 16) is at most floor(N / 16) + G
+unsigned groups_grid(int64_t N, int n_groups) { return (unsigned)(N / 16 + n_groups); }
 
 PcGroupsArgs groups_args(const shapemol_ctx *c, float *d_pos, int64_t N, const int *step_cur, int t_first) {
     const int G1 = c->gg_groups + 1;
@@ -38,9 +39,10 @@ PcGroupsArgs groups_args(const shapemol_ctx *c, float *d_pos, int64_t N, const i
     return a;
 }
 
-// the per-workgroup table of this chain (atom ranges come from the batch vector on the device)
-int groups_table(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N) {
-    const int64_t n_wg = groups_grid(c, N);
+// the per-workgroup table of this chain (atom ranges come from the batch vector on the device); ints = the installed set's
+// [mol_off | cloud_off | atom_off | wg_off], G + 1 each (cloud groups or mesh groups: one table serves whichever guides)
+int groups_table(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int *ints, int n_groups) {
+    const int64_t n_wg = groups_grid(N, n_groups);
     if (n_wg > c->gg_table_cap) {
         c->drop_graphs();                        // a captured step holds the table's address
         if (c->gg_table) { hipFree(c->gg_table); c->gg_table = nullptr; }
@@ -48,10 +50,21 @@ int groups_table(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t
         HIPCHK(hipMalloc((void **)&c->gg_table, (size_t)n_wg * sizeof(int2)));
         c->gg_table_cap = n_wg;
     }
-    const int G1 = c->gg_groups + 1;
-    LAUNCH("prep", SMK(pc_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, c->gg_ints, c->gg_ints + G1, c->gg_groups,
-                       c->gg_ints + 2 * G1, c->gg_ints + 3 * G1, c->gg_table, (int)n_wg));
+    const int G1 = n_groups + 1;
+    LAUNCH("prep", SMK(pc_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, ints, ints + G1, n_groups,
+                       ints + 2 * G1, ints + 3 * G1, c->gg_table, (int)n_wg));
     return 0;
+}
+
+MeshGroupsArgs mesh_groups_args(const shapemol_ctx *c, float *d_pos, int64_t N, const int *step_cur, int t_first) {
+    const int G1 = c->mg_groups + 1;
+    MeshGroupsArgs a{};
+    a.pred_pos = d_pos; a.clouds = c->mg_clouds; a.faces = c->mg_faces; a.fbox = c->mg_fbox; a.bounds = c->mg_bounds;
+    a.cloud_off = c->mg_ints + G1; a.atom_off = c->mg_ints + 2 * G1; a.face_off = c->mg_ints + 4 * G1; a.wg_table = c->gg_table;
+    a.within = c->m_within; a.out_list = c->m_out; a.cnt = c->m_cnt; a.group_flags = c->m_cnt + 4 * c->m_cnt_cap;
+    a.status = c->status; a.cp = c->chain_params;
+    a.step_cur = step_cur; a.n_atoms = (int)N; a.t_first = t_first; a.grad_step = c->mg_grad_step;
+    return a;
 }
 
 // ---- mesh shape guidance: host side
@@ -116,18 +129,26 @@ MeshGuideArgs mesh_args(const MeshView &m, float *pos, int64_t N, const int *ste
     return a;
 }
 
-// the per-step lists of mesh guidance for N atoms: [within N | outmesh N | counters 4]
-int mesh_workspace(shapemol_ctx *c, int64_t N) {
-    if (N <= c->m_cap) return 0;
+// the per-step lists of mesh guidance for N atoms: [within N | outmesh N | counters 4 per group (one group: the single mesh) |
+// unguided-step count 1 per group (mesh groups)]; mesh_counters_clear zeroes the last two for a chain of n_groups
+int mesh_workspace(shapemol_ctx *c, int64_t N, int64_t n_groups) {
+    if (N <= c->m_cap && n_groups <= c->m_cnt_cap) return 0;
+    N = std::max(N, c->m_cap); n_groups = std::max(n_groups, c->m_cnt_cap);
     c->drop_graphs();                            // the captured steps point into the old block
     HIPCHK(hipDeviceSynchronize());
-    if (c->m_within) { hipFree(c->m_within); c->m_within = nullptr; c->m_out = c->m_cnt = nullptr; c->m_cap = 0; }
+    if (c->m_within) { hipFree(c->m_within); c->m_within = nullptr; c->m_out = c->m_cnt = nullptr; c->m_cap = c->m_cnt_cap = 0; }
     unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, (size_t)N * 20 + 16));
+    HIPCHK(hipMalloc((void **)&blk, (size_t)N * 20 + (size_t)n_groups * 20));
     c->m_within = reinterpret_cast<float4 *>(blk);
     c->m_out = reinterpret_cast<int *>(blk + (size_t)N * 16);
     c->m_cnt = reinterpret_cast<int *>(blk + (size_t)N * 20);
-    c->m_cap = N;
+    c->m_cap = N; c->m_cnt_cap = n_groups;
+    return 0;
+}
+int mesh_counters_clear(shapemol_ctx *c, hipStream_t s, int64_t n_groups) {
+    HIPCHK(hipMemsetAsync(c->m_cnt, 0, (size_t)n_groups * 4 * sizeof(int), s));
+    HIPCHK(hipMemsetAsync(c->m_cnt + 4 * c->m_cnt_cap, 0, (size_t)n_groups * sizeof(int), s));
+    c->mg_flag_groups = n_groups;
     return 0;
 }
 
@@ -139,12 +160,17 @@ int enqueue_guidance(shapemol_ctx *c, hipStream_t s, Guide kind, float *pos, int
         const MeshGuideArgs ma = mesh_args(mesh_view(c), pos, N, step_cur, t_first, c->m_grad_step);
         LAUNCH("mesh_classify", SMK(mesh_classify_kernel, guide_grid(N), dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
         LAUNCH("mesh_pull", SMK(mesh_pull_kernel, guide_grid(N), dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
+    } else if (kind == Guide::MeshGroups) {  // each group of molecules against its own mesh
+        const MeshGroupsArgs ma = mesh_groups_args(c, pos, N, step_cur, t_first);
+        const dim3 grid(groups_grid(N, c->mg_groups));
+        LAUNCH("mesh_classify_groups", SMK(mesh_classify_groups_kernel, grid, dim3(256), mesh_groups_lds_bytes(c->mg_max_points), s, ma));
+        LAUNCH("mesh_pull_groups", SMK(mesh_pull_groups_kernel, grid, dim3(256), mesh_groups_lds_bytes(c->mg_max_points), s, ma));
     } else if (kind == Guide::Cloud) {
         PcGuideArgs ga{pos, c->g_cloud, c->chain_params, step_cur, (int)N, (int)c->g_points, t_first, c->g_grad_step, c->g_radius, 0.2};
         LAUNCH("pc_guidance", SMK(pc_guidance_kernel, guide_grid(N), dim3(256), cloud_lds_bytes(c->g_points), s, ga));
     } else if (kind == Guide::Groups) {     // each group of molecules towards its own cloud
         const PcGroupsArgs ga = groups_args(c, pos, N, step_cur, t_first);
-        LAUNCH("pc_guidance_groups", SMK(pc_guidance_groups_kernel, dim3(groups_grid(c, N)), dim3(256), cloud_lds_bytes(c->gg_max_points), s, ga));
+        LAUNCH("pc_guidance_groups", SMK(pc_guidance_groups_kernel, dim3(groups_grid(N, c->gg_groups)), dim3(256), cloud_lds_bytes(c->gg_max_points), s, ga));
     }
     return 0;
 }
@@ -152,8 +178,20 @@ int enqueue_guidance(shapemol_ctx *c, hipStream_t s, Guide kind, float *pos, int
 // shapemol_guide_points*: one always-guided application of the context's guidance of `kind` to given positions
 int guide_alone(shapemol_ctx *c, hipStream_t s, Guide kind, float *d_pos, int64_t N, const double *d_draws, uint64_t seed) {
     LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, guide_alone_params(seed, d_draws), c->steps));
-    const int grad_step = kind == Guide::Mesh ? c->m_grad_step : (kind == Guide::Cloud ? c->g_grad_step : c->gg_grad_step);
+    const int grad_step = kind == Guide::Mesh ? c->m_grad_step : (kind == Guide::MeshGroups ? c->mg_grad_step :
+                          (kind == Guide::Cloud ? c->g_grad_step : c->gg_grad_step));
     return enqueue_guidance(c, s, kind, d_pos, N, nullptr, grad_step + 1);
+}
+
+void mesh_groups_clear(shapemol_ctx *c) {
+    if (c->mg_faces) { hipFree(c->mg_faces); c->mg_faces = nullptr; }
+    c->mg_fbox = nullptr; c->mg_clouds = c->mg_bounds = nullptr; c->mg_ints = nullptr;
+    c->mg_groups = 0; c->mg_max_points = 0; c->mg_mols = 0; c->mg_nfaces = 0; c->mg_draws = nullptr;
+}
+
+void mesh_single_clear(shapemol_ctx *c) {
+    if (c->m_faces) { hipFree(c->m_faces); c->m_faces = nullptr; c->m_fbox = nullptr; c->m_cloud = nullptr; }
+    c->m_nfaces = 0; c->m_points = 0; c->m_draws = nullptr;
 }
 
 void groups_clear(shapemol_ctx *c) {
@@ -234,7 +272,7 @@ int shapemol_guide_points_groups(shapemol_ctx *c, float *d_pos, const int64_t *d
     if (ensure_workspace(c, N, 1)) return 1;
     hipStream_t s = (hipStream_t)stream;
     if (c->gg_points == 0) return 0;             // no group has a cloud: nothing moves
-    if (groups_table(c, s, d_batch, N)) return 1;
+    if (groups_table(c, s, d_batch, N, c->gg_ints, c->gg_groups)) return 1;
     return guide_alone(c, s, Guide::Groups, d_pos, N, d_draws, seed);
 }
 
@@ -281,9 +319,9 @@ int shapemol_set_mesh_guidance(shapemol_ctx *c, const double *h_verts, int64_t n
     if (n_faces > 0 && mesh_image(h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, "shapemol_set_mesh_guidance", img, bounds)) return 1;
     HIPCHK(hipSetDevice(c->device));
     c->drop_graphs();                            // also drains the device: the old mesh may still be in use
-    if (c->m_faces) { hipFree(c->m_faces); c->m_faces = nullptr; c->m_fbox = nullptr; c->m_cloud = nullptr; }
-    c->m_nfaces = 0; c->m_points = 0; c->m_draws = nullptr;
+    mesh_single_clear(c);
     if (n_faces == 0) return 0;
+    mesh_groups_clear(c);                        // a single mesh replaces meshes per group
     unsigned char *blk = nullptr;
     HIPCHK(hipMalloc((void **)&blk, img.size()));
     HIPCHK(hipMemcpy(blk, img.data(), img.size(), hipMemcpyHostToDevice));
@@ -299,11 +337,92 @@ int shapemol_guide_points_mesh(shapemol_ctx *c, float *d_pos, int64_t N, const d
     if (!c || !d_pos || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_mesh: bad argument");
     if (c->m_nfaces <= 0) return fail("shapemol_guide_points_mesh: no mesh set (shapemol_set_mesh_guidance)");
     HIPCHK(hipSetDevice(c->device));
-    if (ensure_workspace(c, std::max<int64_t>(N, 1), 1) || mesh_workspace(c, N)) return 1;
+    if (ensure_workspace(c, std::max<int64_t>(N, 1), 1) || mesh_workspace(c, N, 1)) return 1;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
     HIPCHK(hipMemsetAsync(c->status + ST_MESH, 0, sizeof(int), s));
     return guide_alone(c, s, Guide::Mesh, d_pos, N, d_draws, seed);
+}
+
+int shapemol_set_mesh_guidance_groups(shapemol_ctx *c, int32_t n_groups, const int64_t *h_mol_off, const double *h_verts, const int64_t *h_vert_off,
+                                      const int32_t *h_faces, const int64_t *h_face_off, const double *h_clouds, const int64_t *h_cloud_off,
+                                      int32_t grad_step, const double *d_draws) {
+    const std::string me = "shapemol_set_mesh_guidance_groups: ";
+    if (!c) return fail(me + "null ctx");
+    if (n_groups < 0 || n_groups > (1 << 20)) return fail(me + "n_groups out of range");
+    // host image [faces | face boxes | clouds | bounds G x 5 | ints 5 (G + 1)]; every group's mesh goes through mesh_image, the
+    // single mesh's validation and projection, with its face indices relative to the group's own vertices
+    const int G1 = n_groups + 1;
+    std::vector<std::vector<unsigned char>> imgs(n_groups);
+    std::vector<double> hb((size_t)n_groups * 5, 0.0);
+    int64_t F = 0, P = 0;
+    int max_points = 0;
+    if (n_groups > 0) {
+        if (!h_mol_off || !h_vert_off || !h_face_off || !h_cloud_off) return fail(me + "offsets missing");
+        if (h_mol_off[0] != 0 || h_vert_off[0] != 0 || h_face_off[0] != 0 || h_cloud_off[0] != 0)
+            return fail(me + "group 0: the molecule, vertex, face and cloud offsets must start at 0");
+        for (int g = 0; g < n_groups; ++g) {
+            const std::string grp = me + "group " + std::to_string(g);
+            if (h_mol_off[g + 1] < h_mol_off[g]) return fail(grp + ": the molecule offsets decrease");
+            if (h_vert_off[g + 1] < h_vert_off[g]) return fail(grp + ": the vertex offsets decrease");
+            if (h_face_off[g + 1] < h_face_off[g]) return fail(grp + ": the face offsets decrease");
+            if (h_cloud_off[g + 1] < h_cloud_off[g]) return fail(grp + ": the cloud offsets decrease");
+            const int64_t nv = h_vert_off[g + 1] - h_vert_off[g], nf = h_face_off[g + 1] - h_face_off[g], np = h_cloud_off[g + 1] - h_cloud_off[g];
+            if (nv == 0 && nf == 0 && np == 0) continue;       // a group without a mesh
+            if (!h_verts || !h_faces || !h_clouds) return fail(grp + ": vertices, faces and cloud are required");
+            double bounds[5];
+            if (mesh_image(h_verts + h_vert_off[g] * 3, nv, h_faces + h_face_off[g] * 3, nf, h_clouds + h_cloud_off[g] * 3, np, grp.c_str(), imgs[g], bounds)) return 1;
+            std::copy(bounds, bounds + 5, hb.begin() + (size_t)g * 5);
+            max_points = std::max(max_points, (int)np);
+        }
+        F = h_face_off[n_groups]; P = h_cloud_off[n_groups];
+        if (h_mol_off[n_groups] > (1 << 27)) return fail(me + "too many molecules");
+        if (F > (1 << 27)) return fail(me + "too many faces");
+        if (P > (1 << 27) || h_vert_off[n_groups] > (1 << 27)) return fail(me + "too many cloud points / vertices");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    c->drop_graphs();                            // also drains the device: the old meshes may still be in use
+    mesh_groups_clear(c);
+    if (n_groups == 0) return 0;
+    mesh_single_clear(c);                        // meshes per group replace a single mesh
+    const size_t fb = (size_t)F * sizeof(MeshFace), bb = (size_t)F * sizeof(double4), cb = (size_t)P * 24, nb = hb.size() * sizeof(double);
+    std::vector<unsigned char> img(fb + bb + cb + nb + (size_t)5 * G1 * sizeof(int), 0);
+    int *hi = reinterpret_cast<int *>(img.data() + fb + bb + cb + nb);       // mol_off | cloud_off | atom_off | wg_off | face_off
+    for (int g = 0; g < G1; ++g) { hi[g] = (int)h_mol_off[g]; hi[G1 + g] = (int)h_cloud_off[g]; hi[4 * G1 + g] = (int)h_face_off[g]; }
+    for (int g = 0; g < n_groups; ++g) {
+        if (imgs[g].empty()) continue;
+        const size_t nf = (size_t)(h_face_off[g + 1] - h_face_off[g]), np = (size_t)(h_cloud_off[g + 1] - h_cloud_off[g]);
+        const unsigned char *src = imgs[g].data();
+        std::memcpy(img.data() + (size_t)h_face_off[g] * sizeof(MeshFace), src, nf * sizeof(MeshFace));
+        std::memcpy(img.data() + fb + (size_t)h_face_off[g] * sizeof(double4), src + nf * sizeof(MeshFace), nf * sizeof(double4));
+        std::memcpy(img.data() + fb + bb + (size_t)h_cloud_off[g] * 24, src + nf * (sizeof(MeshFace) + sizeof(double4)), np * 24);
+    }
+    std::memcpy(img.data() + fb + bb + cb, hb.data(), nb);
+    unsigned char *blk = nullptr;
+    HIPCHK(hipMalloc((void **)&blk, img.size()));
+    HIPCHK(hipMemcpy(blk, img.data(), img.size(), hipMemcpyHostToDevice));
+    c->mg_faces = reinterpret_cast<MeshFace *>(blk);
+    c->mg_fbox = reinterpret_cast<double4 *>(blk + fb);
+    c->mg_clouds = reinterpret_cast<double *>(blk + fb + bb);
+    c->mg_bounds = reinterpret_cast<double *>(blk + fb + bb + cb);
+    c->mg_ints = reinterpret_cast<int *>(blk + fb + bb + cb + nb);
+    c->mg_groups = n_groups; c->mg_max_points = max_points; c->mg_mols = h_mol_off[n_groups]; c->mg_nfaces = F;
+    c->mg_grad_step = grad_step; c->mg_draws = d_draws;
+    return 0;
+}
+
+int shapemol_guide_points_mesh_groups(shapemol_ctx *c, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws, uint64_t seed,
+                                      void *stream) {
+    if (!c || !d_pos || !d_batch || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_mesh_groups: bad argument");
+    if (c->mg_groups <= 0) return fail("shapemol_guide_points_mesh_groups: no groups set (shapemol_set_mesh_guidance_groups)");
+    HIPCHK(hipSetDevice(c->device));
+    if (ensure_workspace(c, N, 1) || mesh_workspace(c, N, c->mg_groups)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(c->status + ST_MESH, 0, sizeof(int), s));
+    if (c->mg_nfaces == 0) return 0;             // no group has a mesh: nothing moves
+    if (mesh_counters_clear(c, s, c->mg_groups)) return 1;
+    if (groups_table(c, s, d_batch, N, c->mg_ints, c->mg_groups)) return 1;
+    return guide_alone(c, s, Guide::MeshGroups, d_pos, N, d_draws, seed);
 }
 
 int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces, const double *h_cloud,

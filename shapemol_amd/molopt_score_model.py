@@ -403,11 +403,19 @@ class ScorePosNet3D(nn.Module):
         ``[(point_clouds, kdtree, radius, n_mols), ...]`` -- the next ``n_mols`` molecules of the batch are guided towards that
         cloud, or left unguided where ``point_clouds`` is None; the counts must sum to the number of molecules (``ValueError``
         otherwise).  ``guide_draws`` and ``grad_step`` work as for one cloud (the draws stay indexed by the batch-global atom).  A
-        list together with ``use_mesh_data`` raises ``NotImplementedError``: mesh guidance takes one mesh per chain.
+        list together with a single ``use_mesh_data`` raises ``NotImplementedError``: mesh guidance takes one mesh per chain.
         ``use_mesh_data=(mesh, point_clouds, kdtree)`` is the reference's mesh shape guidance (``:571-580,742-775``), two
         device kernels inside the step, and takes precedence over ``use_pointcloud_data`` as there; the mesh is anything with
         ``.vertices`` (V,3) and ``.faces`` (F,3) (a ``trimesh.Trimesh``) or a ``(vertices, faces)`` pair, the KD-tree is not
         used.  Too few atoms inside the mesh raise ``ValueError`` (``_lib.MeshGuidanceError``), as the reference's KD-tree does.
+        ``use_mesh_data`` may also be a LIST with one entry per group of molecules, in batch order:
+        ``[(mesh, point_clouds, kdtree, n_mols), ...]`` -- one guided step is the reference's ``mesh_shape_guidance`` applied once
+        per group to the next ``n_mols`` molecules with that group's mesh and cloud (the atoms inside the mesh that anchor the
+        pull are the group's own), or nothing where ``mesh`` is None; the counts must sum to the number of molecules
+        (``ValueError`` otherwise).  ``guide_draws``, ``grad_step`` and ``seed`` work as for one mesh; a group with too few atoms
+        inside its mesh raises ``MeshGuidanceError`` as the single mesh does -- for the whole chain, the message and
+        ``.group_steps`` naming the groups and the number of steps in which each was left unguided.  Mesh groups
+        together with point-cloud groups in one chain raise ``NotImplementedError``.
         ``guide_stren > 0`` on a model trained with ``cond_mask_prob > 0`` is the reference's classifier-free guidance
         (``:616-642``): every step also evaluates the score on a zeroed shape, combines ``(1 + w) * cond - w * uncond`` and
         applies ``threshold_CFG(threshold_type, threshold_args)`` with batch-wide statistics, all as device kernels inside the
@@ -422,11 +430,15 @@ class ScorePosNet3D(nn.Module):
         """
         if use_grad:
             raise NotImplementedError("gradient shape guidance is outside the accelerated path (commented out in the reference)")
-        groups = None
+        groups = mesh_groups = None
         if isinstance(use_pointcloud_data, list):
+            if isinstance(use_mesh_data, list):
+                raise NotImplementedError("mesh groups and point-cloud groups in one chain are not supported: give one kind of list")
             if use_mesh_data is not None:
                 raise NotImplementedError("mesh guidance takes one mesh per chain")
             groups = _guidance_groups(use_pointcloud_data, int(ligand_shape.shape[0]))
+        elif isinstance(use_mesh_data, list):        # (with a single point cloud beside: the mesh wins, the reference's if / elif)
+            mesh_groups = _mesh_guidance_groups(use_mesh_data, int(ligand_shape.shape[0]))
         if self.cond_mask_prob == 0:
             assert guide_stren == 0
         # classifier-free guidance: the reference's branch order (:561-642) -- mesh, point cloud, then CFG
@@ -475,8 +487,9 @@ class ScorePosNet3D(nn.Module):
             u = _check_device_tensor("noise[1]", noise[1], torch.float32)
             if tuple(eps.shape) != (num_steps, n, 3) or tuple(u.shape) != (num_steps, n, cc):
                 raise ValueError("noise must be (eps (S,N,3), u (S,N,C))")
-        guided = "mesh" if use_mesh_data is not None else ("groups" if groups is not None else
-                                                           ("cloud" if use_pointcloud_data is not None else None))
+        guided = "mesh_groups" if mesh_groups is not None else (
+            "mesh" if use_mesh_data is not None else ("groups" if groups is not None else
+                                                      ("cloud" if use_pointcloud_data is not None else None)))
         mesh = _mesh_arrays(use_mesh_data) if guided == "mesh" else None
         if seed is None:
             if noise is None:
@@ -497,7 +510,7 @@ class ScorePosNet3D(nn.Module):
             if tuple(gd.shape) != (num_steps, 5, n):
                 raise ValueError("guide_draws must be (S, 5, N) float64")
         if guided:      # (taken out of the context again by _PendingChain._drop_guidance)
-            _install_guidance(lib, ctx, guided, {"mesh": mesh, "groups": groups}.get(guided, use_pointcloud_data), grad_step, gd)
+            _install_guidance(lib, ctx, guided, {"mesh": mesh, "groups": groups, "mesh_groups": mesh_groups}.get(guided, use_pointcloud_data), grad_step, gd)
         tr = _lib.Traj()
         bufs = {}
         if return_traj:
@@ -514,6 +527,7 @@ class ScorePosNet3D(nn.Module):
         out_v = torch.empty((n,), dtype=torch.int64, device=dev)
         pending = _PendingChain(self, ctx, dev, guided, bufs, out_pos, out_v, return_traj, _reuse_host_buffers,
                                 keep=(pos, v, batch, shape, eps, u, gd), offset=offset)
+        pending.n_groups = len(mesh_groups[0]) - 1 if mesh_groups is not None else 0
         try:
             with torch.cuda.device(dev):
                 cur = torch.cuda.current_stream(dev)
@@ -570,6 +584,37 @@ class ScorePosNet3D(nn.Module):
             _clear_guidance(lib, ctx, "groups")
         return pred_ligand_pos
 
+    def mesh_shape_guidance_groups(self, use_mesh_data, pred_ligand_pos, batch_ligand, *, draws=None, seed=None):
+        """One pass of :func:`mesh_shape_guidance` with one mesh per group of molecules: ``use_mesh_data`` is the list
+        ``[(mesh or None, point_clouds, kdtree, n_mols), ...]`` that :meth:`sample_diffusion` takes, ``batch_ligand`` (N,) gives
+        every atom's molecule.  ``pred_ligand_pos`` (N,3) is updated in place and returned; ``draws`` (5,N) / ``seed`` as there.
+        A group with fewer than 3 atoms inside its mesh raises ``MeshGuidanceError`` naming the group (the other groups have been
+        guided); the groups' molecule counts must cover ``batch_ligand`` (``ValueError`` otherwise)."""
+        def payload():
+            if not isinstance(use_mesh_data, list):
+                raise TypeError("use_mesh_data must be a list of (mesh, point_clouds, kdtree, n_mols)")
+            return _mesh_guidance_groups(use_mesh_data, sum(int(e[3]) for e in use_mesh_data if len(e) == 4))
+        pos, batch, groups, gd, seed = _standalone_inputs(pred_ligand_pos, draws, seed, payload, batch_ligand)
+        if pos.shape[0] == 0:
+            return pred_ligand_pos
+        n_mols = int(batch.max().item()) + 1         # (one device read: atoms of molecules beyond the groups would stay unguided silently)
+        if n_mols != int(groups[0][-1]):
+            raise ValueError(f"use_mesh_data: the groups hold {int(groups[0][-1])} molecules, batch_ligand names {n_mols}")
+        ctx, lib = self._context(pos.device), _lib.load()
+        _install_guidance(lib, ctx, "mesh_groups", groups, 0, None)
+        flags = (C.c_int32 * 8)()
+        try:
+            with torch.cuda.device(pos.device):
+                stream = torch.cuda.current_stream(pos.device)
+                _lib.check(lib.shapemol_guide_points_mesh_groups(ctx, _ptr(pos), _ptr(batch), pos.shape[0], _ptr(gd), C.c_uint64(seed),
+                                                                 _stream_ptr(stream)), "shapemol_guide_points_mesh_groups")
+                lib.shapemol_status_stream(ctx, flags, _stream_ptr(stream))        # waits for the pass; only the mesh flag is its own
+        finally:
+            _clear_guidance(lib, ctx, "mesh_groups")
+        if flags[_lib.ST_MESH]:
+            raise _mesh_groups_error(lib, ctx, len(groups[0]) - 1)
+        return pred_ligand_pos
+
     def mesh_shape_guidance(self, use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws=None, seed=None):
         """Method form of the module-level :func:`mesh_shape_guidance`."""
         return mesh_shape_guidance(use_mesh_data, pred_ligand_pos, k=k, ratio=ratio, draws=draws, seed=seed)
@@ -616,6 +661,7 @@ class _PendingChain:
         self.out_pos, self.out_v, self.return_traj, self.reuse, self.keep = out_pos, out_v, return_traj, reuse, keep
         self.side = self.cur = None
         self.done = False
+        self.n_groups = 0                    # mesh groups of the chain (their unguided steps go into a MeshGuidanceError)
 
     def _drop_guidance(self):
         if self.guided:      # whatever happened, the context must not keep the cloud / mesh (and the caller-owned draws pointer) installed
@@ -636,6 +682,8 @@ class _PendingChain:
             flags = (C.c_int32 * 8)()
             rc = _lib.load().shapemol_status_stream(self.ctx, flags, _stream_ptr(self.side))
             if rc and flags[_lib.ST_MESH] and not any(flags[i] for i in range(8) if i != _lib.ST_MESH):
+                if self.n_groups:
+                    raise _mesh_groups_error(_lib.load(), self.ctx, self.n_groups)
                 raise _lib.MeshGuidanceError(f"mesh shape guidance: {_lib.load().shapemol_last_error().decode()}")
             _lib.check(rc, "input check")
         finally:
@@ -719,22 +767,68 @@ def _guidance_groups(entries, n_mols):
     return mol_off, np.ascontiguousarray(np.concatenate(clouds)), cloud_off, np.asarray(radii, dtype=np.float64)
 
 
+def _mesh_guidance_groups(entries, n_mols):
+    """``[(mesh or None, point_clouds, kdtree, n_mols), ...]`` -> (mol_off, verts (sum V_g, 3) float64, vert_off, faces (sum F_g, 3)
+    int32 with indices relative to the group's own vertices, face_off, clouds (sum P_g, 3) float64, cloud_off), offsets (G+1,)
+    int64: host arrays for ``shapemol_set_mesh_guidance_groups``.  The groups' molecule counts must sum to ``n_mols``.  Host logic
+    only; the library checks the meshes and clouds again and names the offending group."""
+    if len(entries) == 0:
+        raise ValueError("use_mesh_data: the list of groups is empty")
+    counts, verts, faces, clouds = [], [], [], []
+    for g, e in enumerate(entries):
+        if not isinstance(e, (tuple, list)) or len(e) != 4:
+            raise ValueError(f"use_mesh_data[{g}] must be (mesh, point_clouds, kdtree, n_mols)")
+        cnt = int(e[3])
+        if cnt < 0:
+            raise ValueError(f"use_mesh_data[{g}]: n_mols < 0")
+        counts.append(cnt)
+        v, f, c = (np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int32), np.zeros((0, 3))) if e[0] is None else _mesh_arrays(tuple(e[:3]))
+        verts.append(v), faces.append(f), clouds.append(c)
+    if sum(counts) != n_mols:
+        raise ValueError(f"use_mesh_data: the groups hold {sum(counts)} molecules, the batch has {n_mols}")
+    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)        # noqa: E731
+    return (np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), np.ascontiguousarray(np.concatenate(verts)), off(verts),
+            np.ascontiguousarray(np.concatenate(faces).astype(np.int32)), off(faces), np.ascontiguousarray(np.concatenate(clouds)),
+            off(clouds))
+
+
+def _mesh_groups_error(lib, ctx, n_groups):
+    """The MeshGuidanceError of a chain / pass with mesh groups: names the groups that were left unguided and in how many steps
+    (``.group_steps``: (G,) int32, from the library's per-group count)."""
+    steps = np.zeros(n_groups, dtype=np.int32)
+    got = lib.shapemol_debug_read(ctx, b"mesh_group_flags", steps.ctypes.data_as(C.c_void_p), steps.nbytes)
+    bad = np.nonzero(steps)[0] if got == steps.nbytes else []
+    which = ", ".join(f"group {g} in {int(steps[g])} step(s)" for g in bad[:16]) + (" ..." if len(bad) > 16 else "")
+    err = _lib.MeshGuidanceError(
+        "mesh shape guidance per group of molecules: " + (which or "a group") + " had fewer than 3 atoms inside its mesh and > 0.4 "
+        "from its cloud (none at all, or fewer than 3 while atoms are to be pulled) and was left unguided there; the reference "
+        "raises ValueError from its KD-tree here.  The other groups were guided; the chain's result is not returned")
+    err.group_steps = steps if got == steps.nbytes else None
+    return err
+
+
 def _cloud_array(points):
     return np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
 
 
 # setter of each kind of guidance, and the arguments that take the guidance out of the context again
 _GUIDANCE = {"mesh": ("shapemol_set_mesh_guidance", (None, 0, None, 0, None, 0, 0, None)),
+             "mesh_groups": ("shapemol_set_mesh_guidance_groups", (0, None, None, None, None, None, None, None, 0, None)),
              "groups": ("shapemol_set_guidance_groups", (0, None, None, None, None, 0, None)),
              "cloud": ("shapemol_set_guidance", (None, 0, 0.0, 0, None))}
 
 
 def _install_guidance(lib, ctx, kind, payload, grad_step, gd):
-    """payload -- "mesh": _mesh_arrays' triple; "groups": _guidance_groups' arrays; "cloud": (point_clouds, kdtree, radius)."""
+    """payload -- "mesh": _mesh_arrays' triple; "groups": _guidance_groups' arrays; "mesh_groups": _mesh_guidance_groups' arrays;
+    "cloud": (point_clouds, kdtree, radius)."""
     vp = lambda a: a.ctypes.data_as(C.c_void_p)        # noqa: E731
     if kind == "mesh":
         verts, faces, cloud = payload
         args = (vp(verts), verts.shape[0], vp(faces), faces.shape[0], vp(cloud), cloud.shape[0])
+    elif kind == "mesh_groups":
+        mol_off, verts, vert_off, faces, face_off, clouds, cloud_off = payload
+        opt = lambda a: vp(a) if len(a) else None      # noqa: E731
+        args = (len(mol_off) - 1, vp(mol_off), opt(verts), vp(vert_off), opt(faces), vp(face_off), opt(clouds), vp(cloud_off))
     elif kind == "groups":
         mol_off, clouds, cloud_off, radii = payload
         args = (len(radii), vp(mol_off), vp(clouds) if len(clouds) else None, vp(cloud_off), vp(radii))

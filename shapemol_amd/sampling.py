@@ -22,7 +22,7 @@ import torch
 
 from .molopt_score_model import log_sample_categorical
 
-__all__ = ["atom_num_sampler", "sample_atom_nums", "sample_diffusion_ligand", "sample_diffusion_ligand_multi", "plan_batches",
+__all__ = ["atom_num_sampler", "sample_atom_nums", "sample_diffusion_ligand", "sample_diffusion_ligand_multi", "plan_batches", "plan_guidance",
            "pack_result", "unbatch"]
 
 
@@ -321,18 +321,53 @@ def _per_condition(value, n_conditions, name):
     return [value] * n_conditions
 
 
+def plan_guidance(conditions):
+    """What guides a job of :func:`sample_diffusion_ligand_multi`: ``(kind, data)`` with kind "mesh", "cloud" or None and, per
+    condition, its ``use_mesh_data`` / ``use_pointcloud_data`` or None.  A condition is ``(shape_emb, use_pointcloud_data or
+    None[, use_mesh_data or None])``; a mesh, where given, guides the condition (the reference's ``if / elif``).  A job whose
+    guided conditions are meshes for some and clouds for others raises ``ValueError``: a chain has groups of one kind.  Host
+    logic only."""
+    kinds, data = set(), []
+    for i, c in enumerate(conditions):
+        if not isinstance(c, (tuple, list)) or len(c) not in (2, 3):
+            raise ValueError(f"conditions[{i}] must be (shape_emb, use_pointcloud_data[, use_mesh_data])")
+        mesh, cloud = (c[2] if len(c) == 3 else None), c[1]
+        if mesh is not None:
+            kinds.add("mesh"), data.append(mesh)
+        elif cloud is not None:
+            kinds.add("cloud"), data.append(cloud)
+        else:
+            data.append(None)
+    if len(kinds) == 2:
+        raise ValueError("sample_diffusion_ligand_multi: the guided conditions mix meshes and point clouds; a chain takes groups of "
+                         "one kind -- run the two kinds as two jobs")
+    return (kinds.pop() if kinds else None), data
+
+
+def guidance_groups(kind, data, segs):
+    """The group list of one batch of :func:`plan_batches` for ``sample_diffusion``: the keyword and its value, or (None, None)
+    when no condition of the batch is guided."""
+    if kind is None or all(data[c] is None for c, _f, _n in segs):
+        return None, None
+    if kind == "mesh":
+        return "use_mesh_data", [(None, None, None, n) if data[c] is None else (data[c][0], data[c][1], None, n) for c, _f, n in segs]
+    return "use_pointcloud_data", [(None, None, None, n) if data[c] is None else (data[c][0], None, data[c][2], n) for c, _f, n in segs]
+
+
 def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256, device="cuda:0", num_steps=None,
                                   center_pos_mode="none", sample_func=None, sample_num_atoms="prior", ref_num_atoms=None,
                                   seed=None, use_graph=True, host_rng=False, grad_step=1000):
     """``sample_diffusion_ligand`` for MANY shape conditions at once: ``num_samples`` molecules for each of ``conditions``, with
     molecules of different conditions sharing the chains.
 
-    conditions       sequence of ``(shape_emb (32, 3), use_pointcloud_data or None)``; ``use_pointcloud_data`` is the
-                     reference's ``(point_clouds, kdtree, radius)`` of that condition, None leaves its molecules unguided.
+    conditions       sequence of ``(shape_emb (32, 3), use_pointcloud_data or None[, use_mesh_data or None])``;
+                     ``use_pointcloud_data`` is the reference's ``(point_clouds, kdtree, radius)`` of that condition,
+                     ``use_mesh_data`` its ``(mesh, point_clouds, kdtree)``; with neither the condition's molecules are unguided.
+                     The guided conditions of a job are all meshes or all clouds (``ValueError`` otherwise, before any chain runs).
     num_samples      molecules per condition.
     batch_size       molecules per chain.  The ``len(conditions) * num_samples`` molecules are laid out condition-major and cut
                      into batches of this size (:func:`plan_batches`); every batch runs as ONE chain, in which each condition's run
-                     of molecules is guided towards its own cloud (``sample_diffusion`` with a list of groups).
+                     of molecules is guided towards its own cloud or by its own mesh (``sample_diffusion`` with a list of groups).
     sample_func, ref_num_atoms   as for :func:`sample_diffusion_ligand`, or a sequence with one entry per condition (the
                      atom-count prior depends on the condition's voxel size).  ``sample_func`` is called once per condition and
                      batch, in batch order.
@@ -344,8 +379,11 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
     two values of ``batch_size`` are not the same computation in the reference.  After ``model.eval()`` (running statistics)
     molecules are independent, and a mixed batch reproduces the per-condition chains on the same per-molecule random numbers.
 
-    The chains run one after the other (installing and removing the clouds drains the device, as for one cloud).
-    Not covered: ``pos_only``, classifier-free guidance and mesh guidance (one mesh per chain); use
+    The chains run one after the other (installing and removing the clouds or meshes drains the device, as for one cloud).
+    With mesh conditions, a condition whose molecules run short of atoms inside its mesh in some step (fewer than 3: the
+    reference's KD-tree error) fails the whole batch it shares: ``MeshGuidanceError`` names the group, i.e. the position of
+    the condition among the batch's conditions (:func:`plan_batches`), and no condition of that batch gets its molecules.
+    Not covered: ``pos_only``, classifier-free guidance, and meshes mixed with clouds in one job; use
     :func:`sample_diffusion_ligand` per condition for those.
 
     Returns a list with, per condition, the reference's 9-tuple in the layout :func:`sample_diffusion_ligand` returns;
@@ -356,7 +394,7 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
     dev = torch.device(device)
     n_cond = len(conditions)
     shapes = [torch.as_tensor(c[0], dtype=torch.float32).reshape(1, -1) for c in conditions]
-    clouds = [c[1] for c in conditions]
+    kind, gdata = plan_guidance(conditions)
     funcs = _per_condition(sample_func, n_cond, "sample_func")
     refs = _per_condition(ref_num_atoms, n_cond, "ref_num_atoms")
     keys = ("pos", "v", "pos_traj", "v_traj", "v0_traj", "vt_traj", "time", "pos_cond_traj", "v_cond_traj")     # the 9-tuple's order
@@ -372,14 +410,13 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
         init_ligand_pos = torch.randn(all_ligand_atoms, 3).to(dev)            # host generator, as the reference
         init_ligand_v = _initial_types(model, all_ligand_atoms, dev, host_rng)
         noise_kw = {"noise": _host_noise(model, num_steps, all_ligand_atoms, dev, True)} if host_rng else {}
-        groups = None
-        if any(clouds[c] is not None for c, _f, _n in segs):
-            groups = [(None, None, None, n) if clouds[c] is None else (clouds[c][0], None, clouds[c][2], n) for c, _f, n in segs]
+        gkey, groups = guidance_groups(kind, gdata, segs)
+        guide_kw = {gkey: groups} if gkey else {}
         r = model.sample_diffusion(
             init_ligand_pos=init_ligand_pos, init_ligand_v=init_ligand_v, batch_ligand=batch_ligand,
             ligand_shape=torch.cat([shapes[c].repeat(n, 1) for c, _f, n in segs]).to(dev), num_steps=num_steps,
-            center_pos_mode=center_pos_mode, use_pointcloud_data=groups, grad_step=grad_step,
-            seed=None if seed is None else int(seed) + i, use_graph=use_graph, _reuse_host_buffers="device", **noise_kw)
+            center_pos_mode=center_pos_mode, grad_step=grad_step,
+            seed=None if seed is None else int(seed) + i, use_graph=use_graph, _reuse_host_buffers="device", **guide_kw, **noise_kw)
         o = _unbatch_result(r, ligand_num_atoms, False)
         dt, m = time.time() - t1, 0
         for c, _first, n in segs:
