@@ -357,6 +357,10 @@ int shapemol_seg_attention_backward(const float *d_q, const float *d_k, const fl
  *          "graph_fuse" (1 = kNN graph + edge weights in one launch when max_mol_atoms is known and <= 128 [default]),
  *          "ddpm_fold"  (_sample only: 1 = the last layer's coordinate update inside the posterior-step kernel when the
  *                        fold above applies and no guidance is set [default]),
+ *          "prologue_tab" (1 = the node prologue of an evaluation (h0, layer-0 queries, layer-0 per-node products) is a gather from
+ *                        tables over every (timestep, atom type) pair, built once per context and node precision mode by the
+ *                        per-atom prologue kernel [default]; 0 = that per-atom kernel at every evaluation.  Same results to the
+ *                        bit; tuning / A/B),
  *          "edge_waves" (waves per workgroup of the edge kernels, 1..12; 0 = automatic: ceil(jobs / CUs) [default]; a
  *                        value other than 0 also selects the separate launches),
  *          "lin_waves"  (1..16 waves per workgroup of node_linear_kernel, tuning),
@@ -382,6 +386,8 @@ int shapemol_set_knn_pins(shapemol_ctx *ctx, const int32_t *h_off, int32_t n_ste
 void shapemol_debug_split_exact(float x, uint16_t *pieces);
 /* Copy an internal device buffer of the last _score to HOST memory (synchronises the device).
  * names: "nbr" (N,KP) i32, "ew" (N,KP) f32, "h" (N,H), "x" (N,3), "pre" (N,4H), "q" (N,H),
+ *        "h0" (N,H), "q_x" (N,H), "pre0" (N,4H), "add0" (B,4H): the node prologue's outputs and the per-molecule term it adds
+ *        (intact after an evaluation with stop_layer = 1),
  *        "att" (N,H), "o3" (N,48), "bnstat" (L,16,2,heads) f64, "dims" (8,) i64,
  *        "captures" (1,) i64 hipGraph captures of this context so far,
  *        "mesh_group_flags" (G,) i32: per group of the last chain / pass with mesh groups, the steps in which the group was

@@ -56,6 +56,13 @@ struct shapemol_ctx {
     float *d_img = nullptr;
     float *ttab = nullptr;      // [T][D] time-embedding table (built once)
     float *etab = nullptr;      // [T][C][H] atom embedding of every (timestep, atom type) pair (built once)
+    // the rest of the node prologue per (timestep, atom type) pair (ensure_prologue_tables; node_prologue_tab_kernel gathers from them).
+    // One device block: [q_tab | pre_tab | v, mol_of, t_mol of the pseudo-batch they are built from | range flag of the build]
+    float *q_tab = nullptr;     // [T][C][H] queries of layer 0's x2h attention
+    float *pre_tab = nullptr;   // [T][C][4H] per-node halves of layer 0's edge MLPs, without the per-molecule term
+    int64_t *tab_v = nullptr; int *tab_mol_of = nullptr, *tab_t_mol = nullptr, *tab_flag = nullptr;
+    int tab_key = 0;            // node precision mode the tables were built in (prologue_tab_key), 0 = not built
+    int prologue_tab = 1;       // 1: the per-step node prologue gathers from the tables; 0: the per-atom MLP kernel
     DevModel dm;
     // workspace
     int64_t capN = 0, capB = 0;
@@ -631,6 +638,60 @@ H2xPlan h2x_plan(const shapemol_ctx *c, int l, bool fold, bool has_next, bool ha
     return p;
 }
 
+// The per-atom node prologue (node_prologue6_kernel / node_prologue16_kernel of the node precision mode in use): its arguments
+// without the per-evaluation bookkeeping, and its launch
+template <int H>
+NodePrologueArgs prologue_args(const shapemol_ctx *c, const int64_t *v, const int *mol_of, const int *t_mol, const float *add_mol,
+                               float *h_out, float *q_out, float *pre_out, int n) {
+    const DevLayer &D0 = c->dm.layer[0];
+    NodePrologueArgs pa{};
+    pa.emb_wT = c->P(c->dm.embwT); pa.emb_b = c->P(c->dm.embb); pa.v = v; pa.mol_of = mol_of; pa.ttab = c->ttab; pa.etab = c->etab; pa.t_mol = t_mol;
+    pa.h_out = h_out;
+    pa.q = follow_of(c, D0.q_x2h, NODE_LN_RELU, q_out, H, H);
+    pa.lin_img6 = c->P(c->node_f16 ? D0.pre16_x2h : D0.pre6_x2h); pa.add_mol = add_mol; pa.pre_out = pre_out;
+    pa.n_lin_tiles = 4 * (H / 16); pa.ld_add = 4 * H; pa.ld_out = 4 * H;
+    pa.n_atoms = n; pa.C = c->cfg.num_classes; pa.D = c->cfg.time_emb_dim;
+    return pa;
+}
+
+template <int H>
+int launch_prologue(shapemol_ctx *c, hipStream_t s, const NodePrologueArgs &pa, int *range_flag = nullptr) {
+    const int n_ct = (pa.n_atoms + 15) / 16;
+    const dim3 grid((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), block(H * 4);
+    if (!range_flag) range_flag = c->status + ST_RANGE;
+    if (c->node_f16 && c->feat_f16) LAUNCH("node_prologue", SMK((node_prologue16_kernel<H, true>), grid, block, 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, range_flag));
+    else if (c->node_f16) LAUNCH("node_prologue", SMK(node_prologue16_kernel<H>, grid, block, 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, range_flag));
+    else LAUNCH("node_prologue", SMK(node_prologue6_kernel<H>, grid, block, 2 * Chain6Lds<H>::FRAG * 16 + Chain6Lds<H>::PRE * 4, s, pa));
+    return 0;
+}
+
+// which of the three prologue kernels the node precision options select; the tables are keyed by it
+int prologue_tab_key(const shapemol_ctx *c) { return 1 + (c->node_f16 ? 1 + (c->feat_f16 ? 1 : 0) : 0); }
+
+// q_tab / pre_tab for the precision mode in use, on the stream of the evaluation that needs them (before any graph capture: the
+// first build allocates).  Built with the prologue kernel itself over the pseudo-batch of T x C atoms, atom (t, c) of type c at
+// timestep t, without a per-molecule term: the table rows are the bits that kernel writes for a real atom with that pair.
+// (Its h0 output goes back onto the etab rows it was read from, unchanged.)
+template <int H>
+int ensure_prologue_tables(shapemol_ctx *c, hipStream_t s) {
+    if (!c->prologue_tab || !(c->chain_bf16 && c->lin_bf16) || c->tab_key == prologue_tab_key(c)) return 0;
+    const int T = c->cfg.num_timesteps, C = c->cfg.num_classes;
+    const size_t rows = (size_t)T * C;
+    if (!c->q_tab) {
+        void *blk = nullptr;
+        HIPCHK(hipMalloc(&blk, rows * 5 * H * sizeof(float) + rows * (sizeof(int64_t) + sizeof(int)) + ((size_t)T + 1) * sizeof(int)));
+        c->q_tab = static_cast<float *>(blk); c->pre_tab = c->q_tab + rows * H;
+        c->tab_v = reinterpret_cast<int64_t *>(c->pre_tab + rows * 4 * H);
+        c->tab_mol_of = reinterpret_cast<int *>(c->tab_v + rows); c->tab_t_mol = c->tab_mol_of + rows; c->tab_flag = c->tab_t_mol + T;
+    }
+    c->tab_key = 0;
+    LAUNCH("prep", SMK(prologue_tab_index_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, c->tab_v, c->tab_mol_of, c->tab_t_mol, c->tab_flag, T, C));
+    const NodePrologueArgs pa = prologue_args<H>(c, c->tab_v, c->tab_mol_of, c->tab_t_mol, nullptr, c->etab, c->q_tab, c->pre_tab, (int)rows);
+    if (launch_prologue<H>(c, s, pa, c->tab_flag)) return 1;
+    c->tab_key = prologue_tab_key(c);
+    return 0;
+}
+
 // One score evaluation on prepared batch data.  x_in/v_in: current state; outputs as given.
 template <int H>
 int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *v_in, int64_t N, int64_t B,
@@ -644,23 +705,17 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                    c->steps + 1, c->bn_acc, c->h_a, n, H, C, D, t_first, L * kBnReplicas * 2 * hd + L};   // + the grid-barrier counters
     const int nlay = c->stop_layer >= 0 ? std::min(c->stop_layer, L) : L;
     const bool fused_prologue = c->chain_bf16 && c->lin_bf16;   // embedding + first queries + first per-node products in one launch
-    if (fused_prologue) {
-        const DevLayer &D0 = c->dm.layer[0];
-        NodePrologueArgs pa{};
-        pa.emb_wT = c->P(c->dm.embwT); pa.emb_b = ae.b; pa.v = v_in; pa.mol_of = c->mol_of; pa.ttab = c->ttab; pa.etab = c->etab; pa.t_mol = c->t_mol;
-        pa.step_ptr = ae.step_ptr; pa.step_cur = ae.step_cur; pa.bn_acc = c->bn_acc; pa.h_out = c->h_a;
-        pa.q = follow_of(c, D0.q_x2h, NODE_LN_RELU, c->q_x, H, H);
-        pa.lin_img6 = c->P(c->node_f16 ? D0.pre16_x2h : D0.pre6_x2h); pa.add_mol = c->add0; pa.pre_out = c->pre0;
-        pa.n_lin_tiles = nlay > 0 ? 4 * (H / 16) : 0; pa.ld_add = 4 * H; pa.ld_out = 4 * H;
-        pa.n_atoms = n; pa.C = C; pa.D = D; pa.t_first = t_first; pa.bn_acc_len = ae.bn_acc_len;
+    if (fused_prologue && c->prologue_tab) {      // the same three outputs, gathered from the per-(timestep, type) tables
+        if (c->tab_key != prologue_tab_key(c)) return fail("run_score: the prologue tables are not built for this precision mode");
+        PrologueTabArgs ta{c->etab, c->q_tab, c->pre_tab, c->tab_flag, v_in, c->mol_of, c->t_mol, ae.step_ptr, ae.step_cur, c->bn_acc,
+                           c->add0, c->h_a, c->q_x, c->pre0, c->status + ST_RANGE, n, C, g.num_timesteps, t_first, ae.bn_acc_len};
+        LAUNCH("node_prologue", SMK(node_prologue_tab_kernel<H>, dim3((unsigned)((N * 16 + kProTabThreads - 1) / kProTabThreads)), dim3(kProTabThreads), 0, s, ta));
+    } else if (fused_prologue) {
+        NodePrologueArgs pa = prologue_args<H>(c, v_in, c->mol_of, c->t_mol, c->add0, c->h_a, c->q_x, c->pre0, n);
+        pa.step_ptr = ae.step_ptr; pa.step_cur = ae.step_cur; pa.bn_acc = c->bn_acc; pa.bn_acc_len = ae.bn_acc_len; pa.t_first = t_first;
+        if (nlay == 0) pa.n_lin_tiles = 0;
         pa.stamps = c->kstamp_sel == 5 ? c->kstamps : nullptr;
-        const int n_ct = (n + 15) / 16;
-        if (c->node_f16 && c->feat_f16) LAUNCH("node_prologue", SMK((node_prologue16_kernel<H, true>), dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4),
-                                                   2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, c->status + ST_RANGE));
-        else if (c->node_f16) LAUNCH("node_prologue", SMK(node_prologue16_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4),
-                                                   2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, c->status + ST_RANGE));
-        else LAUNCH("node_prologue", SMK(node_prologue6_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4),
-                                                   2 * Chain6Lds<H>::FRAG * 16 + Chain6Lds<H>::PRE * 4, s, pa));
+        if (launch_prologue<H>(c, s, pa)) return 1;
     } else {
         LAUNCH("embed", SMK(atom_embed_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, ae));
     }
@@ -916,6 +971,7 @@ void shapemol_destroy(shapemol_ctx *c) {
     for (void *p : c->allocs) hipFree(p);
     hipFree(c->ttab);
     hipFree(c->etab);
+    hipFree(c->q_tab);
     hipFree(c->d_img);
     if (c->g_cloud) hipFree(c->g_cloud);
     if (c->gg_clouds) hipFree(c->gg_clouds);
@@ -960,6 +1016,7 @@ int shapemol_score(shapemol_ctx *c, const float *d_pos, const int64_t *d_v, cons
     if (ensure_workspace(c, N, B)) return 1;
     hipStream_t s = (hipStream_t)stream;
     c->lastN = N; c->lastB = B;
+    if (DISPATCH_H(c, ensure_prologue_tables<128>(c, s), ensure_prologue_tables<32>(c, s))) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
     if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
     LAUNCH("prep", SMK(t_convert_kernel, dim3((B + 255) / 256), dim3(256), 0, s, d_t, (int)B, c->cfg.num_timesteps, c->t_mol, c->status));
@@ -979,6 +1036,7 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     if (ensure_workspace(c, N, B)) return 1;
     hipStream_t s = (hipStream_t)stream;
     c->lastN = N; c->lastB = B;
+    if (DISPATCH_H(c, ensure_prologue_tables<128>(c, s), ensure_prologue_tables<32>(c, s))) return 1;
     const int t_first = c->cfg.num_timesteps - 1;
     const Guide kind = chain_guide(c);
     const bool mesh = kind == Guide::Mesh, mesh_groups = kind == Guide::MeshGroups, cfg = kind == Guide::Cfg;
@@ -1114,6 +1172,7 @@ int shapemol_set_option(shapemol_ctx *c, const char *name, int64_t value) {
     else if (k == "bn_eval") c->bn_eval = value != 0;
     else if (k == "ddpm_fold") c->ddpm_fold = value != 0;
     else if (k == "vn_fold") c->vn_fold = value != 0;
+    else if (k == "prologue_tab") c->prologue_tab = value != 0;      // 0: the per-atom MLP prologue (A/B, equivalence tests)
     else if (k == "lin_bf16") c->lin_bf16 = (int)value;
     else if (k == "chain_bf16") c->chain_bf16 = (int)value;
     else if (k == "vn_fuse") c->vn_fuse = (int)value;
@@ -1140,6 +1199,10 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     else if (k == "ew") { src = c->ew; bytes = N * c->KP * 4; }
     else if (k == "h") { src = c->last_h; bytes = N * g.hidden_dim * 4; }
     else if (k == "x") { src = c->last_x; bytes = N * 3 * 4; }
+    else if (k == "h0") { src = c->h_a; bytes = N * g.hidden_dim * 4; }                   // the prologue's outputs: intact after an
+    else if (k == "q_x") { src = c->q_x; bytes = N * g.hidden_dim * 4; }                  // evaluation with stop_layer = 1
+    else if (k == "pre0") { src = c->pre0; bytes = N * 4 * g.hidden_dim * 4; }
+    else if (k == "add0") { src = c->add0; bytes = (size_t)c->lastB * 4 * g.hidden_dim * 4; }
     else if (k == "pre") { src = c->preAB; bytes = N * 8 * g.hidden_dim * 4; }
     else if (k == "q") { src = c->q_h; bytes = N * g.hidden_dim * 4; }
     else if (k == "att") { src = c->att; bytes = N * g.hidden_dim * 4; }

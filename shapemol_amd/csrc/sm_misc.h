@@ -279,6 +279,91 @@ __global__ void atom_embed_kernel(AtomEmbArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The node prologue as a gather.  Everything node_prologue6_kernel / node_prologue16_kernel compute per atom depends on
+// the atom through its (timestep, atom type) pair alone, apart from the per-molecule term added to the linear outputs.  The
+// tables over all T x C pairs are built once per context and precision mode by running that very kernel over a pseudo-batch
+// (ensure_prologue_tables); an evaluation then copies three rows per atom:
+//     h0[i] = etab[t][v_i]      q[i] = q_tab[t][v_i]      pre0[i] = pre_tab[t][v_i] + add_mol[mol_i]
+// All three are the bits the per-atom kernel writes (it, too, adds the add_mol row to the finished products).
+// 16 lanes per atom, 16-byte accesses.
+// Same bookkeeping as the kernel it replaces: latch the step counter, clear the batch-norm accumulators.
+// ---------------------------------------------------------------------------------------------
+struct PrologueTabArgs {
+    const float *etab, *q_tab, *pre_tab;   // [T][C][H], [T][C][H], [T][C][4H]
+    const int *tab_flag;                   // != 0: an activation left the fp16 range while the tables were built (f16 modes)
+    const int64_t *v;                      // [N]
+    const int *mol_of;
+    const int *t_mol;                      // [B] timestep per molecule (score API)
+    const int *step_ptr;                   // sampling: device step counter (t = t_first - step), else nullptr
+    int *step_cur;
+    double *bn_acc;                        // zeroed here
+    const float *add_mol;                  // [B][4H]
+    float *h_out, *q_out, *pre_out;        // [N][H], [N][H], [N][4H]
+    int *range_flag;
+    int n_atoms, C, T, t_first, bn_acc_len;
+};
+
+constexpr int kProTabThreads = 256;
+
+template <int H>
+__global__ void __launch_bounds__(kProTabThreads)
+node_prologue_tab_kernel(PrologueTabArgs a) {
+    constexpr int R = H / 64;            // 16-byte pieces of an [H] row per lane (16 lanes per atom)
+    static_assert(H % 64 == 0 || H == 32, "16 lanes x 16 bytes cover a row in whole passes");
+    const int gid = blockIdx.x * kProTabThreads + threadIdx.x;
+    const int step = a.step_ptr ? *a.step_ptr : 0;
+    if (gid == 0) {
+        if (a.step_ptr) *a.step_cur = step;
+        if (*a.tab_flag) *a.range_flag = 1;
+    }
+    for (int i = gid; i < a.bn_acc_len; i += gridDim.x * kProTabThreads) a.bn_acc[i] = 0.0;
+    const int atom = gid >> 4, ln = gid & 15;
+    if (atom >= a.n_atoms) return;
+    const int mol = a.mol_of[atom];
+    const int t = min(max(a.step_ptr ? a.t_first - step : a.t_mol[mol], 0), a.T - 1);   // out-of-range steps are flagged by t_convert_kernel
+    const int vi = min(max((int)a.v[atom], 0), a.C - 1);                                // ... and types by v_check_kernel
+    const size_t row = (size_t)t * a.C + vi;
+    if constexpr (H == 32) {             // 8 + 8 + 32 pieces per atom: three per lane
+        const int f = 4 * (ln & 7);
+        const float *src = (ln < 8 ? a.etab : a.q_tab) + row * H + f;
+        const float4 hq = ldg4(src);
+        const float4 p0 = ldg4(a.pre_tab + row * 4 * H + 4 * ln), p1 = ldg4(a.pre_tab + row * 4 * H + 64 + 4 * ln);
+        const float4 m0 = ldg4(a.add_mol + (size_t)mol * 4 * H + 4 * ln), m1 = ldg4(a.add_mol + (size_t)mol * 4 * H + 64 + 4 * ln);
+        stg4((ln < 8 ? a.h_out : a.q_out) + (size_t)atom * H + f, hq);
+        stg4(a.pre_out + (size_t)atom * 4 * H + 4 * ln, float4{p0.x + m0.x, p0.y + m0.y, p0.z + m0.z, p0.w + m0.w});
+        stg4(a.pre_out + (size_t)atom * 4 * H + 64 + 4 * ln, float4{p1.x + m1.x, p1.y + m1.y, p1.z + m1.z, p1.w + m1.w});
+    } else {
+        float4 h[R], q[R], p[4 * R], m[4 * R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            h[r] = ldg4(a.etab + row * H + 64 * r + 4 * ln);
+            q[r] = ldg4(a.q_tab + row * H + 64 * r + 4 * ln);
+        }
+#pragma unroll
+        for (int r = 0; r < 4 * R; ++r) {
+            p[r] = ldg4(a.pre_tab + row * 4 * H + 64 * r + 4 * ln);
+            m[r] = ldg4(a.add_mol + (size_t)mol * 4 * H + 64 * r + 4 * ln);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            stg4(a.h_out + (size_t)atom * H + 64 * r + 4 * ln, h[r]);
+            stg4(a.q_out + (size_t)atom * H + 64 * r + 4 * ln, q[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4 * R; ++r)
+            stg4(a.pre_out + (size_t)atom * 4 * H + 64 * r + 4 * ln, float4{p[r].x + m[r].x, p[r].y + m[r].y, p[r].z + m[r].z, p[r].w + m[r].w});
+    }
+}
+
+// index arrays of the pseudo-batch the tables are built from: atom (t, c) has type c and belongs to "molecule" t, whose timestep is t
+__global__ void prologue_tab_index_kernel(int64_t *v, int *mol_of, int *t_mol, int *flag, int T, int C) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *flag = 0;
+    if (i < T) t_mol[i] = i;
+    if (i < T * C) { v[i] = i % C; mol_of[i] = i / C; }
+}
+
+// ---------------------------------------------------------------------------------------------
 // kNN graph (uni_transformer.py:466-468; torch_geometric knn_graph semantics): one wave per
 // centre atom.  The rank of candidate c is the number of candidates of the same molecule with a
 // smaller (squared distance, index) key; rank < k selects slot `rank`.  The squared distance is

@@ -500,14 +500,18 @@ node_prologue16_kernel(NodePrologueArgs a, int *range_flag) {
     const bool onq = ot < a.q.nt2;
     if (onq) N16::template load_w<NB>(a.q.w2img6, ot, lane, wq1);   // second Linear of the query MLP (reuses the registers)
     auto lin_tile = [&](int tile, const u32x4 (&w)[2][NB]) {
+        // the per-molecule term is added to the finished products, not accumulated onto: the rows of pre_tab (built by this kernel
+        // without the term) plus the term, as node_prologue_tab_kernel adds them, are then these very bits
         f32x4 acc[CC];
 #pragma unroll
-        for (int c = 0; c < CC; ++c) {
-            const float4 t = a.add_mol ? ldg4(a.add_mol + (size_t)a.mol_of[atom_of(c)] * a.ld_add + 16 * tile + 4 * g)
-                                       : float4{0.f, 0.f, 0.f, 0.f};
-            acc[c] = f32x4{t.x, t.y, t.z, t.w};
-        }
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
         N16::template gemm<NB>(w, fh, acc, lane);
+#pragma unroll
+        for (int c = 0; c < CC; ++c) {
+            if (!a.add_mol) continue;
+            const float4 t = ldg4(a.add_mol + (size_t)a.mol_of[atom_of(c)] * a.ld_add + 16 * tile + 4 * g);
+            acc[c][0] += t.x; acc[c][1] += t.y; acc[c][2] += t.z; acc[c][3] += t.w;
+        }
 #pragma unroll
         for (int c = 0; c < CC; ++c)
             if (atom_ok(c)) stg4(a.pre_out + (size_t)atom_of(c) * a.ld_out + 16 * tile + 4 * g, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
