@@ -109,12 +109,16 @@ int shapemol_sample(shapemol_ctx *ctx, const float *d_init_pos, const int64_t *d
  * fraction in [0.2, 0.8), up to five times.  h_cloud: HOST (n_points,3) float64 (copied); n_points = 0 switches it off.
  * d_draws: DEVICE (S,5,N) float64 uniforms, the np.random.random() draw of every (step, iteration, atom) (parity mode;
  * entries of atoms that are not pulled are ignored), or NULL: Philox(seed of the chain).  Replaces the reference's
- * per-step D2H + KD-tree + H2D round trip by one kernel inside the step graph. */
+ * per-step D2H + KD-tree + H2D round trip by one kernel inside the step graph.
+ * A context holds ONE set of cloud groups (shapemol_set_guidance_groups): this call installs a set of one group that spans
+ * whatever batch the following _sample calls bring (no n_mols requirement), in place of the set installed before, and
+ * n_points = 0 empties the slot -- also when the set in it came from shapemol_set_guidance_groups. */
 int shapemol_set_guidance(shapemol_ctx *ctx, const double *h_cloud, int64_t n_points, double radius,
                           int32_t grad_step, const double *d_draws);
 
 /* pointcloud_shape_guidance on its own (models/molopt_score_model.py:699-740): guide d_pos (N,3) f32 in place against the
- * cloud of shapemol_set_guidance; d_draws DEVICE (5,N) float64 or NULL (Philox(seed)). */
+ * cloud of shapemol_set_guidance (shapemol_guide_points_groups without a batch vector: the one group is all N atoms);
+ * d_draws DEVICE (5,N) float64 or NULL (Philox(seed)). */
 int shapemol_guide_points(shapemol_ctx *ctx, float *d_pos, int64_t n_points, const double *d_draws, uint64_t seed, void *stream);
 
 /* Point-cloud shape guidance with one cloud per GROUP of molecules, for the following _sample calls.  Group g is the contiguous
@@ -124,8 +128,8 @@ int shapemol_guide_points(shapemol_ctx *ctx, float *d_pos, int64_t n_points, con
  * (S,5,N) float64 table indexed by the batch-global atom, or NULL: Philox(seed of the chain) keyed by the batch-global atom.
  * Validated on the host (offsets start at 0 and do not decrease, every non-empty cloud has 3 .. 2048 points and a radius > 0);
  * the error names the offending group.  shapemol_sample then requires n_mols == h_mol_off[n_groups].  n_groups = 0 removes the
- * groups.  Installing groups removes a single cloud and shapemol_set_guidance removes the groups; a mesh, when set, takes
- * precedence over both. */
+ * groups.  The set replaces whatever shapemol_set_guidance or this function installed before; a mesh, when set, takes
+ * precedence. */
 int shapemol_set_guidance_groups(shapemol_ctx *ctx, int32_t n_groups, const int64_t *h_mol_off, const double *h_clouds,
                                  const int64_t *h_cloud_off, const double *h_radius, int32_t grad_step, const double *d_draws);
 
@@ -153,11 +157,15 @@ int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_cloud, double 
  * ray (sm_mesh.h), not trimesh's code.  h_cloud: HOST (n_cloud,3) float64, 3 .. 2048 points.  All three are copied;
  * n_faces = 0 switches guidance off.  d_draws: DEVICE (S,5,N) float64 uniforms as for shapemol_set_guidance, or NULL
  * (Philox(seed of the chain), a counter domain of its own).  Fewer than 3 within-atoms (none at all, or fewer than 3 while
- * some atom is to be pulled) raises status flag 6 (the reference's KD-tree raises ValueError there); the step is left unguided. */
+ * some atom is to be pulled) raises status flag 6 (the reference's KD-tree raises ValueError there); the step is left unguided.
+ * A context holds ONE set of mesh groups (shapemol_set_mesh_guidance_groups): this call installs a set of one group that
+ * spans whatever batch the following _sample calls bring (no n_mols requirement), in place of the set installed before, and
+ * n_faces = 0 empties the slot -- also when the set in it came from shapemol_set_mesh_guidance_groups. */
 int shapemol_set_mesh_guidance(shapemol_ctx *ctx, const double *h_verts, int64_t n_verts, const int32_t *h_faces,
                                int64_t n_faces, const double *h_cloud, int64_t n_cloud, int32_t grad_step, const double *d_draws);
 
-/* mesh_shape_guidance on its own: guide d_pos (N,3) f32 DEVICE in place against the mesh of shapemol_set_mesh_guidance;
+/* mesh_shape_guidance on its own: guide d_pos (N,3) f32 DEVICE in place against the mesh of shapemol_set_mesh_guidance
+ * (shapemol_guide_points_mesh_groups without a batch vector: the one group is all N atoms);
  * d_draws DEVICE (5,N) float64 or NULL (Philox(seed)).  Asynchronous on `stream`; the status flag as above (clear before). */
 int shapemol_guide_points_mesh(shapemol_ctx *ctx, float *d_pos, int64_t n_atoms, const double *d_draws, uint64_t seed,
                                void *stream);
@@ -169,11 +177,11 @@ int shapemol_guide_points_mesh(shapemol_ctx *ctx, float *d_pos, int64_t n_atoms,
  * h_cloud_off[g + 1] - 1 of h_clouds (HOST (sum P_g, 3) float64); all are copied.  One guided step is shapemol_set_mesh_guidance's
  * step applied once per group to the group's atoms: the within-atoms and the 3-nearest search among them are PER GROUP.  A
  * group with no vertices, faces and cloud is left unguided.  d_draws is the same DEVICE (S,5,N) float64 table indexed by the
- * batch-global atom, or NULL: Philox(seed of the chain) keyed by the batch-global atom in the single mesh's counter domain.
+ * batch-global atom, or NULL: Philox(seed of the chain) keyed by the batch-global atom (a counter domain of its own).
  * Validated on the host (all offsets start at 0 and do not decrease; every non-empty group has >= 3 vertices, >= 1 face with
  * indices inside the group's vertices and none repeated, and a cloud of 3 .. 2048 points); the error names the offending
- * group.  shapemol_sample then requires n_mols == h_mol_off[n_groups].  n_groups = 0 removes the groups.  Installing groups
- * removes a single mesh and shapemol_set_mesh_guidance removes the groups; mesh groups take precedence over point clouds.  A
+ * group.  shapemol_sample then requires n_mols == h_mol_off[n_groups].  n_groups = 0 removes the groups.  The set replaces
+ * whatever shapemol_set_mesh_guidance or this function installed before; a mesh set takes precedence over point clouds.  A
  * group with fewer than 3 within-atoms (none at all, or fewer than 3 while one of its atoms is to be pulled) raises status
  * flag 6 and is left unguided in that step; the other groups are guided (shapemol_debug_read "mesh_group_flags" tells which). */
 int shapemol_set_mesh_guidance_groups(shapemol_ctx *ctx, int32_t n_groups, const int64_t *h_mol_off, const double *h_verts,

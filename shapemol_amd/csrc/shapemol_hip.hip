@@ -11,10 +11,9 @@
 #include "sm_node16.h"
 #include "sm_edge_stream.h"
 #include "sm_misc.h"
-#include "sm_mesh.h"
-#include "sm_guide_groups.h"
 #include "sm_cfg.h"
-#include "sm_mesh_groups.h"
+#include "sm_guide_groups.h"      // (shape guidance stays behind the other kernel headers: DESIGN.md section 13, layout note)
+#include "sm_mesh.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -45,7 +44,18 @@ constexpr int kGraphUnroll = SM_GRAPH_UNROLL;   // reverse steps per graph launc
 
 struct ProfRec { const char *name; hipEvent_t e0, e1; };
 
-enum class Guide { None, Cloud, Groups, Mesh, MeshGroups, Cfg };      // guidance of a chain's predicted x0: chain_guide (sm_guide_host.h)
+enum class Guide { None, Cloud, Mesh, Cfg };      // guidance of a chain's predicted x0: chain_guide (sm_guide_host.h)
+
+// Device data of shape guidance: per kind ONE set of groups of molecules (sm_guide_host.h installs and clears them).  `whole`: a
+// set of one group that spans whatever batch comes (shapemol_set_guidance / shapemol_set_mesh_guidance): no molecule count
+struct CloudSet {     // one device block: [clouds | radii | mol_off, cloud_off, atom_off, wg_off (G + 1 ints each)]
+    double *clouds = nullptr, *radius = nullptr; int *ints = nullptr;
+    int groups = 0, max_points = 0, grad_step = 0; int64_t mols = 0, points = 0; bool whole = false; const double *draws = nullptr;
+};
+struct MeshSet {      // one device block: [faces | face boxes | clouds | bounds G x 5 | mol_off, cloud_off, atom_off, wg_off, face_off]
+    MeshFace *faces = nullptr; double4 *fbox = nullptr; double *clouds = nullptr, *bounds = nullptr; int *ints = nullptr;
+    int groups = 0, max_points = 0, grad_step = 0; int64_t mols = 0, nfaces = 0; bool whole = false; const double *draws = nullptr;
+};
 
 }  // namespace
 
@@ -110,22 +120,12 @@ struct shapemol_ctx {
                                 // 1 = one looping launch (eight waves per workgroup, next job's rows prefetched), -1 = automatic (= 1) [default]
     float hid_max = 0.f;        // bound of the edge MLPs' hidden activations (LayerNorm outputs): must fit fp16 for edge_bf16 = 3
     int num_cu = 256;
-    // point-cloud shape guidance (shapemol_set_guidance)
-    double *g_cloud = nullptr; int64_t g_points = 0; double g_radius = 0.0; int g_grad_step = 0; const double *g_draws = nullptr;
-    // point-cloud shape guidance per group of molecules (shapemol_set_guidance_groups); replaces the single cloud and vice versa.
-    // One device block: [clouds | radii | mol_off, cloud_off, atom_off, wg_off (G + 1 ints each)]; the workgroup table is sized by the chain
-    double *gg_clouds = nullptr, *gg_radius = nullptr; int *gg_ints = nullptr; int2 *gg_table = nullptr; int64_t gg_table_cap = 0;
-    int gg_groups = 0, gg_max_points = 0, gg_grad_step = 0; int64_t gg_mols = 0, gg_points = 0; const double *gg_draws = nullptr;
-    // mesh shape guidance (shapemol_set_mesh_guidance); takes precedence over the point cloud when both are set
-    MeshFace *m_faces = nullptr; double4 *m_fbox = nullptr; double *m_cloud = nullptr;     // one device block
-    int64_t m_nfaces = 0, m_points = 0; int m_grad_step = 0; const double *m_draws = nullptr; double m_bounds[5] = {};
-    float4 *m_within = nullptr; int *m_out = nullptr, *m_cnt = nullptr; int64_t m_cap = 0, m_cnt_cap = 0;  // per-step lists (one block)
-    // mesh shape guidance per group of molecules (shapemol_set_mesh_guidance_groups); replaces the single mesh and vice versa.
-    // One device block: [faces | face boxes | clouds | bounds G x 5 | mol_off, cloud_off, atom_off, wg_off, face_off (G + 1 ints each)];
-    // the per-step lists are the single mesh's (counters: 4 per group), the workgroup table is the cloud groups'
-    MeshFace *mg_faces = nullptr; double4 *mg_fbox = nullptr; double *mg_clouds = nullptr, *mg_bounds = nullptr; int *mg_ints = nullptr;
-    int mg_groups = 0, mg_max_points = 0, mg_grad_step = 0; int64_t mg_mols = 0, mg_nfaces = 0; const double *mg_draws = nullptr;
-    int64_t mg_flag_groups = 0;     // groups of the last chain / pass with mesh groups (debug_read "mesh_group_flags")
+    // shape guidance of the predicted x0: the installed point-cloud set and mesh set (the mesh takes precedence when both are set),
+    // the per-workgroup table of whichever guides (sized by the chain) and the mesh's per-step lists (one block; counters: 4 per group)
+    CloudSet cs; MeshSet ms;
+    int2 *wg_table = nullptr; int64_t wg_table_cap = 0;
+    float4 *m_within = nullptr; int *m_out = nullptr, *m_cnt = nullptr; int64_t m_cap = 0, m_cnt_cap = 0;
+    int64_t m_flag_groups = 0;      // groups of the last chain / pass with a mesh set (debug_read "mesh_group_flags")
     // classifier-free guidance (shapemol_set_cfg): a second score evaluation per step on a zeroed shape, whose prepared shape
     // data (invariant embedding, shape terms, VN shape part) lives in the parallel *_u buffers; swap_uncond() exchanges the sets
     double cfg_w = 0.0, cfg_p = 0.0; int cfg_type = 0, cfg_has_bounds = 0; float cfg_lo[3] = {}, cfg_hi[3] = {};
@@ -973,11 +973,9 @@ void shapemol_destroy(shapemol_ctx *c) {
     hipFree(c->etab);
     hipFree(c->q_tab);
     hipFree(c->d_img);
-    if (c->g_cloud) hipFree(c->g_cloud);
-    if (c->gg_clouds) hipFree(c->gg_clouds);
-    if (c->gg_table) hipFree(c->gg_table);
-    if (c->m_faces) hipFree(c->m_faces);
-    if (c->mg_faces) hipFree(c->mg_faces);
+    cloud_set_clear(c->cs);
+    mesh_set_clear(c->ms);
+    if (c->wg_table) hipFree(c->wg_table);
     if (c->m_within) hipFree(c->m_within);
     if (c->bn_run) hipFree(c->bn_run);
     if (c->bn_eval_acc) hipFree(c->bn_eval_acc);
@@ -1039,18 +1037,16 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     if (DISPATCH_H(c, ensure_prologue_tables<128>(c, s), ensure_prologue_tables<32>(c, s))) return 1;
     const int t_first = c->cfg.num_timesteps - 1;
     const Guide kind = chain_guide(c);
-    const bool mesh = kind == Guide::Mesh, mesh_groups = kind == Guide::MeshGroups, cfg = kind == Guide::Cfg;
-    if (mesh && mesh_workspace(c, N, 1)) return 1;
-    if (mesh_groups && mesh_workspace(c, N, c->mg_groups)) return 1;
-    if (c->mg_groups > 0 && c->mg_mols != B)
-        return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the mesh guidance groups cover " + std::to_string(c->mg_mols) + " molecules");
-    if (c->gg_groups > 0 && c->gg_mols != B)        // (groups that are set must fit the batch even where another kind, or none, guides)
-        return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the guidance groups cover " + std::to_string(c->gg_mols) + " molecules");
-    if (kind == Guide::Groups && groups_table(c, s, d_batch, N, c->gg_ints, c->gg_groups)) return 1;
-    if (mesh_groups && groups_table(c, s, d_batch, N, c->mg_ints, c->mg_groups)) return 1;
+    const bool mesh = kind == Guide::Mesh, cfg = kind == Guide::Cfg;
+    if (mesh && mesh_workspace(c, N, c->ms.groups)) return 1;
+    if (c->ms.groups > 0 && !c->ms.whole && c->ms.mols != B)        // (groups that are set must fit the batch even where another kind, or none, guides)
+        return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the mesh guidance groups cover " + std::to_string(c->ms.mols) + " molecules");
+    if (c->cs.groups > 0 && !c->cs.whole && c->cs.mols != B)
+        return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the guidance groups cover " + std::to_string(c->cs.mols) + " molecules");
+    if (kind == Guide::Cloud && groups_table(c, s, c->cs.whole ? nullptr : d_batch, N, c->cs.ints, c->cs.groups)) return 1;
+    if (mesh && groups_table(c, s, c->ms.whole ? nullptr : d_batch, N, c->ms.ints, c->ms.groups)) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
-    if (mesh) HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
-    if (mesh_groups && mesh_counters_clear(c, s, c->mg_groups)) return 1;
+    if (mesh && mesh_counters_clear(c, s, c->ms.groups)) return 1;
     if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
     if (cfg) {      // classifier-free guidance: the unconditional evaluation's shape data, from a zeroed shape, once per chain
         swap_uncond(c);
@@ -1062,7 +1058,7 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_init_v, (int)N, c->cfg.num_classes, c->status));
     {
         ChainParams cp{};
-        cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->m_draws : (mesh_groups ? c->mg_draws : (c->gg_groups > 0 ? c->gg_draws : c->g_draws));
+        cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->ms.draws : c->cs.draws;
         if (traj) { cp.tr_pos = traj->pos_traj; cp.tr_v = traj->v_traj; cp.tr_v0 = traj->v0_traj; cp.tr_vt = traj->vt_traj;
                     cp.tr_pos_cond = traj->pos_cond_traj; cp.tr_v_cond = traj->v_cond_traj; }
         if (cfg) { cp.tr_pos_uncond = c->cfg_tr_pos_u; cp.tr_v_uncond = c->cfg_tr_v_u; }
@@ -1210,7 +1206,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     else if (k == "stamps") { src = c->stamps; bytes = 2048 * 8; }
     else if (k == "kstamps") { src = c->kstamps; bytes = (size_t)8 * 16 * 4096 * 8; }
     else if (k == "vn_err") { src = c->status + ST_VN_BARRIER; bytes = 4; }
-    else if (k == "mesh_group_flags") { src = c->m_cnt ? c->m_cnt + 4 * c->m_cnt_cap : nullptr; bytes = (size_t)c->mg_flag_groups * 4; }
+    else if (k == "mesh_group_flags") { src = c->m_cnt ? c->m_cnt + 4 * c->m_cnt_cap : nullptr; bytes = (size_t)c->m_flag_groups * 4; }
     else if (k == "cfg_stat") { src = c->cfg_stat; bytes = 2 * 4; }
     else if (k == "bnstat") { src = c->bn_acc; bytes = (size_t)g.num_layers * kBnReplicas * 2 * g.n_heads * 8; }
     else { fail("shapemol_debug_read: unknown buffer " + k); return -1; }

@@ -1,23 +1,26 @@
 // Host side of the guidance of a chain's predicted x0: which kind a chain uses (chain_guide), the launches of every kind
 // (enqueue_guidance), their device data (setters) and the stand-alone entry points of the C ABI.  Included by
 // shapemol_hip.hip behind shapemol_ctx and the LAUNCH / SMK macros.
+//
+// Shape guidance has one form per kind: a SET of groups of molecules, each group with its own cloud (CloudSet) or mesh
+// (MeshSet).  The single-cloud / single-mesh entry points use a set of one group marked `whole`: it spans whatever batch comes,
+// so it needs no batch vector (its atoms are [0, N)) and carries no molecule count to check.
 #pragma once
 
 namespace {
 
-// The guidance of the chains to come: the reference's if / elif in sample_diffusion -- mesh (one for the batch, or one per group
-// of molecules), else the point cloud (likewise: the setters keep at most one of each two), else classifier-free guidance.
-// Groups without any mesh / cloud guide nothing (and leave the next kind its turn).  The only place that spells this out.
+// The guidance of the chains to come: the reference's if / elif in sample_diffusion -- mesh, else the point cloud, else
+// classifier-free guidance.  Groups without any mesh / cloud guide nothing (and leave the next kind its turn).  The only place
+// that spells this out.
 Guide chain_guide(const shapemol_ctx *c) {
-    if (c->m_nfaces > 0) return Guide::Mesh;
-    if (c->mg_groups > 0 && c->mg_nfaces > 0) return Guide::MeshGroups;
-    if (c->g_points > 0) return Guide::Cloud;
-    if (c->gg_groups > 0 && c->gg_points > 0) return Guide::Groups;
+    if (c->ms.nfaces > 0) return Guide::Mesh;
+    if (c->cs.points > 0) return Guide::Cloud;
     return c->cfg_w != 0.0 ? Guide::Cfg : Guide::None;
 }
 
-// launch shape of the kernels that give every atom 16 lanes (pc_guidance, mesh_classify, mesh_pull); a cloud staged in LDS
-dim3 guide_grid(int64_t N) { return dim3((unsigned)((N * 16 + 255) / 256)); }
+// workgroups of the guidance kernels (16 atoms x 16 lanes each, every workgroup within one group): the sum over the groups of
+// ceil(n_g / 16) is at most floor(N / 16) + G
+unsigned groups_grid(int64_t N, int n_groups) { return (unsigned)(N / 16 + n_groups); }
 size_t cloud_lds_bytes(int64_t n_points) { return (size_t)n_points * 24; }
 // chain parameters of a stand-alone application: one step, always guided (callers pass t_first = grad_step + 1, no step counter)
 ChainParams guide_alone_params(uint64_t seed, const double *d_draws) {
@@ -26,45 +29,82 @@ ChainParams guide_alone_params(uint64_t seed, const double *d_draws) {
     return cp;
 }
 
-// ---- guidance per group of molecules (point clouds, meshes): host side
-// workgroups of the kernels that run per group: the sum over the groups of ceil(n_g / 16) is at most floor(N / 16) + G
-unsigned groups_grid(int64_t N, int n_groups) { return (unsigned)(N / 16 + n_groups); }
-
-PcGroupsArgs groups_args(const shapemol_ctx *c, float *d_pos, int64_t N, const int *step_cur, int t_first) {
-    const int G1 = c->gg_groups + 1;
+PcGroupsArgs cloud_args(const CloudSet &cs, const int2 *table, const ChainParams *cp, float *d_pos, int64_t N, const int *step_cur, int t_first) {
+    const int G1 = cs.groups + 1;
     PcGroupsArgs a{};
-    a.pred_pos = d_pos; a.clouds = c->gg_clouds; a.cloud_off = c->gg_ints + G1; a.radius = c->gg_radius; a.atom_off = c->gg_ints + 2 * G1;
-    a.wg_table = c->gg_table; a.cp = c->chain_params; a.step_cur = step_cur;
-    a.n_atoms = (int)N; a.t_first = t_first; a.grad_step = c->gg_grad_step; a.ratio = 0.2;
+    a.pred_pos = d_pos; a.clouds = cs.clouds; a.cloud_off = cs.ints + G1; a.radius = cs.radius; a.atom_off = cs.ints + 2 * G1;
+    a.wg_table = table; a.cp = cp; a.step_cur = step_cur;
+    a.n_atoms = (int)N; a.t_first = t_first; a.grad_step = cs.grad_step; a.ratio = 0.2;
     return a;
 }
 
-// the per-workgroup table of this chain (atom ranges come from the batch vector on the device); ints = the installed set's
-// [mol_off | cloud_off | atom_off | wg_off], G + 1 each (cloud groups or mesh groups: one table serves whichever guides)
+// within / out_list [N], cnt [G][2][2], flags [G]: the per-step lists (mesh_workspace, or the block of shapemol_mesh_guidance)
+MeshGroupsArgs mesh_args(const MeshSet &ms, const int2 *table, float4 *within, int *out_list, int *cnt, int *flags, int *status,
+                         const ChainParams *cp, float *d_pos, int64_t N, const int *step_cur, int t_first) {
+    const int G1 = ms.groups + 1;
+    MeshGroupsArgs a{};
+    a.pred_pos = d_pos; a.clouds = ms.clouds; a.faces = ms.faces; a.fbox = ms.fbox; a.bounds = ms.bounds;
+    a.cloud_off = ms.ints + G1; a.atom_off = ms.ints + 2 * G1; a.face_off = ms.ints + 4 * G1; a.wg_table = table;
+    a.within = within; a.out_list = out_list; a.cnt = cnt; a.group_flags = flags; a.status = status; a.cp = cp;
+    a.step_cur = step_cur; a.n_atoms = (int)N; a.t_first = t_first; a.grad_step = ms.grad_step;
+    return a;
+}
+
+// the per-workgroup table of this chain (atom ranges come from the batch vector on the device; d_batch = nullptr for a `whole`
+// set: one group, atoms [0, N)); ints = the installed set's [mol_off | cloud_off | atom_off | wg_off], G + 1 each (cloud groups
+// or mesh groups: one table serves whichever guides)
 int groups_table(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int *ints, int n_groups) {
     const int64_t n_wg = groups_grid(N, n_groups);
-    if (n_wg > c->gg_table_cap) {
+    if (n_wg > c->wg_table_cap) {
         c->drop_graphs();                        // a captured step holds the table's address
-        if (c->gg_table) { hipFree(c->gg_table); c->gg_table = nullptr; }
-        c->gg_table_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->gg_table, (size_t)n_wg * sizeof(int2)));
-        c->gg_table_cap = n_wg;
+        if (c->wg_table) { hipFree(c->wg_table); c->wg_table = nullptr; }
+        c->wg_table_cap = 0;
+        HIPCHK(hipMalloc((void **)&c->wg_table, (size_t)n_wg * sizeof(int2)));
+        c->wg_table_cap = n_wg;
     }
     const int G1 = n_groups + 1;
     LAUNCH("prep", SMK(pc_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, ints, ints + G1, n_groups,
-                       ints + 2 * G1, ints + 3 * G1, c->gg_table, (int)n_wg));
+                       ints + 2 * G1, ints + 3 * G1, c->wg_table, (int)n_wg));
     return 0;
 }
 
-MeshGroupsArgs mesh_groups_args(const shapemol_ctx *c, float *d_pos, int64_t N, const int *step_cur, int t_first) {
-    const int G1 = c->mg_groups + 1;
-    MeshGroupsArgs a{};
-    a.pred_pos = d_pos; a.clouds = c->mg_clouds; a.faces = c->mg_faces; a.fbox = c->mg_fbox; a.bounds = c->mg_bounds;
-    a.cloud_off = c->mg_ints + G1; a.atom_off = c->mg_ints + 2 * G1; a.face_off = c->mg_ints + 4 * G1; a.wg_table = c->gg_table;
-    a.within = c->m_within; a.out_list = c->m_out; a.cnt = c->m_cnt; a.group_flags = c->m_cnt + 4 * c->m_cnt_cap;
-    a.status = c->status; a.cp = c->chain_params;
-    a.step_cur = step_cur; a.n_atoms = (int)N; a.t_first = t_first; a.grad_step = c->mg_grad_step;
-    return a;
+// ---- point-cloud guidance: host side
+void cloud_set_clear(CloudSet &cs) {
+    if (cs.clouds) hipFree(cs.clouds);
+    cs = CloudSet{};
+}
+
+// Installs groups that the caller has validated: one device block [clouds | radii | mol_off, cloud_off, atom_off, wg_off
+// (G + 1 ints each)], rounded up to 256 bytes, and `tail_bytes` more behind it for the caller (*tail).
+int cloud_set_install(CloudSet &cs, int n_groups, const int64_t *h_mol_off, const double *h_clouds, const int64_t *h_cloud_off,
+                      const double *h_radius, bool whole, int grad_step, const double *d_draws, size_t tail_bytes = 0,
+                      unsigned char **tail = nullptr) {
+    const int G1 = n_groups + 1;
+    const int64_t P = h_cloud_off[n_groups];
+    std::vector<double> hd((size_t)P * 3 + n_groups);
+    if (P) std::copy(h_clouds, h_clouds + P * 3, hd.begin());
+    std::copy(h_radius, h_radius + n_groups, hd.begin() + P * 3);
+    std::vector<int> hi((size_t)4 * G1, 0);       // mol_off | cloud_off | atom_off | wg_off (the last two are written on the device)
+    int max_points = 0;
+    for (int g = 0; g < G1; ++g) { hi[g] = (int)h_mol_off[g]; hi[G1 + g] = (int)h_cloud_off[g]; }
+    for (int g = 0; g < n_groups; ++g) max_points = std::max(max_points, hi[G1 + g + 1] - hi[G1 + g]);
+    const size_t bytes_d = hd.size() * sizeof(double), bytes_i = hi.size() * sizeof(int), bytes = (bytes_d + bytes_i + 255) / 256 * 256;
+    HIPCHK(hipMalloc((void **)&cs.clouds, bytes + tail_bytes));
+    hipError_t e = hipMemcpy(cs.clouds, hd.data(), bytes_d, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char *)cs.clouds + bytes_d, hi.data(), bytes_i, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cloud_set_clear(cs); return fail(std::string("guidance clouds: hipMemcpy: ") + hipGetErrorString(e)); }
+    cs.radius = cs.clouds + P * 3; cs.ints = (int *)((char *)cs.clouds + bytes_d);
+    cs.groups = n_groups; cs.max_points = max_points; cs.mols = h_mol_off[n_groups]; cs.points = P; cs.whole = whole;
+    cs.grad_step = grad_step; cs.draws = d_draws;
+    if (tail) *tail = (unsigned char *)cs.clouds + bytes;
+    return 0;
+}
+
+// the single-cloud entry points: ONE group of n_points that spans whatever batch comes (`whole`: no molecule count)
+int cloud_set_install_whole(CloudSet &cs, const double *h_cloud, int64_t n_points, double radius, int grad_step, const double *d_draws,
+                            size_t tail_bytes = 0, unsigned char **tail = nullptr) {
+    const int64_t mol_off[2] = {0, 0}, cloud_off[2] = {0, n_points};
+    return cloud_set_install(cs, 1, mol_off, h_cloud, cloud_off, &radius, true, grad_step, d_draws, tail_bytes, tail);
 }
 
 // ---- mesh shape guidance: host side
@@ -111,26 +151,94 @@ int mesh_image(const double *h_verts, int64_t n_verts, const int32_t *h_faces, i
     return 0;
 }
 
-// where a mesh, its per-step lists and its flags live: in a context, or in the temporary block of shapemol_mesh_guidance
-struct MeshView {
-    const MeshFace *faces; const double4 *fbox; const double *cloud; int64_t n_faces, n_points;
-    float4 *within; int *out, *cnt, *status; const ChainParams *cp; const double *bounds;
-};
-MeshView mesh_view(const shapemol_ctx *c) {
-    return {c->m_faces, c->m_fbox, c->m_cloud, c->m_nfaces, c->m_points, c->m_within, c->m_out, c->m_cnt, c->status, c->chain_params, c->m_bounds};
-}
-MeshGuideArgs mesh_args(const MeshView &m, float *pos, int64_t N, const int *step_cur, int t_first, int grad_step) {
-    MeshGuideArgs a{};
-    a.pred_pos = pos; a.cloud = m.cloud; a.faces = m.faces; a.fbox = m.fbox;
-    a.within = m.within; a.out_list = m.out; a.cnt = m.cnt; a.status = m.status; a.cp = m.cp;
-    a.step_cur = step_cur; a.n_atoms = (int)N; a.n_points = (int)m.n_points; a.n_faces = (int)m.n_faces;
-    a.t_first = t_first; a.grad_step = grad_step;
-    a.umin = m.bounds[0]; a.umax = m.bounds[1]; a.vmin = m.bounds[2]; a.vmax = m.bounds[3]; a.wmax = m.bounds[4];
-    return a;
+// host image of a set of mesh groups: [faces | face boxes | clouds | bounds G x 5 | mol_off, cloud_off, atom_off, wg_off,
+// face_off (G + 1 ints each)]
+struct MeshSetImage { std::vector<unsigned char> bytes; int64_t F = 0, P = 0, mols = 0; int groups = 0, max_points = 0; bool whole = false; };
+
+// Validates the groups and builds their image; every group's mesh goes through mesh_image, with its face indices relative to
+// the group's own vertices.  `whole`: the one group of the single-mesh entry point `me`, whose errors name no group.
+int mesh_set_image(const std::string &me, bool whole, int n_groups, const int64_t *h_mol_off, const double *h_verts, const int64_t *h_vert_off,
+                   const int32_t *h_faces, const int64_t *h_face_off, const double *h_clouds, const int64_t *h_cloud_off, MeshSetImage &out) {
+    const int G1 = n_groups + 1;
+    std::vector<std::vector<unsigned char>> imgs(n_groups);
+    std::vector<double> hb((size_t)n_groups * 5, 0.0);
+    int max_points = 0;
+    if (!whole) {
+        if (!h_mol_off || !h_vert_off || !h_face_off || !h_cloud_off) return fail(me + ": offsets missing");
+        if (h_mol_off[0] != 0 || h_vert_off[0] != 0 || h_face_off[0] != 0 || h_cloud_off[0] != 0)
+            return fail(me + ": group 0: the molecule, vertex, face and cloud offsets must start at 0");
+    }
+    for (int g = 0; g < n_groups; ++g) {
+        const std::string grp = whole ? me : me + ": group " + std::to_string(g);
+        const int64_t nv = h_vert_off[g + 1] - h_vert_off[g], nf = h_face_off[g + 1] - h_face_off[g], np = h_cloud_off[g + 1] - h_cloud_off[g];
+        if (!whole) {
+            if (h_mol_off[g + 1] < h_mol_off[g]) return fail(grp + ": the molecule offsets decrease");
+            if (nv < 0) return fail(grp + ": the vertex offsets decrease");
+            if (nf < 0) return fail(grp + ": the face offsets decrease");
+            if (np < 0) return fail(grp + ": the cloud offsets decrease");
+            if (nv == 0 && nf == 0 && np == 0) continue;       // a group without a mesh
+        }
+        double bounds[5];
+        if (mesh_image(h_verts ? h_verts + h_vert_off[g] * 3 : nullptr, nv, h_faces ? h_faces + h_face_off[g] * 3 : nullptr, nf,
+                       h_clouds ? h_clouds + h_cloud_off[g] * 3 : nullptr, np, grp.c_str(), imgs[g], bounds)) return 1;
+        std::copy(bounds, bounds + 5, hb.begin() + (size_t)g * 5);
+        max_points = std::max(max_points, (int)np);
+    }
+    const int64_t F = h_face_off[n_groups], P = h_cloud_off[n_groups];
+    if (h_mol_off[n_groups] > (1 << 27)) return fail(me + ": too many molecules");
+    if (F > (1 << 27)) return fail(me + ": too many faces");
+    if (P > (1 << 27) || h_vert_off[n_groups] > (1 << 27)) return fail(me + ": too many cloud points / vertices");
+    const size_t fb = (size_t)F * sizeof(MeshFace), bb = (size_t)F * sizeof(double4), cb = (size_t)P * 24, nb = hb.size() * sizeof(double);
+    std::vector<unsigned char> &img = out.bytes;
+    img.assign(fb + bb + cb + nb + (size_t)5 * G1 * sizeof(int), 0);
+    int *hi = reinterpret_cast<int *>(img.data() + fb + bb + cb + nb);       // mol_off | cloud_off | atom_off | wg_off | face_off
+    for (int g = 0; g < G1; ++g) { hi[g] = (int)h_mol_off[g]; hi[G1 + g] = (int)h_cloud_off[g]; hi[4 * G1 + g] = (int)h_face_off[g]; }
+    for (int g = 0; g < n_groups; ++g) {
+        if (imgs[g].empty()) continue;
+        const size_t nf = (size_t)(h_face_off[g + 1] - h_face_off[g]), np = (size_t)(h_cloud_off[g + 1] - h_cloud_off[g]);
+        const unsigned char *src = imgs[g].data();
+        std::memcpy(img.data() + (size_t)h_face_off[g] * sizeof(MeshFace), src, nf * sizeof(MeshFace));
+        std::memcpy(img.data() + fb + (size_t)h_face_off[g] * sizeof(double4), src + nf * sizeof(MeshFace), nf * sizeof(double4));
+        std::memcpy(img.data() + fb + bb + (size_t)h_cloud_off[g] * 24, src + nf * (sizeof(MeshFace) + sizeof(double4)), np * 24);
+    }
+    std::memcpy(img.data() + fb + bb + cb, hb.data(), nb);
+    out.F = F; out.P = P; out.mols = h_mol_off[n_groups]; out.groups = n_groups; out.max_points = max_points; out.whole = whole;
+    return 0;
 }
 
-// the per-step lists of mesh guidance for N atoms: [within N | outmesh N | counters 4 per group (one group: the single mesh) |
-// unguided-step count 1 per group (mesh groups)]; mesh_counters_clear zeroes the last two for a chain of n_groups
+// the single-mesh entry point `me`: ONE group that spans whatever batch comes (`whole`: no molecule count, errors name no group)
+int mesh_set_image_whole(const std::string &me, const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces,
+                         const double *h_cloud, int64_t n_cloud, MeshSetImage &out) {
+    const int64_t mol_off[2] = {0, 0}, vert_off[2] = {0, n_verts}, face_off[2] = {0, n_faces}, cloud_off[2] = {0, n_cloud};
+    return mesh_set_image(me, true, 1, mol_off, h_verts, vert_off, h_faces, face_off, h_cloud, cloud_off, out);
+}
+
+void mesh_set_clear(MeshSet &ms) {
+    if (ms.faces) hipFree(ms.faces);
+    ms = MeshSet{};
+}
+
+// one device block: the image, rounded up to 256 bytes, and `tail_bytes` more behind it for the caller (*tail)
+int mesh_set_install(MeshSet &ms, const MeshSetImage &im, int grad_step, const double *d_draws, size_t tail_bytes = 0, unsigned char **tail = nullptr) {
+    const size_t fb = (size_t)im.F * sizeof(MeshFace), bb = (size_t)im.F * sizeof(double4), cb = (size_t)im.P * 24, nb = (size_t)im.groups * 5 * sizeof(double);
+    const size_t bytes = (im.bytes.size() + 255) / 256 * 256;
+    unsigned char *blk = nullptr;
+    HIPCHK(hipMalloc((void **)&blk, bytes + tail_bytes));
+    const hipError_t e = hipMemcpy(blk, im.bytes.data(), im.bytes.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(blk); return fail(std::string("guidance meshes: hipMemcpy: ") + hipGetErrorString(e)); }
+    ms.faces = reinterpret_cast<MeshFace *>(blk);
+    ms.fbox = reinterpret_cast<double4 *>(blk + fb);
+    ms.clouds = reinterpret_cast<double *>(blk + fb + bb);
+    ms.bounds = reinterpret_cast<double *>(blk + fb + bb + cb);
+    ms.ints = reinterpret_cast<int *>(blk + fb + bb + cb + nb);
+    ms.groups = im.groups; ms.max_points = im.max_points; ms.mols = im.mols; ms.nfaces = im.F; ms.whole = im.whole;
+    ms.grad_step = grad_step; ms.draws = d_draws;
+    if (tail) *tail = blk + bytes;
+    return 0;
+}
+
+// the per-step lists of mesh guidance for N atoms: [within N | outmesh N | counters 4 per group | unguided-step count 1 per
+// group]; mesh_counters_clear zeroes the last two for a chain of n_groups
 int mesh_workspace(shapemol_ctx *c, int64_t N, int64_t n_groups) {
     if (N <= c->m_cap && n_groups <= c->m_cnt_cap) return 0;
     N = std::max(N, c->m_cap); n_groups = std::max(n_groups, c->m_cnt_cap);
@@ -148,7 +256,7 @@ int mesh_workspace(shapemol_ctx *c, int64_t N, int64_t n_groups) {
 int mesh_counters_clear(shapemol_ctx *c, hipStream_t s, int64_t n_groups) {
     HIPCHK(hipMemsetAsync(c->m_cnt, 0, (size_t)n_groups * 4 * sizeof(int), s));
     HIPCHK(hipMemsetAsync(c->m_cnt + 4 * c->m_cnt_cap, 0, (size_t)n_groups * sizeof(int), s));
-    c->mg_flag_groups = n_groups;
+    c->m_flag_groups = n_groups;
     return 0;
 }
 
@@ -156,21 +264,15 @@ int mesh_counters_clear(shapemol_ctx *c, hipStream_t s, int64_t n_groups) {
 // evaluations and the posterior step).  In a chain step_cur is the device's step counter and t_first = T - 1; a stand-alone
 // application passes no counter and t_first = grad_step + 1.
 int enqueue_guidance(shapemol_ctx *c, hipStream_t s, Guide kind, float *pos, int64_t N, const int *step_cur, int t_first) {
-    if (kind == Guide::Mesh) {
-        const MeshGuideArgs ma = mesh_args(mesh_view(c), pos, N, step_cur, t_first, c->m_grad_step);
-        LAUNCH("mesh_classify", SMK(mesh_classify_kernel, guide_grid(N), dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
-        LAUNCH("mesh_pull", SMK(mesh_pull_kernel, guide_grid(N), dim3(256), mesh_lds_bytes((int)c->m_points), s, ma));
-    } else if (kind == Guide::MeshGroups) {  // each group of molecules against its own mesh
-        const MeshGroupsArgs ma = mesh_groups_args(c, pos, N, step_cur, t_first);
-        const dim3 grid(groups_grid(N, c->mg_groups));
-        LAUNCH("mesh_classify_groups", SMK(mesh_classify_groups_kernel, grid, dim3(256), mesh_groups_lds_bytes(c->mg_max_points), s, ma));
-        LAUNCH("mesh_pull_groups", SMK(mesh_pull_groups_kernel, grid, dim3(256), mesh_groups_lds_bytes(c->mg_max_points), s, ma));
-    } else if (kind == Guide::Cloud) {
-        PcGuideArgs ga{pos, c->g_cloud, c->chain_params, step_cur, (int)N, (int)c->g_points, t_first, c->g_grad_step, c->g_radius, 0.2};
-        LAUNCH("pc_guidance", SMK(pc_guidance_kernel, guide_grid(N), dim3(256), cloud_lds_bytes(c->g_points), s, ga));
-    } else if (kind == Guide::Groups) {     // each group of molecules towards its own cloud
-        const PcGroupsArgs ga = groups_args(c, pos, N, step_cur, t_first);
-        LAUNCH("pc_guidance_groups", SMK(pc_guidance_groups_kernel, dim3(groups_grid(N, c->gg_groups)), dim3(256), cloud_lds_bytes(c->gg_max_points), s, ga));
+    if (kind == Guide::Mesh) {               // each group of molecules against its own mesh
+        const MeshGroupsArgs ma = mesh_args(c->ms, c->wg_table, c->m_within, c->m_out, c->m_cnt, c->m_cnt + 4 * c->m_cnt_cap, c->status,
+                                            c->chain_params, pos, N, step_cur, t_first);
+        const dim3 grid(groups_grid(N, c->ms.groups));
+        LAUNCH("mesh_classify", SMK(mesh_classify_kernel, grid, dim3(256), mesh_lds_bytes(c->ms.max_points), s, ma));
+        LAUNCH("mesh_pull", SMK(mesh_pull_kernel, grid, dim3(256), mesh_lds_bytes(c->ms.max_points), s, ma));
+    } else if (kind == Guide::Cloud) {       // each group of molecules towards its own cloud
+        const PcGroupsArgs ga = cloud_args(c->cs, c->wg_table, c->chain_params, pos, N, step_cur, t_first);
+        LAUNCH("pc_guidance", SMK(pc_guidance_kernel, dim3(groups_grid(N, c->cs.groups)), dim3(256), cloud_lds_bytes(c->cs.max_points), s, ga));
     }
     return 0;
 }
@@ -178,26 +280,36 @@ int enqueue_guidance(shapemol_ctx *c, hipStream_t s, Guide kind, float *pos, int
 // shapemol_guide_points*: one always-guided application of the context's guidance of `kind` to given positions
 int guide_alone(shapemol_ctx *c, hipStream_t s, Guide kind, float *d_pos, int64_t N, const double *d_draws, uint64_t seed) {
     LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, guide_alone_params(seed, d_draws), c->steps));
-    const int grad_step = kind == Guide::Mesh ? c->m_grad_step : (kind == Guide::MeshGroups ? c->mg_grad_step :
-                          (kind == Guide::Cloud ? c->g_grad_step : c->gg_grad_step));
-    return enqueue_guidance(c, s, kind, d_pos, N, nullptr, grad_step + 1);
+    return enqueue_guidance(c, s, kind, d_pos, N, nullptr, (kind == Guide::Mesh ? c->ms.grad_step : c->cs.grad_step) + 1);
 }
 
-void mesh_groups_clear(shapemol_ctx *c) {
-    if (c->mg_faces) { hipFree(c->mg_faces); c->mg_faces = nullptr; }
-    c->mg_fbox = nullptr; c->mg_clouds = c->mg_bounds = nullptr; c->mg_ints = nullptr;
-    c->mg_groups = 0; c->mg_max_points = 0; c->mg_mols = 0; c->mg_nfaces = 0; c->mg_draws = nullptr;
+// shapemol_guide_points[_mesh] and their _groups siblings: the former have no batch vector and want a `whole` set
+int guide_points_cloud(shapemol_ctx *c, const std::string &me, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws,
+                       uint64_t seed, void *stream) {
+    if (!c || !d_pos || N < 1 || (d_batch && N > (1 << 27))) return fail(me + ": bad argument");
+    if (c->cs.groups <= 0 || c->cs.whole != !d_batch)
+        return fail(me + (d_batch ? ": no groups set (shapemol_set_guidance_groups)" : ": no cloud set (shapemol_set_guidance)"));
+    HIPCHK(hipSetDevice(c->device));
+    if (ensure_workspace(c, N, 1)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->cs.points == 0) return 0;             // no group has a cloud: nothing moves
+    if (groups_table(c, s, d_batch, N, c->cs.ints, c->cs.groups)) return 1;
+    return guide_alone(c, s, Guide::Cloud, d_pos, N, d_draws, seed);
 }
 
-void mesh_single_clear(shapemol_ctx *c) {
-    if (c->m_faces) { hipFree(c->m_faces); c->m_faces = nullptr; c->m_fbox = nullptr; c->m_cloud = nullptr; }
-    c->m_nfaces = 0; c->m_points = 0; c->m_draws = nullptr;
-}
-
-void groups_clear(shapemol_ctx *c) {
-    if (c->gg_clouds) { hipFree(c->gg_clouds); c->gg_clouds = nullptr; }
-    c->gg_radius = nullptr; c->gg_ints = nullptr;
-    c->gg_groups = 0; c->gg_max_points = 0; c->gg_mols = 0; c->gg_points = 0; c->gg_draws = nullptr;
+int guide_points_mesh(shapemol_ctx *c, const std::string &me, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws,
+                      uint64_t seed, void *stream) {
+    if (!c || !d_pos || N < 1 || N > (1 << 27)) return fail(me + ": bad argument");
+    if (c->ms.groups <= 0 || c->ms.whole != !d_batch)
+        return fail(me + (d_batch ? ": no groups set (shapemol_set_mesh_guidance_groups)" : ": no mesh set (shapemol_set_mesh_guidance)"));
+    HIPCHK(hipSetDevice(c->device));
+    if (ensure_workspace(c, N, 1) || mesh_workspace(c, N, c->ms.groups)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(c->status + ST_MESH, 0, sizeof(int), s));
+    if (c->ms.nfaces == 0) return 0;             // no group has a mesh: nothing moves
+    if (mesh_counters_clear(c, s, c->ms.groups)) return 1;
+    if (groups_table(c, s, d_batch, N, c->ms.ints, c->ms.groups)) return 1;
+    return guide_alone(c, s, Guide::Mesh, d_pos, N, d_draws, seed);
 }
 
 }  // namespace
@@ -209,15 +321,10 @@ int shapemol_set_guidance(shapemol_ctx *c, const double *h_cloud, int64_t n_poin
     if (n_points < 0 || n_points > 2048 || (n_points > 0 && n_points < 3)) return fail("shapemol_set_guidance: the cloud needs 3 .. 2048 points (it is staged in LDS)");
     if (n_points > 0 && (!h_cloud || !(radius > 0.0))) return fail("shapemol_set_guidance: cloud / radius missing");
     HIPCHK(hipSetDevice(c->device));
-    c->drop_graphs();                            // also drains the device: the old cloud may still be in use
-    if (c->g_cloud) { hipFree(c->g_cloud); c->g_cloud = nullptr; }
-    c->g_points = 0; c->g_draws = nullptr;
+    c->drop_graphs();                            // also drains the device: the old clouds may still be in use
+    cloud_set_clear(c->cs);
     if (n_points == 0) return 0;
-    groups_clear(c);                             // a single cloud replaces clouds per group
-    HIPCHK(hipMalloc((void **)&c->g_cloud, (size_t)n_points * 3 * sizeof(double)));
-    HIPCHK(hipMemcpy(c->g_cloud, h_cloud, (size_t)n_points * 3 * sizeof(double), hipMemcpyHostToDevice));
-    c->g_points = n_points; c->g_radius = radius; c->g_grad_step = grad_step; c->g_draws = d_draws;
-    return 0;
+    return cloud_set_install_whole(c->cs, h_cloud, n_points, radius, grad_step, d_draws);
 }
 
 int shapemol_set_guidance_groups(shapemol_ctx *c, int32_t n_groups, const int64_t *h_mol_off, const double *h_clouds, const int64_t *h_cloud_off,
@@ -241,47 +348,19 @@ int shapemol_set_guidance_groups(shapemol_ctx *c, int32_t n_groups, const int64_
     }
     HIPCHK(hipSetDevice(c->device));
     c->drop_graphs();                            // also drains the device: the old clouds may still be in use
-    groups_clear(c);
+    cloud_set_clear(c->cs);
     if (n_groups == 0) return 0;
-    if (c->g_cloud) { hipFree(c->g_cloud); c->g_cloud = nullptr; }      // clouds per group replace a single cloud
-    c->g_points = 0; c->g_draws = nullptr;
-    const int G1 = n_groups + 1;
-    const int64_t P = h_cloud_off[n_groups];
-    std::vector<double> hd((size_t)P * 3 + n_groups);
-    if (P) std::copy(h_clouds, h_clouds + P * 3, hd.begin());
-    std::copy(h_radius, h_radius + n_groups, hd.begin() + P * 3);
-    std::vector<int> hi((size_t)4 * G1, 0);       // mol_off | cloud_off | atom_off | wg_off (the last two are written on the device)
-    int max_points = 0;
-    for (int g = 0; g < G1; ++g) { hi[g] = (int)h_mol_off[g]; hi[G1 + g] = (int)h_cloud_off[g]; }
-    for (int g = 0; g < n_groups; ++g) max_points = std::max(max_points, hi[G1 + g + 1] - hi[G1 + g]);
-    const size_t bytes_d = hd.size() * sizeof(double), bytes_i = hi.size() * sizeof(int);
-    HIPCHK(hipMalloc((void **)&c->gg_clouds, bytes_d + bytes_i));
-    HIPCHK(hipMemcpy(c->gg_clouds, hd.data(), bytes_d, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy((char *)c->gg_clouds + bytes_d, hi.data(), bytes_i, hipMemcpyHostToDevice));
-    c->gg_radius = c->gg_clouds + P * 3; c->gg_ints = (int *)((char *)c->gg_clouds + bytes_d);
-    c->gg_groups = n_groups; c->gg_max_points = max_points; c->gg_mols = h_mol_off[n_groups]; c->gg_points = P;
-    c->gg_grad_step = grad_step; c->gg_draws = d_draws;
-    return 0;
+    return cloud_set_install(c->cs, n_groups, h_mol_off, h_clouds, h_cloud_off, h_radius, false, grad_step, d_draws);
 }
 
 int shapemol_guide_points_groups(shapemol_ctx *c, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws, uint64_t seed,
                                  void *stream) {
-    if (!c || !d_pos || !d_batch || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_groups: bad argument");
-    if (c->gg_groups <= 0) return fail("shapemol_guide_points_groups: no groups set (shapemol_set_guidance_groups)");
-    HIPCHK(hipSetDevice(c->device));
-    if (ensure_workspace(c, N, 1)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (c->gg_points == 0) return 0;             // no group has a cloud: nothing moves
-    if (groups_table(c, s, d_batch, N, c->gg_ints, c->gg_groups)) return 1;
-    return guide_alone(c, s, Guide::Groups, d_pos, N, d_draws, seed);
+    if (!d_batch) return fail("shapemol_guide_points_groups: bad argument");
+    return guide_points_cloud(c, "shapemol_guide_points_groups", d_pos, d_batch, N, d_draws, seed, stream);
 }
 
 int shapemol_guide_points(shapemol_ctx *c, float *d_pos, int64_t N, const double *d_draws, uint64_t seed, void *stream) {
-    if (!c || !d_pos || N < 1) return fail("shapemol_guide_points: bad argument");
-    if (c->g_points <= 0) return fail("shapemol_guide_points: no cloud set (shapemol_set_guidance)");
-    HIPCHK(hipSetDevice(c->device));
-    if (ensure_workspace(c, std::max<int64_t>(N, 1), 1)) return 1;
-    return guide_alone(c, (hipStream_t)stream, Guide::Cloud, d_pos, N, d_draws, seed);
+    return guide_points_cloud(c, "shapemol_guide_points", d_pos, nullptr, N, d_draws, seed, stream);
 }
 
 int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_points, double radius, double ratio, float *d_pos, int64_t N,
@@ -290,21 +369,22 @@ int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_points, double
     if (n_points < 3 || n_points > 2048) return fail("shapemol_pointcloud_guidance: the cloud needs 3 .. 2048 points (it is staged in LDS)");
     if (!(radius > 0.0) || !(ratio >= 0.0 && ratio < 0.8)) return fail("shapemol_pointcloud_guidance: radius must be > 0, ratio in [0, 0.8)");
     hipStream_t s = (hipStream_t)stream;
-    const size_t cloud_bytes = (size_t)n_points * 3 * sizeof(double);
-    unsigned char *blk = nullptr;                       // [cloud | ChainParams | step counter]
-    HIPCHK(hipMalloc((void **)&blk, cloud_bytes + sizeof(ChainParams) + 16));
-    double *d_cloud = reinterpret_cast<double *>(blk);
-    ChainParams *d_cp = reinterpret_cast<ChainParams *>(blk + cloud_bytes);
-    int *d_step = reinterpret_cast<int *>(blk + cloud_bytes + sizeof(ChainParams));
-    hipError_t e = hipMemcpyAsync(d_cloud, h_cloud, cloud_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(set_chain_params_kernel, dim3(1), dim3(1), 0, s, d_cp, guide_alone_params(seed, d_draws), d_step);
-        PcGuideArgs ga{d_pos, d_cloud, d_cp, nullptr, (int)N, (int)n_points, 1, 0, radius, ratio};      // t_first - 0 > grad_step: always guided
-        hipLaunchKernelGGL(pc_guidance_kernel, guide_grid(N), dim3(256), cloud_lds_bytes(n_points), s, ga);
-        e = hipGetLastError();
-    }
+    const unsigned n_wg = groups_grid(N, 1);
+    const size_t o_step = (sizeof(ChainParams) + 15) / 16 * 16, o_table = o_step + 16;
+    CloudSet cs;                                        // a set of its own, and behind it [ChainParams | step counter | workgroup table]
+    unsigned char *tail = nullptr;
+    if (cloud_set_install_whole(cs, h_cloud, n_points, radius, 0, nullptr, o_table + n_wg * sizeof(int2), &tail)) return 1;
+    ChainParams *d_cp = reinterpret_cast<ChainParams *>(tail);
+    int2 *d_table = reinterpret_cast<int2 *>(tail + o_table);
+    hipLaunchKernelGGL(set_chain_params_kernel, dim3(1), dim3(1), 0, s, d_cp, guide_alone_params(seed, d_draws), reinterpret_cast<int *>(tail + o_step));
+    hipLaunchKernelGGL(pc_groups_table_kernel, dim3(1), dim3(256), 0, s, (const int64_t *)nullptr, (int)N, cs.ints, cs.ints + 2, 1, cs.ints + 4,
+                       cs.ints + 6, d_table, (int)n_wg);
+    PcGroupsArgs ga = cloud_args(cs, d_table, d_cp, d_pos, N, nullptr, 1);      // t_first - 0 > grad_step = 0: always guided
+    ga.ratio = ratio;
+    hipLaunchKernelGGL(pc_guidance_kernel, dim3(n_wg), dim3(256), cloud_lds_bytes(n_points), s, ga);
+    const hipError_t e = hipGetLastError();
     const hipError_t e2 = hipStreamSynchronize(s);       // the block is freed below; the reference's function is synchronous too
-    hipFree(blk);
+    cloud_set_clear(cs);
     if (e != hipSuccess) return fail(std::string("shapemol_pointcloud_guidance: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(std::string("shapemol_pointcloud_guidance: ") + hipGetErrorString(e2));
     return 0;
@@ -314,115 +394,38 @@ int shapemol_set_mesh_guidance(shapemol_ctx *c, const double *h_verts, int64_t n
                                const double *h_cloud, int64_t n_cloud, int32_t grad_step, const double *d_draws) {
     if (!c) return fail("shapemol_set_mesh_guidance: null ctx");
     if (n_faces < 0) return fail("shapemol_set_mesh_guidance: n_faces < 0");
-    std::vector<unsigned char> img;
-    double bounds[5];
-    if (n_faces > 0 && mesh_image(h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, "shapemol_set_mesh_guidance", img, bounds)) return 1;
+    MeshSetImage img;
+    if (n_faces > 0 && mesh_set_image_whole("shapemol_set_mesh_guidance", h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, img)) return 1;
     HIPCHK(hipSetDevice(c->device));
-    c->drop_graphs();                            // also drains the device: the old mesh may still be in use
-    mesh_single_clear(c);
+    c->drop_graphs();                            // also drains the device: the old meshes may still be in use
+    mesh_set_clear(c->ms);
     if (n_faces == 0) return 0;
-    mesh_groups_clear(c);                        // a single mesh replaces meshes per group
-    unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, img.size()));
-    HIPCHK(hipMemcpy(blk, img.data(), img.size(), hipMemcpyHostToDevice));
-    c->m_faces = reinterpret_cast<MeshFace *>(blk);
-    c->m_fbox = reinterpret_cast<double4 *>(blk + (size_t)n_faces * sizeof(MeshFace));
-    c->m_cloud = reinterpret_cast<double *>(blk + (size_t)n_faces * (sizeof(MeshFace) + sizeof(double4)));
-    std::memcpy(c->m_bounds, bounds, sizeof(bounds));
-    c->m_nfaces = n_faces; c->m_points = n_cloud; c->m_grad_step = grad_step; c->m_draws = d_draws;
-    return 0;
+    return mesh_set_install(c->ms, img, grad_step, d_draws);
 }
 
 int shapemol_guide_points_mesh(shapemol_ctx *c, float *d_pos, int64_t N, const double *d_draws, uint64_t seed, void *stream) {
-    if (!c || !d_pos || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_mesh: bad argument");
-    if (c->m_nfaces <= 0) return fail("shapemol_guide_points_mesh: no mesh set (shapemol_set_mesh_guidance)");
-    HIPCHK(hipSetDevice(c->device));
-    if (ensure_workspace(c, std::max<int64_t>(N, 1), 1) || mesh_workspace(c, N, 1)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(c->m_cnt, 0, 4 * sizeof(int), s));
-    HIPCHK(hipMemsetAsync(c->status + ST_MESH, 0, sizeof(int), s));
-    return guide_alone(c, s, Guide::Mesh, d_pos, N, d_draws, seed);
+    return guide_points_mesh(c, "shapemol_guide_points_mesh", d_pos, nullptr, N, d_draws, seed, stream);
 }
 
 int shapemol_set_mesh_guidance_groups(shapemol_ctx *c, int32_t n_groups, const int64_t *h_mol_off, const double *h_verts, const int64_t *h_vert_off,
                                       const int32_t *h_faces, const int64_t *h_face_off, const double *h_clouds, const int64_t *h_cloud_off,
                                       int32_t grad_step, const double *d_draws) {
-    const std::string me = "shapemol_set_mesh_guidance_groups: ";
-    if (!c) return fail(me + "null ctx");
-    if (n_groups < 0 || n_groups > (1 << 20)) return fail(me + "n_groups out of range");
-    // host image [faces | face boxes | clouds | bounds G x 5 | ints 5 (G + 1)]; every group's mesh goes through mesh_image, the
-    // single mesh's validation and projection, with its face indices relative to the group's own vertices
-    const int G1 = n_groups + 1;
-    std::vector<std::vector<unsigned char>> imgs(n_groups);
-    std::vector<double> hb((size_t)n_groups * 5, 0.0);
-    int64_t F = 0, P = 0;
-    int max_points = 0;
-    if (n_groups > 0) {
-        if (!h_mol_off || !h_vert_off || !h_face_off || !h_cloud_off) return fail(me + "offsets missing");
-        if (h_mol_off[0] != 0 || h_vert_off[0] != 0 || h_face_off[0] != 0 || h_cloud_off[0] != 0)
-            return fail(me + "group 0: the molecule, vertex, face and cloud offsets must start at 0");
-        for (int g = 0; g < n_groups; ++g) {
-            const std::string grp = me + "group " + std::to_string(g);
-            if (h_mol_off[g + 1] < h_mol_off[g]) return fail(grp + ": the molecule offsets decrease");
-            if (h_vert_off[g + 1] < h_vert_off[g]) return fail(grp + ": the vertex offsets decrease");
-            if (h_face_off[g + 1] < h_face_off[g]) return fail(grp + ": the face offsets decrease");
-            if (h_cloud_off[g + 1] < h_cloud_off[g]) return fail(grp + ": the cloud offsets decrease");
-            const int64_t nv = h_vert_off[g + 1] - h_vert_off[g], nf = h_face_off[g + 1] - h_face_off[g], np = h_cloud_off[g + 1] - h_cloud_off[g];
-            if (nv == 0 && nf == 0 && np == 0) continue;       // a group without a mesh
-            if (!h_verts || !h_faces || !h_clouds) return fail(grp + ": vertices, faces and cloud are required");
-            double bounds[5];
-            if (mesh_image(h_verts + h_vert_off[g] * 3, nv, h_faces + h_face_off[g] * 3, nf, h_clouds + h_cloud_off[g] * 3, np, grp.c_str(), imgs[g], bounds)) return 1;
-            std::copy(bounds, bounds + 5, hb.begin() + (size_t)g * 5);
-            max_points = std::max(max_points, (int)np);
-        }
-        F = h_face_off[n_groups]; P = h_cloud_off[n_groups];
-        if (h_mol_off[n_groups] > (1 << 27)) return fail(me + "too many molecules");
-        if (F > (1 << 27)) return fail(me + "too many faces");
-        if (P > (1 << 27) || h_vert_off[n_groups] > (1 << 27)) return fail(me + "too many cloud points / vertices");
-    }
+    const std::string me = "shapemol_set_mesh_guidance_groups";
+    if (!c) return fail(me + ": null ctx");
+    if (n_groups < 0 || n_groups > (1 << 20)) return fail(me + ": n_groups out of range");
+    MeshSetImage img;
+    if (n_groups > 0 && mesh_set_image(me, false, n_groups, h_mol_off, h_verts, h_vert_off, h_faces, h_face_off, h_clouds, h_cloud_off, img)) return 1;
     HIPCHK(hipSetDevice(c->device));
     c->drop_graphs();                            // also drains the device: the old meshes may still be in use
-    mesh_groups_clear(c);
+    mesh_set_clear(c->ms);
     if (n_groups == 0) return 0;
-    mesh_single_clear(c);                        // meshes per group replace a single mesh
-    const size_t fb = (size_t)F * sizeof(MeshFace), bb = (size_t)F * sizeof(double4), cb = (size_t)P * 24, nb = hb.size() * sizeof(double);
-    std::vector<unsigned char> img(fb + bb + cb + nb + (size_t)5 * G1 * sizeof(int), 0);
-    int *hi = reinterpret_cast<int *>(img.data() + fb + bb + cb + nb);       // mol_off | cloud_off | atom_off | wg_off | face_off
-    for (int g = 0; g < G1; ++g) { hi[g] = (int)h_mol_off[g]; hi[G1 + g] = (int)h_cloud_off[g]; hi[4 * G1 + g] = (int)h_face_off[g]; }
-    for (int g = 0; g < n_groups; ++g) {
-        if (imgs[g].empty()) continue;
-        const size_t nf = (size_t)(h_face_off[g + 1] - h_face_off[g]), np = (size_t)(h_cloud_off[g + 1] - h_cloud_off[g]);
-        const unsigned char *src = imgs[g].data();
-        std::memcpy(img.data() + (size_t)h_face_off[g] * sizeof(MeshFace), src, nf * sizeof(MeshFace));
-        std::memcpy(img.data() + fb + (size_t)h_face_off[g] * sizeof(double4), src + nf * sizeof(MeshFace), nf * sizeof(double4));
-        std::memcpy(img.data() + fb + bb + (size_t)h_cloud_off[g] * 24, src + nf * (sizeof(MeshFace) + sizeof(double4)), np * 24);
-    }
-    std::memcpy(img.data() + fb + bb + cb, hb.data(), nb);
-    unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, img.size()));
-    HIPCHK(hipMemcpy(blk, img.data(), img.size(), hipMemcpyHostToDevice));
-    c->mg_faces = reinterpret_cast<MeshFace *>(blk);
-    c->mg_fbox = reinterpret_cast<double4 *>(blk + fb);
-    c->mg_clouds = reinterpret_cast<double *>(blk + fb + bb);
-    c->mg_bounds = reinterpret_cast<double *>(blk + fb + bb + cb);
-    c->mg_ints = reinterpret_cast<int *>(blk + fb + bb + cb + nb);
-    c->mg_groups = n_groups; c->mg_max_points = max_points; c->mg_mols = h_mol_off[n_groups]; c->mg_nfaces = F;
-    c->mg_grad_step = grad_step; c->mg_draws = d_draws;
-    return 0;
+    return mesh_set_install(c->ms, img, grad_step, d_draws);
 }
 
 int shapemol_guide_points_mesh_groups(shapemol_ctx *c, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws, uint64_t seed,
                                       void *stream) {
-    if (!c || !d_pos || !d_batch || N < 1 || N > (1 << 27)) return fail("shapemol_guide_points_mesh_groups: bad argument");
-    if (c->mg_groups <= 0) return fail("shapemol_guide_points_mesh_groups: no groups set (shapemol_set_mesh_guidance_groups)");
-    HIPCHK(hipSetDevice(c->device));
-    if (ensure_workspace(c, N, 1) || mesh_workspace(c, N, c->mg_groups)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(c->status + ST_MESH, 0, sizeof(int), s));
-    if (c->mg_nfaces == 0) return 0;             // no group has a mesh: nothing moves
-    if (mesh_counters_clear(c, s, c->mg_groups)) return 1;
-    if (groups_table(c, s, d_batch, N, c->mg_ints, c->mg_groups)) return 1;
-    return guide_alone(c, s, Guide::MeshGroups, d_pos, N, d_draws, seed);
+    if (!d_batch) return fail("shapemol_guide_points_mesh_groups: bad argument");
+    return guide_points_mesh(c, "shapemol_guide_points_mesh_groups", d_pos, d_batch, N, d_draws, seed, stream);
 }
 
 int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t *h_faces, int64_t n_faces, const double *h_cloud,
@@ -430,33 +433,34 @@ int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t
                            void *stream) {
     if (flag_out) *flag_out = 0;
     if (!d_pos || N < 1 || N > (1 << 27)) return fail("shapemol_mesh_guidance: bad argument");
-    std::vector<unsigned char> img;
-    double bounds[5];
-    if (mesh_image(h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, "shapemol_mesh_guidance", img, bounds)) return 1;
+    MeshSetImage img;
+    if (mesh_set_image_whole("shapemol_mesh_guidance", h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, img)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    // [mesh image | ChainParams | step counter, status [8], counters [4] | within N | outmesh N]
-    const size_t o_cp = (img.size() + 255) / 256 * 256, o_st = o_cp + (sizeof(ChainParams) + 255) / 256 * 256;
-    const size_t o_in = o_st + 256, o_out = o_in + (size_t)N * 16, total = o_out + (size_t)N * 4;
-    unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, total));
-    int *d_misc = reinterpret_cast<int *>(blk + o_st);        // [0] step counter, [4 .. 11] status, [16 .. 19] counters
-    hipError_t e = hipMemcpyAsync(blk, img.data(), img.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_misc, 0, 256, s);
+    // a set of its own, and behind it [ChainParams | step counter, status [8], counters [4], unguided steps | table | within N | outmesh N]
+    const unsigned n_wg = groups_grid(N, 1);
+    const size_t o_misc = (sizeof(ChainParams) + 255) / 256 * 256, o_table = o_misc + 256;
+    const size_t o_in = o_table + ((size_t)n_wg * sizeof(int2) + 255) / 256 * 256, o_out = o_in + (size_t)N * 16;
+    MeshSet ms;
+    unsigned char *tail = nullptr;
+    if (mesh_set_install(ms, img, 0, nullptr, o_out + (size_t)N * 4, &tail)) return 1;
+    int *d_misc = reinterpret_cast<int *>(tail + o_misc);        // [0] step counter, [4 .. 11] status, [16 .. 19] counters, [20] unguided steps
+    hipError_t e = hipMemsetAsync(d_misc, 0, 256, s);
     int32_t flag = 0;
     if (e == hipSuccess) {
-        ChainParams *d_cp = reinterpret_cast<ChainParams *>(blk + o_cp);
+        ChainParams *d_cp = reinterpret_cast<ChainParams *>(tail);
+        int2 *d_table = reinterpret_cast<int2 *>(tail + o_table);
         hipLaunchKernelGGL(set_chain_params_kernel, dim3(1), dim3(1), 0, s, d_cp, guide_alone_params(seed, d_draws), d_misc);
-        const MeshView mv{reinterpret_cast<const MeshFace *>(blk), reinterpret_cast<const double4 *>(blk + (size_t)n_faces * sizeof(MeshFace)),
-                          reinterpret_cast<const double *>(blk + (size_t)n_faces * (sizeof(MeshFace) + sizeof(double4))), n_faces, n_cloud,
-                          reinterpret_cast<float4 *>(blk + o_in), reinterpret_cast<int *>(blk + o_out), d_misc + 16, d_misc + 4, d_cp, bounds};
-        const MeshGuideArgs a = mesh_args(mv, d_pos, N, nullptr, 1, 0);      // t_first - 0 > grad_step: always guided
-        hipLaunchKernelGGL(mesh_classify_kernel, guide_grid(N), dim3(256), mesh_lds_bytes((int)n_cloud), s, a);
-        hipLaunchKernelGGL(mesh_pull_kernel, guide_grid(N), dim3(256), mesh_lds_bytes((int)n_cloud), s, a);
+        hipLaunchKernelGGL(pc_groups_table_kernel, dim3(1), dim3(256), 0, s, (const int64_t *)nullptr, (int)N, ms.ints, ms.ints + 2, 1, ms.ints + 4,
+                           ms.ints + 6, d_table, (int)n_wg);
+        const MeshGroupsArgs a = mesh_args(ms, d_table, reinterpret_cast<float4 *>(tail + o_in), reinterpret_cast<int *>(tail + o_out), d_misc + 16,
+                                           d_misc + 20, d_misc + 4, d_cp, d_pos, N, nullptr, 1);      // t_first - 0 > grad_step = 0: always guided
+        hipLaunchKernelGGL(mesh_classify_kernel, dim3(n_wg), dim3(256), mesh_lds_bytes((int)n_cloud), s, a);
+        hipLaunchKernelGGL(mesh_pull_kernel, dim3(n_wg), dim3(256), mesh_lds_bytes((int)n_cloud), s, a);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_misc + 4 + ST_MESH, sizeof(int32_t), hipMemcpyDeviceToHost, s);
     }
     const hipError_t e2 = hipStreamSynchronize(s);       // the block is freed below; the reference's function is synchronous too
-    hipFree(blk);
+    mesh_set_clear(ms);
     if (e != hipSuccess) return fail(std::string("shapemol_mesh_guidance: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(std::string("shapemol_mesh_guidance: ") + hipGetErrorString(e2));
     if (flag) {

@@ -1,11 +1,12 @@
 // Mesh shape guidance (models/molopt_score_model.py:742-775, applied to the predicted x0 of the steps with t > grad_step,
 // :571-580).  The reference runs it on the host (trimesh containment, sklearn KD-trees, numpy, one D2H + H2D round trip per
-// step); here it is two kernels between the score evaluation and the posterior step:
-//   mesh_classify_kernel  every atom: inside the mesh?  distance to the nearest cloud point?  -> a compacted list of the
-//                         "within" atoms (inside, > 0.4 from the cloud) and one of the "outmesh" atoms (outside, or inside but
-//                         < 0.2 from the cloud).  The two sets are disjoint.
+// step) with one mesh for the batch; here every GROUP of molecules has its own mesh and cloud (the reference's call is a set of
+// one group that spans the batch), and a guided step is two kernels between the score evaluation and the posterior step:
+//   mesh_classify_kernel  every atom: inside its group's mesh?  distance to the nearest cloud point?  -> per group, a compacted
+//                         list of the "within" atoms (inside, > 0.4 from the cloud) and one of the "outmesh" atoms (outside, or
+//                         inside but < 0.2 from the cloud).  The two sets are disjoint.
 //   mesh_pull_kernel      the outmesh atoms only: up to five times, pull the atom away from the mean of its 3 nearest within-atoms
-//                         (over the WHOLE batch, as the reference's KD-tree of all within points) by u * 0.8 + 0.2, and accept
+//                         (over the WHOLE group, as the reference's KD-tree of all within points) by u * 0.8 + 0.2, and accept
 //                         the moved point when it is inside the mesh and > 0.2 from the cloud.  Atoms never accepted keep their
 //                         original position (the reference writes only the accepted ones).
 // Precision as numpy's on the float32 prediction: the mean of the three within-atoms is float32 ((a + b) + c) / 3 in ascending
@@ -127,32 +128,6 @@ SM_DEV void mesh_load_cloud(const MeshGuideArgs &a, double *cloud) {
     __syncthreads();
 }
 
-// LDS: cloud [P][3] doubles, then one tile of kMeshFaceTile face boxes / kMeshWithinTile within-atoms (16 KB)
-inline size_t mesh_lds_bytes(int n_points) { return (size_t)n_points * 24 + 16384; }
-
-// 16 lanes per atom, 256 threads per block
-__global__ void __launch_bounds__(256) mesh_classify_kernel(MeshGuideArgs a) {
-    extern __shared__ double mesh_lds[];
-    const int step = a.step_cur ? *a.step_cur : 0;
-    if (a.t_first - step <= a.grad_step) return;                   // `if i > grad_step` (molopt_score_model.py:573)
-    double *cloud = mesh_lds;
-    double4 *tile = reinterpret_cast<double4 *>(mesh_lds + a.n_points * 3);
-    mesh_load_cloud(a, cloud);
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int atom_raw = gid >> 4, l16 = gid & 15;
-    const bool ok = atom_raw < a.n_atoms;
-    const int atom = ok ? atom_raw : a.n_atoms - 1;
-    const float x = a.pred_pos[atom * 3], y = a.pred_pos[atom * 3 + 1], z = a.pred_pos[atom * 3 + 2];
-    const double p[3] = {(double)x, (double)y, (double)z};
-    const double d = sqrt(mesh_cloud_d2(cloud, a.n_points, p, l16));
-    const bool inside = mesh_contains(a, tile, p, ok, l16);
-    if (ok && l16 == 0) {
-        int *cnt = a.cnt + 2 * (step & 1);
-        if (inside && d > 0.4) a.within[atomicAdd(cnt, 1)] = make_float4(x, y, z, __int_as_float(atom));
-        else if (!inside || d < 0.2) a.out_list[atomicAdd(cnt + 1, 1)] = atom;
-    }
-}
-
 // Three nearest within-atoms of p (key: squared distance, then atom index), identical in the atom's 16 lanes.  Block-uniform.
 SM_DEV Top3 mesh_knn(const MeshGuideArgs &a, float4 *tile, int n_within, const double (&p)[3], bool live, int l16) {
 #pragma clang fp contract(off)
@@ -182,26 +157,119 @@ SM_DEV Top3 mesh_knn(const MeshGuideArgs &a, float4 *tile, int n_within, const d
     return t;
 }
 
-// One block per 16 outmesh atoms (the grid is sized for N: blocks past the outmesh count return at once).  Reads only
-// within-atoms (their positions: the compacted copy and, by index, pred_pos) and writes only outmesh atoms, and the two sets
-// are disjoint: updating pred_pos in place is race-free.
-// The counters: classify of step s adds into slot (s & 1); pull of step s reads that slot and clears slot ((s + 1) & 1), which
-// the previous step used and the next step's classify fills.  Both slots are cleared before a chain starts.
-__global__ void __launch_bounds__(256) mesh_pull_kernel(MeshGuideArgs a) {
+// ---- the kernels.  A group is a contiguous run of molecules of the batch -- the batch vector is sorted, so also a contiguous
+// run of atoms -- with its own mesh and cloud; a group without a mesh leaves its atoms alone.  Per atom the arithmetic is the
+// device functions above, called on a per-group view of the concatenated data (mesh_group_view).  Draws are keyed by the
+// BATCH-GLOBAL atom (fed table [S][5][N] or Philox (atom, step, 200 + j)).
+//
+// Device data, one block per installed set: faces, face boxes and clouds of all groups back to back with CSR offsets per group
+// (face_off, cloud_off), and the projected bounds [G][5] of every mesh.
+//
+// Mapping of workgroups to groups: the per-workgroup table of sm_guide_groups.h (pc_groups_table_kernel, once per chain):
+// group g with n_g atoms and a mesh gets ceil(n_g / 16) workgroups of 256 threads (16 atoms x 16 lanes); entry w holds
+// (group, first atom); the unused tail of the grid floor(N / 16) + G is marked -1 and returns at once, as do the workgroups of
+// groups without a mesh (they have none).  A workgroup stages only its group's cloud and streams only its group's face boxes /
+// within-atoms through the 16 KB tile.  Both kernels use the same table: in the pull kernel the workgroup whose first atom is
+// atom_off[g] + 16 i serves the outmesh slots [16 i, 16 i + 16) of group g and returns when the group has fewer.
+//
+// Per-step lists: within [N] and outmesh [N] are segmented by the groups' atom ranges (group g compacts into
+// [atom_off[g], atom_off[g + 1]): it cannot have more within- or outmesh atoms than atoms); counters [G][2][2] =
+// (n_within, n_outmesh) per group in two alternating slots: classify of step s adds into slot (s & 1); pull of step s reads that
+// slot, and the group's first pull workgroup clears slot ((s + 1) & 1), which the previous step used and the next step's classify
+// fills.  All cleared before a chain starts.
+//
+// A group that fails the reference's KD-tree condition in a step (no within-atom, or fewer than 3 while an atom is to be
+// pulled) raises ST_MESH and adds 1 to group_flags[g]: the number of steps in which group g was left unguided, for the error
+// message of the chain (cleared with the counters).
+//
+// LDS: 24 B x the LARGEST cloud of the set, rounded up to 32 B so that the tile behind a group's cloud is aligned for its
+// double4 / float4 accesses whatever the cloud's size, + the 16 KB tile; one dynamic size per launch (<= 64 KB: two workgroups =
+// 8 waves per CU at the 2048-point limit, five at 512 points).
+struct MeshGroupsArgs {
+    float *pred_pos;              // [N][3] in/out
+    const double *clouds;         // [sum P_g][3]
+    const MeshFace *faces;        // [sum F_g]
+    const double4 *fbox;          // [sum F_g]
+    const double *bounds;         // [G][5] (umin, umax, vmin, vmax, wmax) of every projected mesh
+    const int *face_off;          // [G + 1]
+    const int *cloud_off;         // [G + 1] (equal neighbours: no mesh)
+    const int *atom_off;          // [G + 1] first atom of each group (pc_groups_table_kernel)
+    const int2 *wg_table;         // [gridDim.x] (group or -1, first atom of the workgroup)
+    float4 *within;               // [N], segment of group g at atom_off[g]
+    int *out_list;                // [N], likewise
+    int *cnt;                     // [G][2][2]
+    int *group_flags;             // [G] steps in which the group was left unguided (too few within-atoms)
+    int *status;
+    const ChainParams *cp;
+    const int *step_cur;
+    int n_atoms, t_first, grad_step;
+};
+
+// the argument block of group g: the device functions above then see that group alone
+SM_DEV MeshGuideArgs mesh_group_view(const MeshGroupsArgs &a, int g) {
+    MeshGuideArgs v;
+    const int f0 = a.face_off[g], c0 = a.cloud_off[g], a0 = a.atom_off[g];
+    v.pred_pos = a.pred_pos; v.cloud = a.clouds + (size_t)c0 * 3; v.faces = a.faces + f0; v.fbox = a.fbox + f0;
+    v.within = a.within + a0; v.out_list = a.out_list + a0; v.cnt = a.cnt + 4 * g; v.status = a.status; v.cp = a.cp;
+    v.step_cur = a.step_cur; v.n_atoms = a.n_atoms; v.n_points = a.cloud_off[g + 1] - c0; v.n_faces = a.face_off[g + 1] - f0;
+    v.t_first = a.t_first; v.grad_step = a.grad_step;
+    const double *b = a.bounds + 5 * g;
+    v.umin = b[0]; v.umax = b[1]; v.vmin = b[2]; v.vmax = b[3]; v.wmax = b[4];
+    return v;
+}
+
+// doubles of LDS in front of the tile: the group's cloud, rounded up to a multiple of 32 bytes
+SM_DEV int mesh_tile_off(int n_points) { return (n_points * 3 + 3) & ~3; }
+inline size_t mesh_lds_bytes(int max_points) { return (((size_t)max_points * 3 + 3) & ~(size_t)3) * 8 + 16384; }
+
+// 16 lanes per atom, 256 threads per block, blocks per the workgroup table
+__global__ void __launch_bounds__(256) mesh_classify_kernel(MeshGroupsArgs ga) {
+    extern __shared__ double mesh_lds[];
+    const int step = ga.step_cur ? *ga.step_cur : 0;
+    if (ga.t_first - step <= ga.grad_step) return;                 // `if i > grad_step` (molopt_score_model.py:573)
+    const int2 e = ga.wg_table[blockIdx.x];
+    if (e.x < 0) return;
+    const MeshGuideArgs a = mesh_group_view(ga, e.x);
+    double *cloud = mesh_lds;
+    double4 *tile = reinterpret_cast<double4 *>(mesh_lds + mesh_tile_off(a.n_points));
+    mesh_load_cloud(a, cloud);
+    const int end = ga.atom_off[e.x + 1];                          // > e.y: the table has no workgroup without an atom
+    const int atom_raw = e.y + (threadIdx.x >> 4), l16 = threadIdx.x & 15;
+    const bool ok = atom_raw < end;
+    const int atom = ok ? atom_raw : end - 1;
+    const float x = a.pred_pos[atom * 3], y = a.pred_pos[atom * 3 + 1], z = a.pred_pos[atom * 3 + 2];
+    const double p[3] = {(double)x, (double)y, (double)z};
+    const double d = sqrt(mesh_cloud_d2(cloud, a.n_points, p, l16));
+    const bool inside = mesh_contains(a, tile, p, ok, l16);
+    if (ok && l16 == 0) {
+        int *cnt = a.cnt + 2 * (step & 1);
+        if (inside && d > 0.4) a.within[atomicAdd(cnt, 1)] = make_float4(x, y, z, __int_as_float(atom));
+        else if (!inside || d < 0.2) a.out_list[atomicAdd(cnt + 1, 1)] = atom;
+    }
+}
+
+// One block per 16 outmesh slots of a group (the table gives every group as many blocks as it could have outmesh atoms).
+// Reads only within-atoms (their positions: the compacted copy and, by index, pred_pos) and writes only outmesh atoms of the
+// block's own group, and the two sets are disjoint: updating pred_pos in place is race-free.
+__global__ void __launch_bounds__(256) mesh_pull_kernel(MeshGroupsArgs ga) {
 #pragma clang fp contract(off)
     extern __shared__ double mesh_lds[];
-    const int step = a.step_cur ? *a.step_cur : 0;
-    if (blockIdx.x == 0 && threadIdx.x < 2) a.cnt[2 * ((step + 1) & 1) + threadIdx.x] = 0;
-    if (a.t_first - step <= a.grad_step) return;
-    const int n_within = a.cnt[2 * (step & 1)], n_out = a.cnt[2 * (step & 1) + 1];
-    if (n_within == 0 || (n_within < 3 && n_out > 0)) {        // the reference's KDTree(...) / query(k=3) raise ValueError
-        if (blockIdx.x == 0 && threadIdx.x == 0) a.status[ST_MESH] = 1;
+    const int step = ga.step_cur ? *ga.step_cur : 0;
+    const int2 e = ga.wg_table[blockIdx.x];
+    if (e.x < 0) return;
+    const int base = e.y - ga.atom_off[e.x];                       // first outmesh slot of this block within its group
+    int *gcnt = ga.cnt + 4 * e.x;
+    if (base == 0 && threadIdx.x < 2) gcnt[2 * ((step + 1) & 1) + threadIdx.x] = 0;
+    if (ga.t_first - step <= ga.grad_step) return;
+    const int n_within = gcnt[2 * (step & 1)], n_out = gcnt[2 * (step & 1) + 1];
+    if (n_within == 0 || (n_within < 3 && n_out > 0)) {          // the reference's KDTree(...) / query(k=3) raise ValueError
+        if (base == 0 && threadIdx.x == 0) { ga.status[ST_MESH] = 1; atomicAdd(ga.group_flags + e.x, 1); }
         return;
     }
-    const int base = blockIdx.x * 16;
     if (base >= n_out) return;
+    const MeshGuideArgs a = mesh_group_view(ga, e.x);
     double *cloud = mesh_lds;
-    void *tile = mesh_lds + a.n_points * 3;
+    void *tile = mesh_lds + mesh_tile_off(a.n_points);
     mesh_load_cloud(a, cloud);
     const int slot = base + (threadIdx.x >> 4), l16 = threadIdx.x & 15;
     const bool ok = slot < n_out;

@@ -1059,21 +1059,12 @@ __global__ void clock_stamp_kernel(unsigned long long *out, const int *step_cur,
 // t > grad_step, :583-586): an atom whose three nearest cloud points are on average farther than `radius` is pulled
 // towards their mean by a random fraction in [ratio, 0.8), re-checked, and pulled again up to five times.
 // The reference does this on the host (sklearn KD-tree, numpy float64, one D2H + H2D round trip per step); here it is a
-// kernel between the score evaluation and the posterior step: 16 lanes per atom scan the cloud (brute force, float64 as
-// the KD-tree), every atom runs its own five-iteration loop.  Uniform draws: the reference consumes np.random.random()
+// kernel between the score evaluation and the posterior step (pc_guidance_kernel, sm_guide_groups.h; the per-atom work is
+// pc_guide_atom below): 16 lanes per atom scan the cloud (brute force, float64 as the KD-tree), every atom runs its own
+// five-iteration loop.  `ratio` is the lower end of the pull fraction, u * (0.8 - ratio) + ratio (the reference's default: 0.2).  Uniform draws: the reference consumes np.random.random()
 // in the order of the currently-far atoms of each iteration; parity mode is fed the recorded draw of every
 // (step, iteration, atom), throughput mode uses Philox keyed by the same triple.
 // ---------------------------------------------------------------------------------------------
-struct PcGuideArgs {
-    float *pred_pos;          // [N][3] in/out
-    const double *cloud;      // [P][3]
-    const ChainParams *cp;
-    const int *step_cur;
-    int n_atoms, n_points, t_first, grad_step;
-    double radius;
-    double ratio;             // lower end of the pull fraction: u * (0.8 - ratio) + ratio (the reference's default: 0.2)
-};
-
 // Three nearest cloud points of p.  Every candidate is one 64-bit key: the bits of its squared distance (non-negative
 // doubles order like unsigned integers) with the low 12 bits replaced by ... nothing: keys stay exact; the point index
 // travels beside the key.  Each of the 16 lanes of an atom scans every 16th point (the cloud sits in LDS) and keeps its
@@ -1147,16 +1138,4 @@ SM_DEV void pc_guide_atom(float *pred_pos, const double *cloud, int n_points, do
         if (far && (sqrt(t.d[0]) + sqrt(t.d[1]) + sqrt(t.d[2])) / 3.0 < radius) far = false;
     }
     if (changed && valid && l16 < 3) pred_pos[atom * 3 + l16] = (float)(l16 == 0 ? p[0] : (l16 == 1 ? p[1] : p[2]));
-}
-
-__global__ void __launch_bounds__(256) pc_guidance_kernel(PcGuideArgs a) {
-    extern __shared__ double pc_cloud[];                            // [P][3]
-    const int step = a.step_cur ? *a.step_cur : 0;
-    if (a.t_first - step <= a.grad_step) return;                   // `if i > grad_step` (molopt_score_model.py:585)
-    for (int i = threadIdx.x; i < a.n_points * 3; i += blockDim.x) pc_cloud[i] = a.cloud[i];
-    __syncthreads();
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int atom_raw = gid >> 4, l16 = gid & 15;
-    const int atom = atom_raw < a.n_atoms ? atom_raw : a.n_atoms - 1;
-    pc_guide_atom(a.pred_pos, pc_cloud, a.n_points, a.radius, a.ratio, *a.cp, step, a.n_atoms, atom, atom_raw < a.n_atoms, l16);
 }

@@ -487,10 +487,10 @@ class ScorePosNet3D(nn.Module):
             u = _check_device_tensor("noise[1]", noise[1], torch.float32)
             if tuple(eps.shape) != (num_steps, n, 3) or tuple(u.shape) != (num_steps, n, cc):
                 raise ValueError("noise must be (eps (S,N,3), u (S,N,C))")
-        guided = "mesh_groups" if mesh_groups is not None else (
-            "mesh" if use_mesh_data is not None else ("groups" if groups is not None else
-                                                      ("cloud" if use_pointcloud_data is not None else None)))
-        mesh = _mesh_arrays(use_mesh_data) if guided == "mesh" else None
+        # the kind of set the chain installs (the names of _GUIDANCE's two rows); the mesh wins, as the reference's if / elif
+        guided = "mesh_groups" if use_mesh_data is not None else ("groups" if use_pointcloud_data is not None else None)
+        if guided == "mesh_groups" and mesh_groups is None:
+            mesh_groups = _one_group(guided, use_mesh_data, b)
         if seed is None:
             if noise is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -509,8 +509,10 @@ class ScorePosNet3D(nn.Module):
             gd = _check_device_tensor("guide_draws", guide_draws, torch.float64)
             if tuple(gd.shape) != (num_steps, 5, n):
                 raise ValueError("guide_draws must be (S, 5, N) float64")
+        if guided == "groups" and groups is None:
+            groups = _one_group(guided, use_pointcloud_data, b)
         if guided:      # (taken out of the context again by _PendingChain._drop_guidance)
-            _install_guidance(lib, ctx, guided, {"mesh": mesh, "groups": groups, "mesh_groups": mesh_groups}.get(guided, use_pointcloud_data), grad_step, gd)
+            _install_guidance(lib, ctx, guided, mesh_groups if guided == "mesh_groups" else groups, grad_step, gd)
         tr = _lib.Traj()
         bufs = {}
         if return_traj:
@@ -527,7 +529,7 @@ class ScorePosNet3D(nn.Module):
         out_v = torch.empty((n,), dtype=torch.int64, device=dev)
         pending = _PendingChain(self, ctx, dev, guided, bufs, out_pos, out_v, return_traj, _reuse_host_buffers,
                                 keep=(pos, v, batch, shape, eps, u, gd), offset=offset)
-        pending.n_groups = len(mesh_groups[0]) - 1 if mesh_groups is not None else 0
+        pending.n_groups = len(mesh_groups[0]) - 1 if isinstance(use_mesh_data, list) else 0
         try:
             with torch.cuda.device(dev):
                 cur = torch.cuda.current_stream(dev)
@@ -661,7 +663,7 @@ class _PendingChain:
         self.out_pos, self.out_v, self.return_traj, self.reuse, self.keep = out_pos, out_v, return_traj, reuse, keep
         self.side = self.cur = None
         self.done = False
-        self.n_groups = 0                    # mesh groups of the chain (their unguided steps go into a MeshGuidanceError)
+        self.n_groups = 0                    # mesh groups of a list-form chain (their unguided steps go into a MeshGuidanceError)
 
     def _drop_guidance(self):
         if self.guided:      # whatever happened, the context must not keep the cloud / mesh (and the caller-owned draws pointer) installed
@@ -811,30 +813,32 @@ def _cloud_array(points):
     return np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
 
 
+def _one_group(kind, data, n_mols):
+    """The tuple form ``(mesh, point_clouds, kdtree)`` / ``(point_clouds, kdtree, radius)`` as the payload of a set of ONE group
+    that spans the batch: the only place where the reference's form becomes the form the library runs.  The tuple's own argument
+    checks (and their texts) come first.  What the library itself rejects (a cloud of fewer than 3 or more than 2048 points, a
+    radius <= 0, a face that repeats a vertex, a non-finite vertex) is then reported by the groups setter, as "group 0"."""
+    if kind == "mesh_groups":
+        verts, faces, cloud = _mesh_arrays(data)
+        return _mesh_guidance_groups([((verts, faces), cloud, None, n_mols)], n_mols)
+    return _guidance_groups([(_cloud_array(data[0]), None, float(data[2]), n_mols)], n_mols)
+
+
 # setter of each kind of guidance, and the arguments that take the guidance out of the context again
-_GUIDANCE = {"mesh": ("shapemol_set_mesh_guidance", (None, 0, None, 0, None, 0, 0, None)),
-             "mesh_groups": ("shapemol_set_mesh_guidance_groups", (0, None, None, None, None, None, None, None, 0, None)),
-             "groups": ("shapemol_set_guidance_groups", (0, None, None, None, None, 0, None)),
-             "cloud": ("shapemol_set_guidance", (None, 0, 0.0, 0, None))}
+_GUIDANCE = {"mesh_groups": ("shapemol_set_mesh_guidance_groups", (0, None, None, None, None, None, None, None, 0, None)),
+             "groups": ("shapemol_set_guidance_groups", (0, None, None, None, None, 0, None))}
 
 
 def _install_guidance(lib, ctx, kind, payload, grad_step, gd):
-    """payload -- "mesh": _mesh_arrays' triple; "groups": _guidance_groups' arrays; "mesh_groups": _mesh_guidance_groups' arrays;
-    "cloud": (point_clouds, kdtree, radius)."""
+    """payload -- "mesh_groups": _mesh_guidance_groups' arrays; "groups": _guidance_groups' arrays."""
     vp = lambda a: a.ctypes.data_as(C.c_void_p)        # noqa: E731
-    if kind == "mesh":
-        verts, faces, cloud = payload
-        args = (vp(verts), verts.shape[0], vp(faces), faces.shape[0], vp(cloud), cloud.shape[0])
-    elif kind == "mesh_groups":
+    if kind == "mesh_groups":
         mol_off, verts, vert_off, faces, face_off, clouds, cloud_off = payload
         opt = lambda a: vp(a) if len(a) else None      # noqa: E731
         args = (len(mol_off) - 1, vp(mol_off), opt(verts), vp(vert_off), opt(faces), vp(face_off), opt(clouds), vp(cloud_off))
-    elif kind == "groups":
+    else:
         mol_off, clouds, cloud_off, radii = payload
         args = (len(radii), vp(mol_off), vp(clouds) if len(clouds) else None, vp(cloud_off), vp(radii))
-    else:
-        cloud = _cloud_array(payload[0])
-        args = (vp(cloud), cloud.shape[0], float(payload[2]))
     _lib.check(getattr(lib, _GUIDANCE[kind][0])(ctx, *args, int(grad_step), _ptr(gd)), _GUIDANCE[kind][0])
 
 

@@ -103,18 +103,23 @@ def test_grouped_function_golden(name):
 @pytest.mark.parametrize("use_graph", (True, False))
 def test_one_group_is_the_single_cloud_chain(use_graph):
     """3. Degenerate grouping: one group that spans the whole batch is bit-identical to the tuple form, with fed draws and with
-    device Philox draws (same key: the batch-global atom)."""
+    device Philox draws (same key: the batch-global atom).  Both forms run the group kernel, so both are also compared, to the
+    bit, with what the single-cloud kernel gave before it was removed (tests/golden/make_golden_guided_single_bits.py)."""
     m = hip_model()
     c = golden("chain_guided_b4_s20.npz")
+    bits = golden("guided_single_bits.npz")
     bb, eps, u, B, S = fixture_inputs(c)
     cloud, radius = c["cloud"], float(c["radius"])
-    for extra in (dict(guide_draws=T(c["draws"], DEV)), dict(seed=9)):
+    for tag, extra in (("fed", dict(guide_draws=T(c["draws"], DEV))), ("philox", dict(seed=int(bits["seed"])))):
         kw = dict(use_graph=use_graph, grad_step=int(c["grad_step"]), **extra)
         a = run(m, bb, eps, u, B, S, use_pointcloud_data=(cloud, None, radius), **kw)
         b = run(m, bb, eps, u, B, S, use_pointcloud_data=[(cloud, None, radius, B)], **kw)
         assert torch.equal(a["pos"], b["pos"]) and torch.equal(a["v"], b["v"])
         for k in ("pos_traj", "v_traj", "v0_traj", "vt_traj", "pos_cond_traj", "v_cond_traj"):
             assert torch.equal(torch.stack(a[k]), torch.stack(b[k])), k
+        assert torch.equal(a["pos"].cpu(), T(bits[f"cloud_{tag}_pos"])), tag
+        assert torch.equal(a["v"].cpu(), T(bits[f"cloud_{tag}_v"]).long()), tag
+        assert torch.equal(torch.stack(a["pos_cond_traj"]).cpu(), T(bits[f"cloud_{tag}_pos_cond_traj"])), tag
     assert maxabs(a["pos"], c["pos"]) > 1e-3          # (the Philox chain is a different chain than the fixture's)
 
 

@@ -132,19 +132,25 @@ def test_grouped_chain_golden(name, mode):
 @pytest.mark.parametrize("use_graph", (True, False))
 def test_one_group_is_the_single_mesh_chain(use_graph):
     """G = 1 identity: one group that spans the whole batch is bit-identical to the single-mesh call, with fed draws and with
-    device Philox draws on the same seed (same key: the batch-global atom, same counter domain)."""
+    device Philox draws on the same seed (same key: the batch-global atom, same counter domain).  Both forms run the group
+    kernels, so both are also compared, to the bit, with what the single-mesh kernels gave before they were removed
+    (tests/golden/make_golden_guided_single_bits.py)."""
     m = hip_model()
     c = golden("chain_mesh_guided_b4_s20.npz")
     mf = golden("mesh_fixture.npz")
+    bits = golden("guided_single_bits.npz")
     mesh, cloud = (mf["verts"], mf["faces"]), mf["cloud"]
     bb, eps, u, B, S = fixture_inputs(c)
-    for extra in (dict(guide_draws=T(c["draws"], DEV)), dict(seed=9)):
+    for tag, extra in (("fed", dict(guide_draws=T(c["draws"], DEV))), ("philox", dict(seed=int(bits["seed"])))):
         kw = dict(use_graph=use_graph, grad_step=int(c["grad_step"]), **extra)
         a = run(m, bb, eps, u, B, S, use_mesh_data=(mesh, cloud, None), **kw)
         b = run(m, bb, eps, u, B, S, use_mesh_data=[(mesh, cloud, None, B)], **kw)
         assert torch.equal(a["pos"], b["pos"]) and torch.equal(a["v"], b["v"])
         for k in ("pos_traj", "v_traj", "v0_traj", "vt_traj", "pos_cond_traj", "v_cond_traj"):
             assert torch.equal(torch.stack(a[k]), torch.stack(b[k])), k
+        assert torch.equal(a["pos"].cpu(), T(bits[f"mesh_{tag}_pos"])), tag
+        assert torch.equal(a["v"].cpu(), T(bits[f"mesh_{tag}_v"]).long()), tag
+        assert torch.equal(torch.stack(a["pos_cond_traj"]).cpu(), T(bits[f"mesh_{tag}_pos_cond_traj"])), tag
         if "guide_draws" in extra:
             assert maxabs(a["pos"], c["pos"]) < POS_TOL
     assert maxabs(a["pos"], c["pos"]) > 1e-3          # (the Philox chain is a different chain than the fixture's)

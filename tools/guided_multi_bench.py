@@ -13,9 +13,10 @@ summary line (median and spread of molecules/s per variant).
     python tools/guided_multi_bench.py [--conditions 16] [--samples 50] [--steps 1000] [--grad-step 300] [--batch-sizes 256,800]
 
 Kernel cost (a process of its own, without counters):
-    rocprofv3 --kernel-trace --stats -- python tools/guided_multi_bench.py --kernels single,g1    # pc_guidance / pc_guidance_groups, G = 1
-    rocprofv3 --kernel-trace --stats -- python tools/guided_multi_bench.py --kernels g16          # pc_guidance_groups, 16 groups
-runs B = 256 chains of --kernel-steps guided steps with one cloud (tuple form), one group over the batch, or 16 groups of 16.
+    rocprofv3 --kernel-trace --stats -- python tools/guided_multi_bench.py --kernels single       # pc_guidance_kernel, tuple form
+    rocprofv3 --kernel-trace --stats -- python tools/guided_multi_bench.py --kernels g16          # pc_guidance_kernel, 16 groups
+runs B = 256 chains of --kernel-steps guided steps with one cloud (tuple form: a set of one group, so "single" and "g1" run the
+same kernel), one group over the batch as a list, or 16 groups of 16.
 """
 import argparse
 import contextlib

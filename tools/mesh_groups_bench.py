@@ -2,7 +2,8 @@
 """Mesh shape guidance with one mesh per group of molecules: what it costs and what packing conditions into one chain gains.
 
   --mode step      B = 256, every step guided by the ~5k-face fixture mesh (tests/golden/mesh_fixture.npz): wall time per reverse
-                   step (captured graph, no trajectories) of the single-mesh call and of a one-group list over the batch,
+                   step (captured graph, no trajectories) of the single-mesh call and of a one-group list over the batch (the same
+                   kernels since the tuple form runs as a set of one group: the pair now measures the run-to-run spread),
                    alternating --reps times in one process after a warm-up of both; medians and min / max.
   --mode workload  16 mesh conditions x 50 samples, 1000 steps guided while t > 300, atom counts from the MOSES prior:
                    sample_diffusion_ligand per condition (16 chains of 50) against sample_diffusion_ligand_multi (one chain of
@@ -12,8 +13,8 @@
                    sampling script leaves the module (a mixed batch is then another computation than the chains of 50).
   --mode kernels   chains of --kernel-steps guided steps for `rocprofv3 --kernel-trace --stats -- python
                    tools/mesh_groups_bench.py --mode kernels --kernels NAME` (a process of its own, without counters; one NAME
-                   per process keeps the grouped kernels' statistics apart): single, g1, g16 at B = 256 (one mesh, one group,
-                   16 groups of 16); w800 = the workload's chain, 16 groups of 50 molecules.
+                   per process keeps the variants' statistics apart): single, g1, g16 at B = 256 (one mesh as a tuple -- a set of
+                   one group, the same kernels as g1 --, one group as a list, 16 groups of 16); w800 = the workload's chain, 16 groups of 50 molecules.
 
 A chain in which a group runs out of atoms inside its mesh runs to the end with that group left unguided in such steps, and the
 call then raises MeshGuidanceError instead of returning molecules.  A timing that contains such a call does not measure the
