@@ -96,12 +96,12 @@ def moses_atom_prior():
     return np.asarray(ATOM_NUMS, np.int64), p / p.sum()
 
 
-def synthetic_batch(num_mols, seed=2021, max_atoms=None, atoms_range=None, shape_points=32):
+def synthetic_batch(num_mols, seed=2021, max_atoms=None, atoms_range=None, shape_points=32, num_classes=15):
     """One synthetic sampling batch.
 
     Returns dict(counts (B,) i64, batch (N,) i64, init_pos (N,3) f32, init_v (N,) i64,
     shape (B,32,3) f32).  Atom counts ~ MOSES prior via RandomState(seed) unless
-    `atoms_range=(lo, hi)` asks for the uniform large-molecule stress draw.
+    `atoms_range=(lo, hi)` asks for the uniform large-molecule stress draw.  init_v is drawn from `num_classes` atom types.
     """
     rs = np.random.RandomState(seed)
     if atoms_range is not None:
@@ -114,7 +114,7 @@ def synthetic_batch(num_mols, seed=2021, max_atoms=None, atoms_range=None, shape
     n = int(counts.sum())
     batch = np.repeat(np.arange(num_mols, dtype=np.int64), counts)
     init_pos = hash_normal((n, 3), tag=101, seed=seed)
-    init_v = (hash_u24(n, tag=102, seed=seed) % 15).astype(np.int64)
+    init_v = (hash_u24(n, tag=102, seed=seed) % num_classes).astype(np.int64)
     shape = hash_normal((num_mols, shape_points, 3), tag=103, seed=seed)
     return dict(counts=counts, batch=batch, init_pos=init_pos, init_v=init_v, shape=shape)
 

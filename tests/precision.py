@@ -25,14 +25,15 @@ P2_EXP = (-8, 2)            # P2: per-tensor scale 2^e, e in this closed range
 MARGIN = 1e-5               # least relative kNN margin (d2_{k+1} - d2_k) / d2_k of every profile's batch
 U = 2.0 ** -24              # float32 unit roundoff
 
-# name: (model overrides, molecules, atoms_range or None for the MOSES prior, batch seed of P0-P2, batch seed of P3).
+# name: (model overrides, molecules, atoms_range or None for the MOSES prior, batch seed of P0-P2, batch seed of P3, atom types).
 # The batch seeds are the first that give every atom a kNN margin of at least MARGIN (tests/test_precision_cpu.py checks it).
 CONFIGS = {
-    "b4": ({}, 4, None, 11, 11),
-    "b256": ({}, 256, None, 2021, 2021),
-    "k24": ({"knn": 24}, 16, (26, 48), 24, 24),
-    "k32": ({"knn": 32}, 16, (40, 80), 33, 35),
-    "small": ({"hidden_dim": 32, "n_heads": 4, "num_layers": 2}, 16, None, 16, 16),
+    "b4": ({}, 4, None, 11, 11, 15),
+    "b256": ({}, 256, None, 2021, 2021, 15),
+    "k24": ({"knn": 24}, 16, (26, 48), 24, 24, 15),
+    "k32": ({"knn": 32}, 16, (40, 80), 33, 35, 15),
+    "small": ({"hidden_dim": 32, "n_heads": 4, "num_layers": 2}, 16, None, 16, 16, 15),
+    "c23": ({}, 16, None, 23, 23, 23),      # the `full` vocabulary: two output tiles of the atom-type head, C > 16
 }
 WEIGHT_SEED = 7
 
@@ -69,16 +70,20 @@ def config(name):
     return model_cfg(**ov)
 
 
+def classes(name):
+    return CONFIGS[name][5]
+
+
 def _laplace(shape, tag, seed):
     """Laplace draws of unit variance from hash uniforms (u = 0 excluded by half a grid step)."""
     u = synth.hash_uniform(shape, tag, seed).astype(np.float64) + 2.0 ** -25 - 0.5
     return -np.sign(u) * np.log1p(-2.0 * np.abs(u)) / np.sqrt(2.0)
 
 
-def state_dict(profile, cfg, seed=WEIGHT_SEED):
+def state_dict(profile, cfg, seed=WEIGHT_SEED, num_classes=15):
     """(state dict {key: float32 ndarray}, {key: scale applied}) of a profile."""
     from shapemol_amd.spec import ModelDims, state_dict_spec
-    sdn = synth.synthetic_state_dict(cfg, seed=seed)
+    sdn = synth.synthetic_state_dict(cfg, seed=seed, num_classes=num_classes)
     scales = {}
     if profile == "P1":
         for k in sdn:
@@ -87,7 +92,7 @@ def state_dict(profile, cfg, seed=WEIGHT_SEED):
                 scales[k] = SMALL
     elif profile == "P2":
         lo, hi = P2_EXP
-        for key, (shape, kind, fan_in) in state_dict_spec(ModelDims(cfg, 15)).items():
+        for key, (shape, kind, fan_in) in state_dict_spec(ModelDims(cfg, num_classes)).items():
             if kind not in ("weight", "bias"):
                 continue
             tag = synth.key_tag(key)
@@ -103,9 +108,9 @@ def state_dict(profile, cfg, seed=WEIGHT_SEED):
 
 def batch(profile, cname):
     """dict(pos (N,3) f32, v (N,) i64, batch (N,) i64, shape (B,S,3) f32, t (B,) i64) of a profile in configuration cname."""
-    _, nmol, rng, seed, seed3 = CONFIGS[cname]
+    _, nmol, rng, seed, seed3, ncls = CONFIGS[cname]
     geo = profile == "P3"
-    bb = synth.synthetic_batch(nmol, seed=seed3 if geo else seed, atoms_range=rng)
+    bb = synth.synthetic_batch(nmol, seed=seed3 if geo else seed, atoms_range=rng, num_classes=ncls)
     pos, b = bb["init_pos"].copy(), bb["batch"]
     t = (synth.hash_u24(nmol, 9, seed) % 1000).astype(np.int64)
     if geo:

@@ -116,3 +116,27 @@ def test_gather_single_rank_forced_through_the_collective():
     p.join(timeout=60)
     assert p.exitcode == 0
     assert shortcut and same and (dp, dv, dc) == ("torch.float32", "torch.int64", "torch.int64")
+
+
+def _type_worker(port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    try:
+        v = torch.arange(64, dtype=torch.int64) % 32                  # every atom type a 32-class vocabulary can hold
+        pos, counts = torch.arange(192, dtype=torch.float32).view(64, 3), torch.tensor([31, 33])
+        p1, v1, c1 = gather_molecules(pos, v, counts, _single_rank_too=True)
+        q.put((torch.equal(v1, v) and int(v1.max()) == 31, torch.equal(p1, pos) and torch.equal(c1, counts), str(v1.dtype)))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_gather_round_trips_atom_types_up_to_31():
+    """The packed int32 payload carries atom types of every vocabulary the library accepts (num_classes <= 32)."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_type_worker, args=(_free_port(), q))
+    p.start()
+    types, rest, dv = q.get(timeout=120)
+    p.join(timeout=60)
+    assert p.exitcode == 0
+    assert types and rest and dv == "torch.int64"

@@ -28,9 +28,12 @@ def _ttype(tag):
     return None if tag == "none" else tag
 
 
-def _batch(B, seed, steps):
-    bb = synth.synthetic_batch(B, seed=seed)
-    eps, u = hash_noise(len(bb["batch"]), steps, seed)
+def _batch(B, seed, steps, C=15):
+    bb = synth.synthetic_batch(B, seed=seed, num_classes=C)
+    if C != 15:          # another vocabulary: every class, C - 1 included, among the atom types
+        from vocab import all_classes
+        bb["init_v"] = all_classes(len(bb["batch"]), C, 102, seed)
+    eps, u = hash_noise(len(bb["batch"]), steps, seed, c=C)
     args = (T(bb["init_pos"], DEV), T(bb["init_v"], DEV), T(bb["batch"], DEV), T(bb["shape"], DEV).view(B, -1))
     return args, dict(num_steps=steps, center_pos_mode="none", noise=(T(eps, DEV), T(u, DEV)))
 
@@ -128,12 +131,14 @@ def _cfg_stat(m):
     return np.array([out[0], out[1]], dtype=np.float32)
 
 
-@pytest.mark.parametrize("B", [4, 256, 1024])
-def test_cfg_quantile_equals_torch_quantile(B):
+@pytest.mark.parametrize("B,C", [(4, 15), (256, 15), (1024, 15), (4, 10), (4, 23)], ids=["4", "256", "1024", "4-c10", "4-c23"])
+def test_cfg_quantile_equals_torch_quantile(B, C):
     """The device's radix-select quantile of the combined positions (N*3) and logits (N*C) of a step is torch.quantile's value
-    bit for bit, at several p (ranks on both sides of a half weight, the ends)."""
-    m = hip_model(cond_mask_prob=0.1)
-    args, kw = _batch(B, 21, 1)
+    bit for bit, at several p (ranks on both sides of a half weight, the ends); C = 10 and 23 change the number of logits, their
+    quantile ranks and the block counts of the statistics kernels."""
+    m = hip_model(cond_mask_prob=0.1, num_classes=C)
+    args, kw = _batch(B, 21, 1, C)
+    assert len(torch.unique(args[1])) == C
     for p in (0.995, 0.5, 0.3, 0.0, 1.0, 0.123456):
         r = m.sample_diffusion(*args, **kw, threshold_type="dynamic_threshold", threshold_args={"p": p}, guide_stren=0.7,
                                bounds=None)
@@ -144,17 +149,15 @@ def test_cfg_quantile_equals_torch_quantile(B):
             q = torch.quantile(x.reshape(-1), p).item()
             got.append((q, float(stat[i])))
             assert np.float32(q) == stat[i], (p, i, q, stat[i])
-        record("cfg_quantile_exact", B=B, p=p, values=got)
+        record("cfg_quantile_exact", B=B, C=C, p=p, values=got)
 
 
-@pytest.mark.parametrize("tag", TYPES)
-def test_cfg_step_recomposed_at_size(tag):
-    """B = 256 (about 5.5k atoms), 10 steps: every step recomposed on the host from the device chain's own state -- the
-    model's forward with the shape and with zeros, the restated threshold_CFG (torch.quantile on the device), the posterior
-    with the fed noise -- against the chain's v0_traj, vt_traj and positions."""
-    m = hip_model(cond_mask_prob=0.1)
-    B, S = 256, 10
-    args, kw = _batch(B, 31, S)
+def recomposed_step_errors(tag, B, S, seed, C=15):
+    """A CFG chain of S steps with every step recomposed on the host from the device chain's own state -- the model's forward
+    with the shape and with zeros, the restated threshold_CFG (torch.quantile on the device), the posterior with the fed noise
+    -- against the chain's v0_traj, vt_traj and positions: (worst absolute differences, atoms)."""
+    m = hip_model(cond_mask_prob=0.1, num_classes=C)
+    args, kw = _batch(B, seed, S, C)
     pos0, v0, batch, shape = args
     p = {"none": None, "reference_threshold": 1.05, "dynamic_threshold": 0.99, "rescale": 0.6}[tag]
     targs = {} if p is None else {"p": p}
@@ -189,7 +192,14 @@ def test_cfg_step_recomposed_at_size(tag):
         worst["pos"] = max(worst["pos"], maxabs(xn, r["pos_traj"][s]))
         worst["v0"] = max(worst["v0"], maxabs(lv0, r["v0_traj"][s]))
         worst["vt"] = max(worst["vt"], maxabs(lp, r["vt_traj"][s]))
-    record("cfg_step_recomposed_at_size", tag=tag, n=int(len(batch)), **worst)
+    return worst, int(len(batch))
+
+
+@pytest.mark.parametrize("tag", TYPES)
+def test_cfg_step_recomposed_at_size(tag):
+    """B = 256 (about 5.5k atoms), 10 steps: every step recomposed on the host (recomposed_step_errors)."""
+    worst, n = recomposed_step_errors(tag, 256, 10, 31)
+    record("cfg_step_recomposed_at_size", tag=tag, n=n, **worst)
     assert worst["pos"] <= STEP_TOL and worst["v0"] <= STEP_TOL and worst["vt"] <= STEP_TOL, worst
 
 

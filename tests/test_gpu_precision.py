@@ -46,8 +46,8 @@ def model(profile, cname):
     if key not in _models:
         import shapemol_amd
         cfg = P.config(cname)
-        sdn, _ = P.state_dict(key[0], cfg)
-        m = shapemol_amd.ScorePosNet3D(cfg, 15)
+        sdn, _ = P.state_dict(key[0], cfg, num_classes=P.classes(cname))
+        m = shapemol_amd.ScorePosNet3D(cfg, P.classes(cname))
         m.load_state_dict({k: torch.from_numpy(v) for k, v in sdn.items()}, strict=True)
         _models[key] = m.to(DEV)
     return _models[key]
@@ -58,8 +58,8 @@ def refs(profile, cname):
     key = (profile, cname)
     if key not in _refs:
         cfg = P.config(cname)
-        sdn, _ = P.state_dict("P0" if profile == "P3" else profile, cfg)
-        sd, dm = O.state_dict_from_numpy(sdn), O.Dims(cfg)
+        sdn, _ = P.state_dict("P0" if profile == "P3" else profile, cfg, num_classes=P.classes(cname))
+        sd, dm = O.state_dict_from_numpy(sdn), O.Dims(cfg, P.classes(cname))
         bt = P.batch(profile, cname)
         _refs[key] = (bt, P.oracle_outputs(sd, dm, bt, torch.float32), P.oracle_outputs(sd, dm, bt, torch.float64))
     return _refs[key]
@@ -116,7 +116,8 @@ def _fails(g):
 @pytest.mark.parametrize("cname", list(P.CONFIGS))
 def test_exact_mode_within_float32_floor(cname, profile):
     """The library default (every product on exactly split bf16 operands) at H = 128, k = 8, B = 4 and 256; k = 24 (the KP > 16
-    half-tile path); k = 32 with 40-80-atom molecules; the H = 32 reduced model -- on every profile."""
+    half-tile path); k = 32 with 40-80-atom molecules; the H = 32 reduced model; 23 atom types (two output tiles of the
+    atom-type head, 16 molecules) -- on every profile."""
     g, same_graph = run_gate(profile, cname, {}, "exact")
     assert same_graph, "HIP neighbour lists differ from the oracle's edge lists"
     assert not _fails(g), _fails(g)
@@ -148,6 +149,24 @@ def test_f16x2_modes_fail_the_gate(variant):
         assert same_graph
         worst[profile] = max(v[2] for v in g.values())
     record("precision_gate_negative_control", mode=variant, **{p: w for p, w in worst.items()})
+    assert max(w for w in worst.values() if isinstance(w, float)) >= 3.0, worst
+
+
+def test_f16x2_mode_fails_the_gate_at_23_classes():
+    """The negative control on the 23-type configuration (16 molecules): the two-piece f16 products exceed the gate by at least
+    3x on some profile there too, so the c23 gates of test_exact_mode_within_float32_floor can tell the modes apart."""
+    worst = {}
+    for profile in P.PROFILES:
+        try:
+            g, same_graph = run_gate(profile, "c23", F16X2["f16x2"], "f16x2")
+        except RuntimeError as e:           # ShapeMolLibraryError of the range guard: the mode refused these weights
+            if "fp16 range" not in str(e):
+                raise
+            worst[profile] = str(e)
+            continue
+        assert same_graph
+        worst[profile] = max(v[2] for v in g.values())
+    record("precision_gate_negative_control", mode="f16x2", config="c23", **{p: w for p, w in worst.items()})
     assert max(w for w in worst.values() if isinstance(w, float)) >= 3.0, worst
 
 

@@ -36,12 +36,14 @@ def probe(tmp_path_factory):
     return exe
 
 
-def run_probe(exe, overrides, tmp_path):
+def probe_image(exe, overrides, tmp_path, num_classes=15):
+    """(the probe's report, the image as float32, the state dict, the packed weights) of a model with `num_classes` atom types."""
     from shapemol_amd import _lib, pack_state_dict
     from shapemol_amd.spec import ModelDims
     cfg = model_cfg(**overrides)
-    d = ModelDims(cfg, 15)
-    packed = pack_state_dict(synth.synthetic_state_dict(cfg, seed=7), d.L)
+    d = ModelDims(cfg, num_classes)
+    sdn = synth.synthetic_state_dict(cfg, seed=7, num_classes=num_classes)
+    packed = pack_state_dict(sdn, d.L)
     conf = _lib.Config(d.H, d.heads, d.L, d.k, d.G, d.S, d.S_latent, d.temb, d.C, d.T)
     src, dst = str(tmp_path / "weights.bin"), str(tmp_path / "image.bin")
     with open(src, "wb") as f:
@@ -52,6 +54,11 @@ def run_probe(exe, overrides, tmp_path):
     out = dict(line.split() for line in r.stdout.splitlines())
     image = open(dst, "rb").read()
     assert len(image) == 4 * int(out["size"])
+    return out, image, sdn, packed
+
+
+def run_probe(exe, overrides, tmp_path, num_classes=15):
+    out, image, _, _ = probe_image(exe, overrides, tmp_path, num_classes)
     out["sha256"] = hashlib.sha256(image).hexdigest()
     return out
 
@@ -68,3 +75,34 @@ def test_image_is_what_the_packer_always_built(probe, case, tmp_path):
     assert len(got) > 100                    # every offset is reported
     diff = {k: (got[k], want[k]) for k in got if got[k] != want[k]}
     assert not diff, diff
+
+
+@pytest.mark.parametrize("num_classes,nt2", [(10, 1), (16, 1), (17, 2), (23, 2), (32, 2)])
+def test_atom_type_head_tiles_and_padding(probe, num_classes, nt2, tmp_path):
+    """The atom-type head (v_inference) of a model with another vocabulary: its second Linear is padded to whole 16-row output
+    tiles (nt2 of them), the padding rows of weight and bias are zero and the real rows are the state dict's, and the packed
+    weight count is what state_dict_spec says (the probe reads exactly shapemol_weight_count floats)."""
+    from shapemol_amd.packing import pack_order
+    from shapemol_amd.spec import ModelDims, state_dict_spec
+    out, image, sdn, packed = probe_image(probe, {}, tmp_path, num_classes)
+    cfg = model_cfg()
+    d = ModelDims(cfg, num_classes)
+    spec = state_dict_spec(d)
+    assert packed.size == sum(int(np.prod(spec[k][0])) for k in pack_order(d.L))
+    assert spec["v_inference.2.weight"][0] == (num_classes, d.H) and spec["ligand_atom_emb.weight"][0] == (d.H, num_classes + d.temb)
+    assert int(out["dm.vhead.nt2"]) == nt2
+    im = np.frombuffer(image, np.float32)
+    rows, K = 16 * nt2, d.H
+    b2 = im[int(out["dm.vhead.b2"]):int(out["dm.vhead.b2"]) + rows]
+    assert np.array_equal(b2[:num_classes], sdn["v_inference.2.bias"]) and not b2[num_classes:].any()
+    # the A-fragment image of pack_image: element ((t2 * K / 16 + t) * 64 + lane) * 4 + r is W[16 t2 + lane % 16][16 t + 4 (lane / 16) + r]
+    frag = im[int(out["dm.vhead.w2img"]):int(out["dm.vhead.w2img"]) + rows * K].reshape(nt2, K // 16, 64, 4)
+    t2, t, lane, r = np.meshgrid(np.arange(nt2), np.arange(K // 16), np.arange(64), np.arange(4), indexing="ij")
+    w = np.zeros((rows, K), np.float32)
+    w[16 * t2 + lane % 16, 16 * t + 4 * (lane // 16) + r] = frag
+    assert np.array_equal(w[:num_classes], sdn["v_inference.2.weight"]) and not w[num_classes:].any()
+    # the embedding [H][C + D] and its transpose [C + D][H]
+    e = num_classes + d.temb
+    emb = im[int(out["dm.embw"]):int(out["dm.embw"]) + d.H * e].reshape(d.H, e)
+    embT = im[int(out["dm.embwT"]):int(out["dm.embwT"]) + d.H * e].reshape(e, d.H)
+    assert np.array_equal(emb, sdn["ligand_atom_emb.weight"]) and np.array_equal(embT, emb.T)

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import precision as P
-from util import O, T, golden, oracle_model
+from util import O, T, golden, oracle_model, record
 
 
 def _score(sd, dm, f, pos, v, tkey, dtype):
@@ -114,3 +114,22 @@ def test_gate_separates_emulated_operand_formats(cname):
         assert max(v[2] for v in ex.values()) <= 1.0, (prof, ex)
         worst[prof] = max(v[2] for v in P.gate(P.oracle_outputs(sd, dm, bt, operands=P.f16x2), r32, r64).values())
     assert worst["P1"] >= 3.0, worst
+
+
+def test_c23_profiles_cover_the_vocabulary_and_record_e32():
+    """The 23-type configuration of the gates: every class among the atom types of both batches, the state dicts sized by it, and
+    the float32 oracle's own error e32 per profile and output (recorded: the bound the kernels are held to is 4 e32 + 16 u)."""
+    cfg, C = P.config("c23"), P.classes("c23")
+    assert C == 23 and all(P.classes(n) == 15 for n in P.CONFIGS if n != "c23")
+    dm = O.Dims(cfg, C)
+    for prof in P.PROFILES:
+        sdn, _ = P.state_dict(prof, cfg, num_classes=C)
+        assert sdn["v_inference.2.weight"].shape == (C, dm.H) and sdn["ligand_atom_emb.weight"].shape == (dm.H, C + dm.temb)
+        bt = P.batch(prof, "c23")
+        assert set(bt["v"].tolist()) == set(range(C))
+        sd = O.state_dict_from_numpy(sdn)
+        r64, r32 = P.oracle_outputs(sd, dm, bt), P.oracle_outputs(sd, dm, bt, torch.float32)
+        assert np.array_equal(r32["nbr"], r64["nbr"]) and r64["pred_ligand_v"].shape[1] == C
+        e32 = {k: P.rel_err(r32[k], r64[k]) for k in r64 if k != "nbr"}
+        record("precision_cpu_e32", config="c23", profile=prof, **e32)
+        assert 0 < e32["pred_ligand_v"] < 64 * P.U and 0 < e32["pred_ligand_pos"] < 64 * P.U, e32

@@ -31,23 +31,23 @@ def golden(name):
 _cache = {}
 
 
-def oracle_model(seed=7, **overrides):
-    key = ("o", seed, json.dumps(overrides, sort_keys=True))
+def oracle_model(seed=7, num_classes=15, **overrides):
+    key = ("o", seed, num_classes, json.dumps(overrides, sort_keys=True))
     if key not in _cache:
         cfg = model_cfg(**overrides)
-        sdn = synth.synthetic_state_dict(cfg, seed=seed)
-        _cache[key] = (O.state_dict_from_numpy(sdn), O.Dims(cfg), cfg, sdn)
+        sdn = synth.synthetic_state_dict(cfg, seed=seed, num_classes=num_classes)
+        _cache[key] = (O.state_dict_from_numpy(sdn), O.Dims(cfg, num_classes), cfg, sdn)
     return _cache[key]
 
 
-def hip_model(seed=7, **overrides):
-    """ScorePosNet3D on cuda:0 with the synthetic weights of `seed`."""
-    key = ("h", seed, json.dumps(overrides, sort_keys=True))
+def hip_model(seed=7, num_classes=15, **overrides):
+    """ScorePosNet3D on cuda:0 with the synthetic weights of `seed` and `num_classes` atom types."""
+    key = ("h", seed, num_classes, json.dumps(overrides, sort_keys=True))
     if key not in _cache:
         import shapemol_amd
         cfg = model_cfg(**overrides)
-        m = shapemol_amd.ScorePosNet3D(cfg, 15)
-        sdn = synth.synthetic_state_dict(cfg, seed=seed)
+        m = shapemol_amd.ScorePosNet3D(cfg, num_classes)
+        sdn = synth.synthetic_state_dict(cfg, seed=seed, num_classes=num_classes)
         m.load_state_dict({k: torch.from_numpy(v) for k, v in sdn.items()}, strict=True)
         _cache[key] = m.to("cuda:0")
     return _cache[key]
