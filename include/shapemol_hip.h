@@ -214,6 +214,22 @@ int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t
 int shapemol_set_cfg(shapemol_ctx *ctx, double guide_stren, int32_t threshold_type, double p, const double *h_bounds,
                      float *d_pos_uncond_traj, float *d_v_uncond_traj);
 
+/* The same with one strength and one box per GROUP of molecules: group g is molecules [h_mol_off[g], h_mol_off[g + 1]) of the
+ * batches to come (HOST offsets, G + 1 of them: start at 0, do not decrease; _sample requires n_mols == h_mol_off[G]).  Per
+ * step and group, x = (1 + w_g) * cond - w_g * uncond with h_guide_stren[g] = w_g (HOST, finite), threshold_CFG with the
+ * statistic taken over THAT GROUP's elements only -- bit for bit the statistic of a one-group chain of the group's slice,
+ * whatever the other groups hold -- and the positions clamped into the group's box: h_bounds is HOST (G,3,2) float64 or NULL,
+ * a row that starts with NaN means no clamp for that group.  threshold_type and p are one per chain.  A group with w_g = 0
+ * consumes its raw conditional prediction: no threshold, no clamp (the reference's else branch).  At most 256 groups; more are
+ * refused, as are offsets or strengths that do not validate (the message names the group).  While a set is installed it takes the
+ * place of shapemol_set_cfg's scalars.  n_groups = 0, or every strength 0, removes the set: the chains are unguided.  The
+ * strengths, boxes and group boundaries live in device memory: a captured step depends on (n_atoms, n_mols, threshold_type, p,
+ * n_groups) only.  shapemol_debug_read "cfg_group_stat" gives the statistics of the last step of the last chain that ran with a set, (G,2) f32:
+ * positions | logits (also after the set has been removed). */
+int shapemol_set_cfg_groups(shapemol_ctx *ctx, int32_t n_groups, const int64_t *h_mol_off, const double *h_guide_stren,
+                            int32_t threshold_type, double p, const double *h_bounds, float *d_pos_uncond_traj,
+                            float *d_v_uncond_traj);
+
 /* Input validation happens on the device (no host synchronisation in _score/_sample): an unsorted or
  * out-of-range d_batch, an atom type outside [0, num_classes) or a time step outside [0, num_timesteps)
  * sets a sticky flag (the offending index is clamped, so nothing is read or written out of bounds).

@@ -21,7 +21,7 @@ EXPORTS = (
     "shapemol_set_guidance_groups", "shapemol_guide_points_groups",
     "shapemol_pointcloud_guidance", "shapemol_set_mesh_guidance", "shapemol_guide_points_mesh", "shapemol_mesh_guidance",
     "shapemol_set_mesh_guidance_groups", "shapemol_guide_points_mesh_groups",
-    "shapemol_set_cfg", "shapemol_set_knn_pins", "shapemol_debug_split_exact",
+    "shapemol_set_cfg", "shapemol_set_cfg_groups", "shapemol_set_knn_pins", "shapemol_debug_split_exact",
     "shapemol_mlp_backward_workspace", "shapemol_mlp_forward", "shapemol_mlp_backward",
     "shapemol_seg_attention_forward", "shapemol_seg_attention_backward",
     "shapemol_vn_backward_workspace", "shapemol_vn_forward", "shapemol_vn_backward",
@@ -53,6 +53,7 @@ class MeshGuidanceError(ShapeMolLibraryError, ValueError):
 
 # threshold_CFG's threshold_type -> the library's code (shapemol_set_cfg)
 CFG_THRESHOLDS = {None: 0, "reference_threshold": 1, "dynamic_threshold": 2, "rescale": 3}
+CFG_MAX_GROUPS = 256      # kCfgMaxGroups (csrc/sm_cfg.h): groups of one chain, shapemol_set_cfg_groups
 CFG_DEFAULT_P = {None: 0.0, "reference_threshold": 1.1, "dynamic_threshold": 0.995, "rescale": 0.7}
 
 ST_MESH = 6     # index of the mesh-guidance flag among the eight status flags (shapemol_status)
@@ -117,6 +118,7 @@ def load():
     lib.shapemol_set_mesh_guidance_groups.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.shapemol_guide_points_mesh_groups.argtypes = [vp, vp, vp, i64, vp, u64, vp]
     lib.shapemol_set_cfg.argtypes = [vp, C.c_double, i32, C.c_double, vp, vp, vp]
+    lib.shapemol_set_cfg_groups.argtypes = [vp, i32, vp, vp, i32, C.c_double, vp, vp, vp]
     lib.shapemol_mlp_backward_workspace.restype = C.c_size_t
     lib.shapemol_mlp_backward_workspace.argtypes = [i64, i32, i32, i32]
     lib.shapemol_mlp_forward.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]

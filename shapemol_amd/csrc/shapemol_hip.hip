@@ -57,6 +57,18 @@ struct MeshSet {      // one device block: [faces | face boxes | clouds | bounds
     int groups = 0, max_points = 0, grad_step = 0; int64_t mols = 0, nfaces = 0; bool whole = false; const double *draws = nullptr;
 };
 
+// Classifier-free guidance with one strength and one box per group of molecules (shapemol_set_cfg_groups; sm_cfg.h).  One device
+// block [rows G + 1 | stat G x 2 | histograms G x 2 x kCfgHistWords] that only grows, so a captured step keeps its addresses
+// from one set to the next; the tables that depend on the batch (molecule -> group, workgroups, partials) are workspace
+struct CfgGroupSet {
+    CfgGroup *rows = nullptr; float *stat = nullptr; unsigned *hist = nullptr; int cap = 0;
+    int groups = 0; int64_t mols = 0;
+    int last_groups = 0;                                         // groups of the last chain that ran with a set (debug_read "cfg_group_stat")
+    int type = 0; double p = 0.0;                                // threshold_CFG's type and p: one per chain
+    float *tr_pos_u = nullptr, *tr_v_u = nullptr;                // caller's uncond trajectories (or nullptr)
+    hipStream_t stream = nullptr; bool stream_set = false;      // the stream the last chain that read the rows ran on
+};
+
 }  // namespace
 
 struct shapemol_ctx {
@@ -134,6 +146,8 @@ struct shapemol_ctx {
     float *shape_zero = nullptr;      // [B][S][3] zeros (never written)
     ShapeTermArgs *prep_terms_u = nullptr; VnShapeArgs *prep_vn_u = nullptr;
     float *cfg_stat = nullptr; double *cfg_part = nullptr; unsigned *cfg_hist = nullptr;
+    CfgGroupSet cgs;            // per-group strengths and boxes (takes the place of the scalar form while installed)
+    int *cfg_mol_grp = nullptr; int2 *cfg_blk_tab = nullptr; double *cfg_gpart = nullptr; int64_t cfg_tab_stride = 0;
     int first_step = 0;         // option "first_step": the next chains start at reverse step first_step (t = T-1-first_step)
     // diagnostic: neighbour lists pinned at given (reverse step, atom) pairs (shapemol_set_knn_pins)
     int *pin_off = nullptr, *pin_atom = nullptr, *pin_nbr = nullptr; int64_t n_pins = 0; int pin_steps = 0, pin_k = 0;
@@ -150,8 +164,10 @@ struct shapemol_ctx {
     // (classifier-free guidance: its type and scalars are kernel arguments of the captured step)
     struct GraphKey { int64_t N = 0, B = 0; Guide guide = Guide::None; int fold = 0, gfuse = 0;
                       int cfg = 0 /* 0 off, else 1 + CfgType */; double cfgv[9] = {};   // w, p, has_bounds, box
+                      int cfg_groups = 0;     // groups of the per-group form (its strengths, boxes and layout live in device memory), else 0
                       bool operator==(const GraphKey &o) const {
-                          if (!(N == o.N && B == o.B && guide == o.guide && fold == o.fold && gfuse == o.gfuse && cfg == o.cfg)) return false;
+                          if (!(N == o.N && B == o.B && guide == o.guide && fold == o.fold && gfuse == o.gfuse && cfg == o.cfg &&
+                                cfg_groups == o.cfg_groups)) return false;
                           for (int i = 0; i < 9; ++i) if (cfgv[i] != o.cfgv[i]) return false;
                           return true;
                       } } gkey{};
@@ -225,6 +241,11 @@ int ensure_workspace(shapemol_ctx *c, int64_t N, int64_t B) {
         A(&c->shape_zero, (size_t)capB * g.shape_dim * 3) || A(&c->prep_terms_u, 2 * L + 1) || A(&c->prep_vn_u, L) ||
         A(&c->cfg_stat, 4) || A(&c->cfg_part, (size_t)2 * kCfgMaxBlocks * 4) || A(&c->cfg_hist, (size_t)2 * kCfgHistWords))
         return 1;
+    // per-group classifier-free guidance: workgroup tables and partials for the largest launch bound of this capacity
+    // (elements / 2048 + groups per tensor, cfg_group_blocks), molecule -> group
+    const int64_t stride = capN * std::max(g.num_classes, 3) / 2048 + kCfgMaxGroups + 1;
+    if (A(&c->cfg_mol_grp, capB) || A(&c->cfg_blk_tab, (size_t)2 * stride) || A(&c->cfg_gpart, (size_t)2 * stride * 4)) return 1;
+    c->cfg_tab_stride = stride;
     c->capN = capN; c->capB = capB;
     // argument blocks of the batched prep launches (they point into the workspace just allocated): the conditional set and
     // the unconditional one of classifier-free guidance
@@ -535,12 +556,24 @@ void swap_uncond(shapemol_ctx *c) {
     std::swap(c->prep_terms, c->prep_terms_u); std::swap(c->prep_vn, c->prep_vn_u);
 }
 
+// the launch bound of the per-group statistic kernels for a tensor of n elements: the sum over the groups of
+// min(kCfgMaxBlocks, max(1, ceil(n_g / 2048))) is at most n / 2048 + G
+int cfg_group_blocks(int64_t n, int n_groups) { return (int)(n / 2048 + n_groups); }
+
 CfgArgs cfg_args(const shapemol_ctx *c, int64_t N) {
     CfgArgs a{};
     a.on = chain_guide(c) == Guide::Cfg ? 1 : 0;
     if (!a.on) return a;
     const int C = c->cfg.num_classes;
     a.pos_c = c->pred_pos; a.pos_u = c->pred_pos_u; a.v_c = c->pred_v; a.v_u = c->pred_v_u;
+    if (c->cgs.groups > 0) {      // per group: strengths, boxes, ranges and ranks are the rows' (device memory)
+        a.pf = (float)c->cgs.p; a.qf = (float)(1.0 - c->cgs.p); a.type = c->cgs.type; a.n_atoms = (int)N; a.C = C;
+        a.stat = c->cgs.stat; a.part = c->cfg_gpart; a.hist = c->cgs.hist;
+        a.grp = c->cgs.rows; a.mol_grp = c->cfg_mol_grp; a.blk_tab = c->cfg_blk_tab;
+        a.n_groups = c->cgs.groups; a.tab_stride = (int)c->cfg_tab_stride;
+        for (int w = 0; w < 2; ++w) a.blocks[w] = cfg_group_blocks(N * (w ? C : 3), c->cgs.groups);
+        return a;
+    }
     a.w1 = (float)(1.0 + c->cfg_w); a.w = (float)c->cfg_w; a.pf = (float)c->cfg_p; a.qf = (float)(1.0 - c->cfg_p);
     for (int k = 0; k < 3; ++k) { a.lo[k] = c->cfg_lo[k]; a.hi[k] = c->cfg_hi[k]; }
     a.has_bounds = c->cfg_has_bounds; a.type = c->cfg_type; a.n_atoms = (int)N; a.C = C;
@@ -572,7 +605,7 @@ int run_cfg_stats(shapemol_ctx *c, hipStream_t s, const CfgArgs &a) {
     } else {
         return 0;        // no threshold: the combine and the clamp need no statistic
     }
-    LAUNCH("cfg_stat", SMK(cfg_finalize_kernel, dim3(2), dim3(256), 0, s, a));
+    LAUNCH("cfg_stat", SMK(cfg_finalize_kernel, dim3(2, a.grp ? a.n_groups : 1), dim3(256), 0, s, a));
     return 0;
 }
 
@@ -976,6 +1009,7 @@ void shapemol_destroy(shapemol_ctx *c) {
     cloud_set_clear(c->cs);
     mesh_set_clear(c->ms);
     if (c->wg_table) hipFree(c->wg_table);
+    if (c->cgs.rows) hipFree(c->cgs.rows);
     if (c->m_within) hipFree(c->m_within);
     if (c->bn_run) hipFree(c->bn_run);
     if (c->bn_eval_acc) hipFree(c->bn_eval_acc);
@@ -1043,6 +1077,8 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
         return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the mesh guidance groups cover " + std::to_string(c->ms.mols) + " molecules");
     if (c->cs.groups > 0 && !c->cs.whole && c->cs.mols != B)
         return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the guidance groups cover " + std::to_string(c->cs.mols) + " molecules");
+    if (c->cgs.groups > 0 && c->cgs.mols != B)
+        return fail("shapemol_sample: n_mols = " + std::to_string(B) + " but the classifier-free guidance groups cover " + std::to_string(c->cgs.mols) + " molecules");
     if (kind == Guide::Cloud && groups_table(c, s, c->cs.whole ? nullptr : d_batch, N, c->cs.ints, c->cs.groups)) return 1;
     if (mesh && groups_table(c, s, c->ms.whole ? nullptr : d_batch, N, c->ms.ints, c->ms.groups)) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
@@ -1054,6 +1090,13 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
         swap_uncond(c);
         if (rc) return 1;
         HIPCHK(hipMemsetAsync(c->cfg_hist, 0, (size_t)2 * kCfgHistWords * sizeof(unsigned), s));
+        if (c->cgs.groups > 0) {      // the groups' element ranges, workgroups and ranks, from the batch vector (once per chain)
+            const CfgArgs ca = cfg_args(c, N);
+            HIPCHK(hipMemsetAsync(c->cgs.hist, 0, (size_t)c->cgs.groups * 2 * kCfgHistWords * sizeof(unsigned), s));
+            LAUNCH("prep", SMK(cfg_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, ca.C, ca.n_groups, (int)B, ca.pf, c->cgs.rows,
+                               c->cfg_mol_grp, c->cfg_blk_tab, ca.tab_stride, ca.blocks[0], ca.blocks[1]));
+            c->cgs.stream = s; c->cgs.stream_set = true; c->cgs.last_groups = c->cgs.groups;
+        }
     }
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_init_v, (int)N, c->cfg.num_classes, c->status));
     {
@@ -1061,7 +1104,8 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
         cp.seed = seed; cp.eps = d_eps; cp.u = d_u; cp.step_base = c->first_step; cp.guide_draws = mesh ? c->ms.draws : c->cs.draws;
         if (traj) { cp.tr_pos = traj->pos_traj; cp.tr_v = traj->v_traj; cp.tr_v0 = traj->v0_traj; cp.tr_vt = traj->vt_traj;
                     cp.tr_pos_cond = traj->pos_cond_traj; cp.tr_v_cond = traj->v_cond_traj; }
-        if (cfg) { cp.tr_pos_uncond = c->cfg_tr_pos_u; cp.tr_v_uncond = c->cfg_tr_v_u; }
+        if (cfg && c->cgs.groups > 0) { cp.tr_pos_uncond = c->cgs.tr_pos_u; cp.tr_v_uncond = c->cgs.tr_v_u; }
+        else if (cfg) { cp.tr_pos_uncond = c->cfg_tr_pos_u; cp.tr_v_uncond = c->cfg_tr_v_u; }
         LAUNCH("prep", SMK(set_chain_params_kernel, dim3(1), dim3(1), 0, s, c->chain_params, cp, c->steps));
     }
     HIPCHK(hipMemcpyAsync(c->x_state, d_init_pos, N * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1083,7 +1127,9 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
         shapemol_ctx::GraphKey key{};
         key.N = N; key.B = B; key.guide = kind; key.fold = vn_fold_ok(c, (int)N);
         key.gfuse = c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && c->n_pins == 0;
-        if (cfg) {
+        if (cfg && c->cgs.groups > 0) {
+            key.cfg = 1 + c->cgs.type; key.cfg_groups = c->cgs.groups; key.cfgv[1] = c->cgs.p;
+        } else if (cfg) {
             key.cfg = 1 + c->cfg_type;
             const double v[9] = {c->cfg_w, c->cfg_p, (double)c->cfg_has_bounds, c->cfg_lo[0], c->cfg_lo[1], c->cfg_lo[2], c->cfg_hi[0], c->cfg_hi[1], c->cfg_hi[2]};
             std::copy(v, v + 9, key.cfgv);
@@ -1208,6 +1254,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     else if (k == "vn_err") { src = c->status + ST_VN_BARRIER; bytes = 4; }
     else if (k == "mesh_group_flags") { src = c->m_cnt ? c->m_cnt + 4 * c->m_cnt_cap : nullptr; bytes = (size_t)c->m_flag_groups * 4; }
     else if (k == "cfg_stat") { src = c->cfg_stat; bytes = 2 * 4; }
+    else if (k == "cfg_group_stat") { src = c->cgs.last_groups > 0 ? c->cgs.stat : nullptr; bytes = (size_t)c->cgs.last_groups * 2 * 4; }
     else if (k == "bnstat") { src = c->bn_acc; bytes = (size_t)g.num_layers * kBnReplicas * 2 * g.n_heads * 8; }
     else { fail("shapemol_debug_read: unknown buffer " + k); return -1; }
     if (!src || bytes > max_bytes) { fail("shapemol_debug_read: buffer unavailable or destination too small"); return -1; }
@@ -1256,6 +1303,59 @@ int shapemol_set_cfg(shapemol_ctx *c, double guide_stren, int32_t threshold_type
     }
     c->cfg_tr_pos_u = guide_stren != 0.0 ? d_pos_uncond_traj : nullptr;
     c->cfg_tr_v_u = guide_stren != 0.0 ? d_v_uncond_traj : nullptr;
+    return 0;
+}
+
+int shapemol_set_cfg_groups(shapemol_ctx *c, int32_t n_groups, const int64_t *h_mol_off, const double *h_guide_stren, int32_t threshold_type,
+                            double p, const double *h_bounds, float *d_pos_uncond_traj, float *d_v_uncond_traj) {
+    const std::string me = "shapemol_set_cfg_groups: ";
+    if (!c) return fail(me + "null ctx");
+    if (n_groups < 0) return fail(me + "n_groups < 0");
+    if (n_groups > kCfgMaxGroups) return fail(me + std::to_string(n_groups) + " groups, at most " + std::to_string(kCfgMaxGroups) + " per chain");
+    bool any = false;
+    if (n_groups > 0) {
+        if (!h_mol_off || !h_guide_stren) return fail(me + "offsets / strengths missing");
+        if (threshold_type < CFG_NONE || threshold_type > CFG_RESCALE || !(p == p)) return fail(me + "bad threshold type or p");
+        if (h_mol_off[0] != 0) return fail(me + "group 0: the molecule offsets must start at 0");
+        for (int g = 0; g < n_groups; ++g) {
+            const std::string grp = me + "group " + std::to_string(g) + ": ";
+            if (h_mol_off[g + 1] < h_mol_off[g]) return fail(grp + "the molecule offsets decrease");
+            if (!std::isfinite(h_guide_stren[g])) return fail(grp + "the guidance strength is not finite");
+            any = any || h_guide_stren[g] != 0.0;
+        }
+        if (h_mol_off[n_groups] > (1 << 27)) return fail(me + "too many molecules");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    CfgGroupSet &gs = c->cgs;
+    gs.groups = 0; gs.mols = 0; gs.type = 0; gs.p = 0.0; gs.tr_pos_u = gs.tr_v_u = nullptr;
+    if (!any) return 0;        // no group, or every strength 0: the unguided chain
+    std::vector<CfgGroup> rows((size_t)n_groups + 1, CfgGroup{});
+    for (int g = 0; g <= n_groups; ++g) rows[g].mol0 = (int)h_mol_off[g];
+    for (int g = 0; g < n_groups; ++g) {
+        CfgGroup &r = rows[g];
+        const double w = h_guide_stren[g];
+        r.w1 = (float)(1.0 + w); r.w = (float)w;
+        r.type = w != 0.0 ? threshold_type : CFG_NONE;
+        const double *b = h_bounds ? h_bounds + (size_t)g * 6 : nullptr;
+        r.has_box = w != 0.0 && b && b[0] == b[0];      // (a NaN row: no clamp for this group)
+        for (int k = 0; k < 3; ++k) { r.lo[k] = r.has_box ? (float)b[2 * k] : 0.f; r.hi[k] = r.has_box ? (float)b[2 * k + 1] : 0.f; }
+    }
+    // a chain that reads the rows may still be running: wait for it before they are overwritten (or their block replaced)
+    if (gs.stream_set && hipStreamSynchronize(gs.stream) != hipSuccess) hipDeviceSynchronize();
+    if (n_groups > gs.cap) {
+        c->drop_graphs();                        // the captured steps point into the old block
+        HIPCHK(hipDeviceSynchronize());
+        if (gs.rows) { hipFree(gs.rows); gs.rows = nullptr; gs.stat = nullptr; gs.hist = nullptr; gs.cap = 0; gs.last_groups = 0; }
+        const size_t rb = ((size_t)(n_groups + 1) * sizeof(CfgGroup) + 255) / 256 * 256, sb = ((size_t)n_groups * 2 * sizeof(float) + 255) / 256 * 256;
+        unsigned char *blk = nullptr;
+        HIPCHK(hipMalloc((void **)&blk, rb + sb + (size_t)n_groups * 2 * kCfgHistWords * sizeof(unsigned)));
+        gs.rows = reinterpret_cast<CfgGroup *>(blk); gs.stat = reinterpret_cast<float *>(blk + rb); gs.hist = reinterpret_cast<unsigned *>(blk + rb + sb);
+        gs.cap = n_groups;
+    }
+    HIPCHK(hipMemcpy(gs.rows, rows.data(), rows.size() * sizeof(CfgGroup), hipMemcpyHostToDevice));
+    gs.groups = n_groups; gs.mols = h_mol_off[n_groups];
+    gs.type = threshold_type; gs.p = threshold_type != CFG_NONE ? p : 0.0;
+    gs.tr_pos_u = d_pos_uncond_traj; gs.tr_v_u = d_v_uncond_traj;
     return 0;
 }
 

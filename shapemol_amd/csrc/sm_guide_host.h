@@ -15,7 +15,7 @@ namespace {
 Guide chain_guide(const shapemol_ctx *c) {
     if (c->ms.nfaces > 0) return Guide::Mesh;
     if (c->cs.points > 0) return Guide::Cloud;
-    return c->cfg_w != 0.0 ? Guide::Cfg : Guide::None;
+    return c->cfg_w != 0.0 || c->cgs.groups > 0 ? Guide::Cfg : Guide::None;
 }
 
 // workgroups of the guidance kernels (16 atoms x 16 lanes each, every workgroup within one group): the sum over the groups of

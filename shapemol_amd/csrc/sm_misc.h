@@ -799,6 +799,22 @@ __global__ void ddpm_step_kernel(DdpmArgs aa, CfgArgs cfg) {
         const int C = a.C;
         const int t = a.t_first - step;
         const size_t so = (size_t)(step - a.step_base) * a.n_atoms + i;
+        // ---- classifier-free guidance: the predicted position combined, thresholded and clamped with the values of the atom's group
+        // (or of the whole batch); the trajectories keep the raw predictions.  Done first, while few values are live, and parked
+        // in LDS until the position update below: held in registers across the noise generation, the kernel's widest part, the
+        // three values cost a wave of occupancy
+        __shared__ float cfg_pred[3][128];               // (launched with 128 threads)
+        const int mol = cfg.on ? a.mol_of[i] : 0;
+        if (cfg.on) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float pp = a.pred_pos[i * 3 + k], pu = cfg.pos_u[i * 3 + k];
+                if (a.tr_pos_cond) a.tr_pos_cond[so * 3 + k] = pp;
+                if (a.tr_pos_uncond) a.tr_pos_uncond[so * 3 + k] = pu;
+                const CfgLane gl = cfg_lane(cfg, mol, k);
+                cfg_pred[k][threadIdx.x] = cfg_apply(cfg, gl, cfg_combine(gl.w1, gl.w, pp, pu), gl.stat_pos, true);
+            }
+        }
         float e3[3], uu[MAXC];
         if (a.eps) {
 #pragma unroll
@@ -822,13 +838,7 @@ __global__ void ddpm_step_kernel(DdpmArgs aa, CfgArgs cfg) {
         const float sig = t != 0 ? expf(0.5f * a.logvar[t]) : 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            float pp = a.pred_pos[i * 3 + k];
-            if (cfg.on) {      // combine, threshold, clamp; the trajectories keep the raw predictions
-                const float pu = cfg.pos_u[i * 3 + k];
-                if (a.tr_pos_cond) a.tr_pos_cond[so * 3 + k] = pp;
-                if (a.tr_pos_uncond) a.tr_pos_uncond[so * 3 + k] = pu;
-                pp = cfg_apply(cfg, cfg_combine(cfg, pp, pu), cfg.stat[0], k);
-            }
+            const float pp = cfg.on ? cfg_pred[k][threadIdx.x] : a.pred_pos[i * 3 + k];
             const float xn = (c0 * pp + ct * a.x_t[i * 3 + k]) + sig * e3[k];
             a.x_next[i * 3 + k] = xn;
             if (a.tr_pos) a.tr_pos[so * 3 + k] = xn;
@@ -837,13 +847,15 @@ __global__ void ddpm_step_kernel(DdpmArgs aa, CfgArgs cfg) {
         // ---- atom types
         float lg[MAXC];
         float mx = -INFINITY;
+        CfgLane gl{};
+        if (cfg.on) gl = cfg_lane(cfg, mol, 0);
         for (int c = 0; c < C; ++c) {
             lg[c] = a.pred_v[(size_t)i * C + c];
             if (cfg.on) {
                 const float lu = cfg.v_u[(size_t)i * C + c];
                 if (a.tr_v_cond) a.tr_v_cond[so * C + c] = lg[c];
                 if (a.tr_v_uncond) a.tr_v_uncond[so * C + c] = lu;
-                lg[c] = cfg_apply(cfg, cfg_combine(cfg, lg[c], lu), cfg.stat[1], -1);
+                lg[c] = cfg_apply(cfg, gl, cfg_combine(gl.w1, gl.w, lg[c], lu), gl.stat_v, false);
             }
             mx = fmaxf(mx, lg[c]);
         }
@@ -961,6 +973,9 @@ __global__ void __launch_bounds__(256) ddpm_step16_kernel(DdpmArgs aa, CfgArgs c
             if (atom_ok) a.vf.pred_out[i * 3 + c] = pp_fold;
         }
     }
+    // classifier-free guidance: the values of the atom's group (or of the whole batch); lanes 0..2 read their side of the box
+    CfgLane gl{};
+    if (cfg.on) gl = cfg_lane(cfg, a.mol_of[i], c < 3 ? c : 0);
     // ---- positions (lanes 0..2)
     if (c < 3) {
         float pp = a.vf.enable ? pp_fold : a.pred_pos[i * 3 + c];
@@ -968,7 +983,7 @@ __global__ void __launch_bounds__(256) ddpm_step16_kernel(DdpmArgs aa, CfgArgs c
             const float pu = cfg.pos_u[i * 3 + c];
             if (atom_ok && a.tr_pos_cond) a.tr_pos_cond[so * 3 + c] = pp;
             if (atom_ok && a.tr_pos_uncond) a.tr_pos_uncond[so * 3 + c] = pu;
-            pp = cfg_apply(cfg, cfg_combine(cfg, pp, pu), cfg.stat[0], c);
+            pp = cfg_apply(cfg, gl, cfg_combine(gl.w1, gl.w, pp, pu), gl.stat_pos, true);
         }
         const float sig = t != 0 ? expf(0.5f * a.logvar[t]) : 0.f;
         const float xn = (a.c0[t] * pp + a.ct[t] * a.x_t[i * 3 + c]) + sig * eps;
@@ -984,7 +999,7 @@ __global__ void __launch_bounds__(256) ddpm_step16_kernel(DdpmArgs aa, CfgArgs c
         const float lu = cfg.v_u[(size_t)i * C + c];
         if (atom_ok && a.tr_v_cond) a.tr_v_cond[so * C + c] = lg;
         if (atom_ok && a.tr_v_uncond) a.tr_v_uncond[so * C + c] = lu;
-        lg = cfg_apply(cfg, cfg_combine(cfg, lg, lu), cfg.stat[1], -1);
+        lg = cfg_apply(cfg, gl, cfg_combine(gl.w1, gl.w, lg, lu), gl.stat_v, false);
     }
     const float mx = seg_max<16>(lg);
     const float se = seg_sum<16>(cls ? expf(lg - mx) : 0.f);

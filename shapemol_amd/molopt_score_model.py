@@ -423,6 +423,15 @@ class ScorePosNet3D(nn.Module):
         per-batch box: a (B,3,2) tensor or array of which only ``bounds[0]`` clamps every atom, as there, or a single (3,2) box;
         ``bounds=None`` means no clamp (an extension: the reference's ``bounds[0]`` raises there).  Mesh or point-cloud guidance,
         when given, take precedence and the chain is not CFG-guided, as in the reference's ``if / elif``.
+        ``guide_stren`` may also be a LIST with one entry per group of molecules, in batch order: ``[(guide_stren, n_mols), ...]``
+        -- per step, the next ``n_mols`` molecules are combined with that strength, thresholded with the statistic of THAT GROUP's
+        elements only (what ``threshold_CFG`` computes in a batch that holds the group alone) and clamped into the group's box;
+        the counts must sum to the number of molecules (``ValueError`` otherwise).  ``threshold_type`` / ``threshold_args`` are
+        one per chain.  ``bounds`` is then the reference's per-molecule (B,3,2) tensor, of which each group is clamped by the row
+        of its FIRST molecule (``bounds[0]`` of that condition's own batch), or one (3,2) box for all groups, or None.  A group
+        with strength 0 consumes its raw conditional prediction (no threshold, no clamp); with every strength 0 the chain is
+        the unguided one.  ``pos_uncond_traj`` / ``v_uncond_traj`` hold the unconditional predictions of all atoms, groups of
+        strength 0 included.  At most 256 groups.  Mesh or point-cloud guidance, when given, still win.
         Private to shapemol_amd.sampling: ``_slot`` picks one of the model's library contexts (own workspace and captured
         graphs), ``_async=True`` returns a handle right after the chain has been enqueued; its ``.result()`` waits and
         builds the dict (chains on different slots then run side by side, and a finished chain's trajectories are
@@ -439,7 +448,13 @@ class ScorePosNet3D(nn.Module):
             groups = _guidance_groups(use_pointcloud_data, int(ligand_shape.shape[0]))
         elif isinstance(use_mesh_data, list):        # (with a single point cloud beside: the mesh wins, the reference's if / elif)
             mesh_groups = _mesh_guidance_groups(use_mesh_data, int(ligand_shape.shape[0]))
-        if self.cond_mask_prob == 0:
+        cfg_groups = None
+        if isinstance(guide_stren, list):
+            cfg_groups = _cfg_groups(guide_stren, bounds, int(ligand_shape.shape[0]))
+            if self.cond_mask_prob == 0:
+                assert not cfg_groups[1].any()
+            guide_stren = float(np.abs(cfg_groups[1]).max()) if cfg_groups[1].any() else 0.0      # (> 0: some group is guided)
+        elif self.cond_mask_prob == 0:
             assert guide_stren == 0
         # classifier-free guidance: the reference's branch order (:561-642) -- mesh, point cloud, then CFG
         cfg = use_mesh_data is None and use_pointcloud_data is None and (self.cond_mask_prob or 0) > 0 and guide_stren > 0.0
@@ -452,7 +467,7 @@ class ScorePosNet3D(nn.Module):
                 cfg_p = float((threshold_args or {}).get("p", _lib.CFG_DEFAULT_P[threshold_type]))
             if threshold_type == "dynamic_threshold" and not 0.0 <= cfg_p <= 1.0:
                 raise RuntimeError(f"quantile() q must be in the range [0, 1] but got {cfg_p}")     # torch.quantile's check
-            if bounds is not None:
+            if bounds is not None and cfg_groups is None:
                 bx = bounds.detach().cpu().numpy() if isinstance(bounds, torch.Tensor) else np.asarray(bounds)
                 bx = np.asarray(bx, dtype=np.float64)
                 if bx.ndim == 3:
@@ -538,7 +553,14 @@ class ScorePosNet3D(nn.Module):
                 side.wait_stream(cur)
                 if first_step:
                     _lib.check(lib.shapemol_set_option(ctx, b"first_step", int(first_step)), "shapemol_set_option")
-                if cfg:
+                if cfg and cfg_groups is not None:
+                    off, stren, boxes = cfg_groups
+                    _lib.check(lib.shapemol_set_cfg_groups(ctx, len(stren), off.ctypes.data_as(C.c_void_p), stren.ctypes.data_as(C.c_void_p),
+                                                           _lib.CFG_THRESHOLDS[threshold_type], cfg_p,
+                                                           None if boxes is None else boxes.ctypes.data_as(C.c_void_p),
+                                                           _ptr(bufs.get("pos_uncond_traj")), _ptr(bufs.get("v_uncond_traj"))),
+                               "shapemol_set_cfg_groups")
+                elif cfg:
                     _lib.check(lib.shapemol_set_cfg(ctx, float(guide_stren), _lib.CFG_THRESHOLDS[threshold_type], cfg_p,
                                                     None if cfg_box is None else cfg_box.ctypes.data_as(C.c_void_p),
                                                     _ptr(bufs.get("pos_uncond_traj")), _ptr(bufs.get("v_uncond_traj"))),
@@ -550,7 +572,9 @@ class ScorePosNet3D(nn.Module):
                 finally:
                     if first_step:
                         lib.shapemol_set_option(ctx, b"first_step", 0)
-                    if cfg:      # read when the chain is enqueued: the context goes back to unguided chains at once
+                    if cfg and cfg_groups is not None:      # (the rows stay in device memory for the chain in flight)
+                        lib.shapemol_set_cfg_groups(ctx, 0, None, None, 0, 0.0, None, None, None)
+                    elif cfg:    # read when the chain is enqueued: the context goes back to unguided chains at once
                         lib.shapemol_set_cfg(ctx, 0.0, 0, 0.0, None, None, None)
                 pending.side, pending.cur = side, cur
             _lib.check(rc, "shapemol_sample")
@@ -744,6 +768,43 @@ def pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=3, ratio=0
                                                       _stream_ptr(torch.cuda.current_stream(pos.device)))
     _lib.check(rc, "shapemol_pointcloud_guidance")
     return pred_ligand_pos
+
+
+def _cfg_groups(entries, bounds, n_mols):
+    """The list form of classifier-free guidance, ``[(guide_stren, n_mols), ...]`` with ``bounds`` (B,3,2), (3,2) or None, as the
+    arrays shapemol_set_cfg_groups takes: molecule offsets (G+1) int64, strengths (G) float64 and boxes (G,3,2) float64 or None
+    (each group's box is the row of its first molecule; a group without molecules gets a NaN row: no clamp).  Host logic only."""
+    if not entries:
+        raise ValueError("guide_stren: the list of groups is empty")
+    off, stren = [0], []
+    for i, e in enumerate(entries):
+        if not isinstance(e, (tuple, list)) or len(e) != 2:
+            raise ValueError(f"guide_stren[{i}] must be (guide_stren, n_mols)")
+        w, cnt = float(e[0]), int(e[1])
+        if cnt < 0:
+            raise ValueError(f"guide_stren[{i}]: n_mols must be >= 0")
+        if not np.isfinite(w):
+            raise ValueError(f"guide_stren[{i}]: the guidance strength must be finite")
+        stren.append(w)
+        off.append(off[-1] + cnt)
+    if off[-1] != n_mols:
+        raise ValueError(f"guide_stren: the groups hold {off[-1]} molecules, the batch has {n_mols}")
+    if len(stren) > _lib.CFG_MAX_GROUPS:
+        raise ValueError(f"guide_stren: {len(stren)} groups, a chain takes at most {_lib.CFG_MAX_GROUPS}")
+    boxes = None
+    if bounds is not None:
+        bx = bounds.detach().cpu().numpy() if isinstance(bounds, torch.Tensor) else np.asarray(bounds)
+        bx = np.asarray(bx, dtype=np.float64)
+        if bx.shape == (3, 2):
+            boxes = np.ascontiguousarray(np.broadcast_to(bx, (len(stren), 3, 2)))
+        elif bx.shape == (n_mols, 3, 2):
+            boxes = np.full((len(stren), 3, 2), np.nan)
+            for g in range(len(stren)):
+                if off[g + 1] > off[g]:
+                    boxes[g] = bx[off[g]]
+        else:
+            raise ValueError("bounds must be a (B, 3, 2) or (3, 2) box")
+    return np.asarray(off, dtype=np.int64), np.asarray(stren, dtype=np.float64), boxes
 
 
 def _guidance_groups(entries, n_mols):

@@ -354,9 +354,52 @@ def guidance_groups(kind, data, segs):
     return "use_pointcloud_data", [(None, None, None, n) if data[c] is None else (data[c][0], None, data[c][2], n) for c, _f, n in segs]
 
 
+def plan_cfg(kind, data, guide_stren, bounds, n_conditions):
+    """Classifier-free guidance of a job of :func:`sample_diffusion_ligand_multi`: per condition its strength and its (3,2)
+    float64 box or None, from one value or one per condition each -- or ``(None, None)`` when no condition is CFG-guided.
+    ``kind`` / ``data`` are :func:`plan_guidance`'s.  In a job guided by meshes or clouds a condition that carries one ignores
+    CFG (the reference's ``if / elif``) and the chains are not CFG-guided, so a condition WITHOUT a mesh or cloud but with
+    ``guide_stren > 0`` cannot be served there: ``ValueError``.  Host logic only."""
+    strens = [float(w or 0) for w in _per_condition(guide_stren, n_conditions, "guide_stren")]
+    boxes = _per_condition(bounds, n_conditions, "bounds")
+    for i, w in enumerate(strens):
+        if not np.isfinite(w):
+            raise ValueError(f"guide_stren: condition {i}: the guidance strength must be finite")
+    for i, b in enumerate(boxes):
+        if b is not None:
+            b = np.asarray(b.detach().cpu().numpy() if torch.is_tensor(b) else b, dtype=np.float64)
+            if b.shape != (3, 2):
+                raise ValueError(f"bounds: condition {i}: a (3, 2) box or None, got shape {b.shape}")
+            boxes[i] = b
+    if kind is not None:
+        for i, w in enumerate(strens):
+            if data[i] is None and w > 0:
+                raise ValueError(f"sample_diffusion_ligand_multi: condition {i} has guide_stren > 0 but no mesh or point cloud, in a "
+                                 f"job guided by {'meshes' if kind == 'mesh' else 'point clouds'}: such a chain cannot guide it by "
+                                 "classifier-free guidance -- run it as two jobs")
+        return None, None
+    if not any(w != 0 for w in strens):
+        return None, None
+    return strens, boxes
+
+
+def cfg_groups(strens, boxes, segs):
+    """The classifier-free guidance keywords of one batch of :func:`plan_batches` for ``sample_diffusion``: ``guide_stren`` as
+    the list ``[(strength, n_mols), ...]`` of the batch's segments and ``bounds`` (B,3,2) with every molecule's condition's box
+    (NaN rows: no clamp), or None when no condition of the job has a box.  ``{}`` when the job is not CFG-guided."""
+    if strens is None:
+        return {}
+    kw = {"guide_stren": [(strens[c], n) for c, _f, n in segs], "bounds": None}
+    if any(b is not None for b in boxes):
+        nan = np.full((3, 2), np.nan)
+        kw["bounds"] = np.concatenate([np.broadcast_to(nan if boxes[c] is None else boxes[c], (n, 3, 2)) for c, _f, n in segs])
+    return kw
+
+
 def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256, device="cuda:0", num_steps=None,
                                   center_pos_mode="none", sample_func=None, sample_num_atoms="prior", ref_num_atoms=None,
-                                  seed=None, use_graph=True, host_rng=False, grad_step=1000):
+                                  seed=None, use_graph=True, host_rng=False, grad_step=1000, guide_stren=0,
+                                  threshold_type=None, threshold_args=None, bounds=None):
     """``sample_diffusion_ligand`` for MANY shape conditions at once: ``num_samples`` molecules for each of ``conditions``, with
     molecules of different conditions sharing the chains.
 
@@ -373,6 +416,15 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
                      batch, in batch order.
     seed, host_rng, use_graph, grad_step, num_steps, center_pos_mode   as for :func:`sample_diffusion_ligand`; the initial
                      coordinates, the initial types and (``host_rng``) the chain's noise are drawn per batch, as there.
+    guide_stren, threshold_type, threshold_args, bounds   classifier-free guidance, as for :func:`sample_diffusion_ligand`.
+                     ``guide_stren`` and ``bounds`` are one value for all conditions or a list / tuple with one per condition; a
+                     condition's ``bounds`` is ONE (3,2) box (an array, not nested lists) or None (no clamp).  ``threshold_type`` and
+                     ``threshold_args`` are one per job.  Every batch runs with its conditions as groups (``sample_diffusion`` with a
+                     list ``guide_stren``): the threshold statistic of a condition spans that condition's molecules IN THE BATCH.
+                     A condition that straddles two batches therefore gets its statistic per batch segment -- as in the reference,
+                     whose statistic spans one batch of its ``batch_size``.  In a job guided by meshes or clouds a condition that
+                     carries one ignores CFG, as in the reference; a condition there without a mesh or cloud but with
+                     ``guide_stren > 0`` raises ``ValueError`` before any chain runs (run it as two jobs).
 
     Semantics of a mixed batch.  With the module in train mode -- what the reference's sampling script runs -- the VN batch-norm
     takes its statistics over the whole batch, so a mixed batch is not the same computation as one batch per condition, exactly as
@@ -383,7 +435,7 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
     With mesh conditions, a condition whose molecules run short of atoms inside its mesh in some step (fewer than 3: the
     reference's KD-tree error) fails the whole batch it shares: ``MeshGuidanceError`` names the group, i.e. the position of
     the condition among the batch's conditions (:func:`plan_batches`), and no condition of that batch gets its molecules.
-    Not covered: ``pos_only``, classifier-free guidance, and meshes mixed with clouds in one job; use
+    Not covered: ``pos_only`` and meshes mixed with clouds in one job; use
     :func:`sample_diffusion_ligand` per condition for those.
 
     Returns a list with, per condition, the reference's 9-tuple in the layout :func:`sample_diffusion_ligand` returns;
@@ -395,6 +447,8 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
     n_cond = len(conditions)
     shapes = [torch.as_tensor(c[0], dtype=torch.float32).reshape(1, -1) for c in conditions]
     kind, gdata = plan_guidance(conditions)
+    cfg_strens, cfg_boxes = plan_cfg(kind, gdata, guide_stren, bounds, n_cond)
+    cfg_kw = {} if cfg_strens is None else {"threshold_type": threshold_type, "threshold_args": threshold_args}
     funcs = _per_condition(sample_func, n_cond, "sample_func")
     refs = _per_condition(ref_num_atoms, n_cond, "ref_num_atoms")
     keys = ("pos", "v", "pos_traj", "v_traj", "v0_traj", "vt_traj", "time", "pos_cond_traj", "v_cond_traj")     # the 9-tuple's order
@@ -412,6 +466,7 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
         noise_kw = {"noise": _host_noise(model, num_steps, all_ligand_atoms, dev, True)} if host_rng else {}
         gkey, groups = guidance_groups(kind, gdata, segs)
         guide_kw = {gkey: groups} if gkey else {}
+        guide_kw.update(cfg_kw, **cfg_groups(cfg_strens, cfg_boxes, segs))
         r = model.sample_diffusion(
             init_ligand_pos=init_ligand_pos, init_ligand_v=init_ligand_v, batch_ligand=batch_ligand,
             ligand_shape=torch.cat([shapes[c].repeat(n, 1) for c, _f, n in segs]).to(dev), num_steps=num_steps,
