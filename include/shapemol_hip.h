@@ -270,8 +270,23 @@ size_t shapemol_se_weight_count(int32_t hidden_dim, int32_t latent_dim, int32_t 
 int shapemol_se_create(int32_t hidden_dim, int32_t latent_dim, int32_t layer_num, int32_t num_k, const float *weights,
                        size_t n_weights, int device, shapemol_se_ctx **out);
 void shapemol_se_destroy(shapemol_se_ctx *ctx);
-/* d_points (B,N,3) f32 DEVICE, N a multiple of 16; d_out (B,latent_dim,3) f32 DEVICE. */
+/* d_points (B,N,3) f32 DEVICE; d_out (B,latent_dim,3) f32 DEVICE.  1 <= B <= 65535, B*N <= 2^24, and N a multiple of 16 in
+ * [32, shapemol_se_max_points(ctx)]: the kNN needs N >= num_k = 20, and keeps the 16 x N distances of a row block in LDS, so the
+ * largest N is the device's dynamic LDS per workgroup / 64 bytes, read from the device at creation (2560 where a workgroup can have
+ * 160 KiB).  Anything else is refused with a message before any allocation or launch. */
 int shapemol_se_encode(shapemol_se_ctx *ctx, const float *d_points, int64_t n_shapes, int64_t n_points, float *d_out, void *stream);
+int64_t shapemol_se_max_points(const shapemol_se_ctx *ctx);
+/* Diagnostics (tests only).  _debug_read copies one workspace buffer of the last _encode to HOST memory after a device synchronise;
+ * n_bytes must be the buffer's exact size for the last encode's P = B*N points:
+ *   SHAPEMOL_SE_IDX (P,20) i32 neighbours inside the shape, SHAPEMOL_SE_H0 (P,C,3) f32 conv_pos output, SHAPEMOL_SE_HCAT (P,L,C,3) f32
+ *   the blocks' outputs, SHAPEMOL_SE_Y (P,4C,3) f32 the per-point products [Yf1|Yf2|Yd1|Yd2], SHAPEMOL_SE_XX (P) f32 squared feature norms,
+ *   SHAPEMOL_SE_PD (P,latent_dim+1,3) f32 conv_c products and the shared direction.
+ * idx, y and xx are overwritten by each block: _debug_stop_after(ctx, l) makes the following encodes return after block l (0: after
+ * conv_pos, so idx is conv_pos's; l: blocks 0..l-1 have run, idx / xx / y are those of block l-1 and hcat holds slices 0..l-1),
+ * without touching d_out; -1 restores the full encode. */
+enum { SHAPEMOL_SE_IDX = 0, SHAPEMOL_SE_H0 = 1, SHAPEMOL_SE_HCAT = 2, SHAPEMOL_SE_Y = 3, SHAPEMOL_SE_XX = 4, SHAPEMOL_SE_PD = 5 };
+int shapemol_se_debug_stop_after(shapemol_se_ctx *ctx, int32_t n_blocks);
+int shapemol_se_debug_read(shapemol_se_ctx *ctx, int32_t what, void *h_dst, size_t n_bytes);
 
 /* ---- training building blocks (the operators of a layer, forward and backward) ---------------
  * The MLP block of models/common.py:47-67 -- y = W2 relu(LayerNorm(W1 x + b1)) + b2, eps 1e-5, affine LayerNorm -- forward

@@ -28,6 +28,7 @@ EXPORTS = (
     "shapemol_edge_mlp_backward_workspace", "shapemol_edge_mlp_forward", "shapemol_edge_mlp_backward",
     "shapemol_set_bn_running",
     "shapemol_se_weight_count", "shapemol_se_create", "shapemol_se_destroy", "shapemol_se_encode",
+    "shapemol_se_max_points", "shapemol_se_debug_stop_after", "shapemol_se_debug_read",
 )
 
 
@@ -139,6 +140,10 @@ def load():
     lib.shapemol_se_destroy.argtypes = [vp]
     lib.shapemol_se_destroy.restype = None
     lib.shapemol_se_encode.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.shapemol_se_max_points.argtypes = [vp]
+    lib.shapemol_se_max_points.restype = i64
+    lib.shapemol_se_debug_stop_after.argtypes = [vp, i32]
+    lib.shapemol_se_debug_read.argtypes = [vp, i32, vp, C.c_size_t]
     lib.shapemol_profile_begin.argtypes = [vp]
     lib.shapemol_profile_end.argtypes = [vp, vp, vp, vp, C.c_int]
     if lib.shapemol_abi_version() != ABI_VERSION:

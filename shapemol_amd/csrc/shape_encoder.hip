@@ -21,6 +21,9 @@ constexpr int kC = 128;           // hidden_dim of the shipped shape auto-encode
 
 struct shapemol_se_ctx {
     int C = kC, LAT = 32, L = 4, device = 0;
+    int lds_limit = 0, max_n = 0;   // largest dynamic LDS of a workgroup on the device; largest N whose 16 x N d2 rows fit in it
+    int stop_after = -1;            // shapemol_se_debug_stop_after
+    int64_t lastP = 0;              // points of the last encode (shapemol_se_debug_read)
     float *d_w = nullptr;
     size_t o_pos_wf = 0, o_pos_g = 0, o_pos_b = 0, o_pos_wd = 0, o_c_wf = 0, o_c_g = 0, o_c_b = 0, o_c_wd = 0;
     std::vector<size_t> o_img, o_g, o_b;
@@ -49,8 +52,13 @@ int shapemol_se_create(int32_t hidden_dim, int32_t latent_dim, int32_t layer_num
     SECHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return se_fail("shapemol_se_create: no such HIP device");
     SECHK(hipSetDevice(device));
+    // se_knn_kernel keeps the 16 x N distances of its row block in dynamic LDS: the device's limit per workgroup bounds N
+    int lds = 0;
+    SECHK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    const int max_n = lds / (16 * (int)sizeof(float)) / 16 * 16;
+    if (max_n < 32) return se_fail("shapemol_se_create: the device has less than 2 KB of LDS per workgroup");
     auto *c = new shapemol_se_ctx();
-    c->LAT = latent_dim; c->L = layer_num; c->device = device;
+    c->LAT = latent_dim; c->L = layer_num; c->device = device; c->lds_limit = lds; c->max_n = max_n;
     const int C = kC;
     std::vector<float> img;
     auto put = [&](const float *src, size_t n) { const size_t o = (img.size() + 63) & ~size_t(63); img.resize(o + n); std::memcpy(&img[o], src, n * 4); return o; };
@@ -102,7 +110,10 @@ void shapemol_se_destroy(shapemol_se_ctx *c) {
 
 int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int64_t N, float *d_out, void *stream) {
     if (!c || !d_points || !d_out) return se_fail("shapemol_se_encode: null argument");
-    if (B < 1 || N < kSeK || (N % 16) != 0 || N > 8192 || B * N > (1 << 24)) return se_fail("shapemol_se_encode: need B >= 1, N a multiple of 16 in [32, 8192]");
+    if (B < 1 || B > 65535 || N < 32 || (N % 16) != 0 || N > c->max_n || B * N > (1 << 24))
+        return se_fail("shapemol_se_encode: need 1 <= B <= 65535, N a multiple of 16 in [32, " + std::to_string(c->max_n) + "] (16 * N * 4 bytes of the " +
+                       std::to_string(c->lds_limit) + " bytes of LDS a workgroup can have on this device) and B * N <= 2^24; got B = " +
+                       std::to_string(B) + ", N = " + std::to_string(N));
     SECHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int C = c->C, L = c->L, LAT = c->LAT;
@@ -116,9 +127,11 @@ int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int
         SECHK(hipMalloc((void **)&c->acc, (size_t)kSeReplicas * 2 * 256 * 8));
         c->capP = P;
     }
-    const size_t knn_lds = (size_t)16 * N * sizeof(float);
+    c->lastP = P;
+    const size_t knn_lds = (size_t)16 * N * sizeof(float);      // <= lds_limit (N <= max_n)
     SECHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
     SECHK(hipFuncSetAttribute((const void *)se_knn_kernel<3 * kC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
+    const int n_blocks = c->stop_after < 0 ? L : (c->stop_after < L ? c->stop_after : L);
     const float *W = c->d_w;
     const dim3 knn_grid((unsigned)(N / 16), (unsigned)B);
     // conv_pos on the raw points
@@ -130,7 +143,7 @@ int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int
     hipLaunchKernelGGL(se_edge_stats_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
     hipLaunchKernelGGL(se_edge_apply_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
     // DGCNN blocks
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < n_blocks; ++l) {
         const float *hin = l == 0 ? c->h0 : c->hcat + (size_t)(l - 1) * 3 * C;
         const int ld = l == 0 ? 3 * C : L * 3 * C;
         hipLaunchKernelGGL(se_sqnorm_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s, hin, (int)P, 3 * C, ld, c->xx);
@@ -143,12 +156,43 @@ int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int
         hipLaunchKernelGGL(se_edge_stats_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
         hipLaunchKernelGGL(se_edge_apply_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
     }
+    if (c->stop_after >= 0) { SECHK(hipGetLastError()); return 0; }
     // conv_c + mean over the points
     SeHeadArgs ha{c->hcat, W + c->o_c_wf, W + c->o_c_wd, W + c->o_c_g, W + c->o_c_b, c->pd, c->acc, d_out, (int)P, (int)N, L * C, LAT};
     SECHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
     hipLaunchKernelGGL(se_head_linear_kernel, dim3((unsigned)((P * (LAT + 1) + 3) / 4)), dim3(256), 0, s, ha);
     hipLaunchKernelGGL(se_head_apply_kernel, dim3((unsigned)(B * LAT)), dim3(256), 0, s, ha);
     SECHK(hipGetLastError());
+    return 0;
+}
+
+int64_t shapemol_se_max_points(const shapemol_se_ctx *c) { return c ? c->max_n : 0; }
+
+int shapemol_se_debug_stop_after(shapemol_se_ctx *c, int32_t n_blocks) {
+    if (!c) return se_fail("shapemol_se_debug_stop_after: null argument");
+    if (n_blocks < -1 || n_blocks > c->L) return se_fail("shapemol_se_debug_stop_after: n_blocks must be -1 (off) or in [0, layer_num]");
+    c->stop_after = n_blocks;
+    return 0;
+}
+
+int shapemol_se_debug_read(shapemol_se_ctx *c, int32_t what, void *h_dst, size_t n_bytes) {
+    if (!c || !h_dst) return se_fail("shapemol_se_debug_read: null argument");
+    if (c->lastP == 0) return se_fail("shapemol_se_debug_read: no shapemol_se_encode has run on this context");
+    const size_t P = (size_t)c->lastP, C = c->C, L = c->L, LAT = c->LAT;
+    const void *src = nullptr; size_t need = 0;
+    switch (what) {
+        case SHAPEMOL_SE_IDX:  src = c->idx;  need = P * kSeK * 4; break;
+        case SHAPEMOL_SE_H0:   src = c->h0;   need = P * C * 3 * 4; break;
+        case SHAPEMOL_SE_HCAT: src = c->hcat; need = P * L * C * 3 * 4; break;
+        case SHAPEMOL_SE_Y:    src = c->y;    need = P * 4 * C * 3 * 4; break;
+        case SHAPEMOL_SE_XX:   src = c->xx;   need = P * 4; break;
+        case SHAPEMOL_SE_PD:   src = c->pd;   need = P * (LAT + 1) * 3 * 4; break;
+        default: return se_fail("shapemol_se_debug_read: what must be one of SHAPEMOL_SE_IDX .. SHAPEMOL_SE_PD (0 .. 5), got " + std::to_string(what));
+    }
+    if (n_bytes != need) return se_fail("shapemol_se_debug_read: buffer " + std::to_string(what) + " of the last encode has " + std::to_string(need) + " bytes, n_bytes is " + std::to_string(n_bytes));
+    SECHK(hipSetDevice(c->device));
+    SECHK(hipDeviceSynchronize());
+    SECHK(hipMemcpy(h_dst, src, need, hipMemcpyDeviceToHost));
     return 0;
 }
 

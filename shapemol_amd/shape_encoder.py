@@ -72,9 +72,38 @@ class VN_DGCNN_Encoder(nn.Module):
         except Exception:
             pass
 
+    def max_points(self, device):
+        """Largest N the library accepts on `device` (shapemol_se_max_points)."""
+        with torch.cuda.device(device):
+            return int(_lib.load().shapemol_se_max_points(self._context(torch.device(device))))
+
+    # ---- diagnostics (tests/test_gpu_shape_encoder.py) ----
+    _DEBUG = {"idx": (0, np.int32), "h0": (1, np.float32), "hcat": (2, np.float32), "y": (3, np.float32), "xx": (4, np.float32),
+              "pd": (5, np.float32)}
+
+    def debug_stop_after(self, device, n_blocks):
+        """Following forwards return after block `n_blocks` (0: after conv_pos; -1: full encode again), leaving the output unset."""
+        _lib.check(_lib.load().shapemol_se_debug_stop_after(self._context(torch.device(device)), n_blocks), "shapemol_se_debug_stop_after")
+
+    def debug_read(self, device, name, n_total):
+        """Workspace buffer `name` of the last forward on `device` (n_total = B * N points of it) as a numpy array
+        (shapemol_se_debug_read): idx (P, k), h0 (P, C, 3), hcat (P, L, C, 3), y (P, 4C, 3), xx (P,), pd (P, latent + 1, 3)."""
+        code, dt = self._DEBUG[name]
+        C_, L, LAT = self.hidden_dim, self.layer_num, self.latent_dim
+        shape = {"idx": (n_total, self.num_k), "h0": (n_total, C_, 3), "hcat": (n_total, L, C_, 3), "y": (n_total, 4 * C_, 3), "xx": (n_total,),
+                 "pd": (n_total, LAT + 1, 3)}[name]
+        a = np.empty(shape, dt)
+        _lib.check(_lib.load().shapemol_se_debug_read(self._context(torch.device(device)), code, a.ctypes.data_as(C.c_void_p), a.nbytes),
+                   "shapemol_se_debug_read")
+        return a
+
     @torch.no_grad()
     def forward(self, input):
-        """input (B, 1, N, 3) (or (B, N, 3)) float32 device tensor -> latent (B, latent_dim, 3)."""
+        """input (B, 1, N, 3) (or (B, N, 3)) float32 device tensor -> latent (B, latent_dim, 3).
+
+        1 <= B <= 65535, B * N <= 2^24, and N a multiple of 16 in [32, ``max_points(device)``]: the kNN needs N >= num_k = 20 and
+        keeps the 16 x N distances of a row block in LDS, so the largest N is the device's dynamic LDS per workgroup / 64 bytes
+        (2560 where a workgroup can have 160 KiB).  Anything else raises ShapeMolLibraryError before any launch."""
         if not isinstance(input, torch.Tensor) or not input.is_cuda:
             raise RuntimeError("input must be a tensor on a HIP device (shapemol_amd has no CPU path)")
         x = input.reshape(input.shape[0], -1, 3).to(torch.float32).contiguous()
