@@ -429,6 +429,10 @@ void shapemol_debug_split_exact(float x, uint16_t *pieces);
  *        (intact after an evaluation with stop_layer = 1),
  *        "att" (N,H), "o3" (N,48), "bnstat" (L,16,2,heads) f64, "dims" (8,) i64,
  *        "captures" (1,) i64 hipGraph captures of this context so far,
+ *        "launch" (8,) i64 the launch forms the most recent score evaluation chose (host memory, no synchronise): {chain step?,
+ *        fused kNN graph + edge-weight kernel, a coordinate update folded into an x2h kernel, the last one folded into the
+ *        posterior kernel, x2h attention + node stage in one launch, streaming edge kernels' tiles per workgroup, their grid
+ *        (0, 0 on the other edge kernels), CUs}; after a graph replay: the decisions taken when that step was captured,
  *        "mesh_group_flags" (G,) i32: per group of the last chain / pass with mesh groups, the steps in which the group was
  *        left unguided for want of within-atoms (status flag 6 says that some group was, this says which and how often).
  * Returns the number of bytes written, or -1. */

@@ -158,6 +158,10 @@ struct shapemol_ctx {
     // graph cache
     hipGraphExec_t gexec = nullptr, gexec_u = nullptr;     // one step / kGraphUnroll steps
     int64_t n_captures = 0;                                // graph captures so far (debug_read "captures")
+    // the launch forms the most recent run_score chose (debug_read "launch"): {sampling, fused graph kernel, a coordinate update
+    // folded into an x2h kernel, the last one folded into the DDPM kernel, x2h_chain16_kernel used, streaming kernels' tiles per
+    // workgroup, their grid (0, 0 on the other edge kernels), CUs}; graph_rec: those of the captured step, which a replay reports
+    int64_t launch_rec[8] = {}, graph_rec[8] = {};
     // the captured step depends on the batch geometry only: seed, noise and trajectory pointers live in chain_params
     // what a captured step depends on besides the options (which drop the graphs when set): sizes, guidance, and the two
     // launch decisions taken from the max_mol_atoms hint (folded coordinate update, fused graph kernel)
@@ -754,6 +758,10 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
     }
     // (chains only: the hint is set for the batch of a chain; a score evaluation on other data must not trust a stale one)
     const bool graph_fused = sampling && c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && KP <= 32 && c->n_pins == 0;
+    int64_t (&rec)[8] = c->launch_rec;
+    std::fill(rec, rec + 8, 0);
+    rec[0] = sampling; rec[1] = graph_fused; rec[7] = c->num_cu;
+    if (c->edge_bf16 == 2 && nlay > 0) { rec[5] = stream_chunk(c, n); rec[6] = (stream_jobs(c, n) + rec[5] - 1) / rec[5]; }
     if (reuse_graph) {
     } else if (graph_fused) {
         GraphArgs ga{x_in, c->mol_span, n, g.knn, KP, c->nbr, c->P(c->dm.ew.w1), c->P(c->dm.ew.b1), c->P(c->dm.ew.g), c->P(c->dm.ew.be),
@@ -846,7 +854,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                 na.lin_img16 = c->P(Dl.lin16_img); na.add_mol = c->addp + (size_t)l * c->capB * 8 * H; na.mol_of = c->mol_of;
                 na.pre_out = c->preAB; na.n_lin_tiles = lin_tiles; na.ld_add = 8 * H; na.ld_out = 8 * H;
             }
-            if (xc_fused) { if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
+            if (xc_fused) { rec[4] = 1; if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
             else if (c->chain_bf16 && c->node_f16 && c->feat_f16) LAUNCH("node_chain", SMK((node_chain16_kernel<H, true>), dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
             else if (c->chain_bf16 && c->node_f16) LAUNCH("node_chain", SMK(node_chain16_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
             else if (c->chain_bf16) LAUNCH("node_chain", SMK(node_chain6_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain6Lds<H>::BYTES, s, na));
@@ -863,6 +871,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
             const H2xPlan plan = h2x_plan(c, l, fold, has_next, half_tiles, stat_acc, cur_x, x_next, out_pos);
             pending = plan.pending; stats_done = plan.stats_done; vn_done = plan.vn_done;
             if (plan.ddpm.enable) c->ddpm_vf = plan.ddpm;
+            rec[2] |= plan.pending.enable; rec[3] |= plan.ddpm.enable;
             if (f16) {
                 Edge16Args ea{};
                 ea.image_k = c->P(Dl.i16_kh); ea.image_v = c->P(Dl.i16_vh);
@@ -1155,12 +1164,14 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
             c->drop_graphs();
             if (capture(1, &c->gexec)) return 1;
             c->gkey = key;
+            std::copy(c->launch_rec, c->launch_rec + 8, c->graph_rec);
         }
         // both executables are built at the first capture, whatever this chain's length: a short warm-up chain then leaves
         // nothing to capture inside a later, timed chain
         if (!c->gexec_u && capture(kGraphUnroll, &c->gexec_u)) return 1;
         int st = 0;
         c->gstream = s; c->gstream_set = true;
+        std::copy(c->graph_rec, c->graph_rec + 8, c->launch_rec);      // a replay takes the decisions of its capture
         for (; st + kGraphUnroll <= num_steps; st += kGraphUnroll) HIPCHK(hipGraphLaunch(c->gexec_u, s));
         for (; st < num_steps; ++st) HIPCHK(hipGraphLaunch(c->gexec, s));
     } else {
@@ -1237,6 +1248,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     int64_t dims[8] = {N, c->lastB, c->KP, g.hidden_dim, g.n_heads, g.num_layers, c->capN, c->capB};
     if (k == "dims") { if (max_bytes < sizeof(dims)) return -1; std::memcpy(dst, dims, sizeof(dims)); return sizeof(dims); }
     if (k == "captures") { if (max_bytes < 8) return -1; std::memcpy(dst, &c->n_captures, 8); return 8; }
+    if (k == "launch") { if (max_bytes < sizeof(c->launch_rec)) return -1; std::memcpy(dst, c->launch_rec, sizeof(c->launch_rec)); return sizeof(c->launch_rec); }
     if (k == "nbr") { src = c->nbr; bytes = N * c->KP * 4; }
     else if (k == "ew") { src = c->ew; bytes = N * c->KP * 4; }
     else if (k == "h") { src = c->last_h; bytes = N * g.hidden_dim * 4; }

@@ -1002,22 +1002,32 @@ def test_fp16_range_guard_of_the_node_kernels():
     assert torch.isfinite(out["pred_ligand_h"]).all()
 
 
-def test_fused_launches_equal_separate_launches():
+def test_fused_launches_equal_separate_launches(mode):
     """The fused launches of a step (kNN graph + edge weights: graph_kernel; x2h attention + node stage:
     x2h_chain16_kernel) run the same arithmetic in the same order as the kernels they replace: a chain with them is
     bit-identical to a chain without; the last layer's coordinate update inside the DDPM kernel equals the separate launch
-    to rounding."""
-    m = hip("f16x2")
-    for B, seed, rng in ((48, 9, None), (10, 4, (40, 80))):      # MOSES-size molecules; larger ones (two candidate chunks per lane)
-        bb = synth.synthetic_batch(B, seed=seed, atoms_range=rng)
+    to rounding.  Both precision modes (x2h_chain16_kernel exists in f16x2 only: compared where the library's launch record
+    says it ran)."""
+    import chain_forms as CF
+    m = hip(mode)
+    batches = [(synth.synthetic_batch(48, seed=9), 9),                                # MOSES-size molecules
+               (synth.synthetic_batch(10, seed=4, atoms_range=(40, 80)), 4),         # larger ones (two candidate chunks per lane)
+               (CF.batch(CF.graph_counts(8), 5), 5)]                                  # every chunk edge up to the 128-atom cap, odd N
+    for bb, seed in batches:
         eps, u = hash_noise(len(bb["batch"]), 6, seed)
         r1 = _chain(m, bb["init_pos"], bb["init_v"], bb["batch"], bb["shape"], 6, eps, u)
+        rec = dict(zip(CF.LAUNCH, m.debug_read("launch", (8,), np.int64).tolist()))
+        assert rec["sampling"] == 1 and rec["graph_fused"] == 1 and rec["x2h_chain"] == (1 if mode == "f16x2" else 0), rec
         for opt in ("graph_fuse", "x2h_chain", "ddpm_fold"):
+            if opt == "x2h_chain" and not rec["x2h_chain"]:
+                continue
             try:
                 m.set_option(opt, 0)
                 r0 = _chain(m, bb["init_pos"], bb["init_v"], bb["batch"], bb["shape"], 6, eps, u)
+                rec0 = dict(zip(CF.LAUNCH, m.debug_read("launch", (8,), np.int64).tolist()))
             finally:
                 m.set_option(opt, 1)
+            assert rec0[{"graph_fuse": "graph_fused", "x2h_chain": "x2h_chain", "ddpm_fold": "ddpm_fold"}[opt]] == 0, (opt, rec0)
             if opt == "ddpm_fold":      # the last layer's update sums the channels in a tree instead of in sequence: equal to rounding
                 assert torch.equal(r1["v"], r0["v"]) and maxabs(r1["pos"], r0["pos"]) < 2e-5, opt
                 assert maxabs(torch.stack(r1["pos_cond_traj"]), torch.stack(r0["pos_cond_traj"])) < 2e-5, opt
