@@ -288,6 +288,38 @@ enum { SHAPEMOL_SE_IDX = 0, SHAPEMOL_SE_H0 = 1, SHAPEMOL_SE_HCAT = 2, SHAPEMOL_S
 int shapemol_se_debug_stop_after(shapemol_se_ctx *ctx, int32_t n_blocks);
 int shapemol_se_debug_read(shapemol_se_ctx *ctx, int32_t what, void *h_dst, size_t n_bytes);
 
+/* ---- shape decoder: the auto-encoder's implicit field --------------------------------------------------------------
+ * DecoderInner.forward (models/shape_pointcloud_modelAE.py:21-103, blocks: ResnetBlockFC, models/shape_vn_layers.py:210-252):
+ * the signed distance (SHAPEMOL_SD_SIGNEDDIST, no output activation) or occupancy (SHAPEMOL_SD_OCCUPANCY, sigmoid) that a
+ * shape latent z (latent,3) encodes, at query points.  ReLU activations (PointCloud_AE never sets `leaky`).  hidden 128,
+ * latent 1..256, layer_num 1..8; anything else, or a wrong weight count, is refused with a message that names the limit.
+ * weights (HOST, float32, shapemol_sd_weight_count of them): z_in.map_to_feat (latent,latent); fc_in weight (H,2*latent+1),
+ * bias (H); per block {fc_0 weight (H,H), bias (H), fc_1 weight (H,H), bias (H)}; fc_out weight (H), bias (1). */
+typedef struct shapemol_sd_ctx shapemol_sd_ctx;
+enum { SHAPEMOL_SD_SIGNEDDIST = 0, SHAPEMOL_SD_OCCUPANCY = 1 };
+size_t shapemol_sd_weight_count(int32_t hidden, int32_t latent, int32_t layer_num);
+int shapemol_sd_create(int32_t hidden, int32_t latent, int32_t layer_num, int32_t loss_type, const float *weights,
+                       size_t n_weights, int device, shapemol_sd_ctx **out);
+void shapemol_sd_destroy(shapemol_sd_ctx *ctx);
+/* d_p (n_points,3) f32, d_z (n_shapes,latent,3) f32, d_out (n_points) f32, all DEVICE.  The shape of point i is
+ * d_shape_of[i] (int32 DEVICE, any order; clamped into [0, n_shapes) by the kernel -- validate it before the call), or,
+ * with d_shape_of null, i / points_per_shape (then n_points must be n_shapes * points_per_shape).  A point's result does
+ * not depend on the other points of the call.  n_shapes in 1..65535 and n_points < 2^31, else refused with a message
+ * before any allocation or launch; n_points == 0 returns 0 without a launch.
+ * A context holds the per-shape workspace (z_inv, G, c) that every decode rewrites: use it from one stream at a time (order
+ * decodes on different streams with events), or create one context per stream.  The first decode with more shapes than any
+ * before it grows that workspace, which synchronises the device once. */
+int shapemol_sd_decode(shapemol_sd_ctx *ctx, const float *d_p, const int32_t *d_shape_of, int64_t n_points,
+                       int64_t points_per_shape, const float *d_z, int64_t n_shapes, float *d_out, void *stream);
+/* Points a workgroup of the decode kernel takes per iteration (tests derive their edge shapes from it). */
+int64_t shapemol_sd_tile(const shapemol_sd_ctx *ctx);
+/* Diagnostics (tests only): the per-shape prologue of the last _decode, copied to HOST memory after a device synchronise;
+ * n_bytes must be the exact size for its B = n_shapes: SHAPEMOL_SD_ZINV (B,latent) f32 z_inv = sum_xyz z * z_in(z),
+ * SHAPEMOL_SD_G (B,H,3) f32 G = W_z z and SHAPEMOL_SD_C (B,H) f32 c = W_inv z_inv + bias of the factored fc_in
+ * fc_in(feature) = w_0 |p|^2 + G p + c. */
+enum { SHAPEMOL_SD_ZINV = 0, SHAPEMOL_SD_G = 1, SHAPEMOL_SD_C = 2 };
+int shapemol_sd_debug_read(shapemol_sd_ctx *ctx, int32_t what, void *h_dst, size_t n_bytes);
+
 /* ---- training building blocks (the operators of a layer, forward and backward) ---------------
  * The MLP block of models/common.py:47-67 -- y = W2 relu(LayerNorm(W1 x + b1)) + b2, eps 1e-5, affine LayerNorm -- forward
  * with the quantities its backward needs, and the backward: what torch.autograd does for the 58 MLPs of one score

@@ -29,6 +29,8 @@ EXPORTS = (
     "shapemol_set_bn_running",
     "shapemol_se_weight_count", "shapemol_se_create", "shapemol_se_destroy", "shapemol_se_encode",
     "shapemol_se_max_points", "shapemol_se_debug_stop_after", "shapemol_se_debug_read",
+    "shapemol_sd_weight_count", "shapemol_sd_create", "shapemol_sd_destroy", "shapemol_sd_decode",
+    "shapemol_sd_tile", "shapemol_sd_debug_read",
 )
 
 
@@ -144,6 +146,15 @@ def load():
     lib.shapemol_se_max_points.restype = i64
     lib.shapemol_se_debug_stop_after.argtypes = [vp, i32]
     lib.shapemol_se_debug_read.argtypes = [vp, i32, vp, C.c_size_t]
+    lib.shapemol_sd_weight_count.restype = C.c_size_t
+    lib.shapemol_sd_weight_count.argtypes = [i32, i32, i32]
+    lib.shapemol_sd_create.argtypes = [i32, i32, i32, i32, vp, C.c_size_t, C.c_int, C.POINTER(vp)]
+    lib.shapemol_sd_destroy.argtypes = [vp]
+    lib.shapemol_sd_destroy.restype = None
+    lib.shapemol_sd_decode.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp]
+    lib.shapemol_sd_tile.argtypes = [vp]
+    lib.shapemol_sd_tile.restype = i64
+    lib.shapemol_sd_debug_read.argtypes = [vp, i32, vp, C.c_size_t]
     lib.shapemol_profile_begin.argtypes = [vp]
     lib.shapemol_profile_end.argtypes = [vp, vp, vp, vp, C.c_int]
     if lib.shapemol_abi_version() != ABI_VERSION:

@@ -1,0 +1,213 @@
+"""Drop-in for the reference's shape auto-encoder ``PointCloud_AE`` and its decoder ``DecoderInner``
+(``models/shape_pointcloud_modelAE.py:21-150``): the implicit field -- signed distance or occupancy -- that a shape latent
+``z (Z, 3)`` encodes, evaluated at query points.  ``utils/shape.py:226-238`` builds the auto-encoder and the sampling script
+passes it on as ``shape_AE``.
+
+``DecoderInner`` has the reference's constructor arguments and forward contract (``p (B, T, 3), z (B, Z, 3) -> (B, T)``; ReLU
+activations: ``PointCloud_AE`` never sets ``leaky``).  State-dict keys follow the reference for ``z_in``, ``fc_in`` and
+``fc_out``; the residual blocks are registered here as ``blocks.{i}.fc_0.*`` / ``fc_1.*`` -- in the reference they live in a
+plain Python list, so they are neither saved in ``se_model.pt`` nor moved by ``.to()``: loading that checkpoint
+with ``strict=False`` leaves them at their initial values, exactly as the reference leaves them at random initial values.
+All arithmetic runs in libshapemol_hip.so (``shapemol_sd_*``, hand-written HIP); there is no CPU path and no backward.
+A module owns one library context whose per-shape workspace every call rewrites: calls of one module on different streams must
+be ordered by the caller (events or a synchronise); the first call with more shapes than any before it synchronises the device.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .shape_encoder import VN_DGCNN_Encoder
+
+__all__ = ["DecoderInner", "PointCloud_AE"]
+
+
+class _VNLinear(nn.Module):
+    """Parameter container with the reference's names (models/shape_vn_layers.py:VNLinear)."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.map_to_feat = nn.Linear(cin, cout, bias=False)
+
+
+class _ResnetBlockFC(nn.Module):
+    """Parameter container of models/shape_vn_layers.py:210-252 with size_in == size_out (no shortcut); fc_1.weight starts at
+    zero, as there."""
+
+    def __init__(self, size):
+        super().__init__()
+        self.fc_0 = nn.Linear(size, size)
+        self.fc_1 = nn.Linear(size, size)
+        nn.init.zeros_(self.fc_1.weight)
+
+
+class DecoderInner(nn.Module):
+    def __init__(self, dim=3, z_dim=128, hidden_size=128, layer_num=4, loss_type="occupancy"):
+        super().__init__()
+        if dim != 3:
+            raise ValueError("DecoderInner: dim must be 3")
+        self.z_dim, self.hidden_size, self.layer_num, self.loss_type = z_dim, hidden_size, layer_num, loss_type
+        self.z_in = _VNLinear(z_dim, z_dim)
+        self.fc_in = nn.Linear(2 * z_dim + 1, hidden_size)
+        self.blocks = nn.ModuleList([_ResnetBlockFC(hidden_size) for _ in range(layer_num)])
+        self.fc_out = nn.Linear(hidden_size, 1)
+        self._ctx, self._key = None, None
+
+    def _pack(self):
+        parts = [self.z_in.map_to_feat.weight, self.fc_in.weight, self.fc_in.bias]
+        for b in self.blocks:
+            parts += [b.fc_0.weight, b.fc_0.bias, b.fc_1.weight, b.fc_1.bias]
+        parts += [self.fc_out.weight, self.fc_out.bias]
+        return np.concatenate([p.detach().cpu().numpy().astype(np.float32).reshape(-1) for p in parts])
+
+    def _context(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"{device} is not a HIP device (shapemol_amd has no CPU path)")
+        if device.index is None:                           # 'cuda' and 'cuda:<current>' are one context
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (str(device), self.loss_type) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self._ctx is not None and key == self._key:
+            return self._ctx
+        lib = _lib.load()
+        self._release()
+        w = self._pack()
+        ctx = C.c_void_p()
+        idx = device.index
+        _lib.check(lib.shapemol_sd_create(self.hidden_size, self.z_dim, self.layer_num, 1 if self.loss_type == "occupancy" else 0,
+                                          w.ctypes.data_as(C.c_void_p), w.size, idx, C.byref(ctx)), "shapemol_sd_create")
+        self._ctx, self._key = ctx, key
+        return ctx
+
+    def _release(self):
+        if getattr(self, "_ctx", None) is not None:
+            _lib.load().shapemol_sd_destroy(self._ctx)
+            self._ctx = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def tile(self, device):
+        """Points a workgroup of the decode kernel takes per iteration (shapemol_sd_tile)."""
+        with torch.cuda.device(device):
+            return int(_lib.load().shapemol_sd_tile(self._context(device)))
+
+    # ---- diagnostics (tests/test_gpu_shape_decoder.py) ----
+    _DEBUG = {"z_inv": 0, "G": 1, "c": 2}
+
+    def debug_read(self, device, name, n_shapes):
+        """The per-shape prologue of the last decode on `device` as a numpy array (shapemol_sd_debug_read): z_inv (B, Z),
+        G (B, H, 3), c (B, H) of fc_in(feature) = w_0 |p|^2 + G p + c."""
+        shape = {"z_inv": (n_shapes, self.z_dim), "G": (n_shapes, self.hidden_size, 3), "c": (n_shapes, self.hidden_size)}[name]
+        a = np.empty(shape, np.float32)
+        _lib.check(_lib.load().shapemol_sd_debug_read(self._context(device), self._DEBUG[name], a.ctypes.data_as(C.c_void_p), a.nbytes),
+                   "shapemol_sd_debug_read")
+        return a
+
+    def _decode(self, p, shape_of, per_shape, z):
+        dev = p.device
+        n, b = p.shape[0], z.shape[0]
+        out = torch.empty((n,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.load().shapemol_sd_decode(self._context(dev), C.c_void_p(p.data_ptr()), C.c_void_p(shape_of.data_ptr()) if shape_of is not None else None,
+                                                n, per_shape, C.c_void_p(z.data_ptr()), b, C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, "shapemol_sd_decode")
+        return out
+
+    def _latent(self, z, dev):
+        if not isinstance(z, torch.Tensor) or not z.is_cuda:
+            raise RuntimeError("z must be a tensor on a HIP device (shapemol_amd has no CPU path)")
+        if z.device != dev:
+            raise RuntimeError(f"z is on {z.device}, the points are on {dev}")
+        z = z.reshape(z.shape[0], -1, 3).to(torch.float32).contiguous()
+        if z.shape[1] != self.z_dim:
+            raise ValueError(f"z has {z.shape[1]} latent vectors per shape, the decoder was built for z_dim = {self.z_dim}")
+        return z
+
+    @torch.no_grad()
+    def forward(self, p, z, c=None, **kwargs):
+        """p (B, T, 3), z (B, Z, 3) (or (B, 3 Z)) float32 device tensors -> (B, T): the field of shape b at its T points.
+        1 <= B <= 65535 and B * T < 2^31, else ShapeMolLibraryError before any launch; T == 0 gives an empty tensor."""
+        if not isinstance(p, torch.Tensor) or not p.is_cuda:
+            raise RuntimeError("p must be a tensor on a HIP device (shapemol_amd has no CPU path)")
+        if p.dim() != 3 or p.shape[2] != 3:
+            raise ValueError(f"p must be (B, T, 3), got {tuple(p.shape)}")
+        z = self._latent(z, p.device)
+        if z.shape[0] != p.shape[0]:
+            raise ValueError(f"p has {p.shape[0]} shapes, z has {z.shape[0]}")
+        b, t = p.shape[0], p.shape[1]
+        x = p.to(torch.float32).contiguous().view(b * t, 3)
+        return self._decode(x, None, t, z).view(b, t)
+
+    @torch.no_grad()
+    def decode_atoms(self, pos, batch, z):
+        """The field of shape batch[i] at pos[i]: pos (N, 3) float32, batch (N,) integer in [0, B) in any order, z (B, Z, 3)
+        -> (N,).  The natural use: the signed distance or occupancy of every generated atom under its molecule's shape
+        condition.  An entry of batch outside [0, B) raises ValueError (checked with device ops before the call)."""
+        if not isinstance(pos, torch.Tensor) or not pos.is_cuda or not isinstance(batch, torch.Tensor) or not batch.is_cuda:
+            raise RuntimeError("pos and batch must be tensors on a HIP device (shapemol_amd has no CPU path)")
+        if pos.dim() != 2 or pos.shape[1] != 3 or batch.dim() != 1 or batch.shape[0] != pos.shape[0]:
+            raise ValueError(f"pos must be (N, 3) and batch (N,), got {tuple(pos.shape)} and {tuple(batch.shape)}")
+        if batch.dtype.is_floating_point or batch.dtype == torch.bool:
+            raise ValueError("batch must be an integer tensor")
+        z = self._latent(z, pos.device)
+        n, b = pos.shape[0], z.shape[0]
+        if n and bool(((batch < 0) | (batch >= b)).any()):
+            raise ValueError(f"batch must lie in [0, {b}) (the number of shapes in z); got values from {int(batch.min())} to {int(batch.max())}")
+        return self._decode(pos.to(torch.float32).contiguous(), batch.to(torch.int32).contiguous(), 0, z)
+
+
+def _get(config, name):
+    return config[name] if isinstance(config, dict) else getattr(config, name)
+
+
+class PointCloud_AE(nn.Module):
+    """``PointCloud_AE(config)`` of the reference: ``.encoder`` (the device ``VN_DGCNN_Encoder``) and ``.generator`` (the device
+    ``DecoderInner``), built from ``config.{encoder, hidden_dim, latent_dim, layer_num, num_k, point_dim, loss_type}``
+    (``ckpt['config'].model`` of ``se_model.pt``; an attribute object or a dict)."""
+
+    def __init__(self, config):
+        super().__init__()
+        enc = _get(config, "encoder")
+        if enc == "VN_Resnet":
+            raise NotImplementedError("PointCloud_AE: the VN_Resnet encoder has no device implementation; the shipped model uses VN_DGCNN")
+        if enc != "VN_DGCNN":
+            raise ValueError(f"PointCloud_AE: unknown encoder {enc!r}")
+        hidden, latent, layers = _get(config, "hidden_dim"), _get(config, "latent_dim"), _get(config, "layer_num")
+        self.encoder = VN_DGCNN_Encoder(hidden, latent, layers, _get(config, "num_k"))
+        self.generator = DecoderInner(_get(config, "point_dim"), latent, hidden, layers, _get(config, "loss_type"))
+        self.loss_type = _get(config, "loss_type")
+
+    @torch.no_grad()
+    def forward(self, inputs, z_vector, point_coord, is_training=False):
+        """(latent, field) with the reference's call contract: a given cloud batch ``inputs (B, 1, N, 3)`` is encoded and takes the
+        place of ``z_vector``; the field is evaluated where both a latent and ``point_coord (B, T, 3)`` exist and is ``None``
+        otherwise.  ``is_training`` always encodes and always decodes (there is still no backward)."""
+        if is_training or inputs is not None:
+            latent = self.encoder(inputs)
+        else:
+            latent = z_vector
+        if is_training or (latent is not None and point_coord is not None):
+            return latent, self.generator(point_coord, latent)
+        return latent, None
+
+    @torch.no_grad()
+    def get_val_loss(self, point_clouds, sample_points, sample_values):
+        """Validation triple of clouds ``(B, N, 3)`` against ``sample_values (B, T)`` at ``sample_points (B, T, 3)``: the mean
+        squared error of the field, the fraction of points whose thresholded field (> 0.5) equals the sample value, and that
+        fraction among the occupied samples (value 1) alone; three 0-d device tensors."""
+        field = self.forward(point_clouds[:, None], None, sample_points)[1]
+        mse = (field - sample_values).square().mean()
+        hit = (field > 0.5).to(sample_values.dtype) == sample_values
+        occupied = sample_values == 1
+        n_occupied = int(occupied.sum())                     # a host count, as the reference divides by one (same rounding)
+        return mse, hit.sum() / hit.numel(), (hit & occupied).sum() / n_occupied
+
+    def get_train_loss(self, point_clouds, sample_points, sample_values):
+        raise NotImplementedError("PointCloud_AE.get_train_loss: the device auto-encoder has no backward; train it with the reference")

@@ -168,3 +168,18 @@ def shape_encoder_state_dict(hidden=128, latent=32, layers=4, seed=17):
         vn(f"blocks.{i}", 2 * hidden, hidden)
     vn("conv_c", layers * hidden, latent, shared=True)
     return fill_state_dict(spec, seed=seed)
+
+
+def shape_decoder_state_dict(hidden=128, latent=32, layers=4, seed=19):
+    """Hash-filled weights of the shape decoder under the keys of shapemol_amd.shape_autoencoder.DecoderInner
+    (z_in.map_to_feat.weight, fc_in.*, blocks.{i}.fc_0.* / fc_1.*, fc_out.*).  fc_1.weight is filled like every other weight
+    (the reference initialises it to zero, which would leave a block's second product untested)."""
+    spec = {"z_in.map_to_feat.weight": ((latent, latent), "weight", latent),
+            "fc_in.weight": ((hidden, 2 * latent + 1), "weight", 2 * latent + 1), "fc_in.bias": ((hidden,), "bias", 2 * latent + 1)}
+    for i in range(layers):
+        for fc in ("fc_0", "fc_1"):
+            spec[f"blocks.{i}.{fc}.weight"] = ((hidden, hidden), "weight", hidden)
+            spec[f"blocks.{i}.{fc}.bias"] = ((hidden,), "bias", hidden)
+    spec["fc_out.weight"] = ((1, hidden), "weight", hidden)
+    spec["fc_out.bias"] = ((1,), "bias", hidden)
+    return fill_state_dict(spec, seed=seed)
