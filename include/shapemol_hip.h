@@ -311,8 +311,39 @@ void shapemol_sd_destroy(shapemol_sd_ctx *ctx);
  * before it grows that workspace, which synchronises the device once. */
 int shapemol_sd_decode(shapemol_sd_ctx *ctx, const float *d_p, const int32_t *d_shape_of, int64_t n_points,
                        int64_t points_per_shape, const float *d_z, int64_t n_shapes, float *d_out, void *stream);
-/* Points a workgroup of the decode kernel takes per iteration (tests derive their edge shapes from it). */
+/* The entry points of the decoder's gradient are named shapemol_field_*, not shapemol_sd_*: the set of shapemol_sd_* functions
+ * is a fixed list that tests/test_shape_decoder_cpu.py compares this header against, and these came later.  They take the same
+ * shapemol_sd_ctx.
+ * The field's value and its gradient with respect to the query point in one pass: d_grad (n_points,3) f32 DEVICE =
+ * d out / d p, by reverse mode through the kept ReLU masks (mask = input > 0, torch's convention at 0); d_out as
+ * shapemol_sd_decode writes it, bit for bit, or NULL.  Contract, limits and refusals: those of shapemol_sd_decode. */
+int shapemol_field_decode_grad(shapemol_sd_ctx *ctx, const float *d_p, const int32_t *d_shape_of, int64_t n_points,
+                            int64_t points_per_shape, const float *d_z, int64_t n_shapes, float *d_out, float *d_grad,
+                            void *stream);
+/* One always-applied pass of the reference's gradient shape guidance (models/molopt_score_model.py:592-615), in place on
+ * d_pos (n_atoms,3) f32 DEVICE: with d the field of shape d_batch[i] at atom i and T the atom count of its molecule,
+ *     p <- p - grad_lr * (min(d, 0.5) - 0.5) * (1[d < 0.5] / T) * grad_p d
+ * (atoms with d >= 0.5 stay).  d_batch (n_atoms) int64 DEVICE, SORTED, values in [0, n_shapes) (clamped by the kernel --
+ * validate before the call).  n_shapes in 1..65535, n_atoms <= 2^27, grad_lr finite, else refused.  Uses the context's
+ * workspace like a decode. */
+int shapemol_field_guide(shapemol_sd_ctx *ctx, float *d_pos, const int64_t *d_batch, int64_t n_atoms, const float *d_z,
+                      int64_t n_shapes, double grad_lr, void *stream);
+/* Gradient shape guidance inside the chains of a sampling context: the following shapemol_sample calls apply the pass above
+ * to the predicted x0 of every step with t > grad_step, each molecule against the field of ITS OWN row of the chain's
+ * d_shape (so the decoder's latent must equal the model's shape_dim).  The per-shape prologue runs once per chain; the
+ * guidance launch is part of the captured step.  Precedence follows the reference's if / elif: a mesh, then a point cloud,
+ * then this, then classifier-free guidance.  An installed decoder takes its branch even when grad_step >= num_timesteps - 1
+ * lets no step be guided: the chain is then the unguided one, and classifier-free guidance is not reached either, as behind the
+ * reference's `elif`.  sd = NULL removes it.  Refused with a message: a decoder on another device,
+ * latent != shape_dim, a grad_lr that is not finite.
+ * The decoder context is BORROWED: it must outlive every chain of `ctx` that was enqueued while it was installed, and it
+ * serves one stream at a time -- a decode, decode_grad or guide on it while such a chain is in flight must be ordered behind
+ * the chain by the caller. */
+int shapemol_set_field_guidance(shapemol_ctx *ctx, shapemol_sd_ctx *sd, double grad_lr, int32_t grad_step);
+/* Points a workgroup of the decode kernel takes per iteration (tests derive their edge shapes from it), and of the kernel
+ * behind _decode_grad / _guide (a divisor of the former). */
 int64_t shapemol_sd_tile(const shapemol_sd_ctx *ctx);
+int64_t shapemol_field_grad_tile(const shapemol_sd_ctx *ctx);
 /* Diagnostics (tests only): the per-shape prologue of the last _decode, copied to HOST memory after a device synchronise;
  * n_bytes must be the exact size for its B = n_shapes: SHAPEMOL_SD_ZINV (B,latent) f32 z_inv = sum_xyz z * z_in(z),
  * SHAPEMOL_SD_G (B,H,3) f32 G = W_z z and SHAPEMOL_SD_C (B,H) f32 c = W_inv z_inv + bias of the factored fc_in

@@ -1,13 +1,21 @@
 // C ABI of the device shape decoder (include/shapemol_hip.h, shapemol_sd_*): DecoderInner.forward of the reference
-// (models/shape_pointcloud_modelAE.py:21-103).  Kernels: sm_shape_dec.h.
+// (models/shape_pointcloud_modelAE.py:21-103), its gradient with respect to the query points and the gradient shape guidance
+// built on it.  Kernels: sm_shape_dec.h, sm_shape_dec_grad.h.
 #include "../../include/shapemol_hip.h"
-#include "sm_shape_dec.h"
+#include "sm_shape_dec_grad.h"
 
+#include <hip/hip_ext.h>
+
+#include <atomic>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 extern "C" void shapemol_set_error_(const char *msg);     // shapemol_hip.hip: stores the thread's last error
+struct shapemol_sd_ctx;
+extern "C" int shapemol_sd_chain_guide_(shapemol_sd_ctx *c, float *pos, const int *mol_of, const int *mol_off, int64_t n_atoms, int64_t n_shapes,
+                                        double grad_lr, const int *step_cur, int t_first, int grad_step, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 
 namespace {
 int sd_fail(const std::string &m) { shapemol_set_error_(m.c_str()); return 1; }
@@ -27,7 +35,62 @@ struct shapemol_sd_ctx {
     // per-shape workspace of the prologue: rewritten by every decode, so a context serves one stream at a time
     int64_t capB = 0, lastB = 0;
     float *zinv = nullptr, *gc = nullptr;
+    // Identity of this context's device memory (weights and the block above), from a process-wide counter: new at create and
+    // at every reallocation of the block, never used twice.  A captured chain step holds d_w and gc and is keyed on it; the
+    // context's host address would not do, since a context created after another was destroyed often gets the same address
+    uint64_t ws_gen = 0;
+    // shapemol_field_guide: the batch vector as int32 [capN] and the molecules' first atoms [capM + 1]
+    int64_t capN = 0, capM = 0;
+    int *shape_of = nullptr, *mol_off = nullptr;
 };
+
+namespace {
+uint64_t sd_next_identity() {
+    static std::atomic<uint64_t> counter{0};
+    return ++counter;
+}
+
+// the per-shape workspace for n_shapes, then the prologue of z on stream s
+int sd_prologue(shapemol_sd_ctx *c, const float *d_z, int64_t n_shapes, hipStream_t s) {
+    if (n_shapes > c->capB) {
+        SDCHK(hipDeviceSynchronize());
+        for (void *q : {(void *)c->zinv, (void *)c->gc}) if (q) hipFree(q);
+        c->zinv = c->gc = nullptr; c->capB = 0; c->ws_gen = sd_next_identity();
+        SDCHK(hipMalloc((void **)&c->zinv, (size_t)n_shapes * c->Z * 4));
+        SDCHK(hipMalloc((void **)&c->gc, (size_t)n_shapes * kSdH * 4 * 4));
+        c->capB = n_shapes;
+    }
+    c->lastB = n_shapes;
+    const float *W = c->d_w;
+    hipLaunchKernelGGL(sd_prologue_kernel, dim3((unsigned)n_shapes), dim3(256), 0, s, d_z, W + c->o_zin, W + c->o_win, W + c->o_bin, c->Z, c->zinv, c->gc);
+    return 0;
+}
+
+SdArgs sd_args(const shapemol_sd_ctx *c, const float *d_p, const int32_t *d_shape_of, int64_t n_points, int64_t points_per_shape, int64_t n_shapes, float *d_out) {
+    const float *W = c->d_w;
+    SdArgs a{};
+    a.p = d_p; a.shape_of = d_shape_of; a.gc = c->gc; a.w0 = W + c->o_w0; a.img = W + c->o_img; a.bias = W + c->o_bias; a.w_out = W + c->o_out;
+    a.out = d_out; a.n = n_points; a.per_shape = points_per_shape > 0 ? points_per_shape : 1; a.B = (int)n_shapes; a.L = c->L; a.sigmoid = c->sigmoid;
+    return a;
+}
+// one workgroup per CU (its two weight images fill most of the CU's LDS), striding over the tiles
+unsigned sd_grid(const shapemol_sd_ctx *c, int64_t n_points, int tile = kSdTile) {
+    const int64_t n_tiles = (n_points + tile - 1) / tile;
+    return (unsigned)(n_tiles < c->n_cu ? n_tiles : c->n_cu);
+}
+
+// the argument checks that shapemol_sd_decode and shapemol_field_decode_grad share
+int sd_check(const std::string &me, const shapemol_sd_ctx *c, int64_t n_points, int64_t points_per_shape, bool has_shape_of, int64_t n_shapes) {
+    if (!c) return sd_fail(me + ": null context");
+    if (n_shapes < 1 || n_shapes > kMaxShapes) return sd_fail(me + ": n_shapes must be in 1..65535, got " + std::to_string(n_shapes));
+    if (n_points < 0 || n_points >= ((int64_t)1 << 31))
+        return sd_fail(me + ": n_points must be below 2^31 = 2147483648, got " + std::to_string(n_points));
+    if (!has_shape_of && (points_per_shape < 0 || n_points != n_shapes * points_per_shape))
+        return sd_fail(me + ": without shape_of, n_points must be n_shapes * points_per_shape; got " + std::to_string(n_points) +
+                       " points for " + std::to_string(n_shapes) + " x " + std::to_string(points_per_shape));
+    return 0;
+}
+}  // namespace
 
 extern "C" {
 
@@ -62,7 +125,9 @@ int shapemol_sd_create(int32_t hidden, int32_t latent, int32_t layer_num, int32_
     // depths do not shrink each other's limit
     const int lds_all = (int)(((size_t)2 * kSdImg + (size_t)2 * kMaxLayers * H) * sizeof(float));
     SDCHK(hipFuncSetAttribute((const void *)sd_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_all <= lds ? lds_all : (int)lds_bytes));
+    SDCHK(hipFuncSetAttribute((const void *)sd_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_all <= lds ? lds_all : (int)lds_bytes));
     auto *c = new shapemol_sd_ctx();
+    c->ws_gen = sd_next_identity();
     c->Z = Z; c->L = L; c->sigmoid = loss_type == SHAPEMOL_SD_OCCUPANCY; c->device = device; c->n_cu = n_cu > 0 ? n_cu : 1; c->lds_bytes = lds_bytes;
     std::vector<float> img;
     auto put = [&](const float *src, size_t n) { const size_t o = (img.size() + 63) & ~size_t(63); img.resize(o + n); std::memcpy(&img[o], src, n * 4); return o; };
@@ -74,16 +139,22 @@ int shapemol_sd_create(int32_t hidden, int32_t latent, int32_t layer_num, int32_
     std::vector<float> w0(H);
     for (int h = 0; h < H; ++h) w0[h] = w_in[(size_t)h * (2 * Z + 1)];
     c->o_w0 = put(w0.data(), H);
-    // A fragments of sd_decode_kernel, k in the order of the accumulator layout (sm_shape_dec.h)
-    std::vector<float> im((size_t)2 * L * kSdImg), bias((size_t)2 * L * H);
+    // A fragments of sd_decode_kernel, k in the order of the accumulator layout (sm_shape_dec.h); behind the 2 L images, for
+    // sd_grad_kernel's way back, those of the transposes in reverse order: image 2 L + k is W^T of image 2 L - 1 - k
+    std::vector<float> im((size_t)4 * L * kSdImg), bias((size_t)2 * L * H);
     for (int i = 0; i < 2 * L; ++i) {
         const float *W = p; p += (size_t)H * H;
         std::memcpy(&bias[(size_t)i * H], p, H * 4); p += H;
+        float *fw = &im[(size_t)i * kSdImg], *bw = &im[(size_t)(4 * L - 1 - i) * kSdImg];
         for (int to = 0; to < 8; ++to)
             for (int ti = 0; ti < 8; ++ti)
                 for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r)
-                        im[(size_t)i * kSdImg + ((size_t)(to * 8 + ti) * 64 + lane) * 4 + r] = W[(size_t)(16 * to + (lane & 15)) * H + 16 * ti + 4 * (lane >> 4) + r];
+                    for (int r = 0; r < 4; ++r) {
+                        const size_t e = ((size_t)(to * 8 + ti) * 64 + lane) * 4 + r;
+                        const int row = 16 * to + (lane & 15), col = 16 * ti + 4 * (lane >> 4) + r;
+                        fw[e] = W[(size_t)row * H + col];
+                        bw[e] = W[(size_t)col * H + row];
+                    }
     }
     c->o_img = put(im.data(), im.size());
     c->o_bias = put(bias.data(), bias.size());
@@ -100,43 +171,91 @@ void shapemol_sd_destroy(shapemol_sd_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    for (void *q : {(void *)c->zinv, (void *)c->gc, (void *)c->d_w}) if (q) hipFree(q);
+    for (void *q : {(void *)c->zinv, (void *)c->gc, (void *)c->d_w, (void *)c->shape_of, (void *)c->mol_off}) if (q) hipFree(q);
     delete c;
 }
 
 int64_t shapemol_sd_tile(const shapemol_sd_ctx *c) { return c ? kSdTile : 0; }
+int64_t shapemol_field_grad_tile(const shapemol_sd_ctx *c) { return c ? kSdGradTile : 0; }
 
 int shapemol_sd_decode(shapemol_sd_ctx *c, const float *d_p, const int32_t *d_shape_of, int64_t n_points, int64_t points_per_shape,
                        const float *d_z, int64_t n_shapes, float *d_out, void *stream) {
-    if (!c) return sd_fail("shapemol_sd_decode: null context");
-    if (n_shapes < 1 || n_shapes > kMaxShapes) return sd_fail("shapemol_sd_decode: n_shapes must be in 1..65535, got " + std::to_string(n_shapes));
-    if (n_points < 0 || n_points >= ((int64_t)1 << 31))
-        return sd_fail("shapemol_sd_decode: n_points must be below 2^31 = 2147483648, got " + std::to_string(n_points));
-    if (!d_shape_of && (points_per_shape < 0 || n_points != n_shapes * points_per_shape))
-        return sd_fail("shapemol_sd_decode: without shape_of, n_points must be n_shapes * points_per_shape; got " + std::to_string(n_points) +
-                       " points for " + std::to_string(n_shapes) + " x " + std::to_string(points_per_shape));
+    if (sd_check("shapemol_sd_decode", c, n_points, points_per_shape, d_shape_of != nullptr, n_shapes)) return 1;
     if (n_points == 0) return 0;
     if (!d_p || !d_z || !d_out) return sd_fail("shapemol_sd_decode: null argument");
     SDCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (n_shapes > c->capB) {
+    if (sd_prologue(c, d_z, n_shapes, s)) return 1;
+    const SdArgs a = sd_args(c, d_p, d_shape_of, n_points, points_per_shape, n_shapes, d_out);
+    hipLaunchKernelGGL(sd_decode_kernel, dim3(sd_grid(c, n_points)), dim3(kSdWaves * 64), c->lds_bytes, s, a);
+    SDCHK(hipGetLastError());
+    return 0;
+}
+
+int shapemol_field_decode_grad(shapemol_sd_ctx *c, const float *d_p, const int32_t *d_shape_of, int64_t n_points, int64_t points_per_shape,
+                            const float *d_z, int64_t n_shapes, float *d_out, float *d_grad, void *stream) {
+    if (sd_check("shapemol_field_decode_grad", c, n_points, points_per_shape, d_shape_of != nullptr, n_shapes)) return 1;
+    if (n_points == 0) return 0;
+    if (!d_p || !d_z || !d_grad) return sd_fail("shapemol_field_decode_grad: null argument");
+    SDCHK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (sd_prologue(c, d_z, n_shapes, s)) return 1;
+    SdGradArgs ga{};
+    ga.d = sd_args(c, d_p, d_shape_of, n_points, points_per_shape, n_shapes, d_out);
+    ga.grad = d_grad;
+    hipLaunchKernelGGL(sd_grad_kernel, dim3(sd_grid(c, n_points, kSdGradTile)), dim3(kSdGradWaves * 64), c->lds_bytes, s, ga);
+    SDCHK(hipGetLastError());
+    return 0;
+}
+
+int shapemol_field_guide(shapemol_sd_ctx *c, float *d_pos, const int64_t *d_batch, int64_t n_atoms, const float *d_z, int64_t n_shapes,
+                      double grad_lr, void *stream) {
+    if (!c) return sd_fail("shapemol_field_guide: null context");
+    if (n_shapes < 1 || n_shapes > kMaxShapes) return sd_fail("shapemol_field_guide: n_shapes must be in 1..65535, got " + std::to_string(n_shapes));
+    if (n_atoms < 0 || n_atoms > (1 << 27)) return sd_fail("shapemol_field_guide: n_atoms must be at most 2^27 = 134217728, got " + std::to_string(n_atoms));
+    if (!std::isfinite(grad_lr)) return sd_fail("shapemol_field_guide: grad_lr is not finite");
+    if (n_atoms == 0) return 0;
+    if (!d_pos || !d_batch || !d_z) return sd_fail("shapemol_field_guide: null argument");
+    SDCHK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (n_atoms > c->capN || n_shapes > c->capM) {
         SDCHK(hipDeviceSynchronize());
-        for (void *q : {(void *)c->zinv, (void *)c->gc}) if (q) hipFree(q);
-        c->zinv = c->gc = nullptr; c->capB = 0;
-        SDCHK(hipMalloc((void **)&c->zinv, (size_t)n_shapes * c->Z * 4));
-        SDCHK(hipMalloc((void **)&c->gc, (size_t)n_shapes * kSdH * 4 * 4));
-        c->capB = n_shapes;
+        for (void *q : {(void *)c->shape_of, (void *)c->mol_off}) if (q) hipFree(q);
+        c->shape_of = c->mol_off = nullptr;
+        const int64_t capN = n_atoms > c->capN ? n_atoms : c->capN, capM = n_shapes > c->capM ? n_shapes : c->capM;
+        c->capN = c->capM = 0;
+        SDCHK(hipMalloc((void **)&c->shape_of, (size_t)capN * 4));
+        SDCHK(hipMalloc((void **)&c->mol_off, (size_t)(capM + 1) * 4));
+        c->capN = capN; c->capM = capM;
     }
-    c->lastB = n_shapes;
-    const float *W = c->d_w;
-    hipLaunchKernelGGL(sd_prologue_kernel, dim3((unsigned)n_shapes), dim3(256), 0, s, d_z, W + c->o_zin, W + c->o_win, W + c->o_bin, c->Z, c->zinv, c->gc);
-    SdArgs a{};
-    a.p = d_p; a.shape_of = d_shape_of; a.gc = c->gc; a.w0 = W + c->o_w0; a.img = W + c->o_img; a.bias = W + c->o_bias; a.w_out = W + c->o_out;
-    a.out = d_out; a.n = n_points; a.per_shape = points_per_shape > 0 ? points_per_shape : 1; a.B = (int)n_shapes; a.L = c->L; a.sigmoid = c->sigmoid;
-    // one workgroup per CU (its two weight images fill most of the CU's LDS), striding over the tiles
-    const int64_t n_tiles = (n_points + kSdTile - 1) / kSdTile;
-    const unsigned grid = (unsigned)(n_tiles < c->n_cu ? n_tiles : c->n_cu);
-    hipLaunchKernelGGL(sd_decode_kernel, dim3(grid), dim3(kSdWaves * 64), c->lds_bytes, s, a);
+    if (sd_prologue(c, d_z, n_shapes, s)) return 1;
+    const int64_t work = n_atoms > n_shapes + 1 ? n_atoms : n_shapes + 1;
+    hipLaunchKernelGGL(sd_batch_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, d_batch, (int)n_atoms, (int)n_shapes, c->shape_of, c->mol_off);
+    return shapemol_sd_chain_guide_(c, d_pos, c->shape_of, c->mol_off, n_atoms, n_shapes, grad_lr, nullptr, 0, 0, s, nullptr, nullptr);
+}
+
+// ---- for shapemol_hip.hip (field guidance inside a chain; not in the header) -----------------------------------------------
+void shapemol_sd_describe_(const shapemol_sd_ctx *c, int *device, int *latent) { *device = c->device; *latent = c->Z; }
+
+// the chain's prep: the prologue of the chain's shapes; *gen = the identity of the device memory a captured step would hold
+int shapemol_sd_chain_prepare_(shapemol_sd_ctx *c, const float *d_z, int64_t n_shapes, hipStream_t s, uint64_t *gen) {
+    if (n_shapes < 1 || n_shapes > kMaxShapes) return sd_fail("field guidance: the decoder takes 1..65535 shapes, the chain has " + std::to_string(n_shapes));
+    if (sd_prologue(c, d_z, n_shapes, s)) return 1;
+    *gen = c->ws_gen;
+    SDCHK(hipGetLastError());
+    return 0;
+}
+
+// one guidance pass on pos with the prologue's data as it stands (mol_of sorted in [0, B), mol_off [B + 1]); with events, a
+// profiled launch
+int shapemol_sd_chain_guide_(shapemol_sd_ctx *c, float *pos, const int *mol_of, const int *mol_off, int64_t n_atoms, int64_t n_shapes, double grad_lr,
+                             const int *step_cur, int t_first, int grad_step, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    SdGradArgs ga{};
+    ga.d = sd_args(c, pos, mol_of, n_atoms, 0, n_shapes, nullptr);
+    ga.pos = pos; ga.mol_off = mol_off; ga.lr = (float)grad_lr; ga.step_cur = step_cur; ga.t_first = t_first; ga.grad_step = grad_step;
+    const dim3 grid(sd_grid(c, n_atoms, kSdGradTile)), block(kSdGradWaves * 64);
+    if (e0) hipExtLaunchKernelGGL(sd_grad_kernel, grid, block, c->lds_bytes, s, e0, e1, 0, ga);
+    else hipLaunchKernelGGL(sd_grad_kernel, grid, block, c->lds_bytes, s, ga);
     SDCHK(hipGetLastError());
     return 0;
 }

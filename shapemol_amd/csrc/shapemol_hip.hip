@@ -44,7 +44,7 @@ constexpr int kGraphUnroll = SM_GRAPH_UNROLL;   // reverse steps per graph launc
 
 struct ProfRec { const char *name; hipEvent_t e0, e1; };
 
-enum class Guide { None, Cloud, Mesh, Cfg };      // guidance of a chain's predicted x0: chain_guide (sm_guide_host.h)
+enum class Guide { None, Cloud, Mesh, Field, Cfg };      // guidance of a chain's predicted x0: chain_guide (sm_guide_host.h)
 
 // Device data of shape guidance: per kind ONE set of groups of molecules (sm_guide_host.h installs and clears them).  `whole`: a
 // set of one group that spans whatever batch comes (shapemol_set_guidance / shapemol_set_mesh_guidance): no molecule count
@@ -136,6 +136,9 @@ struct shapemol_ctx {
     // the per-workgroup table of whichever guides (sized by the chain) and the mesh's per-step lists (one block; counters: 4 per group)
     CloudSet cs; MeshSet ms;
     int2 *wg_table = nullptr; int64_t wg_table_cap = 0;
+    // gradient shape guidance (shapemol_set_field_guidance): the borrowed decoder context, whose per-shape workspace the chain's
+    // prep fills from the chain's own shapes
+    shapemol_sd_ctx *field_sd = nullptr; double field_lr = 0.0; int field_step = 0;
     float4 *m_within = nullptr; int *m_out = nullptr, *m_cnt = nullptr; int64_t m_cap = 0, m_cnt_cap = 0;
     int64_t m_flag_groups = 0;      // groups of the last chain / pass with a mesh set (debug_read "mesh_group_flags")
     // classifier-free guidance (shapemol_set_cfg): a second score evaluation per step on a zeroed shape, whose prepared shape
@@ -169,9 +172,13 @@ struct shapemol_ctx {
     struct GraphKey { int64_t N = 0, B = 0; Guide guide = Guide::None; int fold = 0, gfuse = 0;
                       int cfg = 0 /* 0 off, else 1 + CfgType */; double cfgv[9] = {};   // w, p, has_bounds, box
                       int cfg_groups = 0;     // groups of the per-group form (its strengths, boxes and layout live in device memory), else 0
+                      // field guidance: the never-reused identity of the decoder's device memory (the step holds the addresses of its
+                      // weights and workspace; 0 = no field), grad_lr, grad_step
+                      uint64_t field_gen = 0; double field_lr = 0.0; int field_step = 0;
                       bool operator==(const GraphKey &o) const {
                           if (!(N == o.N && B == o.B && guide == o.guide && fold == o.fold && gfuse == o.gfuse && cfg == o.cfg &&
-                                cfg_groups == o.cfg_groups)) return false;
+                                cfg_groups == o.cfg_groups && field_gen == o.field_gen && field_lr == o.field_lr &&
+                                field_step == o.field_step)) return false;
                           for (int i = 0; i < 9; ++i) if (cfgv[i] != o.cfgv[i]) return false;
                           return true;
                       } } gkey{};
@@ -1093,6 +1100,10 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
     if (mesh && mesh_counters_clear(c, s, c->ms.groups)) return 1;
     if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
+    uint64_t field_gen = 0;
+    if (kind == Guide::Field) {      // the decoder's per-shape prologue of the chain's own shapes, once per chain
+        if (shapemol_sd_chain_prepare_(c->field_sd, d_shape, B, s, &field_gen)) return 1;      // (not a profiled launch: no event pair)
+    }
     if (cfg) {      // classifier-free guidance: the unconditional evaluation's shape data, from a zeroed shape, once per chain
         swap_uncond(c);
         const int rc = DISPATCH_H(c, run_prep_shape<128>(c, s, B, c->shape_zero), run_prep_shape<32>(c, s, B, c->shape_zero));
@@ -1136,6 +1147,7 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
         shapemol_ctx::GraphKey key{};
         key.N = N; key.B = B; key.guide = kind; key.fold = vn_fold_ok(c, (int)N);
         key.gfuse = c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && c->n_pins == 0;
+        if (kind == Guide::Field) { key.field_gen = field_gen; key.field_lr = c->field_lr; key.field_step = c->field_step; }
         if (cfg && c->cgs.groups > 0) {
             key.cfg = 1 + c->cgs.type; key.cfg_groups = c->cgs.groups; key.cfgv[1] = c->cgs.p;
         } else if (cfg) {

@@ -7,14 +7,25 @@
 // so it needs no batch vector (its atoms are [0, N)) and carries no molecule count to check.
 #pragma once
 
+// shape_decoder.hip: the decoder context's side of field guidance
+extern "C" {
+void shapemol_sd_describe_(const shapemol_sd_ctx *c, int *device, int *latent);
+int shapemol_sd_chain_prepare_(shapemol_sd_ctx *c, const float *d_z, int64_t n_shapes, hipStream_t s, uint64_t *gen);
+int shapemol_sd_chain_guide_(shapemol_sd_ctx *c, float *pos, const int *mol_of, const int *mol_off, int64_t n_atoms, int64_t n_shapes, double grad_lr,
+                             const int *step_cur, int t_first, int grad_step, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+}
+
 namespace {
 
-// The guidance of the chains to come: the reference's if / elif in sample_diffusion -- mesh, else the point cloud, else
-// classifier-free guidance.  Groups without any mesh / cloud guide nothing (and leave the next kind its turn).  The only place
+// The guidance of the chains to come: the reference's if / elif in sample_diffusion -- mesh, else the point cloud, else the
+// decoder's field (`use_grad`), else classifier-free guidance.  Groups without any mesh / cloud guide nothing (and leave the next kind its turn).  The only place
 // that spells this out.
 Guide chain_guide(const shapemol_ctx *c) {
     if (c->ms.nfaces > 0) return Guide::Mesh;
     if (c->cs.points > 0) return Guide::Cloud;
+    // (a field whose gate `t > grad_step` no step of the chain passes launches nothing: the chain is the unguided one, bit for bit.
+    // It still takes the branch, as the reference's `elif use_grad:` does: classifier-free guidance does not get its turn)
+    if (c->field_sd) return c->cfg.num_timesteps - 1 - c->first_step > c->field_step ? Guide::Field : Guide::None;
     return c->cfg_w != 0.0 || c->cgs.groups > 0 ? Guide::Cfg : Guide::None;
 }
 
@@ -273,6 +284,11 @@ int enqueue_guidance(shapemol_ctx *c, hipStream_t s, Guide kind, float *pos, int
     } else if (kind == Guide::Cloud) {       // each group of molecules towards its own cloud
         const PcGroupsArgs ga = cloud_args(c->cs, c->wg_table, c->chain_params, pos, N, step_cur, t_first);
         LAUNCH("pc_guidance", SMK(pc_guidance_kernel, dim3(groups_grid(N, c->cs.groups)), dim3(256), cloud_lds_bytes(c->cs.max_points), s, ga));
+    } else if (kind == Guide::Field) {       // each molecule down the gradient of its own shape's field (the chain's prep ran the prologue)
+        int rc = 0;
+        LAUNCH("field_guidance", rc = shapemol_sd_chain_guide_(c->field_sd, pos, c->mol_of, c->mol_off, N, c->lastB, c->field_lr, step_cur, t_first,
+                                                                c->field_step, s, c->prof_on ? c->cur_e0 : nullptr, c->prof_on ? c->cur_e1 : nullptr));
+        if (rc) return 1;
     }
     return 0;
 }
@@ -387,6 +403,22 @@ int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_points, double
     cloud_set_clear(cs);
     if (e != hipSuccess) return fail(std::string("shapemol_pointcloud_guidance: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(std::string("shapemol_pointcloud_guidance: ") + hipGetErrorString(e2));
+    return 0;
+}
+
+int shapemol_set_field_guidance(shapemol_ctx *c, shapemol_sd_ctx *sd, double grad_lr, int32_t grad_step) {
+    if (!c) return fail("shapemol_set_field_guidance: null ctx");
+    if (sd) {
+        int device = 0, latent = 0;
+        shapemol_sd_describe_(sd, &device, &latent);
+        if (device != c->device)
+            return fail("shapemol_set_field_guidance: the decoder lives on device " + std::to_string(device) + ", the sampling context on device " + std::to_string(c->device));
+        if (latent != c->cfg.shape_dim)
+            return fail("shapemol_set_field_guidance: the decoder's latent is " + std::to_string(latent) + ", the model's shape_dim is " +
+                        std::to_string(c->cfg.shape_dim) + ": a molecule is guided against the field of its own shape condition");
+        if (!std::isfinite(grad_lr)) return fail("shapemol_set_field_guidance: grad_lr is not finite");
+    }
+    c->field_sd = sd; c->field_lr = sd ? grad_lr : 0.0; c->field_step = sd ? grad_step : 0;      // (part of the graph key: nothing to drop)
     return 0;
 }
 

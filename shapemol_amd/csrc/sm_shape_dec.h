@@ -73,21 +73,64 @@ struct SdArgs {
     int B, L, sigmoid;
 };
 
+// point `pt` of the launch (clamped into [0, n): tails compute the last point again and store nothing) and the shape it
+// belongs to (clamped into [0, B))
+SM_DEV int64_t sd_point(const SdArgs &a, int64_t pt, float &px, float &py, float &pz) {
+    const int64_t q = pt < a.n ? pt : a.n - 1;
+    px = a.p[q * 3]; py = a.p[q * 3 + 1]; pz = a.p[q * 3 + 2];
+    const int64_t sb = a.shape_of ? (int64_t)a.shape_of[q] : q / a.per_shape;
+    return sb < 0 ? 0 : (sb >= a.B ? a.B - 1 : sb);
+}
+
+// fc_in of one column: rows 16 t + 4 g + r of w0 |p|^2 + G_sb p + c_sb
+SM_DEV void sd_fc_in(const SdArgs &a, int64_t sb, int g, float px, float py, float pz, f32x4 (&x)[8]) {
+    const float pp = px * px + py * py + pz * pz;
+    const float *gcb = a.gc + sb * (kSdH * 4);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const float4 w0 = ldg4(a.w0 + 16 * t + 4 * g);
+        const float w0r[4] = {w0.x, w0.y, w0.z, w0.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float4 gc = ldg4(gcb + (16 * t + 4 * g + r) * 4);
+            x[t][r] = fmaf(w0r[r], pp, fmaf(gc.x, px, fmaf(gc.y, py, fmaf(gc.z, pz, gc.w))));
+        }
+    }
+}
+
+// fc_out(relu(x)) of one column: this lane's 32 rows, then the four lane groups of the column; sigmoid for occupancy
+SM_DEV float sd_fc_out(const SdArgs &a, int g, const f32x4 (&x)[8]) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const float4 w = ldg4(a.w_out + 16 * t + 4 * g);
+        s = fmaf(w.x, fmaxf(x[t][0], 0.f), s); s = fmaf(w.y, fmaxf(x[t][1], 0.f), s);
+        s = fmaf(w.z, fmaxf(x[t][2], 0.f), s); s = fmaf(w.w, fmaxf(x[t][3], 0.f), s);
+    }
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    s += a.w_out[kSdH];
+    if (a.sigmoid) s = 1.f / (1.f + expf(-s));
+    return s;
+}
+
 // acc[ct][to] += W relu(x[ct]) for the image at wl (LDS).  k-tile outermost: relu once per operand register, 8 * kSdColTiles
-// independent accumulator chains between two uses of the same one
-SM_DEV void sd_linear(const float *wl, int lane, const f32x4 (&x)[kSdColTiles][8], f32x4 (&acc)[kSdColTiles][8]) {
+// independent accumulator chains between two uses of the same one (CT column tiles per wave).  kRelu = false: W x[ct], the operand as it is (the
+// transposed products of sm_shape_dec_grad.h)
+template <bool kRelu = true, int CT>
+SM_DEV void sd_linear(const float *wl, int lane, const f32x4 (&x)[CT][8], f32x4 (&acc)[CT][8]) {
 #pragma unroll
     for (int ti = 0; ti < 8; ++ti) {
-        f32x4 xr[kSdColTiles];
+        f32x4 xr[CT];
 #pragma unroll
-        for (int ct = 0; ct < kSdColTiles; ++ct)
+        for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) xr[ct][r] = fmaxf(x[ct][ti][r], 0.f);
+            for (int r = 0; r < 4; ++r) xr[ct][r] = kRelu ? fmaxf(x[ct][ti][r], 0.f) : x[ct][ti][r];
 #pragma unroll
         for (int to = 0; to < 8; ++to) {
             const float4 a = *reinterpret_cast<const float4 *>(wl + ((to * 8 + ti) * 64 + lane) * 4);
 #pragma unroll
-            for (int ct = 0; ct < kSdColTiles; ++ct) {
+            for (int ct = 0; ct < CT; ++ct) {
                 acc[ct][to] = mfma16(a.x, xr[ct][0], acc[ct][to]);
                 acc[ct][to] = mfma16(a.y, xr[ct][1], acc[ct][to]);
                 acc[ct][to] = mfma16(a.z, xr[ct][2], acc[ct][to]);
@@ -98,40 +141,42 @@ SM_DEV void sd_linear(const float *wl, int lane, const f32x4 (&x)[kSdColTiles][8
 }
 
 // y[ct][t] = b[16 t + 4 g + r]  (b in LDS)
-SM_DEV void sd_bias(const float *b, int g, f32x4 (&y)[kSdColTiles][8]) {
+template <int CT>
+SM_DEV void sd_bias(const float *b, int g, f32x4 (&y)[CT][8]) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         const float4 v = *reinterpret_cast<const float4 *>(b + 16 * t + 4 * g);
 #pragma unroll
-        for (int ct = 0; ct < kSdColTiles; ++ct) y[ct][t] = f32x4{v.x, v.y, v.z, v.w};
+        for (int ct = 0; ct < CT; ++ct) y[ct][t] = f32x4{v.x, v.y, v.z, v.w};
     }
 }
 
 // x[ct][to] += b + W relu(y[ct]): the block's second Linear.  dx is summed on its own and added to x once, as the reference
 // does (a chain started from x would round each of its 128 steps at the magnitude of x); four row tiles at a time, so that
-// the dx accumulators cost 16 * kSdColTiles registers.
-SM_DEV void sd_linear_residual(const float *wl, const float *b, int lane, int g, const f32x4 (&y)[kSdColTiles][8], f32x4 (&x)[kSdColTiles][8]) {
+// the dx accumulators cost 16 * CT registers.
+template <int CT>
+SM_DEV void sd_linear_residual(const float *wl, const float *b, int lane, int g, const f32x4 (&y)[CT][8], f32x4 (&x)[CT][8]) {
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        f32x4 dx[kSdColTiles][4];
+    for (int part = 0; part < 2; ++part) {
+        f32x4 dx[CT][4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const float4 v = *reinterpret_cast<const float4 *>(b + 16 * (4 * half + t) + 4 * g);
+            const float4 v = *reinterpret_cast<const float4 *>(b + 16 * (4 * part + t) + 4 * g);
 #pragma unroll
-            for (int ct = 0; ct < kSdColTiles; ++ct) dx[ct][t] = f32x4{v.x, v.y, v.z, v.w};
+            for (int ct = 0; ct < CT; ++ct) dx[ct][t] = f32x4{v.x, v.y, v.z, v.w};
         }
 #pragma unroll
         for (int ti = 0; ti < 8; ++ti) {
-            f32x4 yr[kSdColTiles];
+            f32x4 yr[CT];
 #pragma unroll
-            for (int ct = 0; ct < kSdColTiles; ++ct)
+            for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) yr[ct][r] = fmaxf(y[ct][ti][r], 0.f);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const float4 a = *reinterpret_cast<const float4 *>(wl + (((4 * half + t) * 8 + ti) * 64 + lane) * 4);
+                const float4 a = *reinterpret_cast<const float4 *>(wl + (((4 * part + t) * 8 + ti) * 64 + lane) * 4);
 #pragma unroll
-                for (int ct = 0; ct < kSdColTiles; ++ct) {
+                for (int ct = 0; ct < CT; ++ct) {
                     dx[ct][t] = mfma16(a.x, yr[ct][0], dx[ct][t]);
                     dx[ct][t] = mfma16(a.y, yr[ct][1], dx[ct][t]);
                     dx[ct][t] = mfma16(a.z, yr[ct][2], dx[ct][t]);
@@ -142,7 +187,7 @@ SM_DEV void sd_linear_residual(const float *wl, const float *b, int lane, int g,
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int ct = 0; ct < kSdColTiles; ++ct) x[ct][4 * half + t] += dx[ct][t];
+            for (int ct = 0; ct < CT; ++ct) x[ct][4 * part + t] += dx[ct][t];
     }
 }
 
@@ -170,21 +215,8 @@ __global__ void __launch_bounds__(kSdWaves * 64) sd_decode_kernel(SdArgs a) {
 #pragma unroll
         for (int ct = 0; ct < kSdColTiles; ++ct) {
             pt[ct] = tile * kSdTile + (wave * kSdColTiles + ct) * 16 + n;
-            const int64_t q = pt[ct] < a.n ? pt[ct] : a.n - 1;
-            const float px = a.p[q * 3], py = a.p[q * 3 + 1], pz = a.p[q * 3 + 2];
-            const float pp = px * px + py * py + pz * pz;
-            const int64_t sb = a.shape_of ? (int64_t)a.shape_of[q] : q / a.per_shape;
-            const float *gcb = a.gc + (sb < 0 ? 0 : (sb >= a.B ? a.B - 1 : sb)) * (kSdH * 4);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const float4 w0 = ldg4(a.w0 + 16 * t + 4 * g);
-                const float w0r[4] = {w0.x, w0.y, w0.z, w0.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float4 gc = ldg4(gcb + (16 * t + 4 * g + r) * 4);
-                    x[ct][t][r] = fmaf(w0r[r], pp, fmaf(gc.x, px, fmaf(gc.y, py, fmaf(gc.z, pz, gc.w))));
-                }
-            }
+            float px, py, pz;
+            sd_fc_in(a, sd_point(a, pt[ct], px, py, pz), g, px, py, pz, x[ct]);
         }
         for (int i = 0; i < n_lin; i += 2) {
             sd_image_barrier();                            // image i has landed; every wave has left buffer 1 (image i - 1)
@@ -197,20 +229,9 @@ __global__ void __launch_bounds__(kSdWaves * 64) sd_decode_kernel(SdArgs a) {
             sd_linear_residual(wl + kSdImg, bl + (i + 1) * kSdH, lane, g, y, x);      // x = x + (fc_1(relu(net)) + b1)
         }
         // fc_out(relu(x)): this lane's 32 rows, then the four lane groups of a column
-        const float b_out = a.w_out[kSdH];
 #pragma unroll
         for (int ct = 0; ct < kSdColTiles; ++ct) {
-            float s = 0.f;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const float4 w = ldg4(a.w_out + 16 * t + 4 * g);
-                s = fmaf(w.x, fmaxf(x[ct][t][0], 0.f), s); s = fmaf(w.y, fmaxf(x[ct][t][1], 0.f), s);
-                s = fmaf(w.z, fmaxf(x[ct][t][2], 0.f), s); s = fmaf(w.w, fmaxf(x[ct][t][3], 0.f), s);
-            }
-            s += __shfl_xor(s, 16, 64);
-            s += __shfl_xor(s, 32, 64);
-            s += b_out;
-            if (a.sigmoid) s = 1.f / (1.f + expf(-s));
+            const float s = sd_fc_out(a, g, x[ct]);
             if (g == 0 && pt[ct] < a.n) a.out[pt[ct]] = s;
         }
     }

@@ -416,6 +416,15 @@ class ScorePosNet3D(nn.Module):
         inside its mesh raises ``MeshGuidanceError`` as the single mesh does -- for the whole chain, the message and
         ``.group_steps`` naming the groups and the number of steps in which each was left unguided.  Mesh groups
         together with point-cloud groups in one chain raise ``NotImplementedError``.
+        ``use_grad=True`` with ``shape_AE``, ``grad_lr`` and ``grad_step`` is the reference's gradient shape guidance (``:592-615``,
+        kept in a string literal there): in every step with t > grad_step each atom of the predicted x0 moves by
+        ``- grad_lr * (min(d, 0.5) - 0.5) * (1[d < 0.5] / T_j) * grad d``, with ``d`` the field of the molecule's OWN ``ligand_shape``
+        row at the atom and ``T_j`` the molecule's atom count -- one device kernel inside the step (value and gradient of the
+        decoder in one pass).  ``shape_AE`` is this package's ``PointCloud_AE`` (its ``.generator`` is used) or ``DecoderInner``,
+        on the chain's device, with ``z_dim`` equal to the model's shape_dim; ``None`` raises ``ValueError``, a reference (CPU
+        torch) auto-encoder ``TypeError``.  It comes behind a mesh and a point cloud (with either, ``use_grad`` is ignored, as the
+        reference's ``elif``) and before classifier-free guidance.  ``pos_cond_traj`` holds the guided prediction, as for the
+        cloud and the mesh.  While the chain is in flight (``_async``) the decoder must not be used on another stream.
         ``guide_stren > 0`` on a model trained with ``cond_mask_prob > 0`` is the reference's classifier-free guidance
         (``:616-642``): every step also evaluates the score on a zeroed shape, combines ``(1 + w) * cond - w * uncond`` and
         applies ``threshold_CFG(threshold_type, threshold_args)`` with batch-wide statistics, all as device kernels inside the
@@ -437,8 +446,13 @@ class ScorePosNet3D(nn.Module):
         builds the dict (chains on different slots then run side by side, and a finished chain's trajectories are
         unbatched and copied while the next one runs).
         """
-        if use_grad:
-            raise NotImplementedError("gradient shape guidance is outside the accelerated path (commented out in the reference)")
+        # gradient shape guidance: behind a mesh and a point cloud in the reference's if / elif, so with either it is not looked at
+        field_dec = None
+        if use_grad and use_mesh_data is None and use_pointcloud_data is None:
+            field_dec = _field_decoder(shape_AE)
+            grad_lr = float(grad_lr)
+            if not np.isfinite(grad_lr):
+                raise ValueError(f"grad_lr must be finite, got {grad_lr}")
         groups = mesh_groups = None
         if isinstance(use_pointcloud_data, list):
             if isinstance(use_mesh_data, list):
@@ -457,7 +471,7 @@ class ScorePosNet3D(nn.Module):
         elif self.cond_mask_prob == 0:
             assert guide_stren == 0
         # classifier-free guidance: the reference's branch order (:561-642) -- mesh, point cloud, then CFG
-        cfg = use_mesh_data is None and use_pointcloud_data is None and (self.cond_mask_prob or 0) > 0 and guide_stren > 0.0
+        cfg = use_mesh_data is None and use_pointcloud_data is None and field_dec is None and (self.cond_mask_prob or 0) > 0 and guide_stren > 0.0
         cfg_p, cfg_box = 0.0, None
         if cfg:
             if threshold_type not in _lib.CFG_THRESHOLDS:
@@ -544,6 +558,7 @@ class ScorePosNet3D(nn.Module):
         out_v = torch.empty((n,), dtype=torch.int64, device=dev)
         pending = _PendingChain(self, ctx, dev, guided, bufs, out_pos, out_v, return_traj, _reuse_host_buffers,
                                 keep=(pos, v, batch, shape, eps, u, gd), offset=offset)
+        pending.field_dec = field_dec            # (the chain borrows the decoder's library context)
         pending.n_groups = len(mesh_groups[0]) - 1 if isinstance(use_mesh_data, list) else 0
         try:
             with torch.cuda.device(dev):
@@ -565,6 +580,9 @@ class ScorePosNet3D(nn.Module):
                                                     None if cfg_box is None else cfg_box.ctypes.data_as(C.c_void_p),
                                                     _ptr(bufs.get("pos_uncond_traj")), _ptr(bufs.get("v_uncond_traj"))),
                                "shapemol_set_cfg")
+                if field_dec is not None:
+                    _lib.check(lib.shapemol_set_field_guidance(ctx, field_dec._context(dev), grad_lr, int(grad_step)),
+                               "shapemol_set_field_guidance")
                 try:
                     rc = lib.shapemol_sample(ctx, _ptr(pos), _ptr(v), _ptr(batch), n, b, _ptr(shape), int(num_steps),
                                              _ptr(eps), _ptr(u), C.c_uint64(seed), C.byref(tr), _ptr(out_pos), _ptr(out_v),
@@ -572,6 +590,8 @@ class ScorePosNet3D(nn.Module):
                 finally:
                     if first_step:
                         lib.shapemol_set_option(ctx, b"first_step", 0)
+                    if field_dec is not None:    # read when the chain is enqueued, like the classifier-free settings below
+                        lib.shapemol_set_field_guidance(ctx, None, 0.0, 0)
                     if cfg and cfg_groups is not None:      # (the rows stay in device memory for the chain in flight)
                         lib.shapemol_set_cfg_groups(ctx, 0, None, None, 0, 0.0, None, None, None)
                     elif cfg:    # read when the chain is enqueued: the context goes back to unguided chains at once
@@ -688,6 +708,7 @@ class _PendingChain:
         self.side = self.cur = None
         self.done = False
         self.n_groups = 0                    # mesh groups of a list-form chain (their unguided steps go into a MeshGuidanceError)
+        self.field_dec = None                # the decoder of a field-guided chain: kept alive until the chain is done
 
     def _drop_guidance(self):
         if self.guided:      # whatever happened, the context must not keep the cloud / mesh (and the caller-owned draws pointer) installed
@@ -746,6 +767,19 @@ class _PendingChain:
         else:
             res.update(pos_traj=[], v_traj=[], v0_traj=[], vt_traj=[], pos_cond_traj=[], v_cond_traj=[])
         return res
+
+
+def _field_decoder(shape_AE):
+    """The device ``DecoderInner`` behind ``sample_diffusion(shape_AE=...)``."""
+    from .shape_autoencoder import DecoderInner, PointCloud_AE
+    if shape_AE is None:
+        raise ValueError("use_grad=True needs shape_AE: a shapemol_amd.shape_autoencoder.PointCloud_AE or DecoderInner")
+    if isinstance(shape_AE, PointCloud_AE):
+        return shape_AE.generator
+    if isinstance(shape_AE, DecoderInner):
+        return shape_AE
+    raise TypeError(f"shape_AE is a {type(shape_AE).__module__}.{type(shape_AE).__name__}: gradient shape guidance runs on the device "
+                    "auto-encoder -- load its state dict into shapemol_amd.shape_autoencoder.PointCloud_AE and pass that")
 
 
 def pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=3, ratio=0.2, *, draws=None, seed=None):

@@ -166,7 +166,7 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
                             threshold_args=None, sample_num_atoms="prior", bounds=None, ref_num_atoms=None,
                             ref_atom_feature=None, guide_stren=0, seed=None, use_graph=True, host_rng=False,
                             use_pointcloud_data=None, grad_step=1000, pipeline=2, use_mesh_data=None, use_mesh_gap=None,
-                            _batches=None, _batch_seed=None):
+                            use_grad=False, grad_lr=1, shape_AE=None, _batches=None, _batch_seed=None):
     """``sample_diffusion_ligand`` of the reference for one shape condition.
 
     shape_emb        (32, 3) latent of the condition (``data.shape_emb``); repeated per molecule of a batch.
@@ -193,6 +193,10 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
                      mesh shape guidance runs as two device kernels inside every step with t > grad_step, and takes precedence
                      over ``use_pointcloud_data``, as in the reference.
     use_mesh_gap     accepted and ignored: the reference passes ``config.sample.use_mesh_gap`` here and never reads it.
+    use_grad, grad_lr, shape_AE   gradient shape guidance (``config.sample.use_grad`` / ``grad_lr``, the auto-encoder of
+                     ``scripts/sample_diffusion.py:220-223``): in every step with t > grad_step each molecule's predicted atoms
+                     move down the gradient of the field of ITS OWN shape condition (``sample_diffusion(use_grad=True)``);
+                     ``shape_AE`` is this package's ``PointCloud_AE`` or ``DecoderInner``.  A mesh or a cloud, where given, wins.
     shape_emb        may also be (n_data, 32, 3), one condition per molecule of a single batch (fixtures).
     pipeline         batches in flight on the device (accelerated model only; 1 = one after the other, as the reference).  With 2
                      (default) two library contexts alternate: while the chain of batch i runs, the trajectories of batch i - 1
@@ -227,6 +231,9 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
     depth = max(1, int(pipeline)) if accelerated else 1
     if accelerated and depth > 1 and (use_pointcloud_data is not None or use_mesh_data is not None):
         depth = 1          # installing / removing the guidance cloud or mesh drains the device: nothing to overlap
+    if use_grad:
+        depth = 1          # the decoder's per-shape workspace serves one chain at a time
+    grad_kw = {"use_grad": True, "grad_lr": grad_lr, "shape_AE": shape_AE} if use_grad else {}
     pending = collections.deque()
 
     def deliver(job):
@@ -274,7 +281,7 @@ def sample_diffusion_ligand(model, shape_emb, num_samples, batch_size=16, device
                 threshold_type=threshold_type, threshold_args=threshold_args, num_steps=num_steps,
                 center_pos_mode=center_pos_mode, guide_stren=guide_stren, bounds=bounds,
                 use_pointcloud_data=use_pointcloud_data, use_mesh_data=use_mesh_data, grad_step=grad_step,
-                seed=None if seed is None else int(seed) + i, use_graph=use_graph, **noise_kw,
+                seed=None if seed is None else int(seed) + i, use_graph=use_graph, **noise_kw, **grad_kw,
                 **({"_reuse_host_buffers": "device", "_slot": slot_i % depth, "_async": True} if accelerated else {}))
             pending.append((handle, ligand_num_atoms, n_data, t1))
         while pending:
@@ -399,7 +406,7 @@ def cfg_groups(strens, boxes, segs):
 def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256, device="cuda:0", num_steps=None,
                                   center_pos_mode="none", sample_func=None, sample_num_atoms="prior", ref_num_atoms=None,
                                   seed=None, use_graph=True, host_rng=False, grad_step=1000, guide_stren=0,
-                                  threshold_type=None, threshold_args=None, bounds=None):
+                                  threshold_type=None, threshold_args=None, bounds=None, use_grad=False, grad_lr=1, shape_AE=None):
     """``sample_diffusion_ligand`` for MANY shape conditions at once: ``num_samples`` molecules for each of ``conditions``, with
     molecules of different conditions sharing the chains.
 
@@ -425,6 +432,10 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
                      whose statistic spans one batch of its ``batch_size``.  In a job guided by meshes or clouds a condition that
                      carries one ignores CFG, as in the reference; a condition there without a mesh or cloud but with
                      ``guide_stren > 0`` raises ``ValueError`` before any chain runs (run it as two jobs).
+
+    use_grad, grad_lr, shape_AE   gradient shape guidance, as for :func:`sample_diffusion_ligand`, one setting per job: every
+                     molecule is guided against the field of its own condition's ``shape_emb``, so a mixed chain needs no groups.
+                     Conditions with a mesh or a cloud make the job mesh- or cloud-guided instead (the reference's ``elif``).
 
     Semantics of a mixed batch.  With the module in train mode -- what the reference's sampling script runs -- the VN batch-norm
     takes its statistics over the whole batch, so a mixed batch is not the same computation as one batch per condition, exactly as
@@ -467,6 +478,8 @@ def sample_diffusion_ligand_multi(model, conditions, num_samples, batch_size=256
         gkey, groups = guidance_groups(kind, gdata, segs)
         guide_kw = {gkey: groups} if gkey else {}
         guide_kw.update(cfg_kw, **cfg_groups(cfg_strens, cfg_boxes, segs))
+        if use_grad:
+            guide_kw.update(use_grad=True, grad_lr=grad_lr, shape_AE=shape_AE)
         r = model.sample_diffusion(
             init_ligand_pos=init_ligand_pos, init_ligand_v=init_ligand_v, batch_ligand=batch_ligand,
             ligand_shape=torch.cat([shapes[c].repeat(n, 1) for c, _f, n in segs]).to(dev), num_steps=num_steps,

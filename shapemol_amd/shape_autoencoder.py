@@ -8,7 +8,9 @@ activations: ``PointCloud_AE`` never sets ``leaky``).  State-dict keys follow th
 ``fc_out``; the residual blocks are registered here as ``blocks.{i}.fc_0.*`` / ``fc_1.*`` -- in the reference they live in a
 plain Python list, so they are neither saved in ``se_model.pt`` nor moved by ``.to()``: loading that checkpoint
 with ``strict=False`` leaves them at their initial values, exactly as the reference leaves them at random initial values.
-All arithmetic runs in libshapemol_hip.so (``shapemol_sd_*``, hand-written HIP); there is no CPU path and no backward.
+All arithmetic runs in libshapemol_hip.so (``shapemol_sd_*``, hand-written HIP); there is no CPU path.  The one derivative is
+the field's gradient with respect to the query points (``decode_grad``, ``decode_atoms_grad``, the autograd function ``field``
+and the guidance pass ``guide_atoms`` built on it); there is no gradient with respect to ``z`` or the weights.
 A module owns one library context whose per-shape workspace every call rewrites: calls of one module on different streams must
 be ordered by the caller (events or a synchronise); the first call with more shapes than any before it synchronises the device.
 """
@@ -109,6 +111,24 @@ class DecoderInner(nn.Module):
                    "shapemol_sd_debug_read")
         return a
 
+    def grad_tile(self, device):
+        """Points a workgroup of the value-and-gradient kernel takes per iteration (shapemol_field_grad_tile)."""
+        with torch.cuda.device(device):
+            return int(_lib.load().shapemol_field_grad_tile(self._context(device)))
+
+    def _decode_grad(self, p, shape_of, per_shape, z):
+        dev = p.device
+        n, b = p.shape[0], z.shape[0]
+        out = torch.empty((n,), dtype=torch.float32, device=dev)
+        grad = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.load().shapemol_field_decode_grad(self._context(dev), C.c_void_p(p.data_ptr()),
+                                                     C.c_void_p(shape_of.data_ptr()) if shape_of is not None else None, n, per_shape,
+                                                     C.c_void_p(z.data_ptr()), b, C.c_void_p(out.data_ptr()), C.c_void_p(grad.data_ptr()),
+                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, "shapemol_field_decode_grad")
+        return out, grad
+
     def _decode(self, p, shape_of, per_shape, z):
         dev = p.device
         n, b = p.shape[0], z.shape[0]
@@ -130,10 +150,8 @@ class DecoderInner(nn.Module):
             raise ValueError(f"z has {z.shape[1]} latent vectors per shape, the decoder was built for z_dim = {self.z_dim}")
         return z
 
-    @torch.no_grad()
-    def forward(self, p, z, c=None, **kwargs):
-        """p (B, T, 3), z (B, Z, 3) (or (B, 3 Z)) float32 device tensors -> (B, T): the field of shape b at its T points.
-        1 <= B <= 65535 and B * T < 2^31, else ShapeMolLibraryError before any launch; T == 0 gives an empty tensor."""
+    def _dense(self, p, z):
+        """Checked arguments of the dense forms: (x (B T, 3) float32 contiguous, z (B, Z, 3), B, T)."""
         if not isinstance(p, torch.Tensor) or not p.is_cuda:
             raise RuntimeError("p must be a tensor on a HIP device (shapemol_amd has no CPU path)")
         if p.dim() != 3 or p.shape[2] != 3:
@@ -142,14 +160,10 @@ class DecoderInner(nn.Module):
         if z.shape[0] != p.shape[0]:
             raise ValueError(f"p has {p.shape[0]} shapes, z has {z.shape[0]}")
         b, t = p.shape[0], p.shape[1]
-        x = p.to(torch.float32).contiguous().view(b * t, 3)
-        return self._decode(x, None, t, z).view(b, t)
+        return p.detach().to(torch.float32).contiguous().view(b * t, 3), z, b, t
 
-    @torch.no_grad()
-    def decode_atoms(self, pos, batch, z):
-        """The field of shape batch[i] at pos[i]: pos (N, 3) float32, batch (N,) integer in [0, B) in any order, z (B, Z, 3)
-        -> (N,).  The natural use: the signed distance or occupancy of every generated atom under its molecule's shape
-        condition.  An entry of batch outside [0, B) raises ValueError (checked with device ops before the call)."""
+    def _atoms(self, pos, batch, z):
+        """Checked arguments of the per-atom forms: (pos (N, 3) float32 contiguous, batch (N,) integer, z (B, Z, 3))."""
         if not isinstance(pos, torch.Tensor) or not pos.is_cuda or not isinstance(batch, torch.Tensor) or not batch.is_cuda:
             raise RuntimeError("pos and batch must be tensors on a HIP device (shapemol_amd has no CPU path)")
         if pos.dim() != 2 or pos.shape[1] != 3 or batch.dim() != 1 or batch.shape[0] != pos.shape[0]:
@@ -160,7 +174,83 @@ class DecoderInner(nn.Module):
         n, b = pos.shape[0], z.shape[0]
         if n and bool(((batch < 0) | (batch >= b)).any()):
             raise ValueError(f"batch must lie in [0, {b}) (the number of shapes in z); got values from {int(batch.min())} to {int(batch.max())}")
-        return self._decode(pos.to(torch.float32).contiguous(), batch.to(torch.int32).contiguous(), 0, z)
+        return pos.detach().to(torch.float32).contiguous(), batch, z
+
+    @torch.no_grad()
+    def forward(self, p, z, c=None, **kwargs):
+        """p (B, T, 3), z (B, Z, 3) (or (B, 3 Z)) float32 device tensors -> (B, T): the field of shape b at its T points.
+        1 <= B <= 65535 and B * T < 2^31, else ShapeMolLibraryError before any launch; T == 0 gives an empty tensor."""
+        x, z, b, t = self._dense(p, z)
+        return self._decode(x, None, t, z).view(b, t)
+
+    @torch.no_grad()
+    def decode_atoms(self, pos, batch, z):
+        """The field of shape batch[i] at pos[i]: pos (N, 3) float32, batch (N,) integer in [0, B) in any order, z (B, Z, 3)
+        -> (N,).  The natural use: the signed distance or occupancy of every generated atom under its molecule's shape
+        condition.  An entry of batch outside [0, B) raises ValueError (checked with device ops before the call)."""
+        pos, batch, z = self._atoms(pos, batch, z)
+        return self._decode(pos, batch.to(torch.int32).contiguous(), 0, z)
+
+    @torch.no_grad()
+    def decode_grad(self, p, z):
+        """``forward`` and its gradient with respect to the points in one kernel: -> (out (B, T), grad (B, T, 3) = d out / d p).
+        ``out`` equals ``forward(p, z)`` bit for bit.  The gradient of a ReLU network is piecewise constant: it is the one of
+        the linear piece the float32 evaluation lands in (mask = input > 0)."""
+        x, z, b, t = self._dense(p, z)
+        out, grad = self._decode_grad(x, None, t, z)
+        return out.view(b, t), grad.view(b, t, 3)
+
+    @torch.no_grad()
+    def decode_atoms_grad(self, pos, batch, z):
+        """``decode_atoms`` and its gradient: -> (out (N,), grad (N, 3)): per atom the signed distance (or occupancy) under its
+        molecule's shape condition and the direction in which it grows."""
+        pos, batch, z = self._atoms(pos, batch, z)
+        return self._decode_grad(pos, batch.to(torch.int32).contiguous(), 0, z)
+
+    @torch.no_grad()
+    def guide_atoms(self, pos, batch, z, grad_lr):
+        """One pass of the reference's gradient shape guidance (``models/molopt_score_model.py:592-615``) as one kernel: with
+        ``d`` the field of shape ``batch[i]`` at atom i and ``T`` the atom count of its molecule,
+        ``p' = p - grad_lr * (min(d, 0.5) - 0.5) * (1[d < 0.5] / T) * grad_p d``; atoms with ``d >= 0.5`` stay.  ``batch`` must be
+        sorted (``ValueError`` otherwise).  Returns a new tensor; ``pos`` is left untouched."""
+        pos, batch, z = self._atoms(pos, batch, z)
+        grad_lr = float(grad_lr)
+        if not np.isfinite(grad_lr):
+            raise ValueError(f"grad_lr must be finite, got {grad_lr}")
+        n = pos.shape[0]
+        if n > 1 and bool((batch[1:] < batch[:-1]).any()):
+            raise ValueError("batch must be sorted (atoms of a molecule are contiguous)")
+        out = pos.clone()
+        batch = batch.to(torch.int64).contiguous()
+        dev = pos.device
+        with torch.cuda.device(dev):
+            rc = _lib.load().shapemol_field_guide(self._context(dev), C.c_void_p(out.data_ptr()), C.c_void_p(batch.data_ptr()), n,
+                                               C.c_void_p(z.data_ptr()), z.shape[0], grad_lr,
+                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, "shapemol_field_guide")
+        return out
+
+    def field(self, p, z):
+        """``forward`` as a ``torch.autograd.Function`` differentiable in ``p`` only: p (B, T, 3) -> (B, T), whose backward is
+        ``grad_out[..., None] * grad`` with the gradient the forward kernel saved.  For guidance rules written in torch.  A ``z``
+        that requires grad, or a second derivative, raises ``RuntimeError``."""
+        if isinstance(z, torch.Tensor) and z.requires_grad:
+            raise RuntimeError("DecoderInner.field is differentiable in p only: z must not require grad")
+        return _Field.apply(p, z, self)
+
+
+class _Field(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, z, dec):
+        out, grad = dec.decode_grad(p, z)
+        ctx.save_for_backward(grad)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # (a second derivative raises: the gradient is piecewise constant)
+    def backward(ctx, grad_out):
+        grad, = ctx.saved_tensors
+        return grad_out.unsqueeze(-1) * grad, None, None
 
 
 def _get(config, name):
@@ -188,7 +278,7 @@ class PointCloud_AE(nn.Module):
     def forward(self, inputs, z_vector, point_coord, is_training=False):
         """(latent, field) with the reference's call contract: a given cloud batch ``inputs (B, 1, N, 3)`` is encoded and takes the
         place of ``z_vector``; the field is evaluated where both a latent and ``point_coord (B, T, 3)`` exist and is ``None``
-        otherwise.  ``is_training`` always encodes and always decodes (there is still no backward)."""
+        otherwise.  ``is_training`` always encodes and always decodes (there is no backward through ``z`` or the weights)."""
         if is_training or inputs is not None:
             latent = self.encoder(inputs)
         else:

@@ -9,7 +9,11 @@ and, as the baseline the kernel is judged against, the same MLP evaluated with t
 einsum 'bmi,bni->bmn' over (B, T, 3) in one piece, on the atoms with the latent gathered per atom).  Prints one JSON line.  The achieved
 fraction is of the peak of the instruction the kernel uses, v_mfma_f32_16x16x4_f32: 157.3 TFLOP/s on an MI355X.
 
-    python tools/shape_decoder_bench.py [--reps 20] [--warmup 3]
+    python tools/shape_decoder_bench.py [--reps 20] [--warmup 3] [--grad]
+
+--grad adds, per workload, the value-and-gradient kernel (decode_grad / decode_atoms_grad) next to the decode kernel in the same
+run, torch device autograd of the same MLP (forward + autograd.grad of the sum with respect to the points), and on the atoms the
+guidance pass guide_atoms.
 """
 import argparse
 import json
@@ -74,6 +78,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--grid", type=int, default=64)
+    ap.add_argument("--grad", action="store_true")
     a = ap.parse_args()
     loss_type = "signeddist"
     sd = synth.shape_decoder_state_dict(H, Z, L, seed=19)
@@ -95,6 +100,15 @@ def main():
     res["grid"] = {"points": n, "ms_median": med, "ms_min": best, "points_per_s": n / med * 1e3, "tflops": n * flops_per_point() / med / 1e9,
                    "fraction_of_peak": n * flops_per_point() / (med * 1e-3) / PEAK_FP32_MFMA, "torch_ms_median": tmed, "torch_ms_min": tbest,
                    "speedup_vs_torch": tmed / med, "max_abs_diff_vs_torch": d}
+    if a.grad:
+        def torch_grad(p, shape_of, zz):
+            q = p.clone().requires_grad_(True)
+            return torch.autograd.grad(ref(q, shape_of, zz).sum(), q)[0]
+        gmed, gbest = timed(lambda: dec.decode_grad(pts, z), a.reps, a.warmup)
+        tgmed, tgbest = timed(lambda: torch_grad(pts, None, z), max(3, a.reps // 4), 1)
+        gd = float((dec.decode_grad(pts, z)[1] - torch_grad(pts, None, z)).abs().max())
+        res["grid"].update(grad_ms_median=gmed, grad_ms_min=gbest, grad_over_decode=gmed / med, torch_autograd_ms_median=tgmed,
+                           torch_autograd_ms_min=tgbest, grad_speedup_vs_torch_autograd=tgmed / gmed, grad_max_abs_diff_vs_torch=gd)
     # atoms workload
     M = 256
     counts = 9 + synth.hash_u24(M, 631, 5) % 26
@@ -108,6 +122,12 @@ def main():
     res["atoms"] = {"molecules": M, "points": n, "ms_median": med, "ms_min": best, "points_per_s": n / med * 1e3,
                     "fraction_of_peak": n * flops_per_point() / (med * 1e-3) / PEAK_FP32_MFMA, "torch_ms_median": tmed, "torch_ms_min": tbest,
                     "speedup_vs_torch": tmed / med, "max_abs_diff_vs_torch": d}
+    if a.grad:
+        gmed, gbest = timed(lambda: dec.decode_atoms_grad(pos, batch, zm), a.reps, a.warmup)
+        umed, ubest = timed(lambda: dec.guide_atoms(pos, batch, zm, 1.0), a.reps, a.warmup)
+        tgmed, tgbest = timed(lambda: torch_grad(pos, batch, zm), a.reps, a.warmup)
+        res["atoms"].update(grad_ms_median=gmed, grad_ms_min=gbest, grad_over_decode=gmed / med, guide_ms_median=umed, guide_ms_min=ubest,
+                            torch_autograd_ms_median=tgmed, torch_autograd_ms_min=tgbest, grad_speedup_vs_torch_autograd=tgmed / gmed)
     print(json.dumps(res))
 
 
