@@ -344,6 +344,26 @@ int shapemol_set_field_guidance(shapemol_ctx *ctx, shapemol_sd_ctx *sd, double g
  * behind _decode_grad / _guide (a divisor of the former). */
 int64_t shapemol_sd_tile(const shapemol_sd_ctx *ctx);
 int64_t shapemol_field_grad_tile(const shapemol_sd_ctx *ctx);
+/* Training the decoder.  One call is the forward and the whole backward of a loss whose gradient with respect to the field is
+ * d_upstream: dense form only (shape b owns points b * points_per_shape .. (b + 1) * points_per_shape - 1 of d_p).
+ *   d_upstream (B T) f32 DEVICE  dLoss / d out (for occupancy the kernel multiplies by s (1 - s) itself)
+ *   d_out      (B T) f32 DEVICE or NULL: the value, bit for bit shapemol_sd_decode's
+ *   d_grad_p   (B T,3) or NULL, d_grad_z (B,latent,3), d_grad_weights (shapemol_sd_weight_count floats, in the order of the
+ *              weights of shapemol_sd_create): every element is written
+ * Deterministic: no atomics, every sum over points and shapes in a fixed order; two calls on the same inputs give the same bits.
+ * The points are taken in chunks of chunk_points (a multiple of shapemol_field_train_tile; 0 = one tile per compute unit); the
+ * workspace is sized by the chunk, not by B T, and like the per-shape workspace it grows behind a device synchronise and
+ * serves one stream at a time.  Refused: what shapemol_sd_decode refuses, a NULL upstream, a chunk that is no multiple of the
+ * tile. */
+int shapemol_field_train(shapemol_sd_ctx *ctx, const float *d_p, int64_t n_shapes, int64_t points_per_shape, const float *d_z,
+                         const float *d_upstream, float *d_out, float *d_grad_p, float *d_grad_z, float *d_grad_weights,
+                         int64_t chunk_points, void *stream);
+/* New weights for an existing context from DEVICE memory: d_weights holds shapemol_sd_weight_count floats in the order of
+ * shapemol_sd_create.  One kernel on `stream` rewrites the forward and transposed images, the biases, w_0 and w_out; nothing
+ * touches the host or synchronises.  The context's identity advances, so a chain step captured with the old field
+ * (shapemol_set_field_guidance) is captured again.  One stream at a time, as every use of the context. */
+int shapemol_field_load_weights(shapemol_sd_ctx *ctx, const float *d_weights, size_t n_weights, void *stream);
+int64_t shapemol_field_train_tile(const shapemol_sd_ctx *ctx);
 /* Diagnostics (tests only): the per-shape prologue of the last _decode, copied to HOST memory after a device synchronise;
  * n_bytes must be the exact size for its B = n_shapes: SHAPEMOL_SD_ZINV (B,latent) f32 z_inv = sum_xyz z * z_in(z),
  * SHAPEMOL_SD_G (B,H,3) f32 G = W_z z and SHAPEMOL_SD_C (B,H) f32 c = W_inv z_inv + bias of the factored fc_in

@@ -5,7 +5,7 @@ Public surface (mirrors the reference's models/molopt_score_model.py):
 and, outside it, the frozen shape encoder that produces the conditioning (models/shape_pointcloud_modelAE.py):
     VN_DGCNN_Encoder
 and the auto-encoder it is half of, with the decoder that evaluates the field a latent encodes:
-    PointCloud_AE, DecoderInner
+    PointCloud_AE, DecoderInner      (training: DecoderInner.train_field, PointCloud_AE.get_generator_train_loss)
 plus helpers: synthetic weights/inputs (synth), schedules (diffusion), the C-ABI binding (_lib).
 """
 from .molopt_score_model import ScorePosNet3D, log_sample_categorical, pointcloud_shape_guidance, mesh_shape_guidance  # noqa: F401

@@ -31,7 +31,7 @@ EXPORTS = (
     "shapemol_se_max_points", "shapemol_se_debug_stop_after", "shapemol_se_debug_read",
     "shapemol_sd_weight_count", "shapemol_sd_create", "shapemol_sd_destroy", "shapemol_sd_decode",
     "shapemol_sd_tile", "shapemol_sd_debug_read", "shapemol_field_decode_grad", "shapemol_field_guide", "shapemol_field_grad_tile",
-    "shapemol_set_field_guidance",
+    "shapemol_set_field_guidance", "shapemol_field_train", "shapemol_field_load_weights", "shapemol_field_train_tile",
 )
 
 
@@ -159,6 +159,10 @@ def load():
     lib.shapemol_field_grad_tile.restype = i64
     lib.shapemol_field_decode_grad.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp]
     lib.shapemol_field_guide.argtypes = [vp, vp, vp, i64, vp, i64, C.c_double, vp]
+    lib.shapemol_field_train.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.shapemol_field_load_weights.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.shapemol_field_train_tile.argtypes = [vp]
+    lib.shapemol_field_train_tile.restype = i64
     lib.shapemol_set_field_guidance.argtypes = [vp, vp, C.c_double, i32]
     lib.shapemol_sd_debug_read.argtypes = [vp, i32, vp, C.c_size_t]
     lib.shapemol_profile_begin.argtypes = [vp]

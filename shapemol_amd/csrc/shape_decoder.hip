@@ -1,8 +1,9 @@
 // C ABI of the device shape decoder (include/shapemol_hip.h, shapemol_sd_*): DecoderInner.forward of the reference
 // (models/shape_pointcloud_modelAE.py:21-103), its gradient with respect to the query points and the gradient shape guidance
-// built on it.  Kernels: sm_shape_dec.h, sm_shape_dec_grad.h.
+// built on it, and the training step (weight and latent gradients, weights from device memory).  Kernels: sm_shape_dec.h,
+// sm_shape_dec_grad.h, sm_shape_dec_train.h.
 #include "../../include/shapemol_hip.h"
-#include "sm_shape_dec_grad.h"
+#include "sm_shape_dec_train.h"
 
 #include <hip/hip_ext.h>
 
@@ -42,6 +43,14 @@ struct shapemol_sd_ctx {
     // shapemol_field_guide: the batch vector as int32 [capN] and the molecules' first atoms [capM + 1]
     int64_t capN = 0, capM = 0;
     int *shape_of = nullptr, *mol_off = nullptr;
+    // shapemol_field_train: the chunk workspace (slots, up: capT points; partials of capSplits splits), the float64 accumulators
+    // of the blocks' gradients, and per shape (capS) the fc_in sums and dz_inv.  Grown like the per-shape workspace: behind a
+    // device synchronise, one stream at a time
+    size_t n_weights = 0;
+    int64_t capT = 0, capS = 0;
+    int capSplits = 0;
+    float *tr_slots = nullptr, *tr_up = nullptr, *tr_pw = nullptr, *tr_dzinv = nullptr;
+    double *tr_pb = nullptr, *tr_accW = nullptr, *tr_accS = nullptr;
 };
 
 namespace {
@@ -126,8 +135,10 @@ int shapemol_sd_create(int32_t hidden, int32_t latent, int32_t layer_num, int32_
     const int lds_all = (int)(((size_t)2 * kSdImg + (size_t)2 * kMaxLayers * H) * sizeof(float));
     SDCHK(hipFuncSetAttribute((const void *)sd_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_all <= lds ? lds_all : (int)lds_bytes));
     SDCHK(hipFuncSetAttribute((const void *)sd_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_all <= lds ? lds_all : (int)lds_bytes));
+    SDCHK(hipFuncSetAttribute((const void *)sd_train_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_all <= lds ? lds_all : (int)lds_bytes));
     auto *c = new shapemol_sd_ctx();
     c->ws_gen = sd_next_identity();
+    c->n_weights = need;
     c->Z = Z; c->L = L; c->sigmoid = loss_type == SHAPEMOL_SD_OCCUPANCY; c->device = device; c->n_cu = n_cu > 0 ? n_cu : 1; c->lds_bytes = lds_bytes;
     std::vector<float> img;
     auto put = [&](const float *src, size_t n) { const size_t o = (img.size() + 63) & ~size_t(63); img.resize(o + n); std::memcpy(&img[o], src, n * 4); return o; };
@@ -171,7 +182,8 @@ void shapemol_sd_destroy(shapemol_sd_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    for (void *q : {(void *)c->zinv, (void *)c->gc, (void *)c->d_w, (void *)c->shape_of, (void *)c->mol_off}) if (q) hipFree(q);
+    for (void *q : {(void *)c->zinv, (void *)c->gc, (void *)c->d_w, (void *)c->shape_of, (void *)c->mol_off, (void *)c->tr_slots, (void *)c->tr_up,
+                    (void *)c->tr_pw, (void *)c->tr_dzinv, (void *)c->tr_pb, (void *)c->tr_accW, (void *)c->tr_accS}) if (q) hipFree(q);
     delete c;
 }
 
@@ -232,6 +244,100 @@ int shapemol_field_guide(shapemol_sd_ctx *c, float *d_pos, const int64_t *d_batc
     const int64_t work = n_atoms > n_shapes + 1 ? n_atoms : n_shapes + 1;
     hipLaunchKernelGGL(sd_batch_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, d_batch, (int)n_atoms, (int)n_shapes, c->shape_of, c->mol_off);
     return shapemol_sd_chain_guide_(c, d_pos, c->shape_of, c->mol_off, n_atoms, n_shapes, grad_lr, nullptr, 0, 0, s, nullptr, nullptr);
+}
+
+// ---- training (sm_shape_dec_train.h) -----------------------------------------------------------------------------------------
+int64_t shapemol_field_train_tile(const shapemol_sd_ctx *c) { return c ? kSdTrainTile : 0; }
+
+int shapemol_field_load_weights(shapemol_sd_ctx *c, const float *d_weights, size_t n_weights, void *stream) {
+    if (!c) return sd_fail("shapemol_field_load_weights: null context");
+    if (!d_weights) return sd_fail("shapemol_field_load_weights: null argument");
+    if (n_weights != c->n_weights)
+        return sd_fail("shapemol_field_load_weights: weight count mismatch: " + std::to_string(n_weights) + " given, " + std::to_string(c->n_weights) + " needed");
+    SDCHK(hipSetDevice(c->device));
+    SdRepackArgs a{};
+    a.w = d_weights; a.dst = c->d_w; a.o_zin = c->o_zin; a.o_win = c->o_win; a.o_bin = c->o_bin; a.o_w0 = c->o_w0; a.o_img = c->o_img;
+    a.o_bias = c->o_bias; a.o_out = c->o_out; a.Z = c->Z; a.L = c->L;
+    hipLaunchKernelGGL(sd_repack_kernel, dim3(16, 1 + 2 * c->L), dim3(256), 0, (hipStream_t)stream, a);
+    SDCHK(hipGetLastError());
+    c->ws_gen = sd_next_identity();                        // a captured chain step was recorded with the old field: it is captured again
+    return 0;
+}
+
+int shapemol_field_train(shapemol_sd_ctx *c, const float *d_p, int64_t n_shapes, int64_t points_per_shape, const float *d_z, const float *d_upstream,
+                         float *d_out, float *d_grad_p, float *d_grad_z, float *d_grad_weights, int64_t chunk_points, void *stream) {
+    const std::string me = "shapemol_field_train";
+    if (!c) return sd_fail(me + ": null context");
+    if (points_per_shape < 0 || points_per_shape >= ((int64_t)1 << 31)) return sd_fail(me + ": points_per_shape must be in 0 .. 2^31 - 1, got " + std::to_string(points_per_shape));
+    const int64_t n_points = n_shapes * points_per_shape;
+    if (sd_check(me, c, n_points, points_per_shape, false, n_shapes)) return 1;
+    if (chunk_points < 0 || chunk_points % kSdTrainTile)
+        return sd_fail(me + ": chunk_points must be 0 (the default) or a multiple of the tile (" + std::to_string(kSdTrainTile) + "), got " + std::to_string(chunk_points));
+    if (!d_upstream) return sd_fail(me + ": null upstream gradient");
+    if (!d_z || !d_grad_z || !d_grad_weights || (n_points > 0 && !d_p)) return sd_fail(me + ": null argument");
+    SDCHK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int L = c->L, Z = c->Z;
+    if (n_points == 0) {
+        SDCHK(hipMemsetAsync(d_grad_z, 0, (size_t)n_shapes * Z * 3 * 4, s));
+        SDCHK(hipMemsetAsync(d_grad_weights, 0, c->n_weights * 4, s));
+        return 0;
+    }
+    const int64_t all_tiles = (n_points + kSdTrainTile - 1) / kSdTrainTile;
+    int64_t chunk = chunk_points ? chunk_points : (int64_t)c->n_cu * kSdTrainTile;
+    if (chunk > all_tiles * kSdTrainTile) chunk = all_tiles * kSdTrainTile;
+    auto splits_of = [](int64_t groups) { const int64_t v = (groups + 7) / 8; return (int)(v < kSdMaxSplits ? v : kSdMaxSplits); };
+    const int need_splits = splits_of(chunk / 16);
+    if (chunk > c->capT || need_splits > c->capSplits || n_shapes > c->capS) {
+        SDCHK(hipDeviceSynchronize());
+        if (chunk > c->capT || need_splits > c->capSplits) {
+            for (void *q : {(void *)c->tr_slots, (void *)c->tr_up, (void *)c->tr_pw, (void *)c->tr_pb}) if (q) hipFree(q);
+            c->tr_slots = c->tr_up = c->tr_pw = nullptr; c->tr_pb = nullptr;
+            const int64_t capT = chunk > c->capT ? chunk : c->capT;
+            const int capSplits = need_splits > c->capSplits ? need_splits : c->capSplits;
+            c->capT = 0; c->capSplits = 0;
+            SDCHK(hipMalloc((void **)&c->tr_slots, (size_t)(4 * L + 2) * capT * kSdH * 4));
+            SDCHK(hipMalloc((void **)&c->tr_up, (size_t)capT * 4));
+            SDCHK(hipMalloc((void **)&c->tr_pw, (size_t)2 * L * capSplits * kSdImg * 4));
+            SDCHK(hipMalloc((void **)&c->tr_pb, (size_t)2 * L * capSplits * kSdH * 8));
+            c->capT = capT; c->capSplits = capSplits;
+        }
+        if (!c->tr_accW) SDCHK(hipMalloc((void **)&c->tr_accW, (size_t)2 * L * (kSdImg + kSdH) * 8));
+        if (n_shapes > c->capS) {
+            for (void *q : {(void *)c->tr_accS, (void *)c->tr_dzinv}) if (q) hipFree(q);
+            c->tr_accS = nullptr; c->tr_dzinv = nullptr; c->capS = 0;
+            SDCHK(hipMalloc((void **)&c->tr_accS, (size_t)n_shapes * kSdSums * kSdH * 8));
+            SDCHK(hipMalloc((void **)&c->tr_dzinv, (size_t)n_shapes * Z * 4));
+            c->capS = n_shapes;
+        }
+    }
+    if (sd_prologue(c, d_z, n_shapes, s)) return 1;
+    const size_t slot_sz = (size_t)c->capT * kSdH;
+    const int lin_blocks = (kSdImg + kSdH + 255) / 256;
+    for (int64_t first = 0; first < n_points; first += chunk) {
+        const int64_t n = n_points - first < chunk ? n_points - first : chunk;
+        const int64_t groups = (n + kSdTrainTile - 1) / kSdTrainTile * (kSdTrainTile / 16);
+        SdTrainArgs ta{};
+        ta.d = sd_args(c, d_p + first * 3, nullptr, n, points_per_shape, n_shapes, d_out ? d_out + first : nullptr);
+        ta.first = first; ta.up_in = d_upstream + first; ta.grad = d_grad_p ? d_grad_p + first * 3 : nullptr;
+        ta.slots = c->tr_slots; ta.up = c->tr_up; ta.cap = c->capT;
+        hipLaunchKernelGGL(sd_train_kernel, dim3(sd_grid(c, n, kSdTrainTile)), dim3(kSdGradWaves * 64), c->lds_bytes, s, ta);
+        int splits = splits_of(groups);
+        const int per_split = (int)((groups + splits - 1) / splits);
+        splits = (int)((groups + per_split - 1) / per_split);
+        hipLaunchKernelGGL(sd_dw_kernel, dim3(2 * L, splits), dim3(256), 0, s, c->tr_slots, slot_sz, L, groups, per_split, c->tr_pw, c->tr_pb);
+        hipLaunchKernelGGL(sd_dw_reduce_kernel, dim3(lin_blocks, 2 * L), dim3(256), 0, s, c->tr_pw, c->tr_pb, splits, first == 0 ? 1 : 0, c->tr_accW);
+        hipLaunchKernelGGL(sd_shape_sums_kernel, dim3((unsigned)n_shapes), dim3(512), 0, s, c->tr_slots, slot_sz, L, c->tr_up, d_p + first * 3, first, n,
+                           points_per_shape, first == 0 ? 1 : 0, c->tr_accS);
+    }
+    const float *W = c->d_w;
+    hipLaunchKernelGGL(sd_prologue_back_kernel, dim3((unsigned)n_shapes), dim3(256), 0, s, d_z, W + c->o_zin, W + c->o_win, Z, c->tr_accS, c->tr_dzinv, d_grad_z);
+    const size_t n_head = (size_t)Z * Z + (size_t)kSdH * (2 * Z + 1) + kSdH, o_out = n_head + (size_t)2 * L * (kSdImg + kSdH);
+    hipLaunchKernelGGL(sd_head_weights_kernel, dim3((unsigned)((n_head + kSdH + 1 + 255) / 256)), dim3(256), 0, s, d_z, c->zinv, c->tr_dzinv, c->tr_accS, Z,
+                       (int)n_shapes, o_out, d_grad_weights);
+    hipLaunchKernelGGL(sd_dw_finish_kernel, dim3(lin_blocks, 2 * L), dim3(256), 0, s, c->tr_accW, d_grad_weights + n_head);
+    SDCHK(hipGetLastError());
+    return 0;
 }
 
 // ---- for shapemol_hip.hip (field guidance inside a chain; not in the header) -----------------------------------------------

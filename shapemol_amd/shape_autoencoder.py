@@ -8,9 +8,14 @@ activations: ``PointCloud_AE`` never sets ``leaky``).  State-dict keys follow th
 ``fc_out``; the residual blocks are registered here as ``blocks.{i}.fc_0.*`` / ``fc_1.*`` -- in the reference they live in a
 plain Python list, so they are neither saved in ``se_model.pt`` nor moved by ``.to()``: loading that checkpoint
 with ``strict=False`` leaves them at their initial values, exactly as the reference leaves them at random initial values.
-All arithmetic runs in libshapemol_hip.so (``shapemol_sd_*``, hand-written HIP); there is no CPU path.  The one derivative is
-the field's gradient with respect to the query points (``decode_grad``, ``decode_atoms_grad``, the autograd function ``field``
-and the guidance pass ``guide_atoms`` built on it); there is no gradient with respect to ``z`` or the weights.
+All arithmetic runs in libshapemol_hip.so (``shapemol_sd_*`` / ``shapemol_field_*``, hand-written HIP); there is no CPU path.
+Inference has one derivative, the field's gradient with respect to the query points (``decode_grad``, ``decode_atoms_grad``, the
+autograd function ``field`` and the guidance pass ``guide_atoms`` built on it).  Training goes through ``DecoderInner.train_field``
+(dense form only): the field as an autograd function differentiable in ``p``, ``z`` and every decoder parameter, whose backward is
+one deterministic library call (``shapemol_field_train``); ``PointCloud_AE.get_generator_train_loss`` is the reference's training
+loss on it.  The encoder has no backward, so a latent that comes from the encoder is a constant of that loss.
+Once a module has a context, changed parameters that live on the context's device are repacked there by a kernel
+(``shapemol_field_load_weights``) -- an optimiser step costs no host packing and no new context.
 A module owns one library context whose per-shape workspace every call rewrites: calls of one module on different streams must
 be ordered by the caller (events or a synchronise); the first call with more shapes than any before it synchronises the device.
 """
@@ -64,6 +69,20 @@ class DecoderInner(nn.Module):
         parts += [self.fc_out.weight, self.fc_out.bias]
         return np.concatenate([p.detach().cpu().numpy().astype(np.float32).reshape(-1) for p in parts])
 
+    def _params(self):
+        """The parameters in the order of ``_pack`` (the library's weight order)."""
+        parts = [self.z_in.map_to_feat.weight, self.fc_in.weight, self.fc_in.bias]
+        for b in self.blocks:
+            parts += [b.fc_0.weight, b.fc_0.bias, b.fc_1.weight, b.fc_1.bias]
+        return parts + [self.fc_out.weight, self.fc_out.bias]
+
+    def _load_weights(self, ctx, flat, device):
+        """Repack the context's weights from one flat float32 device vector in ``_pack`` order (a kernel on the current stream)."""
+        with torch.cuda.device(device):
+            rc = _lib.load().shapemol_field_load_weights(ctx, C.c_void_p(flat.data_ptr()), flat.numel(),
+                                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+        _lib.check(rc, "shapemol_field_load_weights")
+
     def _context(self, device):
         device = torch.device(device)
         if device.type != "cuda":
@@ -72,6 +91,12 @@ class DecoderInner(nn.Module):
             device = torch.device("cuda", torch.cuda.current_device())
         key = (str(device), self.loss_type) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._ctx is not None and key == self._key:
+            return self._ctx
+        if self._ctx is not None and key[:2] == self._key[:2] and all(p.device == device for p in self.parameters()):
+            # the same context, new values (an optimiser step, load_state_dict): repacked on the device
+            flat = torch.cat([p.detach().to(torch.float32).reshape(-1) for p in self._params()])
+            self._load_weights(self._ctx, flat, device)
+            self._key = key
             return self._ctx
         lib = _lib.load()
         self._release()
@@ -238,6 +263,27 @@ class DecoderInner(nn.Module):
             raise RuntimeError("DecoderInner.field is differentiable in p only: z must not require grad")
         return _Field.apply(p, z, self)
 
+    def train_tile(self, device):
+        """Points a workgroup of the training kernel takes per iteration (shapemol_field_train_tile); a chunk is a multiple."""
+        with torch.cuda.device(device):
+            return int(_lib.load().shapemol_field_train_tile(self._context(device)))
+
+    def train_field(self, p, z, chunk_points=0):
+        """``forward`` as a ``torch.autograd.Function`` differentiable in ``p``, ``z`` and every decoder parameter (``z_in``,
+        ``fc_in``, every block, ``fc_out``): p (B, T, 3), z (B, Z, 3) -> (B, T), equal to ``forward(p, z)`` bit for bit.  The
+        forward loads the parameters' current device values into the context and evaluates the field; the backward runs the
+        forward again inside the training call (the operands a weight gradient needs live in a workspace bounded by
+        ``chunk_points``, 0 = the library's default, so they cannot be kept from one call to the next) and returns every
+        gradient from that one call, deterministically.  Once differentiable.  The parameters must live on p's device."""
+        x, zz, b, t = self._dense(p, z)
+        dev = p.device
+        params = self._params()
+        if any(q.device != dev for q in params):
+            raise RuntimeError(f"the decoder's parameters must be on {dev}, where the points are (shapemol_amd has no CPU path)")
+        if not isinstance(z, torch.Tensor) or z.dtype != torch.float32 or p.dtype != torch.float32:
+            raise ValueError("train_field takes float32 p and z")
+        return _TrainField.apply(p, z, self, int(chunk_points), *params)
+
 
 class _Field(torch.autograd.Function):
     @staticmethod
@@ -251,6 +297,47 @@ class _Field(torch.autograd.Function):
     def backward(ctx, grad_out):
         grad, = ctx.saved_tensors
         return grad_out.unsqueeze(-1) * grad, None, None
+
+
+class _TrainField(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, z, dec, chunk_points, *params):
+        x, zz, b, t = dec._dense(p, z)
+        dev = p.device
+        flat = torch.cat([q.detach().to(torch.float32).reshape(-1) for q in params])
+        handle = dec._context(dev)                         # (repacks by itself when a parameter changed)
+        ctx.dec, ctx.dims, ctx.chunk = dec, (b, t), chunk_points
+        ctx.shapes = [q.shape for q in params]
+        ctx.z_shape = z.shape
+        ctx.save_for_backward(x, zz, flat)
+        ctx.weights_key = dec._key
+        return dec._decode(x, None, t, zz).view(b, t)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, zz, flat = ctx.saved_tensors
+        dec, (b, t) = ctx.dec, ctx.dims
+        dev = x.device
+        handle = dec._context(dev)
+        if dec._key != ctx.weights_key:                    # the module's parameters moved on since the forward: this graph's values
+            dec._load_weights(handle, flat, dev)
+            dec._key = dec._key[:2] + (None,)              # (and the next call repacks the current ones)
+        up = grad_out.detach().to(torch.float32).contiguous()
+        gp = torch.empty((b * t, 3), dtype=torch.float32, device=dev)
+        gz = torch.empty_like(zz)
+        gw = torch.empty_like(flat)
+        with torch.cuda.device(dev):
+            rc = _lib.load().shapemol_field_train(handle, C.c_void_p(x.data_ptr()), b, t, C.c_void_p(zz.data_ptr()), C.c_void_p(up.data_ptr()),
+                                                  None, C.c_void_p(gp.data_ptr()), C.c_void_p(gz.data_ptr()), C.c_void_p(gw.data_ptr()),
+                                                  ctx.chunk, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, "shapemol_field_train")
+        grads, o = [], 0
+        for shp in ctx.shapes:
+            n = int(np.prod(shp))
+            grads.append(gw[o:o + n].view(shp))
+            o += n
+        return (gp.view(b, t, 3), gz.view(ctx.z_shape), None, None, *grads)
 
 
 def _get(config, name):
@@ -300,4 +387,16 @@ class PointCloud_AE(nn.Module):
         return mse, hit.sum() / hit.numel(), (hit & occupied).sum() / n_occupied
 
     def get_train_loss(self, point_clouds, sample_points, sample_values):
-        raise NotImplementedError("PointCloud_AE.get_train_loss: the device auto-encoder has no backward; train it with the reference")
+        raise NotImplementedError("PointCloud_AE.get_train_loss: the device encoder has no backward (kNN graph features, VN batch norm); "
+                                  "get_generator_train_loss trains the generator (and a given latent) on the same loss")
+
+    def get_generator_train_loss(self, point_clouds, sample_points, sample_values, z_vector=None):
+        """The reference's ``get_train_loss`` formula, ``mean((net_out - sample_values) ** 2)``, differentiable in the generator's
+        parameters and in a given ``z_vector`` (B, Z, 3).  Without ``z_vector`` the latent is the device encoder's of
+        ``point_clouds (B, N, 3)``, under ``no_grad``: the encoder receives no gradient.  For the generator's parameters the
+        gradient is the one the reference's ``loss.backward()`` gives."""
+        if z_vector is None:
+            with torch.no_grad():
+                z_vector = self.encoder(point_clouds[:, None])
+        net_out = self.generator.train_field(sample_points, z_vector)
+        return torch.mean((net_out - sample_values) ** 2)
