@@ -7,10 +7,12 @@
 
 #include <hip/hip_ext.h>
 
+#include <array>
 #include <atomic>
 #include <cmath>
-#include <cstring>
+#include <initializer_list>
 #include <string>
+#include <utility>
 #include <vector>
 
 extern "C" void shapemol_set_error_(const char *msg);     // shapemol_hip.hip: stores the thread's last error
@@ -44,11 +46,10 @@ struct shapemol_sd_ctx {
     int64_t capN = 0, capM = 0;
     int *shape_of = nullptr, *mol_off = nullptr;
     // shapemol_field_train: the chunk workspace (slots, up: capT points; partials of capSplits splits), the float64 accumulators
-    // of the blocks' gradients, and per shape (capS) the fc_in sums and dz_inv.  Grown like the per-shape workspace: behind a
-    // device synchronise, one stream at a time
+    // of the blocks' gradients, and per shape (capS) the fc_in sums and dz_inv.  Grown like the per-shape workspace (sd_grow):
+    // behind a device synchronise, one stream at a time
     size_t n_weights = 0;
-    int64_t capT = 0, capS = 0;
-    int capSplits = 0;
+    int64_t capT = 0, capSplits = 0, capS = 0;
     float *tr_slots = nullptr, *tr_up = nullptr, *tr_pw = nullptr, *tr_dzinv = nullptr;
     double *tr_pb = nullptr, *tr_accW = nullptr, *tr_accS = nullptr;
 };
@@ -59,20 +60,51 @@ uint64_t sd_next_identity() {
     return ++counter;
 }
 
+// every device pointer a context owns: what shapemol_sd_destroy frees
+std::array<void **, 12> sd_buffers(shapemol_sd_ctx *c) {
+    return {(void **)&c->d_w, (void **)&c->zinv, (void **)&c->gc, (void **)&c->shape_of, (void **)&c->mol_off, (void **)&c->tr_slots, (void **)&c->tr_up,
+            (void **)&c->tr_pw, (void **)&c->tr_pb, (void **)&c->tr_accW, (void **)&c->tr_accS, (void **)&c->tr_dzinv};
+}
+
+// The workspace buffers that share the capacity `cap`, for `need` (bytes per buffer given for `need`): nothing when they hold
+// it, else new ones behind a device synchronise -- a kernel in flight may still use the old.  A capacity only grows.  While
+// the buffers are gone the capacity is 0 and the pointers are null, so after a failed malloc the next call grows again.
+int sd_grow(std::initializer_list<std::pair<void **, size_t>> bufs, int64_t &cap, int64_t need) {
+    if (need <= cap) return 0;
+    SDCHK(hipDeviceSynchronize());
+    for (const auto &b : bufs) { if (*b.first) hipFree(*b.first); *b.first = nullptr; }
+    cap = 0;
+    for (const auto &b : bufs) SDCHK(hipMalloc(b.first, b.second));
+    cap = need;
+    return 0;
+}
+
 // the per-shape workspace for n_shapes, then the prologue of z on stream s
 int sd_prologue(shapemol_sd_ctx *c, const float *d_z, int64_t n_shapes, hipStream_t s) {
-    if (n_shapes > c->capB) {
-        SDCHK(hipDeviceSynchronize());
-        for (void *q : {(void *)c->zinv, (void *)c->gc}) if (q) hipFree(q);
-        c->zinv = c->gc = nullptr; c->capB = 0; c->ws_gen = sd_next_identity();
-        SDCHK(hipMalloc((void **)&c->zinv, (size_t)n_shapes * c->Z * 4));
-        SDCHK(hipMalloc((void **)&c->gc, (size_t)n_shapes * kSdH * 4 * 4));
-        c->capB = n_shapes;
-    }
+    if (n_shapes > c->capB) c->ws_gen = sd_next_identity();                    // a captured chain step holds gc
+    if (sd_grow({{(void **)&c->zinv, (size_t)n_shapes * c->Z * 4}, {(void **)&c->gc, (size_t)n_shapes * kSdH * 4 * 4}}, c->capB, n_shapes)) return 1;
     c->lastB = n_shapes;
     const float *W = c->d_w;
     hipLaunchKernelGGL(sd_prologue_kernel, dim3((unsigned)n_shapes), dim3(256), 0, s, d_z, W + c->o_zin, W + c->o_win, W + c->o_bin, c->Z, c->zinv, c->gc);
     return 0;
+}
+
+// the offsets of the context's block, every piece on a 64-float boundary; returns the block's floats
+size_t sd_layout(shapemol_sd_ctx *c) {
+    size_t end = 0;
+    auto put = [&](size_t n) { const size_t o = (end + 63) & ~size_t(63); end = o + n; return o; };
+    const size_t H = kSdH, Z = c->Z, L = c->L;
+    c->o_zin = put(Z * Z); c->o_win = put(H * (2 * Z + 1)); c->o_bin = put(H); c->o_w0 = put(H);
+    c->o_img = put(4 * L * kSdImg); c->o_bias = put(2 * L * H); c->o_out = put(H + 1);
+    return end;
+}
+
+// the block's contents from a flat device vector in the weights' order (sd_repack_kernel, sm_shape_dec.h)
+void sd_repack(const shapemol_sd_ctx *c, const float *d_weights, hipStream_t s) {
+    SdRepackArgs a{};
+    a.w = d_weights; a.dst = c->d_w; a.o_zin = c->o_zin; a.o_win = c->o_win; a.o_bin = c->o_bin; a.o_w0 = c->o_w0; a.o_img = c->o_img;
+    a.o_bias = c->o_bias; a.o_out = c->o_out; a.Z = c->Z; a.L = c->L;
+    hipLaunchKernelGGL(sd_repack_kernel, dim3(16, 1 + 2 * c->L), dim3(256), 0, s, a);
 }
 
 SdArgs sd_args(const shapemol_sd_ctx *c, const float *d_p, const int32_t *d_shape_of, int64_t n_points, int64_t points_per_shape, int64_t n_shapes, float *d_out) {
@@ -140,39 +172,19 @@ int shapemol_sd_create(int32_t hidden, int32_t latent, int32_t layer_num, int32_
     c->ws_gen = sd_next_identity();
     c->n_weights = need;
     c->Z = Z; c->L = L; c->sigmoid = loss_type == SHAPEMOL_SD_OCCUPANCY; c->device = device; c->n_cu = n_cu > 0 ? n_cu : 1; c->lds_bytes = lds_bytes;
-    std::vector<float> img;
-    auto put = [&](const float *src, size_t n) { const size_t o = (img.size() + 63) & ~size_t(63); img.resize(o + n); std::memcpy(&img[o], src, n * 4); return o; };
-    const float *p = w;
-    c->o_zin = put(p, (size_t)Z * Z); p += (size_t)Z * Z;
-    const float *w_in = p;
-    c->o_win = put(p, (size_t)H * (2 * Z + 1)); p += (size_t)H * (2 * Z + 1);
-    c->o_bin = put(p, H); p += H;
-    std::vector<float> w0(H);
-    for (int h = 0; h < H; ++h) w0[h] = w_in[(size_t)h * (2 * Z + 1)];
-    c->o_w0 = put(w0.data(), H);
-    // A fragments of sd_decode_kernel, k in the order of the accumulator layout (sm_shape_dec.h); behind the 2 L images, for
-    // sd_grad_kernel's way back, those of the transposes in reverse order: image 2 L + k is W^T of image 2 L - 1 - k
-    std::vector<float> im((size_t)4 * L * kSdImg), bias((size_t)2 * L * H);
-    for (int i = 0; i < 2 * L; ++i) {
-        const float *W = p; p += (size_t)H * H;
-        std::memcpy(&bias[(size_t)i * H], p, H * 4); p += H;
-        float *fw = &im[(size_t)i * kSdImg], *bw = &im[(size_t)(4 * L - 1 - i) * kSdImg];
-        for (int to = 0; to < 8; ++to)
-            for (int ti = 0; ti < 8; ++ti)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const size_t e = ((size_t)(to * 8 + ti) * 64 + lane) * 4 + r;
-                        const int row = 16 * to + (lane & 15), col = 16 * ti + 4 * (lane >> 4) + r;
-                        fw[e] = W[(size_t)row * H + col];
-                        bw[e] = W[(size_t)col * H + row];
-                    }
-    }
-    c->o_img = put(im.data(), im.size());
-    c->o_bias = put(bias.data(), bias.size());
-    c->o_out = put(p, H + 1); p += H + 1;
-    if (hipMalloc((void **)&c->d_w, img.size() * 4) != hipSuccess || hipMemcpy(c->d_w, img.data(), img.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    // the block, then its contents by the kernel that holds the layout (sd_repack_kernel), from a staging copy of w
+    const size_t n_block = sd_layout(c);
+    float *stage = nullptr;
+    hipError_t e = hipMalloc((void **)&c->d_w, n_block * 4);
+    if (e == hipSuccess) e = hipMemset(c->d_w, 0, n_block * 4);               // (the alignment gaps)
+    if (e == hipSuccess) e = hipMalloc((void **)&stage, need * 4);
+    if (e == hipSuccess) e = hipMemcpy(stage, w, need * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { sd_repack(c, stage, nullptr); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (stage) hipFree(stage);
+    if (e != hipSuccess) {
         if (c->d_w) hipFree(c->d_w);
-        delete c; return sd_fail("shapemol_sd_create: device allocation failed");
+        delete c; return sd_fail(std::string("shapemol_sd_create: device allocation failed: ") + hipGetErrorString(e));
     }
     *out = c;
     return 0;
@@ -182,8 +194,7 @@ void shapemol_sd_destroy(shapemol_sd_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    for (void *q : {(void *)c->zinv, (void *)c->gc, (void *)c->d_w, (void *)c->shape_of, (void *)c->mol_off, (void *)c->tr_slots, (void *)c->tr_up,
-                    (void *)c->tr_pw, (void *)c->tr_dzinv, (void *)c->tr_pb, (void *)c->tr_accW, (void *)c->tr_accS}) if (q) hipFree(q);
+    for (void **q : sd_buffers(c)) if (*q) hipFree(*q);
     delete c;
 }
 
@@ -230,16 +241,8 @@ int shapemol_field_guide(shapemol_sd_ctx *c, float *d_pos, const int64_t *d_batc
     if (!d_pos || !d_batch || !d_z) return sd_fail("shapemol_field_guide: null argument");
     SDCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (n_atoms > c->capN || n_shapes > c->capM) {
-        SDCHK(hipDeviceSynchronize());
-        for (void *q : {(void *)c->shape_of, (void *)c->mol_off}) if (q) hipFree(q);
-        c->shape_of = c->mol_off = nullptr;
-        const int64_t capN = n_atoms > c->capN ? n_atoms : c->capN, capM = n_shapes > c->capM ? n_shapes : c->capM;
-        c->capN = c->capM = 0;
-        SDCHK(hipMalloc((void **)&c->shape_of, (size_t)capN * 4));
-        SDCHK(hipMalloc((void **)&c->mol_off, (size_t)(capM + 1) * 4));
-        c->capN = capN; c->capM = capM;
-    }
+    if (sd_grow({{(void **)&c->shape_of, (size_t)n_atoms * 4}}, c->capN, n_atoms)) return 1;
+    if (sd_grow({{(void **)&c->mol_off, (size_t)(n_shapes + 1) * 4}}, c->capM, n_shapes)) return 1;
     if (sd_prologue(c, d_z, n_shapes, s)) return 1;
     const int64_t work = n_atoms > n_shapes + 1 ? n_atoms : n_shapes + 1;
     hipLaunchKernelGGL(sd_batch_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, d_batch, (int)n_atoms, (int)n_shapes, c->shape_of, c->mol_off);
@@ -255,10 +258,7 @@ int shapemol_field_load_weights(shapemol_sd_ctx *c, const float *d_weights, size
     if (n_weights != c->n_weights)
         return sd_fail("shapemol_field_load_weights: weight count mismatch: " + std::to_string(n_weights) + " given, " + std::to_string(c->n_weights) + " needed");
     SDCHK(hipSetDevice(c->device));
-    SdRepackArgs a{};
-    a.w = d_weights; a.dst = c->d_w; a.o_zin = c->o_zin; a.o_win = c->o_win; a.o_bin = c->o_bin; a.o_w0 = c->o_w0; a.o_img = c->o_img;
-    a.o_bias = c->o_bias; a.o_out = c->o_out; a.Z = c->Z; a.L = c->L;
-    hipLaunchKernelGGL(sd_repack_kernel, dim3(16, 1 + 2 * c->L), dim3(256), 0, (hipStream_t)stream, a);
+    sd_repack(c, d_weights, (hipStream_t)stream);
     SDCHK(hipGetLastError());
     c->ws_gen = sd_next_identity();                        // a captured chain step was recorded with the old field: it is captured again
     return 0;
@@ -288,29 +288,11 @@ int shapemol_field_train(shapemol_sd_ctx *c, const float *d_p, int64_t n_shapes,
     if (chunk > all_tiles * kSdTrainTile) chunk = all_tiles * kSdTrainTile;
     auto splits_of = [](int64_t groups) { const int64_t v = (groups + 7) / 8; return (int)(v < kSdMaxSplits ? v : kSdMaxSplits); };
     const int need_splits = splits_of(chunk / 16);
-    if (chunk > c->capT || need_splits > c->capSplits || n_shapes > c->capS) {
-        SDCHK(hipDeviceSynchronize());
-        if (chunk > c->capT || need_splits > c->capSplits) {
-            for (void *q : {(void *)c->tr_slots, (void *)c->tr_up, (void *)c->tr_pw, (void *)c->tr_pb}) if (q) hipFree(q);
-            c->tr_slots = c->tr_up = c->tr_pw = nullptr; c->tr_pb = nullptr;
-            const int64_t capT = chunk > c->capT ? chunk : c->capT;
-            const int capSplits = need_splits > c->capSplits ? need_splits : c->capSplits;
-            c->capT = 0; c->capSplits = 0;
-            SDCHK(hipMalloc((void **)&c->tr_slots, (size_t)(4 * L + 2) * capT * kSdH * 4));
-            SDCHK(hipMalloc((void **)&c->tr_up, (size_t)capT * 4));
-            SDCHK(hipMalloc((void **)&c->tr_pw, (size_t)2 * L * capSplits * kSdImg * 4));
-            SDCHK(hipMalloc((void **)&c->tr_pb, (size_t)2 * L * capSplits * kSdH * 8));
-            c->capT = capT; c->capSplits = capSplits;
-        }
-        if (!c->tr_accW) SDCHK(hipMalloc((void **)&c->tr_accW, (size_t)2 * L * (kSdImg + kSdH) * 8));
-        if (n_shapes > c->capS) {
-            for (void *q : {(void *)c->tr_accS, (void *)c->tr_dzinv}) if (q) hipFree(q);
-            c->tr_accS = nullptr; c->tr_dzinv = nullptr; c->capS = 0;
-            SDCHK(hipMalloc((void **)&c->tr_accS, (size_t)n_shapes * kSdSums * kSdH * 8));
-            SDCHK(hipMalloc((void **)&c->tr_dzinv, (size_t)n_shapes * Z * 4));
-            c->capS = n_shapes;
-        }
-    }
+    if (sd_grow({{(void **)&c->tr_slots, (size_t)(4 * L + 2) * chunk * kSdH * 4}, {(void **)&c->tr_up, (size_t)chunk * 4}}, c->capT, chunk)) return 1;
+    if (sd_grow({{(void **)&c->tr_pw, (size_t)2 * L * need_splits * kSdImg * 4}, {(void **)&c->tr_pb, (size_t)2 * L * need_splits * kSdH * 8}}, c->capSplits, need_splits))
+        return 1;
+    if (sd_grow({{(void **)&c->tr_accS, (size_t)n_shapes * kSdSums * kSdH * 8}, {(void **)&c->tr_dzinv, (size_t)n_shapes * Z * 4}}, c->capS, n_shapes)) return 1;
+    if (!c->tr_accW) SDCHK(hipMalloc((void **)&c->tr_accW, (size_t)2 * L * (kSdImg + kSdH) * 8));    // once: its size is the context's
     if (sd_prologue(c, d_z, n_shapes, s)) return 1;
     const size_t slot_sz = (size_t)c->capT * kSdH;
     const int lin_blocks = (kSdImg + kSdH + 255) / 256;

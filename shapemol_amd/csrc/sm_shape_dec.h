@@ -114,6 +114,27 @@ SM_DEV float sd_fc_out(const SdArgs &a, int g, const f32x4 (&x)[8]) {
     return s;
 }
 
+// fc_in backwards of one column, sd_fc_in's sibling: with x the gradient at fc_in's output, d/dp = 2 p (w0 . x) + G_sb^T x over the
+// column's 128 rows -- this lane's 32, then the four lane groups of the column
+SM_DEV void sd_fc_in_back(const SdArgs &a, int64_t sb, int g, float px, float py, float pz, const f32x4 (&x)[8], float &gx, float &gy, float &gz) {
+    const float *gcb = a.gc + sb * (kSdH * 4);
+    float s0 = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const float4 w0 = ldg4(a.w0 + 16 * t + 4 * g);
+        const float w0r[4] = {w0.x, w0.y, w0.z, w0.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float4 gc = ldg4(gcb + (16 * t + 4 * g + r) * 4);
+            const float gv = x[t][r];
+            s0 = fmaf(w0r[r], gv, s0); sx = fmaf(gc.x, gv, sx); sy = fmaf(gc.y, gv, sy); sz = fmaf(gc.z, gv, sz);
+        }
+    }
+    s0 += __shfl_xor(s0, 16, 64); sx += __shfl_xor(sx, 16, 64); sy += __shfl_xor(sy, 16, 64); sz += __shfl_xor(sz, 16, 64);
+    s0 += __shfl_xor(s0, 32, 64); sx += __shfl_xor(sx, 32, 64); sy += __shfl_xor(sy, 32, 64); sz += __shfl_xor(sz, 32, 64);
+    gx = fmaf(2.f * px, s0, sx); gy = fmaf(2.f * py, s0, sy); gz = fmaf(2.f * pz, s0, sz);
+}
+
 // acc[ct][to] += W relu(x[ct]) for the image at wl (LDS).  k-tile outermost: relu once per operand register, 8 * kSdColTiles
 // independent accumulator chains between two uses of the same one (CT column tiles per wave).  kRelu = false: W x[ct], the operand as it is (the
 // transposed products of sm_shape_dec_grad.h)
@@ -234,5 +255,41 @@ __global__ void __launch_bounds__(kSdWaves * 64) sd_decode_kernel(SdArgs a) {
             const float s = sd_fc_out(a, g, x[ct]);
             if (g == 0 && pt[ct] < a.n) a.out[pt[ct]] = s;
         }
+    }
+}
+
+// ---- the context's weight block from one flat vector (the one definition of the image layout) ---------------------------------
+// Behind the 2 L forward images, for the reverse sweep of sm_shape_dec_grad.h, those of the transposes in reverse order: image
+// 2 L + k is W^T of image 2 L - 1 - k.  shapemol_sd_create and shapemol_field_load_weights both launch this kernel.
+struct SdRepackArgs {
+    const float *w;          // z_in | fc_in.weight | fc_in.bias | 2 L x (weight, bias) | fc_out.weight, fc_out.bias
+    float *dst;              // the context's block
+    size_t o_zin, o_win, o_bin, o_w0, o_img, o_bias, o_out;
+    int Z, L;
+};
+// grid (x, 1 + 2 L): y == 0 the head and tail pieces, y == 1 + i Linear i (forward image i, transposed image 4 L - 1 - i, bias i)
+__global__ void __launch_bounds__(256) sd_repack_kernel(SdRepackArgs a) {
+    const int Z = a.Z, ld = 2 * Z + 1;
+    const size_t n_zin = (size_t)Z * Z, n_win = (size_t)kSdH * ld, o_lin = n_zin + n_win + kSdH;
+    if (blockIdx.y == 0) {
+        const size_t total = n_zin + n_win + kSdH + kSdH + (kSdH + 1);
+        for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+            if (e < n_zin) a.dst[a.o_zin + e] = a.w[e];
+            else if (e < n_zin + n_win) a.dst[a.o_win + (e - n_zin)] = a.w[e];
+            else if (e < o_lin) a.dst[a.o_bin + (e - n_zin - n_win)] = a.w[e];
+            else if (e < o_lin + kSdH) a.dst[a.o_w0 + (e - o_lin)] = a.w[n_zin + (e - o_lin) * ld];
+            else a.dst[a.o_out + (e - o_lin - kSdH)] = a.w[o_lin + (size_t)2 * a.L * (kSdImg + kSdH) + (e - o_lin - kSdH)];
+        }
+        return;
+    }
+    const int i = blockIdx.y - 1;
+    const float *W = a.w + o_lin + (size_t)i * (kSdImg + kSdH);
+    float *fw = a.dst + a.o_img + (size_t)i * kSdImg, *bw = a.dst + a.o_img + (size_t)(4 * a.L - 1 - i) * kSdImg;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < kSdImg + kSdH; e += gridDim.x * 256) {
+        if (e >= kSdImg) { a.dst[a.o_bias + (size_t)i * kSdH + (e - kSdImg)] = W[e]; continue; }
+        const int r = e & 3, lane = (e >> 2) & 63, ti = (e >> 8) & 7, to = e >> 11;
+        const int row = 16 * to + (lane & 15), col = 16 * ti + 4 * (lane >> 4) + r;
+        fw[e] = W[row * kSdH + col];
+        bw[e] = W[col * kSdH + row];
     }
 }

@@ -38,6 +38,18 @@ struct SdGradArgs {
     float lr;                // guidance: grad_lr
     const int *step_cur;     // chain: the device's reverse-step counter, else null (always applied)
     int t_first, grad_step;  // chain: step s is guided when t_first - s > grad_step
+
+    // sd_sweep's Mode (below)
+    static constexpr bool kTaps = false;
+    SM_DEV int64_t point(int64_t pt, float &px, float &py, float &pz) const { return sd_point(d, pt, px, py, pz); }
+    SM_DEV float top(int, int64_t, float val) const { return d.sigmoid ? val * (1.f - val) : 1.f; }
+    SM_DEV void epilogue(int64_t q, int64_t sb, float val, float px, float py, float pz, float gx, float gy, float gz) const {
+        if (pos && val < 0.5f) {                           // the guidance update
+            const int cnt = mol_off[sb + 1] - mol_off[sb];
+            const float k = lr * (val - 0.5f), inv = 1.f / (float)(cnt > 0 ? cnt : 1);
+            pos[q * 3] = px - k * (inv * gx); pos[q * 3 + 1] = py - k * (inv * gy); pos[q * 3 + 2] = pz - k * (inv * gz);
+        }
+    }
 };
 
 // bit 4 t + r = (x[t][r] > 0)
@@ -104,9 +116,16 @@ SM_DEV void sd_linear_back_residual(const float *wl, int lane, const f32x4 (&gy)
     }
 }
 
-__global__ void __launch_bounds__(kSdGradWaves * 64) sd_grad_kernel(SdGradArgs ga) {
-    if (ga.step_cur && ga.t_first - *ga.step_cur <= ga.grad_step) return;      // `if i > grad_step` (molopt_score_model.py:595)
-    const SdArgs &a = ga.d;
+// The forward and reverse sweep over a workgroup's tiles: the one body of sd_grad_kernel and of sd_train_kernel
+// (sm_shape_dec_train.h).  Mode is the kernel's argument struct; what the two kernels do differently is decided when the body is
+// specialised, never at run time:
+//     m.point(pt, px, py, pz)      the point and its shape (sd_point's contract)
+//     m.top(g, pt, val)            the factor on w_out at the top of the way back
+//     Mode::kTaps, m.tap(..)       training: the sweep's operands and upstream gradients go out to slots as they are formed
+//     m.grad                       [n][3] or null
+//     m.epilogue(..)               after value and gradient are stored
+template <class Mode>
+SM_DEV void sd_sweep(const SdArgs &a, const Mode &m) {
     extern __shared__ float wl[];                          // [2][kSdImg]: the image in use and the next one; [2 L][H] biases
     float *bl = wl + 2 * kSdImg;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
@@ -118,15 +137,16 @@ __global__ void __launch_bounds__(kSdGradWaves * 64) sd_grad_kernel(SdGradArgs g
         const bool last_tile = tile + gridDim.x >= n_tiles;
         f32x4 x[kSdGradColTiles][8], y[kSdGradColTiles][8];
         unsigned mk[kSdGradColTiles][kSdMasks];
-        int64_t pt[kSdGradColTiles], sb[kSdGradColTiles];
+        int64_t pt[kSdGradColTiles], sb[kSdGradColTiles], grp[kSdGradColTiles];
         float px[kSdGradColTiles], py[kSdGradColTiles], pz[kSdGradColTiles];
 #pragma unroll
         for (int ct = 0; ct < kSdGradColTiles; ++ct) {
 #pragma unroll
             for (int k = 0; k < kSdMasks; ++k) mk[ct][k] = 0;
-            pt[ct] = tile * kSdGradTile + (wave * kSdGradColTiles + ct) * 16 + n;
+            grp[ct] = tile * (kSdGradTile / 16) + wave * kSdGradColTiles + ct;
+            pt[ct] = grp[ct] * 16 + n;
             // (guidance: a tail lane may read the last point while its owner stores the update; a tail's result is dropped)
-            sb[ct] = sd_point(a, pt[ct], px[ct], py[ct], pz[ct]);
+            sb[ct] = m.point(pt[ct], px[ct], py[ct], pz[ct]);
             sd_fc_in(a, sb[ct], g, px[ct], py[ct], pz[ct], x[ct]);
         }
         // ---- forward: as sd_decode_kernel, keeping the masks of x (slot 2 b) and net (slot 2 b + 1) of block b
@@ -134,80 +154,85 @@ __global__ void __launch_bounds__(kSdGradWaves * 64) sd_grad_kernel(SdGradArgs g
             sd_image_barrier();                            // image i has landed; every wave has left buffer 1 (image i - 1)
             dma_to_lds(wl + kSdImg, a.img + (size_t)(i + 1) * kSdImg, kSdImg / 4, wave, kSdGradWaves, lane);
 #pragma unroll
-            for (int ct = 0; ct < kSdGradColTiles; ++ct) sd_mask_put(mk[ct], i, sd_relu_mask(x[ct]));
+            for (int ct = 0; ct < kSdGradColTiles; ++ct) {
+                sd_mask_put(mk[ct], i, sd_relu_mask(x[ct]));
+                if constexpr (Mode::kTaps) m.tap(i, grp[ct], lane, x[ct], true);
+            }
             sd_bias(bl + i * kSdH, g, y);
             sd_linear(wl, lane, x, y);
             sd_image_barrier();                            // image i + 1 has landed; every wave has left buffer 0
             dma_to_lds(wl, a.img + (size_t)(i + 2) * kSdImg, kSdImg / 4, wave, kSdGradWaves, lane);      // (i + 2 <= 2 L < 4 L)
 #pragma unroll
-            for (int ct = 0; ct < kSdGradColTiles; ++ct) sd_mask_put(mk[ct], i + 1, sd_relu_mask(y[ct]));
+            for (int ct = 0; ct < kSdGradColTiles; ++ct) {
+                sd_mask_put(mk[ct], i + 1, sd_relu_mask(y[ct]));
+                if constexpr (Mode::kTaps) m.tap(i + 1, grp[ct], lane, y[ct], true);
+            }
             sd_linear_residual(wl + kSdImg, bl + (i + 1) * kSdH, lane, g, y, x);
         }
-        // ---- fc_out, and its way back: g = w_out (.) m_last (times s (1 - s)); x becomes g
+        // ---- fc_out, and its way back: g = f w_out (.) m_last with f = m.top(..); x becomes g
         float val[kSdGradColTiles];
 #pragma unroll
         for (int ct = 0; ct < kSdGradColTiles; ++ct) {
             val[ct] = sd_fc_out(a, g, x[ct]);
-            const unsigned m = sd_relu_mask(x[ct]);
-            const float sf = a.sigmoid ? val[ct] * (1.f - val[ct]) : 1.f;
+            const unsigned mask = sd_relu_mask(x[ct]);
+            const float f = m.top(g, pt[ct], val[ct]);
+            if constexpr (Mode::kTaps) {                   // slot 4 L + 1 takes f relu(x_L)
+#pragma unroll
+                for (int t = 0; t < 8; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) y[ct][t][r] = f * fmaxf(x[ct][t][r], 0.f);
+                m.tap(n_img + 1, grp[ct], lane, y[ct], false);
+            }
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const float4 w = ldg4(a.w_out + 16 * t + 4 * g);
-                x[ct][t] = f32x4{w.x * sf, w.y * sf, w.z * sf, w.w * sf};
+                x[ct][t] = f32x4{w.x * f, w.y * f, w.z * f, w.w * f};
             }
-            sd_mask_apply(m, x[ct]);
+            sd_mask_apply(mask, x[ct]);
         }
-        // ---- backward through the blocks: images 2 L + 2 k (W1^T) and 2 L + 2 k + 1 (W0^T) of block L - 1 - k
+        // ---- backward through the blocks: images 2 L + 2 k (W1^T) and 2 L + 2 k + 1 (W0^T) of block L - 1 - k; the taps take
+        // dY of fc_1 (g) and of fc_0 (g_y)
         for (int j = n_lin; j < n_img; j += 2) {
             const int b = (n_img - 2 - j) >> 1;
             sd_image_barrier();                            // image j has landed; every wave has left buffer 1
             dma_to_lds(wl + kSdImg, a.img + (size_t)(j + 1) * kSdImg, kSdImg / 4, wave, kSdGradWaves, lane);
 #pragma unroll
-            for (int ct = 0; ct < kSdGradColTiles; ++ct)
+            for (int ct = 0; ct < kSdGradColTiles; ++ct) {
+                if constexpr (Mode::kTaps) m.tap(n_lin + 2 * b + 1, grp[ct], lane, x[ct], false);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) y[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
             sd_linear<false>(wl, lane, x, y);              // g_y = m_y (.) (W1^T g)
             unsigned mx[kSdGradColTiles];
 #pragma unroll
             for (int ct = 0; ct < kSdGradColTiles; ++ct) {
                 sd_mask_apply(sd_mask_get(mk[ct], 2 * b + 1), y[ct]);
                 mx[ct] = sd_mask_get(mk[ct], 2 * b);
+                if constexpr (Mode::kTaps) m.tap(n_lin + 2 * b, grp[ct], lane, y[ct], false);
             }
             sd_image_barrier();                            // image j + 1 has landed; every wave has left buffer 0
             if (j + 2 < n_img || !last_tile)
                 dma_to_lds(wl, a.img + (size_t)(j + 2 < n_img ? j + 2 : 0) * kSdImg, kSdImg / 4, wave, kSdGradWaves, lane);
             sd_linear_back_residual(wl + kSdImg, lane, y, mx, x);      // g = g + m_x (.) (W0^T g_y)
         }
-        // ---- fc_in backwards: grad = 2 p (w0 . g) + G^T g over the column's 128 rows, then the epilogue
+        // ---- fc_in backwards (the tap takes g at its output), then the stores and the epilogue
 #pragma unroll
         for (int ct = 0; ct < kSdGradColTiles; ++ct) {
-            const float *gcb = a.gc + sb[ct] * (kSdH * 4);
-            float s0 = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const float4 w0 = ldg4(a.w0 + 16 * t + 4 * g);
-                const float w0r[4] = {w0.x, w0.y, w0.z, w0.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float4 gc = ldg4(gcb + (16 * t + 4 * g + r) * 4);
-                    const float gv = x[ct][t][r];
-                    s0 = fmaf(w0r[r], gv, s0); sx = fmaf(gc.x, gv, sx); sy = fmaf(gc.y, gv, sy); sz = fmaf(gc.z, gv, sz);
-                }
-            }
-            s0 += __shfl_xor(s0, 16, 64); sx += __shfl_xor(sx, 16, 64); sy += __shfl_xor(sy, 16, 64); sz += __shfl_xor(sz, 16, 64);
-            s0 += __shfl_xor(s0, 32, 64); sx += __shfl_xor(sx, 32, 64); sy += __shfl_xor(sy, 32, 64); sz += __shfl_xor(sz, 32, 64);
-            const float gx = fmaf(2.f * px[ct], s0, sx), gy = fmaf(2.f * py[ct], s0, sy), gz = fmaf(2.f * pz[ct], s0, sz);
+            if constexpr (Mode::kTaps) m.tap(n_img, grp[ct], lane, x[ct], false);
+            float gx, gy, gz;
+            sd_fc_in_back(a, sb[ct], g, px[ct], py[ct], pz[ct], x[ct], gx, gy, gz);
             if (g != 0 || pt[ct] >= a.n) continue;
             const int64_t q = pt[ct];
             if (a.out) a.out[q] = val[ct];
-            if (ga.grad) { ga.grad[q * 3] = gx; ga.grad[q * 3 + 1] = gy; ga.grad[q * 3 + 2] = gz; }
-            if (ga.pos && val[ct] < 0.5f) {
-                const int cnt = ga.mol_off[sb[ct] + 1] - ga.mol_off[sb[ct]];
-                const float k = ga.lr * (val[ct] - 0.5f), inv = 1.f / (float)(cnt > 0 ? cnt : 1);
-                ga.pos[q * 3] = px[ct] - k * (inv * gx); ga.pos[q * 3 + 1] = py[ct] - k * (inv * gy); ga.pos[q * 3 + 2] = pz[ct] - k * (inv * gz);
-            }
+            if (m.grad) { m.grad[q * 3] = gx; m.grad[q * 3 + 1] = gy; m.grad[q * 3 + 2] = gz; }
+            m.epilogue(q, sb[ct], val[ct], px[ct], py[ct], pz[ct], gx, gy, gz);
         }
     }
+}
+
+__global__ void __launch_bounds__(kSdGradWaves * 64) sd_grad_kernel(SdGradArgs ga) {
+    if (ga.step_cur && ga.t_first - *ga.step_cur <= ga.grad_step) return;      // `if i > grad_step` (molopt_score_model.py:595)
+    sd_sweep(ga.d, ga);
 }
 
 // shapemol_field_guide: the batch vector as the kernel wants it -- shape_of [n] = batch (int32), mol_off [B + 1] = first atom of

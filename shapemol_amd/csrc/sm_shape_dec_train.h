@@ -1,9 +1,9 @@
 // Training the shape decoder: the loss's gradient with respect to every decoder parameter, the latent z and the query points,
 // deterministic (no atomics; every sum over points and shapes in a fixed order, float64 where partials meet).
 //
-// Phase one, sd_train_kernel: sd_grad_kernel's forward and reverse sweep, call for call (so the value is the decode kernel's bit
-// for bit), with the upstream gradient u at the top (times s (1 - s) for occupancy) -- and on the way it STORES what the sweep
-// otherwise throws away, per point of the chunk:
+// Phase one, sd_train_kernel: sd_sweep (sm_shape_dec_grad.h), the very body sd_grad_kernel runs (so the value is the decode
+// kernel's bit for bit), with the upstream gradient u at the top (times s (1 - s) for occupancy) -- and on the way its taps STORE
+// what the sweep otherwise throws away, per point of the chunk:
 //     slot i          (i < 2 L)   the ReLU'd operand of Linear i            A_i  = relu(x) (i even), relu(net) (i odd)
 //     slot 2 L + i    (i < 2 L)   the upstream gradient of Linear i's output dY_i = g_y (i even), g (i odd)
 //     slot 4 L                    g at fc_in's output (after the last block backwards)
@@ -33,16 +33,6 @@ constexpr int kSdGroup = 16 * kSdH;                        // floats of a 16-poi
 constexpr int kSdSums = 7;                                 // per shape and hidden unit: G_x G_y G_z c |p|^2 e u
 constexpr int kSdMaxSplits = 64;
 
-struct SdTrainArgs {
-    SdArgs d;                // the chunk's points: d.p, d.out already offset; d.n = points of the chunk
-    int64_t first;           // index of the chunk's first point in the whole launch (its shape is (first + i) / per_shape)
-    const float *up_in;      // [n] upstream gradient (offset)
-    float *grad;             // [n][3] (offset) or null
-    float *slots;            // [4 L + 2][cap * 128]
-    float *up;               // [cap]
-    int64_t cap;             // points a slot holds (whole tiles)
-};
-
 SM_DEV void sd_store_frag(float *slot, int64_t grp, int lane, const f32x4 (&x)[8], bool relu) {
     float *dst = slot + grp * kSdGroup + lane * 4;
 #pragma unroll
@@ -53,127 +43,37 @@ SM_DEV void sd_store_frag(float *slot, int64_t grp, int lane, const f32x4 (&x)[8
     }
 }
 
-__global__ void __launch_bounds__(kSdGradWaves * 64) sd_train_kernel(SdTrainArgs ta) {
-    const SdArgs &a = ta.d;
-    extern __shared__ float wl[];                          // [2][kSdImg]; [2 L][H] biases
-    float *bl = wl + 2 * kSdImg;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
-    const int64_t n_tiles = (a.n + kSdTrainTile - 1) / kSdTrainTile;
-    const int n_lin = 2 * a.L, n_img = 4 * a.L;
-    const size_t slot_sz = (size_t)ta.cap * kSdH;
-    if ((int64_t)blockIdx.x < n_tiles) dma_to_lds(wl, a.img, kSdImg / 4, wave, kSdGradWaves, lane);
-    for (int e = threadIdx.x; e < n_lin * kSdH; e += kSdGradWaves * 64) bl[e] = a.bias[e];
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const bool last_tile = tile + gridDim.x >= n_tiles;
-        f32x4 x[kSdGradColTiles][8], y[kSdGradColTiles][8];
-        unsigned mk[kSdGradColTiles][kSdMasks];
-        int64_t pt[kSdGradColTiles], sb[kSdGradColTiles], grp[kSdGradColTiles];
-        float px[kSdGradColTiles], py[kSdGradColTiles], pz[kSdGradColTiles];
-#pragma unroll
-        for (int ct = 0; ct < kSdGradColTiles; ++ct) {
-#pragma unroll
-            for (int k = 0; k < kSdMasks; ++k) mk[ct][k] = 0;
-            grp[ct] = tile * (kSdTrainTile / 16) + wave * kSdGradColTiles + ct;
-            pt[ct] = grp[ct] * 16 + n;
-            const int64_t q = pt[ct] < a.n ? pt[ct] : a.n - 1;
-            px[ct] = a.p[q * 3]; py[ct] = a.p[q * 3 + 1]; pz[ct] = a.p[q * 3 + 2];
-            const int64_t s = (ta.first + q) / a.per_shape;
-            sb[ct] = s >= a.B ? a.B - 1 : s;
-            sd_fc_in(a, sb[ct], g, px[ct], py[ct], pz[ct], x[ct]);
-        }
-        // ---- forward, as sd_grad_kernel; the operands of both Linears of a block go out as they are formed
-        for (int i = 0; i < n_lin; i += 2) {
-            sd_image_barrier();
-            dma_to_lds(wl + kSdImg, a.img + (size_t)(i + 1) * kSdImg, kSdImg / 4, wave, kSdGradWaves, lane);
-#pragma unroll
-            for (int ct = 0; ct < kSdGradColTiles; ++ct) {
-                sd_mask_put(mk[ct], i, sd_relu_mask(x[ct]));
-                sd_store_frag(ta.slots + (size_t)i * slot_sz, grp[ct], lane, x[ct], true);
-            }
-            sd_bias(bl + i * kSdH, g, y);
-            sd_linear(wl, lane, x, y);
-            sd_image_barrier();
-            dma_to_lds(wl, a.img + (size_t)(i + 2) * kSdImg, kSdImg / 4, wave, kSdGradWaves, lane);
-#pragma unroll
-            for (int ct = 0; ct < kSdGradColTiles; ++ct) {
-                sd_mask_put(mk[ct], i + 1, sd_relu_mask(y[ct]));
-                sd_store_frag(ta.slots + (size_t)(i + 1) * slot_sz, grp[ct], lane, y[ct], true);
-            }
-            sd_linear_residual(wl + kSdImg, bl + (i + 1) * kSdH, lane, g, y, x);
-        }
-        // ---- fc_out and its way back: g = u' w_out (.) m_last, u' = u (times s (1 - s)); slot 4 L + 1 takes u' relu(x_L)
-        float val[kSdGradColTiles];
-#pragma unroll
-        for (int ct = 0; ct < kSdGradColTiles; ++ct) {
-            val[ct] = sd_fc_out(a, g, x[ct]);
-            const unsigned m = sd_relu_mask(x[ct]);
-            const float u = pt[ct] < a.n ? ta.up_in[pt[ct]] : 0.f;
-            const float uf = a.sigmoid ? u * (val[ct] * (1.f - val[ct])) : u;
-            if (g == 0) ta.up[pt[ct]] = uf;
-#pragma unroll
-            for (int t = 0; t < 8; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) y[ct][t][r] = uf * fmaxf(x[ct][t][r], 0.f);
-            sd_store_frag(ta.slots + (size_t)(n_img + 1) * slot_sz, grp[ct], lane, y[ct], false);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const float4 w = ldg4(a.w_out + 16 * t + 4 * g);
-                x[ct][t] = f32x4{w.x * uf, w.y * uf, w.z * uf, w.w * uf};
-            }
-            sd_mask_apply(m, x[ct]);
-        }
-        // ---- backward through the blocks: dY of fc_1 (g) and of fc_0 (g_y) go out
-        for (int j = n_lin; j < n_img; j += 2) {
-            const int b = (n_img - 2 - j) >> 1;
-            sd_image_barrier();
-            dma_to_lds(wl + kSdImg, a.img + (size_t)(j + 1) * kSdImg, kSdImg / 4, wave, kSdGradWaves, lane);
-#pragma unroll
-            for (int ct = 0; ct < kSdGradColTiles; ++ct) {
-                sd_store_frag(ta.slots + (size_t)(n_lin + 2 * b + 1) * slot_sz, grp[ct], lane, x[ct], false);
-#pragma unroll
-                for (int t = 0; t < 8; ++t) y[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            sd_linear<false>(wl, lane, x, y);
-            unsigned mx[kSdGradColTiles];
-#pragma unroll
-            for (int ct = 0; ct < kSdGradColTiles; ++ct) {
-                sd_mask_apply(sd_mask_get(mk[ct], 2 * b + 1), y[ct]);
-                mx[ct] = sd_mask_get(mk[ct], 2 * b);
-                sd_store_frag(ta.slots + (size_t)(n_lin + 2 * b) * slot_sz, grp[ct], lane, y[ct], false);
-            }
-            sd_image_barrier();
-            if (j + 2 < n_img || !last_tile)
-                dma_to_lds(wl, a.img + (size_t)(j + 2 < n_img ? j + 2 : 0) * kSdImg, kSdImg / 4, wave, kSdGradWaves, lane);
-            sd_linear_back_residual(wl + kSdImg, lane, y, mx, x);
-        }
-        // ---- fc_in backwards: g goes out; grad_p = 2 p (w0 . g) + G^T g
-#pragma unroll
-        for (int ct = 0; ct < kSdGradColTiles; ++ct) {
-            sd_store_frag(ta.slots + (size_t)n_img * slot_sz, grp[ct], lane, x[ct], false);
-            const float *gcb = a.gc + sb[ct] * (kSdH * 4);
-            float s0 = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const float4 w0 = ldg4(a.w0 + 16 * t + 4 * g);
-                const float w0r[4] = {w0.x, w0.y, w0.z, w0.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float4 gc = ldg4(gcb + (16 * t + 4 * g + r) * 4);
-                    const float gv = x[ct][t][r];
-                    s0 = fmaf(w0r[r], gv, s0); sx = fmaf(gc.x, gv, sx); sy = fmaf(gc.y, gv, sy); sz = fmaf(gc.z, gv, sz);
-                }
-            }
-            s0 += __shfl_xor(s0, 16, 64); sx += __shfl_xor(sx, 16, 64); sy += __shfl_xor(sy, 16, 64); sz += __shfl_xor(sz, 16, 64);
-            s0 += __shfl_xor(s0, 32, 64); sx += __shfl_xor(sx, 32, 64); sy += __shfl_xor(sy, 32, 64); sz += __shfl_xor(sz, 32, 64);
-            if (g != 0 || pt[ct] >= a.n) continue;
-            const int64_t q = pt[ct];
-            if (a.out) a.out[q] = val[ct];
-            if (ta.grad) {
-                ta.grad[q * 3] = fmaf(2.f * px[ct], s0, sx); ta.grad[q * 3 + 1] = fmaf(2.f * py[ct], s0, sy); ta.grad[q * 3 + 2] = fmaf(2.f * pz[ct], s0, sz);
-            }
-        }
+struct SdTrainArgs {
+    SdArgs d;                // the chunk's points: d.p, d.out already offset; d.n = points of the chunk
+    int64_t first;           // index of the chunk's first point in the whole launch (its shape is (first + i) / per_shape)
+    const float *up_in;      // [n] upstream gradient (offset)
+    float *grad;             // [n][3] (offset) or null
+    float *slots;            // [4 L + 2][cap * 128]
+    float *up;               // [cap]
+    int64_t cap;             // points a slot holds (whole tiles)
+
+    // sd_sweep's Mode (sm_shape_dec_grad.h)
+    static constexpr bool kTaps = true;
+    SM_DEV int64_t point(int64_t pt, float &px, float &py, float &pz) const {
+        const int64_t q = pt < d.n ? pt : d.n - 1;
+        px = d.p[q * 3]; py = d.p[q * 3 + 1]; pz = d.p[q * 3 + 2];
+        const int64_t s = (first + q) / d.per_shape;
+        return s >= d.B ? d.B - 1 : s;
     }
-}
+    // u' = u (times s (1 - s)), kept in up[]; tail lanes of the last tile take u = 0
+    SM_DEV float top(int g, int64_t pt, float val) const {
+        const float u = pt < d.n ? up_in[pt] : 0.f;
+        const float uf = d.sigmoid ? u * (val * (1.f - val)) : u;
+        if (g == 0) up[pt] = uf;
+        return uf;
+    }
+    SM_DEV void tap(int slot, int64_t grp, int lane, const f32x4 (&x)[8], bool relu) const {
+        sd_store_frag(slots + (size_t)slot * ((size_t)cap * kSdH), grp, lane, x, relu);
+    }
+    SM_DEV void epilogue(int64_t, int64_t, float, float, float, float, float, float, float) const {}
+};
+
+__global__ void __launch_bounds__(kSdGradWaves * 64) sd_train_kernel(SdTrainArgs ta) { sd_sweep(ta.d, ta); }
 
 // ---- phase two: dW_i = dY_i^T A_i over the chunk's groups, split over the groups ------------------------------------------------
 // grid (2 L, splits), 256 threads.  Wave w owns output row tiles 2 w, 2 w + 1 and all eight column tiles.
@@ -383,38 +283,4 @@ __global__ void __launch_bounds__(256) sd_dw_finish_kernel(const double *accW, f
     const int lin = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= kSdImg + kSdH) return;
     gw_blocks[(size_t)lin * (kSdImg + kSdH) + i] = (float)accW[(size_t)lin * (kSdImg + kSdH) + i];
-}
-
-// ---- weights from device memory: the context's images from one flat vector in the host packing's order ---------------------------
-struct SdRepackArgs {
-    const float *w;          // z_in | fc_in.weight | fc_in.bias | 2 L x (weight, bias) | fc_out.weight, fc_out.bias
-    float *dst;              // the context's block
-    size_t o_zin, o_win, o_bin, o_w0, o_img, o_bias, o_out;
-    int Z, L;
-};
-// grid (x, 1 + 2 L): y == 0 the head and tail pieces, y == 1 + i Linear i (forward image i, transposed image 4 L - 1 - i, bias i)
-__global__ void __launch_bounds__(256) sd_repack_kernel(SdRepackArgs a) {
-    const int Z = a.Z, ld = 2 * Z + 1;
-    const size_t n_zin = (size_t)Z * Z, n_win = (size_t)kSdH * ld, o_lin = n_zin + n_win + kSdH;
-    if (blockIdx.y == 0) {
-        const size_t total = n_zin + n_win + kSdH + kSdH + (kSdH + 1);
-        for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-            if (e < n_zin) a.dst[a.o_zin + e] = a.w[e];
-            else if (e < n_zin + n_win) a.dst[a.o_win + (e - n_zin)] = a.w[e];
-            else if (e < o_lin) a.dst[a.o_bin + (e - n_zin - n_win)] = a.w[e];
-            else if (e < o_lin + kSdH) a.dst[a.o_w0 + (e - o_lin)] = a.w[n_zin + (e - o_lin) * ld];
-            else a.dst[a.o_out + (e - o_lin - kSdH)] = a.w[o_lin + (size_t)2 * a.L * (kSdImg + kSdH) + (e - o_lin - kSdH)];
-        }
-        return;
-    }
-    const int i = blockIdx.y - 1;
-    const float *W = a.w + o_lin + (size_t)i * (kSdImg + kSdH);
-    float *fw = a.dst + a.o_img + (size_t)i * kSdImg, *bw = a.dst + a.o_img + (size_t)(4 * a.L - 1 - i) * kSdImg;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < kSdImg + kSdH; e += gridDim.x * 256) {
-        if (e >= kSdImg) { a.dst[a.o_bias + (size_t)i * kSdH + (e - kSdImg)] = W[e]; continue; }
-        const int r = e & 3, lane = (e >> 2) & 63, ti = (e >> 8) & 7, to = e >> 11;
-        const int row = 16 * to + (lane & 15), col = 16 * ti + 4 * (lane >> 4) + r;
-        fw[e] = W[row * kSdH + col];
-        bw[e] = W[col * kSdH + row];
-    }
 }

@@ -62,19 +62,21 @@ class DecoderInner(nn.Module):
         self.fc_out = nn.Linear(hidden_size, 1)
         self._ctx, self._key = None, None
 
-    def _pack(self):
-        parts = [self.z_in.map_to_feat.weight, self.fc_in.weight, self.fc_in.bias]
-        for b in self.blocks:
-            parts += [b.fc_0.weight, b.fc_0.bias, b.fc_1.weight, b.fc_1.bias]
-        parts += [self.fc_out.weight, self.fc_out.bias]
-        return np.concatenate([p.detach().cpu().numpy().astype(np.float32).reshape(-1) for p in parts])
-
     def _params(self):
-        """The parameters in the order of ``_pack`` (the library's weight order)."""
+        """The parameters in the library's weight order."""
         parts = [self.z_in.map_to_feat.weight, self.fc_in.weight, self.fc_in.bias]
         for b in self.blocks:
             parts += [b.fc_0.weight, b.fc_0.bias, b.fc_1.weight, b.fc_1.bias]
         return parts + [self.fc_out.weight, self.fc_out.bias]
+
+    def _pack(self):
+        """The host's flat float32 vector of ``_params()``."""
+        return np.concatenate([p.detach().cpu().numpy().astype(np.float32).reshape(-1) for p in self._params()])
+
+    @staticmethod
+    def _flat(params):
+        """One flat float32 vector of ``params`` on their device (what ``_load_weights`` takes)."""
+        return torch.cat([p.detach().to(torch.float32).reshape(-1) for p in params])
 
     def _load_weights(self, ctx, flat, device):
         """Repack the context's weights from one flat float32 device vector in ``_pack`` order (a kernel on the current stream)."""
@@ -94,8 +96,7 @@ class DecoderInner(nn.Module):
             return self._ctx
         if self._ctx is not None and key[:2] == self._key[:2] and all(p.device == device for p in self.parameters()):
             # the same context, new values (an optimiser step, load_state_dict): repacked on the device
-            flat = torch.cat([p.detach().to(torch.float32).reshape(-1) for p in self._params()])
-            self._load_weights(self._ctx, flat, device)
+            self._load_weights(self._ctx, self._flat(self._params()), device)
             self._key = key
             return self._ctx
         lib = _lib.load()
@@ -141,29 +142,25 @@ class DecoderInner(nn.Module):
         with torch.cuda.device(device):
             return int(_lib.load().shapemol_field_grad_tile(self._context(device)))
 
-    def _decode_grad(self, p, shape_of, per_shape, z):
+    def _launch(self, p, shape_of, per_shape, z, with_grad):
+        """shapemol_sd_decode, or with ``with_grad`` shapemol_field_decode_grad, on the current stream -> (out, grad or None)."""
         dev = p.device
         n, b = p.shape[0], z.shape[0]
         out = torch.empty((n,), dtype=torch.float32, device=dev)
-        grad = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        grad = torch.empty((n, 3), dtype=torch.float32, device=dev) if with_grad else None
+        name = "shapemol_field_decode_grad" if with_grad else "shapemol_sd_decode"
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None  # noqa: E731
         with torch.cuda.device(dev):
-            rc = _lib.load().shapemol_field_decode_grad(self._context(dev), C.c_void_p(p.data_ptr()),
-                                                     C.c_void_p(shape_of.data_ptr()) if shape_of is not None else None, n, per_shape,
-                                                     C.c_void_p(z.data_ptr()), b, C.c_void_p(out.data_ptr()), C.c_void_p(grad.data_ptr()),
-                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(rc, "shapemol_field_decode_grad")
+            args = [self._context(dev), ptr(p), ptr(shape_of), n, per_shape, ptr(z), b, ptr(out)] + ([ptr(grad)] if with_grad else [])
+            rc = getattr(_lib.load(), name)(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, name)
         return out, grad
 
+    def _decode_grad(self, p, shape_of, per_shape, z):
+        return self._launch(p, shape_of, per_shape, z, True)
+
     def _decode(self, p, shape_of, per_shape, z):
-        dev = p.device
-        n, b = p.shape[0], z.shape[0]
-        out = torch.empty((n,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().shapemol_sd_decode(self._context(dev), C.c_void_p(p.data_ptr()), C.c_void_p(shape_of.data_ptr()) if shape_of is not None else None,
-                                                n, per_shape, C.c_void_p(z.data_ptr()), b, C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(rc, "shapemol_sd_decode")
-        return out
+        return self._launch(p, shape_of, per_shape, z, False)[0]
 
     def _latent(self, z, dev):
         if not isinstance(z, torch.Tensor) or not z.is_cuda:
@@ -303,9 +300,8 @@ class _TrainField(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p, z, dec, chunk_points, *params):
         x, zz, b, t = dec._dense(p, z)
-        dev = p.device
-        flat = torch.cat([q.detach().to(torch.float32).reshape(-1) for q in params])
-        handle = dec._context(dev)                         # (repacks by itself when a parameter changed)
+        flat = dec._flat(params)
+        dec._context(p.device)                             # (repacks by itself when a parameter changed)
         ctx.dec, ctx.dims, ctx.chunk = dec, (b, t), chunk_points
         ctx.shapes = [q.shape for q in params]
         ctx.z_shape = z.shape

@@ -61,6 +61,23 @@ def test_gate_at_the_edges(case):
         assert _same(res, _run(dec, p, z, v, w, chunk_tiles * tile))          # two calls: identical bits
 
 
+@pytest.mark.parametrize("chunk_tiles", (0, 2))
+@pytest.mark.parametrize("loss_type", ("signeddist", "occupancy"))
+def test_training_sweep_is_the_gradient_sweep(loss_type, chunk_tiles):
+    """With the upstream gradient all ones the training kernel and the value-and-gradient kernel do the same operations on the
+    same operands (w * 1 and 1 * (s (1 - s)) are exact): value and point gradient are the same bits.  B = 3, T = 183: 16-point
+    groups and tiles mix shapes, and with chunks of two tiles a shape spans chunks."""
+    case = next(c for c in GC.all_cases() if c[:2] == (3, 183) and c[4] == loss_type)
+    sd, p, z = DT.case(*case)[:3]
+    dec = _decoder(case[3], case[2], loss_type, sd=sd)
+    pd, zd = p.to(DEV).requires_grad_(True), z.to(DEV).requires_grad_(True)
+    out = dec.train_field(pd, zd, chunk_points=chunk_tiles * GC.TILE)
+    out.sum().backward()
+    val, grad = dec.decode_grad(p.to(DEV), z.to(DEV))
+    assert torch.equal(out.detach(), val)
+    assert torch.equal(pd.grad, grad)
+
+
 def test_workgroups_stride_over_tiles():
     """One chunk of more tiles than the device has compute units: every workgroup takes several tiles, the last of one point."""
     case = GC.STRIDE_CASE
