@@ -486,6 +486,14 @@ int shapemol_seg_attention_backward(const float *d_q, const float *d_k, const fl
  *          "edge_waves" (waves per workgroup of the edge kernels, 1..12; 0 = automatic: ceil(jobs / CUs) [default]; a
  *                        value other than 0 also selects the separate launches),
  *          "lin_waves"  (1..16 waves per workgroup of node_linear_kernel, tuning),
+ *          "node_levels" (exact-mode node kernels: 1 = the node stage of a layer by dependency level -- node_out6_kernel (h' only),
+ *                        then node_after6_kernel (follow-up MLPs and per-node products of h' side by side in one grid) [default];
+ *                        0 = node_chain6_kernel + node_linear6_kernel.  Same results to the bit; tuning / A/B),
+ *          "after_order" (node_after6_kernel's grid: 0 = follow-up jobs first, 1 = interleaved with the linear jobs in
+ *                        proportion, 2 = linear jobs first [default]; tuning, same results),
+ *          "after_waves" (1..16 waves of node_after6_kernel's linear jobs [default 16]; the workgroup has max(H / 16,
+ *                        after_waves) waves, and up to 8 let two workgroups share a CU; tuning, same results),
+ *          "after_lin_wgs" (workgroups aimed at for node_after6_kernel's linear jobs, 0 = automatic [default]; tuning, same results),
  *          "stream_whole_rounds" (streaming edge kernels, k <= 16: 1 = tiles per workgroup rounded up to whole rounds of two; 0 =
  *                        ceil(tiles / CUs), the last round of an odd count has one tile [default]; tuning, same results),
  *          "stamps", "kstamp_sel" (clock-stamp diagnostics; only meaningful in the --stamps build).

@@ -8,3 +8,5 @@
 template __global__ void node_chain6_kernel<128>(NodeChainArgs);
 template __global__ void node_linear6_kernel<128>(NodeLinArgs);
 template __global__ void node_prologue6_kernel<128>(NodePrologueArgs);
+template __global__ void node_out6_kernel<128>(NodeChainArgs);
+template __global__ void node_after6_kernel<128>(NodeAfterArgs);

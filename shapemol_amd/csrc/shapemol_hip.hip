@@ -125,6 +125,11 @@ struct shapemol_ctx {
     int graph_fuse = 1;         // 1: kNN graph + edge weights in one launch (graph_kernel) when max_mol_atoms <= kGraphCap is known
     int x2h_chain = 1;          // 1: x2h attention and the node stage of a layer in one launch (x2h_chain16_kernel) when every wave has one job
                                 // launch (measured: 28.5 us against 15.3 + 11.1 us, eight dependent weight blocks per wave)
+    int node_levels = 1;        // 1: the exact-mode node stage as node_out6_kernel (h' only) + node_after6_kernel (follow-up MLPs and per-node products
+                                // side by side); 0: node_chain6_kernel + node_linear6_kernel
+    int after_order = 2;        // node_after6_kernel's grid: 0 follow-up jobs first, 1 interleaved with the linear jobs, 2 linear jobs first
+    int after_waves = 16;       // ... waves of its linear jobs (the workgroup has max(H / 16, after_waves) waves)
+    int after_lin_wgs = 0;      // ... workgroups aimed at for its linear jobs (0 = automatic)
     int node_f16 = 0;           // 1: node kernels on two-piece f16 operands (sm_node16.h) instead of exactly split bf16 (sm_node.h) [default 0]
     int feat_f16 = 0;           // 1: "f16 features" -- matrix products on the leading f16 piece only (one product per term instead of
                                 // three; accumulation, LayerNorm, softmax, coordinates fp32).  Reduced precision, NOT a parity mode
@@ -165,6 +170,9 @@ struct shapemol_ctx {
     // folded into an x2h kernel, the last one folded into the DDPM kernel, x2h_chain16_kernel used, streaming kernels' tiles per
     // workgroup, their grid (0, 0 on the other edge kernels), CUs}; graph_rec: those of the captured step, which a replay reports
     int64_t launch_rec[8] = {}, graph_rec[8] = {};
+    // the node stage of the last layer the most recent run_score issued (debug_read "launch_node"): {two-level form used, follow-up
+    // jobs, linear jobs, waves per workgroup, job order, column tiles per linear job, linear staging chunk, dynamic LDS bytes}
+    int64_t node_rec[8] = {};
     // the captured step depends on the batch geometry only: seed, noise and trajectory pointers live in chain_params
     // what a captured step depends on besides the options (which drop the graphs when set): sizes, guidance, and the two
     // launch decisions taken from the max_mol_atoms hint (folded coordinate update, fused graph kernel)
@@ -342,6 +350,7 @@ template <int H>
 int set_edge_attr(int KP) {
     constexpr size_t pro6 = 2 * Chain6Lds<H>::FRAG * 16 + Chain6Lds<H>::PRE * 4, pro16 = 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4;
     ATTR(pro6, node_prologue6_kernel<H>); ATTR(Chain6Lds<H>::BYTES, node_chain6_kernel<H>); ATTR(kLin6Chunk * 3 * H * 32, node_linear6_kernel<H>);
+    ATTR(Out6Lds<H>::BYTES, node_out6_kernel<H>); ATTR(After6Lds<H>::bytes(kLin6Chunk), node_after6_kernel<H>);
     ATTR(pro16, node_prologue16_kernel<H>); ATTR(Chain16Lds<H>::BYTES, node_chain16_kernel<H>); ATTR(kLin16Chunk * 2 * H * 32, node_linear16_kernel<H>);
     ATTR(pro16, node_prologue16_kernel<H, true>); ATTR(Chain16Lds<H>::BYTES, node_chain16_kernel<H, true>); ATTR(kLin16Chunk * 2 * H * 32, node_linear16_kernel<H, true>);
     return KP == 8 ? set_edge_attr_k<H, 8>() : (KP == 16 ? set_edge_attr_k<H, 16>() : set_edge_attr_k<H, 32>());
@@ -533,6 +542,38 @@ int launch_linear(shapemol_ctx *c, hipStream_t s, const char *name, const float 
     } else {
         LAUNCH(name, SMK(node_linear_kernel<H>, dim3(ogroups * agroups), dim3(nwave * 64), 0, s, a));
     }
+    return 0;
+}
+
+// The exact-mode node stage in two dependency levels: h' (node_out6_kernel), then the follow-up MLPs and the per-node products of h'
+// in one launch (node_after6_kernel).  na as for node_chain6_kernel; the products as launch_linear would compute them.
+constexpr int kAfterChunk = 6;      // linear staging chunk of 8-wave workgroups: 6 * 3 * H * 32 = 72 KB at H = 128, two workgroups per CU
+template <int H>
+int launch_node_levels(shapemol_ctx *c, hipStream_t s, const NodeChainArgs &na, const float *lin_img6, const float *add_mol, int ld_add,
+                       float *out, int ld_out, int lin_tiles) {
+    constexpr int NT = H / 16;
+    const int n = na.n_atoms, n_ct = (n + 15) / 16, n_pairs = (n_ct + CHAIN_COLS - 1) / CHAIN_COLS;
+    LAUNCH("node_chain", SMK(node_out6_kernel<H>, dim3(n_pairs), dim3(H * 4), Out6Lds<H>::BYTES, s, na));
+    const int lw = c->after_waves, bw = std::max(lw, NT);
+    const int per_cu = bw <= 8 ? 2 : 1;                   // workgroups that share a CU (128 VGPRs per lane; LDS: kAfterChunk)
+    const int slots = c->num_cu * per_cu;
+    NodeAfterArgs a{};
+    a.f[0] = na.f[0]; a.f[1] = na.f[1];
+    a.n_pairs = n_pairs; a.n_fjobs = na.n_follow * n_pairs; a.order = c->after_order;
+    int tpg = 1;
+    if (lin_tiles > 0) {      // the linear jobs fill the workgroup slots that the follow-up jobs leave, at least half of all
+        const int ogroups = (lin_tiles + lw - 1) / lw;
+        const int lin_wgs = c->after_lin_wgs > 0 ? c->after_lin_wgs : std::max(slots - a.n_fjobs, slots / 2);
+        const int want_groups = std::max(1, lin_wgs / ogroups);
+        tpg = std::max(1, (n_ct + want_groups - 1) / want_groups);
+        a.n_ljobs = ogroups * ((n_ct + tpg - 1) / tpg);
+    }
+    a.lin_chunk = std::min(tpg, per_cu == 2 ? kAfterChunk : kLin6Chunk);
+    a.lin = NodeLinArgs{na.h_out, lin_img6, add_mol, c->mol_of, out, n, lin_tiles, tpg, ld_add, ld_out, nullptr, lw};
+    const size_t shm = After6Lds<H>::bytes(a.lin_chunk);
+    const int64_t rec[8] = {1, a.n_fjobs, a.n_ljobs, bw, a.order, tpg, a.lin_chunk, (int64_t)shm};
+    std::copy(rec, rec + 8, c->node_rec);
+    LAUNCH("node_pre", SMK(node_after6_kernel<H>, dim3(a.n_fjobs + a.n_ljobs), dim3(bw * 64), shm, s, a));
     return 0;
 }
 
@@ -767,6 +808,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
     const bool graph_fused = sampling && c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && KP <= 32 && c->n_pins == 0;
     int64_t (&rec)[8] = c->launch_rec;
     std::fill(rec, rec + 8, 0);
+    std::fill(c->node_rec, c->node_rec + 8, 0);
     rec[0] = sampling; rec[1] = graph_fused; rec[7] = c->num_cu;
     if (c->edge_bf16 == 2 && nlay > 0) { rec[5] = stream_chunk(c, n); rec[6] = (stream_jobs(c, n) + rec[5] - 1) / rec[5]; }
     if (reuse_graph) {
@@ -861,14 +903,17 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
                 na.lin_img16 = c->P(Dl.lin16_img); na.add_mol = c->addp + (size_t)l * c->capB * 8 * H; na.mol_of = c->mol_of;
                 na.pre_out = c->preAB; na.n_lin_tiles = lin_tiles; na.ld_add = 8 * H; na.ld_out = 8 * H;
             }
-            if (xc_fused) { rec[4] = 1; if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
+            const bool levels = c->node_levels && c->chain_bf16 && c->lin_bf16 && !c->node_f16 && !lin_fused;
+            float *lin_add = c->addp + (size_t)l * c->capB * 8 * H;
+            if (levels) { if (launch_node_levels<H>(c, s, na, c->P(Dl.lin6_img), lin_add, 8 * H, c->preAB, 8 * H, lin_tiles)) return 1; }
+            else if (xc_fused) { rec[4] = 1; if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
             else if (c->chain_bf16 && c->node_f16 && c->feat_f16) LAUNCH("node_chain", SMK((node_chain16_kernel<H, true>), dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
             else if (c->chain_bf16 && c->node_f16) LAUNCH("node_chain", SMK(node_chain16_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
             else if (c->chain_bf16) LAUNCH("node_chain", SMK(node_chain6_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain6Lds<H>::BYTES, s, na));
             else LAUNCH("node_chain", SMK(node_chain_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), 0, s, na));
             cur_h = dst;
             // per-node halves of the edge MLPs' first Linear: h2x of this layer | x2h of the next one
-            if (!lin_fused && launch_linear<H>(c, s, "node_pre", cur_h, c->P(Dl.lin_img), c->P(Dl.lin6_img), c->P(Dl.lin16_img), c->addp + (size_t)l * c->capB * 8 * H, 8 * H,
+            if (!lin_fused && !levels && launch_linear<H>(c, s, "node_pre", cur_h, c->P(Dl.lin_img), c->P(Dl.lin6_img), c->P(Dl.lin16_img), lin_add, 8 * H,
                                  c->preAB, 8 * H, lin_tiles, n, (c->kstamp_sel == 0 && l == 0) ? c->kstamps : nullptr)) return 1;
         }
         float *x_next = (last && out_pos) ? out_pos : ((cur_x == c->x_a) ? c->x_b : c->x_a);
@@ -1241,6 +1286,10 @@ int shapemol_set_option(shapemol_ctx *c, const char *name, int64_t value) {
     else if (k == "lin_bf16") c->lin_bf16 = (int)value;
     else if (k == "chain_bf16") c->chain_bf16 = (int)value;
     else if (k == "vn_fuse") c->vn_fuse = (int)value;
+    else if (k == "node_levels") c->node_levels = value != 0;
+    else if (k == "after_order") { if (value < 0 || value > 2) return fail("after_order must be 0 (follow-up jobs first), 1 (interleaved) or 2 (linear jobs first)"); c->after_order = (int)value; }
+    else if (k == "after_waves") { if (value < 1 || value > 16) return fail("after_waves must be 1..16"); c->after_waves = (int)value; }
+    else if (k == "after_lin_wgs") { if (value < 0 || value > 4096) return fail("after_lin_wgs must be 0 (automatic) .. 4096"); c->after_lin_wgs = (int)value; }
     else if (k == "lin_waves") { if (value < 1 || value > 16) return fail("lin_waves must be 1..16"); c->lin_waves = (int)value; }
     else if (k == "stamps") c->stamp_on = (int)value;
     else if (k == "kstamp_sel") c->kstamp_sel = (int)value;
@@ -1261,6 +1310,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     if (k == "dims") { if (max_bytes < sizeof(dims)) return -1; std::memcpy(dst, dims, sizeof(dims)); return sizeof(dims); }
     if (k == "captures") { if (max_bytes < 8) return -1; std::memcpy(dst, &c->n_captures, 8); return 8; }
     if (k == "launch") { if (max_bytes < sizeof(c->launch_rec)) return -1; std::memcpy(dst, c->launch_rec, sizeof(c->launch_rec)); return sizeof(c->launch_rec); }
+    if (k == "launch_node") { if (max_bytes < sizeof(c->node_rec)) return -1; std::memcpy(dst, c->node_rec, sizeof(c->node_rec)); return sizeof(c->node_rec); }
     if (k == "nbr") { src = c->nbr; bytes = N * c->KP * 4; }
     else if (k == "ew") { src = c->ew; bytes = N * c->KP * 4; }
     else if (k == "h") { src = c->last_h; bytes = N * g.hidden_dim * 4; }

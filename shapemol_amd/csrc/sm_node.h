@@ -106,20 +106,19 @@ node_linear_kernel(NodeLinArgs a) {
 // and every wave reads ready-made B fragments: no vector work in the multiply loop at all.
 constexpr int kLin6Chunk = 8;     // column tiles staged at a time: 3 * H * 32 bytes each (12 KB at H = 128)
 
+// One workgroup's share of the product: job = (atom group) * ogroups + (group of a.nwave output blocks), `chunk` column tiles
+// staged at a time in frag ([tile][piece][NB][64]).  Called by the a.nwave waves of the job.
 template <int H>
-__global__ void __launch_bounds__(kNodeThreads)
-node_linear6_kernel(NodeLinArgs a) {
+SM_DEV void linear6_job(const NodeLinArgs &a, int job, int chunk, u32x4 *frag) {
     constexpr int NB = H / 32;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lin6_lds[];
-    u32x4 *frag = reinterpret_cast<u32x4 *>(lin6_lds);              // [tile][piece][NB][64]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = lane & 15, g = lane >> 4;
     const int nwave = a.nwave;      // (reading blockDim costs two dependent loads from the implicit kernel arguments at the head of the launch)
     const int ogroups = (a.n_out_tiles + nwave - 1) / nwave;
-    const int ot_raw = (blockIdx.x % ogroups) * nwave + wave;
+    const int ot_raw = (job % ogroups) * nwave + wave;
     const bool ot_ok = ot_raw < a.n_out_tiles;
     const int ot = ot_ok ? ot_raw : a.n_out_tiles - 1;
-    const int ag = blockIdx.x / ogroups;
+    const int ag = job / ogroups;
     const int n_ct = (a.n_atoms + 15) / 16;
     const int ct0 = ag * a.tiles_per_group, ct1 = min(ct0 + a.tiles_per_group, n_ct);
 
@@ -132,8 +131,8 @@ node_linear6_kernel(NodeLinArgs a) {
             for (int b = 0; b < NB; ++b) w[p][b] = wi[(p * NB + b) * 64];
     }
 
-    for (int cb = ct0; cb < ct1; cb += kLin6Chunk) {
-        const int nc = min(kLin6Chunk, ct1 - cb);
+    for (int cb = ct0; cb < ct1; cb += chunk) {
+        const int nc = min(chunk, ct1 - cb);
         __syncthreads();                                            // previous chunk fully consumed
         for (int idx = threadIdx.x; idx < nc * NB * 64; idx += nwave * 64) {
             const int sl = idx & 63, sb = (idx >> 6) % NB, sc = idx / (64 * NB);
@@ -173,6 +172,13 @@ node_linear6_kernel(NodeLinArgs a) {
             if (ot_ok && two && atom1 < a.n_atoms) stg4(a.out + (size_t)atom1 * a.ld_out + 16 * ot + 4 * g, float4{acc1[0], acc1[1], acc1[2], acc1[3]});
         }
     }
+}
+
+template <int H>
+__global__ void __launch_bounds__(kNodeThreads)
+node_linear6_kernel(NodeLinArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lin6_lds[];
+    linear6_job<H>(a, blockIdx.x, kLin6Chunk, reinterpret_cast<u32x4 *>(lin6_lds));
 }
 
 struct NodeMlpArgs {
@@ -911,5 +917,264 @@ node_prologue6_kernel(NodePrologueArgs a) {
 #pragma unroll
         for (int c = 0; c < CC; ++c)
             if (atom_ok(c)) stg4(a.q.out + (size_t)atom_of(c) * a.q.ld_out + f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
+// The node stage by dependency level (option node_levels = 1): only h' needs the x2h attention's output; the follow-up
+// MLPs and all per-node products read h' and nothing else.  Instead of node_chain6_kernel (h' and the follow-ups in series
+// on ceil(n_ct / 2) workgroups) + node_linear6_kernel:
+//   node_out6_kernel   : stages 0-1 of node_chain6_kernel -- h' = h + MLP_out([att | h]) -> h_out, nothing else;
+//   node_after6_kernel : one launch whose workgroups are either a follow-up job (one follow-up MLP on one pair of column
+//                        tiles: stage 2 of node_chain6_kernel for that MLP, h' staged from global memory) or a linear job
+//                        (linear6_job on h').
+// Team layout, fragment slots and the MFMA order per output element are those of node_chain6_kernel and node_linear6_kernel:
+// every output has the same bits in both forms (tests/test_gpu_node_levels.py).
+// -------------------------------------------------------------------------------------------------
+template <int H>
+struct Team6 {       // the steps of node_chain6_kernel's team of H / 16 waves over CHAIN_COLS column tiles
+    static constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS, XS = Chain6Lds<H>::XS;
+    static constexpr int LPC = NB * 4;                     // lanes per column in the normalise pass
+    static_assert(CC == 2, "the normalise pass covers exactly 32 columns");
+    const int lane = threadIdx.x & 63, ot = threadIdx.x >> 6;
+    const int n = lane & 15, g = lane >> 4;
+    const int f0 = 16 * ot + 4 * g;
+
+    template <int KB>
+    SM_DEV void load_piece(const float *img, int p, u32x4 (&w)[3][KB]) const {      // piece p of this wave's block of a split image
+        const u32x4 *wi = reinterpret_cast<const u32x4 *>(img) + (size_t)ot * 3 * KB * 64 + lane;
+#pragma unroll
+        for (int b = 0; b < KB; ++b) w[p][b] = wi[(p * KB + b) * 64];
+    }
+    template <int KB>
+    SM_DEV void load_w(const float *img, u32x4 (&w)[3][KB]) const {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) load_piece(img, p, w);
+    }
+    // acc[c] += W * X_c over KB k-steps; fragments at f[((piece * KB + b) * CC + c) * 64 + slot]
+    template <int KB>
+    SM_DEV void gemm6(const u32x4 (&w)[3][KB], const u32x4 *f, f32x4 (&acc)[CC]) const {
+#pragma unroll
+        for (int b = 0; b < KB; ++b) {
+            u32x4 xh[CC], xm[CC], xl[CC];
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+                xh[c] = f[((0 * KB + b) * CC + c) * 64 + frag_slot(b, lane)];
+                xm[c] = f[((1 * KB + b) * CC + c) * 64 + frag_slot(b, lane)];
+                xl[c] = f[((2 * KB + b) * CC + c) * 64 + frag_slot(b, lane)];
+            }
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[2][b], xh[c], acc[c]);      // smallest terms first
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[1][b], xm[c], acc[c]);
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xl[c], acc[c]);
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[1][b], xh[c], acc[c]);
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xm[c], acc[c]);
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xh[c], acc[c]);
+        }
+    }
+    SM_DEV void store_pre(float *pre, const f32x4 (&acc)[CC]) const {
+#pragma unroll
+        for (int c = 0; c < CC; ++c) stg4(pre + (c * 16 + n) * XS + f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
+    }
+    // eight floats of fragment (k-step sb, column tile sc, lane sl) -> the three piece fragments of a K = KB * 32 buffer
+    template <int KB>
+    SM_DEV void put_frag(u32x4 *fo, int sb, int sc, int sl, const float (&v)[8]) const {
+        u32x4 hi, mid, lo;
+        split3_bf16(v, hi, mid, lo);
+        u32x4 *dst = fo + (sb * CC + sc) * 64 + frag_slot(sb, sl);
+        dst[0] = hi; dst[KB * CC * 64] = mid; dst[2 * KB * CC * 64] = lo;
+    }
+    // activation of a pre-activation buffer -> fragments: LPC lanes per column, 8 features per lane
+    SM_DEV void normalise(const float *pre, int mode, const float *gam, const float *bet, u32x4 *fo) const {
+        const int col = ot * (64 / LPC) + lane / LPC, ln = lane % LPC;
+        const int b = ln >> 2, gg = ln & 3;
+        const int fa = 32 * b + 4 * gg;
+        const float4 p0 = ldg4(pre + col * XS + fa), p1 = ldg4(pre + col * XS + fa + 16);
+        float v[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+        if (mode == NODE_LN_RELU) {
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) s += v[i];
+            const float mean = seg_sum<LPC>(s) * (1.0f / H);
+            float q = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { const float d = v[i] - mean; q += d * d; }
+            const float var = seg_sum<LPC>(q) * (1.0f / H);
+            const float rstd = 1.0f / sqrtf(var + 1e-5f);
+            const float4 g0 = ldg4(gam + fa), g1 = ldg4(gam + fa + 16), b0 = ldg4(bet + fa), b1 = ldg4(bet + fa + 16);
+            const float ga[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+            const float be[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = fmaxf((v[i] - mean) * rstd * ga[i] + be[i], 0.f);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = (v[i] > 20.f ? v[i] : log1pf(expf(v[i]))) - 0.6931471805599453f;
+        }
+        put_frag<NB>(fo, b, col >> 4, gg * 16 + (col & 15), v);
+    }
+};
+
+template <int H>
+struct Out6Lds {     // one K = 2H fragment buffer (later the hidden tile) + one pre-activation buffer
+    static constexpr size_t BYTES = (size_t)2 * Chain6Lds<H>::FRAG * 16 + (size_t)Chain6Lds<H>::PRE * 4;
+};
+
+template <int H>
+__global__ void __launch_bounds__(H * 4)
+node_out6_kernel(NodeChainArgs a) {
+    using L = Chain6Lds<H>;
+    constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS;
+    extern __shared__ __attribute__((aligned(16))) unsigned char out6_lds[];
+    u32x4 *fin = reinterpret_cast<u32x4 *>(out6_lds);      // [att | h] fragments (K = 2H); later the hidden tile
+    float *pre0 = reinterpret_cast<float *>(fin + 2 * L::FRAG);
+    const Team6<H> t;
+    const int ct0 = blockIdx.x * CC;
+    auto atom_of = [&](int c) { return min((ct0 + c) * 16 + t.n, a.n_atoms - 1); };
+    auto atom_ok = [&](int c) { return (ct0 + c) * 16 + t.n < a.n_atoms; };
+
+    // ---- stage 0: weights of the output MLP; [att | h] tiles -> fragments (activation rows requested before the weights,
+    // as in node_chain6_kernel) ------------------------------------------------------------------------
+    u32x4 w1[3][2 * NB], w2[3][NB];
+    constexpr int SITER = CC * 2 * NB * 64 / (NT * 64);
+    float4 sv0[SITER], sv1[SITER];
+#pragma unroll
+    for (int it = 0; it < SITER; ++it) {
+        const int idx = threadIdx.x + it * NT * 64;
+        const int sl = idx & 63, sb = (idx >> 6) % (2 * NB), sc = idx / (64 * 2 * NB);
+        const int at = min((ct0 + sc) * 16 + (sl & 15), a.n_atoms - 1);
+        const float *src = (sb < NB ? a.att + (size_t)at * H + 32 * sb : a.h + (size_t)at * H + 32 * (sb - NB)) + 4 * (sl >> 4);
+        sv0[it] = ldg4(src); sv1[it] = ldg4(src + 16);
+    }
+    float4 hres[CC];
+#pragma unroll
+    for (int c = 0; c < CC; ++c) hres[c] = ldg4(a.h + (size_t)atom_of(c) * H + t.f0);    // residual
+    const float4 b1 = ldg4(a.b1 + t.f0), b2 = ldg4(a.b2 + t.f0);
+    t.load_w(a.w1img6, w1);
+#pragma unroll
+    for (int it = 0; it < SITER; ++it) {
+        const int idx = threadIdx.x + it * NT * 64;
+        const int sl = idx & 63, sb = (idx >> 6) % (2 * NB), sc = idx / (64 * 2 * NB);
+        const float v[8] = {sv0[it].x, sv0[it].y, sv0[it].z, sv0[it].w, sv1[it].x, sv1[it].y, sv1[it].z, sv1[it].w};
+        t.template put_frag<2 * NB>(fin, sb, sc, sl, v);
+    }
+    t.load_w(a.w2img6, w2);
+    __syncthreads();
+
+    // ---- stage 1: h' = h + W2 relu(LN(W1 [att | h] + b1)) + b2 ---------------------------------------
+    {
+        f32x4 acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b1.x, b1.y, b1.z, b1.w};
+        t.gemm6(w1, fin, acc);
+        t.store_pre(pre0, acc);
+    }
+    __syncthreads();                                       // (every wave has also finished reading fin)
+    t.normalise(pre0, NODE_LN_RELU, a.ln_g, a.ln_b, fin);
+    __syncthreads();
+    f32x4 acc[CC];
+#pragma unroll
+    for (int c = 0; c < CC; ++c) acc[c] = f32x4{b2.x, b2.y, b2.z, b2.w};
+    t.gemm6(w2, fin, acc);
+#pragma unroll
+    for (int c = 0; c < CC; ++c) {
+        const float4 hn = {acc[c][0] + hres[c].x, acc[c][1] + hres[c].y, acc[c][2] + hres[c].z, acc[c][3] + hres[c].w};
+        if (atom_ok(c)) stg4(a.h_out + (size_t)atom_of(c) * H + t.f0, hn);
+    }
+}
+
+struct NodeAfterArgs {
+    NodeLinArgs lin;              // the linear jobs' product (in = h'; nwave = waves of a linear job)
+    NodeFollow f[2];              // the follow-up MLPs on h' (= lin.in)
+    int n_pairs;                  // pairs of column tiles: follow-up job j is MLP j / n_pairs on pair j % n_pairs
+    int n_fjobs, n_ljobs;         // follow-up jobs (n_follow * n_pairs) and linear jobs of the grid
+    int order;                    // 0: follow-up jobs first, 1: the two kinds interleaved in proportion, 2: linear jobs first
+    int lin_chunk;                // column tiles a linear job stages at a time
+};
+
+template <int H>
+struct After6Lds {   // a follow-up job: one fragment buffer (h', later the hidden tile) + one pre-activation buffer
+    static constexpr size_t FOLLOW = (size_t)Chain6Lds<H>::FRAG * 16 + (size_t)Chain6Lds<H>::PRE * 4;
+    static constexpr size_t bytes(int lin_chunk) { const size_t l = (size_t)lin_chunk * 3 * H * 32; return l > FOLLOW ? l : FOLLOW; }
+};
+
+// The workgroup has max(H / 16, lin.nwave) waves; the waves a job does not use leave before its first barrier.
+template <int H>
+__global__ void __launch_bounds__(kNodeThreads)
+node_after6_kernel(NodeAfterArgs a) {
+    using L = Chain6Lds<H>;
+    constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS;
+    extern __shared__ __attribute__((aligned(16))) unsigned char after6_lds[];
+    const int blk = blockIdx.x;
+    int fj = -1, lj = -1;
+    if (a.order == 0) { if (blk < a.n_fjobs) fj = blk; else lj = blk - a.n_fjobs; }
+    else if (a.order == 2) { if (blk < a.n_ljobs) lj = blk; else fj = blk - a.n_ljobs; }
+    else {           // linear job i sits where floor(blk * n_ljobs / total) steps from i to i + 1
+        const long long tot = a.n_fjobs + a.n_ljobs;
+        const int lo = (int)((long long)blk * a.n_ljobs / tot), hi = (int)((long long)(blk + 1) * a.n_ljobs / tot);
+        if (hi > lo) lj = lo; else fj = blk - lo;
+    }
+    if (lj >= 0) {
+        if ((int)(threadIdx.x >> 6) >= a.lin.nwave) return;
+        linear6_job<H>(a.lin, lj, a.lin_chunk, reinterpret_cast<u32x4 *>(after6_lds));
+        return;
+    }
+    const Team6<H> t;
+    if (t.ot >= NT) return;
+    const NodeFollow &F = a.f[fj / a.n_pairs];
+    const int ct0 = (fj % a.n_pairs) * CC, n_atoms = a.lin.n_atoms;
+    u32x4 *fh = reinterpret_cast<u32x4 *>(after6_lds);     // fragments of h'; later the hidden tile
+    float *pre = reinterpret_cast<float *>(fh + L::FRAG);
+
+    // ---- h' tiles of the pair -> fragments (one per thread; rows requested before the weights) --------
+    static_assert(CC * NB * 64 == NT * 64, "one fragment per thread");
+    const int sl = t.lane, sb = t.ot % NB, sc = t.ot / NB;
+    const int at = min((ct0 + sc) * 16 + (sl & 15), n_atoms - 1);
+    const float *src = a.lin.in + (size_t)at * H + 32 * sb + 4 * (sl >> 4);
+    const float4 v0 = ldg4(src), v1 = ldg4(src + 16);
+    const float4 b1 = ldg4(F.b1 + t.f0);
+    u32x4 w1[3][NB], w2[3][NB];
+    t.load_w(F.w1img6, w1);
+    {
+        const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        t.template put_frag<NB>(fh, sb, sc, sl, v);
+    }
+    // second Linear's block: the low and middle pieces a stage ahead, the leading piece once the first product has freed
+    // registers (all three ahead need more than the 128 VGPRs that let two workgroups share a CU: 8 spilled)
+    const bool on = t.ot < F.nt2;
+    if (on) { t.load_piece(F.w2img6, 2, w2); t.load_piece(F.w2img6, 1, w2); }
+    __syncthreads();
+    {
+        f32x4 acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b1.x, b1.y, b1.z, b1.w};
+        t.gemm6(w1, fh, acc);
+        t.store_pre(pre, acc);
+    }
+    if (on) t.load_piece(F.w2img6, 0, w2);
+    __syncthreads();                                       // (every wave has also finished reading fh)
+    t.normalise(pre, F.mode, F.ln_g, F.ln_b, fh);
+    __syncthreads();
+    if (!on) return;
+    const float4 b = ldg4(F.b2 + t.f0);
+    f32x4 acc[CC];
+#pragma unroll
+    for (int c = 0; c < CC; ++c) acc[c] = f32x4{b.x, b.y, b.z, b.w};
+    t.gemm6(w2, fh, acc);
+#pragma unroll
+    for (int c = 0; c < CC; ++c) {
+        const int atom = (ct0 + c) * 16 + t.n;
+        if (atom >= n_atoms) continue;
+        if (t.f0 + 4 <= F.n_store && (F.ld_out & 3) == 0) {
+            stg4(F.out + (size_t)atom * F.ld_out + t.f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (t.f0 + r < F.n_store) F.out[(size_t)atom * F.ld_out + t.f0 + r] = acc[c][r];
+        }
     }
 }
