@@ -4,15 +4,13 @@
 // sm_shape_dec_grad.h, sm_shape_dec_train.h.
 #include "../../include/shapemol_hip.h"
 #include "sm_shape_dec_train.h"
+#include "sm_devmem.h"
 
 #include <hip/hip_ext.h>
 
-#include <array>
 #include <atomic>
 #include <cmath>
-#include <initializer_list>
 #include <string>
-#include <utility>
 #include <vector>
 
 extern "C" void shapemol_set_error_(const char *msg);     // shapemol_hip.hip: stores the thread's last error
@@ -33,25 +31,27 @@ constexpr int kMaxLatent = 256, kMaxLayers = 8, kMaxShapes = 65535;
 struct shapemol_sd_ctx {
     int Z = 32, L = 4, sigmoid = 0, device = 0, n_cu = 1;
     size_t lds_bytes = 0;
-    float *d_w = nullptr;
+    // device memory: every group of buffers beside the capacity it shares (sm_devmem.h: grown by grow(), freed with the context)
+    float *d_w = nullptr; DevList mem_w;
     size_t o_zin = 0, o_win = 0, o_bin = 0, o_w0 = 0, o_img = 0, o_bias = 0, o_out = 0;
     // per-shape workspace of the prologue: rewritten by every decode, so a context serves one stream at a time
     int64_t capB = 0, lastB = 0;
-    float *zinv = nullptr, *gc = nullptr;
+    float *zinv = nullptr, *gc = nullptr; DevList mem_B;
     // Identity of this context's device memory (weights and the block above), from a process-wide counter: new at create and
     // at every reallocation of the block, never used twice.  A captured chain step holds d_w and gc and is keyed on it; the
     // context's host address would not do, since a context created after another was destroyed often gets the same address
     uint64_t ws_gen = 0;
     // shapemol_field_guide: the batch vector as int32 [capN] and the molecules' first atoms [capM + 1]
     int64_t capN = 0, capM = 0;
-    int *shape_of = nullptr, *mol_off = nullptr;
+    int *shape_of = nullptr, *mol_off = nullptr; DevList mem_N, mem_M;
     // shapemol_field_train: the chunk workspace (slots, up: capT points; partials of capSplits splits), the float64 accumulators
-    // of the blocks' gradients, and per shape (capS) the fc_in sums and dz_inv.  Grown like the per-shape workspace (sd_grow):
+    // of the blocks' gradients, and per shape (capS) the fc_in sums and dz_inv.  Grown like the per-shape workspace (grow):
     // behind a device synchronise, one stream at a time
     size_t n_weights = 0;
     int64_t capT = 0, capSplits = 0, capS = 0;
     float *tr_slots = nullptr, *tr_up = nullptr, *tr_pw = nullptr, *tr_dzinv = nullptr;
     double *tr_pb = nullptr, *tr_accW = nullptr, *tr_accS = nullptr;
+    DevList mem_T, mem_splits, mem_S, mem_accW;
 };
 
 namespace {
@@ -60,29 +60,10 @@ uint64_t sd_next_identity() {
     return ++counter;
 }
 
-// every device pointer a context owns: what shapemol_sd_destroy frees
-std::array<void **, 12> sd_buffers(shapemol_sd_ctx *c) {
-    return {(void **)&c->d_w, (void **)&c->zinv, (void **)&c->gc, (void **)&c->shape_of, (void **)&c->mol_off, (void **)&c->tr_slots, (void **)&c->tr_up,
-            (void **)&c->tr_pw, (void **)&c->tr_pb, (void **)&c->tr_accW, (void **)&c->tr_accS, (void **)&c->tr_dzinv};
-}
-
-// The workspace buffers that share the capacity `cap`, for `need` (bytes per buffer given for `need`): nothing when they hold
-// it, else new ones behind a device synchronise -- a kernel in flight may still use the old.  A capacity only grows.  While
-// the buffers are gone the capacity is 0 and the pointers are null, so after a failed malloc the next call grows again.
-int sd_grow(std::initializer_list<std::pair<void **, size_t>> bufs, int64_t &cap, int64_t need) {
-    if (need <= cap) return 0;
-    SDCHK(hipDeviceSynchronize());
-    for (const auto &b : bufs) { if (*b.first) hipFree(*b.first); *b.first = nullptr; }
-    cap = 0;
-    for (const auto &b : bufs) SDCHK(hipMalloc(b.first, b.second));
-    cap = need;
-    return 0;
-}
-
 // the per-shape workspace for n_shapes, then the prologue of z on stream s
 int sd_prologue(shapemol_sd_ctx *c, const float *d_z, int64_t n_shapes, hipStream_t s) {
     if (n_shapes > c->capB) c->ws_gen = sd_next_identity();                    // a captured chain step holds gc
-    if (sd_grow({{(void **)&c->zinv, (size_t)n_shapes * c->Z * 4}, {(void **)&c->gc, (size_t)n_shapes * kSdH * 4 * 4}}, c->capB, n_shapes)) return 1;
+    SDCHK(grow(c->mem_B, {dev_buf(&c->zinv, (size_t)n_shapes * c->Z * 4), dev_buf(&c->gc, (size_t)n_shapes * kSdH * 4 * 4)}, c->capB, n_shapes));
     c->lastB = n_shapes;
     const float *W = c->d_w;
     hipLaunchKernelGGL(sd_prologue_kernel, dim3((unsigned)n_shapes), dim3(256), 0, s, d_z, W + c->o_zin, W + c->o_win, W + c->o_bin, c->Z, c->zinv, c->gc);
@@ -175,15 +156,13 @@ int shapemol_sd_create(int32_t hidden, int32_t latent, int32_t layer_num, int32_
     // the block, then its contents by the kernel that holds the layout (sd_repack_kernel), from a staging copy of w
     const size_t n_block = sd_layout(c);
     float *stage = nullptr;
-    hipError_t e = hipMalloc((void **)&c->d_w, n_block * 4);
-    if (e == hipSuccess) e = hipMemset(c->d_w, 0, n_block * 4);               // (the alignment gaps)
-    if (e == hipSuccess) e = hipMalloc((void **)&stage, need * 4);
+    DevList mem_stage;                                                          // (freed when this function returns)
+    hipError_t e = c->mem_w.alloc(&c->d_w, n_block * 4, true);                  // (zeroed: the alignment gaps)
+    if (e == hipSuccess) e = mem_stage.alloc(&stage, need * 4);
     if (e == hipSuccess) e = hipMemcpy(stage, w, need * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) { sd_repack(c, stage, nullptr); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (stage) hipFree(stage);
     if (e != hipSuccess) {
-        if (c->d_w) hipFree(c->d_w);
         delete c; return sd_fail(std::string("shapemol_sd_create: device allocation failed: ") + hipGetErrorString(e));
     }
     *out = c;
@@ -194,8 +173,7 @@ void shapemol_sd_destroy(shapemol_sd_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    for (void **q : sd_buffers(c)) if (*q) hipFree(*q);
-    delete c;
+    delete c;                 // its lists release what they own
 }
 
 int64_t shapemol_sd_tile(const shapemol_sd_ctx *c) { return c ? kSdTile : 0; }
@@ -241,8 +219,8 @@ int shapemol_field_guide(shapemol_sd_ctx *c, float *d_pos, const int64_t *d_batc
     if (!d_pos || !d_batch || !d_z) return sd_fail("shapemol_field_guide: null argument");
     SDCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (sd_grow({{(void **)&c->shape_of, (size_t)n_atoms * 4}}, c->capN, n_atoms)) return 1;
-    if (sd_grow({{(void **)&c->mol_off, (size_t)(n_shapes + 1) * 4}}, c->capM, n_shapes)) return 1;
+    SDCHK(grow(c->mem_N, {dev_buf(&c->shape_of, (size_t)n_atoms * 4)}, c->capN, n_atoms));
+    SDCHK(grow(c->mem_M, {dev_buf(&c->mol_off, (size_t)(n_shapes + 1) * 4)}, c->capM, n_shapes));
     if (sd_prologue(c, d_z, n_shapes, s)) return 1;
     const int64_t work = n_atoms > n_shapes + 1 ? n_atoms : n_shapes + 1;
     hipLaunchKernelGGL(sd_batch_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, d_batch, (int)n_atoms, (int)n_shapes, c->shape_of, c->mol_off);
@@ -288,11 +266,11 @@ int shapemol_field_train(shapemol_sd_ctx *c, const float *d_p, int64_t n_shapes,
     if (chunk > all_tiles * kSdTrainTile) chunk = all_tiles * kSdTrainTile;
     auto splits_of = [](int64_t groups) { const int64_t v = (groups + 7) / 8; return (int)(v < kSdMaxSplits ? v : kSdMaxSplits); };
     const int need_splits = splits_of(chunk / 16);
-    if (sd_grow({{(void **)&c->tr_slots, (size_t)(4 * L + 2) * chunk * kSdH * 4}, {(void **)&c->tr_up, (size_t)chunk * 4}}, c->capT, chunk)) return 1;
-    if (sd_grow({{(void **)&c->tr_pw, (size_t)2 * L * need_splits * kSdImg * 4}, {(void **)&c->tr_pb, (size_t)2 * L * need_splits * kSdH * 8}}, c->capSplits, need_splits))
-        return 1;
-    if (sd_grow({{(void **)&c->tr_accS, (size_t)n_shapes * kSdSums * kSdH * 8}, {(void **)&c->tr_dzinv, (size_t)n_shapes * Z * 4}}, c->capS, n_shapes)) return 1;
-    if (!c->tr_accW) SDCHK(hipMalloc((void **)&c->tr_accW, (size_t)2 * L * (kSdImg + kSdH) * 8));    // once: its size is the context's
+    SDCHK(grow(c->mem_T, {dev_buf(&c->tr_slots, (size_t)(4 * L + 2) * chunk * kSdH * 4), dev_buf(&c->tr_up, (size_t)chunk * 4)}, c->capT, chunk));
+    SDCHK(grow(c->mem_splits, {dev_buf(&c->tr_pw, (size_t)2 * L * need_splits * kSdImg * 4), dev_buf(&c->tr_pb, (size_t)2 * L * need_splits * kSdH * 8)},
+               c->capSplits, need_splits));
+    SDCHK(grow(c->mem_S, {dev_buf(&c->tr_accS, (size_t)n_shapes * kSdSums * kSdH * 8), dev_buf(&c->tr_dzinv, (size_t)n_shapes * Z * 4)}, c->capS, n_shapes));
+    if (!c->tr_accW) SDCHK(c->mem_accW.alloc(&c->tr_accW, (size_t)2 * L * (kSdImg + kSdH) * 8));    // once: its size is the context's
     if (sd_prologue(c, d_z, n_shapes, s)) return 1;
     const size_t slot_sz = (size_t)c->capT * kSdH;
     const int lin_blocks = (kSdImg + kSdH + 255) / 256;

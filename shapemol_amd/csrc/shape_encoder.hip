@@ -2,6 +2,7 @@
 // (models/shape_pointcloud_modelAE.py:207-255).  Kernels: sm_shape.h.
 #include "../../include/shapemol_hip.h"
 #include "sm_shape.h"
+#include "sm_devmem.h"
 
 #include <cstring>
 #include <string>
@@ -24,11 +25,11 @@ struct shapemol_se_ctx {
     int lds_limit = 0, max_n = 0;   // largest dynamic LDS of a workgroup on the device; largest N whose 16 x N d2 rows fit in it
     int stop_after = -1;            // shapemol_se_debug_stop_after
     int64_t lastP = 0;              // points of the last encode (shapemol_se_debug_read)
-    float *d_w = nullptr;
+    float *d_w = nullptr; DevList mem_w;
     size_t o_pos_wf = 0, o_pos_g = 0, o_pos_b = 0, o_pos_wd = 0, o_c_wf = 0, o_c_g = 0, o_c_b = 0, o_c_wd = 0;
     std::vector<size_t> o_img, o_g, o_b;
-    // workspace
-    int64_t capP = 0;
+    // workspace (sm_devmem.h: grown by grow() for capP points, freed with the context)
+    int64_t capP = 0; DevList mem_P;
     float *h0 = nullptr, *hcat = nullptr, *y = nullptr, *xx = nullptr, *pd = nullptr;
     int *idx = nullptr;
     double *acc = nullptr;
@@ -93,7 +94,7 @@ int shapemol_se_create(int32_t hidden_dim, int32_t latent_dim, int32_t layer_num
     c->o_c_g = put(p, latent_dim); p += latent_dim;
     c->o_c_b = put(p, latent_dim); p += latent_dim;
     c->o_c_wd = put(p, (size_t)layer_num * C); p += (size_t)layer_num * C;
-    if (hipMalloc((void **)&c->d_w, img.size() * 4) != hipSuccess || hipMemcpy(c->d_w, img.data(), img.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    if (c->mem_w.alloc(&c->d_w, img.size() * 4) != hipSuccess || hipMemcpy(c->d_w, img.data(), img.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         delete c; return se_fail("shapemol_se_create: device allocation failed");
     }
     *out = c;
@@ -104,8 +105,7 @@ void shapemol_se_destroy(shapemol_se_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    for (void *q : {(void *)c->h0, (void *)c->hcat, (void *)c->y, (void *)c->xx, (void *)c->pd, (void *)c->idx, (void *)c->acc, (void *)c->d_w}) if (q) hipFree(q);
-    delete c;
+    delete c;                 // its lists release what they own
 }
 
 int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int64_t N, float *d_out, void *stream) {
@@ -118,15 +118,9 @@ int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int
     hipStream_t s = (hipStream_t)stream;
     const int C = c->C, L = c->L, LAT = c->LAT;
     const int64_t P = B * N;
-    if (P > c->capP) {
-        SECHK(hipDeviceSynchronize());
-        for (void *q : {(void *)c->h0, (void *)c->hcat, (void *)c->y, (void *)c->xx, (void *)c->pd, (void *)c->idx, (void *)c->acc}) if (q) hipFree(q);
-        SECHK(hipMalloc((void **)&c->h0, P * C * 3 * 4)); SECHK(hipMalloc((void **)&c->hcat, P * L * C * 3 * 4));
-        SECHK(hipMalloc((void **)&c->y, P * 4 * C * 3 * 4)); SECHK(hipMalloc((void **)&c->xx, P * 4));
-        SECHK(hipMalloc((void **)&c->pd, P * (LAT + 1) * 3 * 4)); SECHK(hipMalloc((void **)&c->idx, P * kSeK * 4));
-        SECHK(hipMalloc((void **)&c->acc, (size_t)kSeReplicas * 2 * 256 * 8));
-        c->capP = P;
-    }
+    SECHK(grow(c->mem_P, {dev_buf(&c->h0, P * C * 3 * 4), dev_buf(&c->hcat, P * L * C * 3 * 4), dev_buf(&c->y, P * 4 * C * 3 * 4), dev_buf(&c->xx, P * 4),
+                          dev_buf(&c->pd, P * (LAT + 1) * 3 * 4), dev_buf(&c->idx, P * kSeK * 4), dev_buf(&c->acc, (size_t)kSeReplicas * 2 * 256 * 8)},
+               c->capP, P));
     c->lastP = P;
     const size_t knn_lds = (size_t)16 * N * sizeof(float);      // <= lds_limit (N <= max_n)
     SECHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));

@@ -18,7 +18,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -26,6 +25,7 @@
 #include <vector>
 
 #include "sm_pack.h"
+#include "sm_devmem.h"
 
 namespace {
 
@@ -35,6 +35,7 @@ namespace {
         if (e_ != hipSuccess)                                                                \
             return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                  \
     } while (0)
+int hip_fail(const char *what, hipError_t e) { return fail(std::string(what) + ": " + hipGetErrorString(e)); }
 
 constexpr int kEdgeThreadsDefault = 768;
 #ifndef SM_GRAPH_UNROLL
@@ -46,8 +47,9 @@ struct ProfRec { const char *name; hipEvent_t e0, e1; };
 
 enum class Guide { None, Cloud, Mesh, Field, Cfg };      // guidance of a chain's predicted x0: chain_guide (sm_guide_host.h)
 
-// Device data of shape guidance: per kind ONE set of groups of molecules (sm_guide_host.h installs and clears them).  `whole`: a
-// set of one group that spans whatever batch comes (shapemol_set_guidance / shapemol_set_mesh_guidance): no molecule count
+// Device data of shape guidance: per kind ONE set of groups of molecules (sm_guide_host.h installs and clears them, each in a
+// DevList beside the set).  `whole`: a set of one group that spans whatever batch comes (shapemol_set_guidance /
+// shapemol_set_mesh_guidance): no molecule count
 struct CloudSet {     // one device block: [clouds | radii | mol_off, cloud_off, atom_off, wg_off (G + 1 ints each)]
     double *clouds = nullptr, *radius = nullptr; int *ints = nullptr;
     int groups = 0, max_points = 0, grad_step = 0; int64_t mols = 0, points = 0; bool whole = false; const double *draws = nullptr;
@@ -61,7 +63,7 @@ struct MeshSet {      // one device block: [faces | face boxes | clouds | bounds
 // block [rows G + 1 | stat G x 2 | histograms G x 2 x kCfgHistWords] that only grows, so a captured step keeps its addresses
 // from one set to the next; the tables that depend on the batch (molecule -> group, workgroups, partials) are workspace
 struct CfgGroupSet {
-    CfgGroup *rows = nullptr; float *stat = nullptr; unsigned *hist = nullptr; int cap = 0;
+    CfgGroup *rows = nullptr; float *stat = nullptr; unsigned *hist = nullptr; int64_t cap = 0; DevList mem;
     int groups = 0; int64_t mols = 0;
     int last_groups = 0;                                         // groups of the last chain that ran with a set (debug_read "cfg_group_stat")
     int type = 0; double p = 0.0;                                // threshold_CFG's type and p: one per chain
@@ -69,12 +71,18 @@ struct CfgGroupSet {
     hipStream_t stream = nullptr; bool stream_set = false;      // the stream the last chain that read the rows ran on
 };
 
+// The prepared shape data one score evaluation reads (run_prep_shape writes it): invariant embedding, shape terms of layer 0
+// and of every layer, VN shape part, and the argument blocks of run_prep_shape's two batched launches
+struct ShapePrep { float *inv = nullptr, *add0 = nullptr, *addp = nullptr, *ps = nullptr; ShapeTermArgs *terms = nullptr; VnShapeArgs *vn = nullptr; };
+
 }  // namespace
 
+// Device memory (sm_devmem.h): every group of buffers is owned by the DevList declared beside its pointers, and freed with the context
 struct shapemol_ctx {
     shapemol_config cfg{};
     int device = 0;
     int KP = 8;
+    DevList mem_model;          // d_img, ttab, etab (shapemol_create)
     float *d_img = nullptr;
     float *ttab = nullptr;      // [T][D] time-embedding table (built once)
     float *etab = nullptr;      // [T][C][H] atom embedding of every (timestep, atom type) pair (built once)
@@ -82,17 +90,18 @@ struct shapemol_ctx {
     // One device block: [q_tab | pre_tab | v, mol_of, t_mol of the pseudo-batch they are built from | range flag of the build]
     float *q_tab = nullptr;     // [T][C][H] queries of layer 0's x2h attention
     float *pre_tab = nullptr;   // [T][C][4H] per-node halves of layer 0's edge MLPs, without the per-molecule term
-    int64_t *tab_v = nullptr; int *tab_mol_of = nullptr, *tab_t_mol = nullptr, *tab_flag = nullptr;
+    int64_t *tab_v = nullptr; int *tab_mol_of = nullptr, *tab_t_mol = nullptr, *tab_flag = nullptr; DevList mem_tab;
     int tab_key = 0;            // node precision mode the tables were built in (prologue_tab_key), 0 = not built
     int prologue_tab = 1;       // 1: the per-step node prologue gathers from the tables; 0: the per-atom MLP kernel
     DevModel dm;
     // workspace
     int64_t capN = 0, capB = 0;
-    std::vector<void *> allocs;
+    DevList ws{256};            // every workspace buffer: zero-filled, 256 bytes of padding behind each
+    ShapePrep prep[2];          // 0: the chain's shape condition, 1: the zeroed shape of classifier-free guidance
     int *mol_of = nullptr, *mol_off = nullptr, *t_mol = nullptr, *nbr = nullptr, *steps = nullptr;
-    float *temb = nullptr, *inv = nullptr, *add0 = nullptr, *addp = nullptr, *ps = nullptr, *ew = nullptr;
+    float *temb = nullptr, *ew = nullptr;
     float *h_a = nullptr, *h_b = nullptr, *pre0 = nullptr, *preAB = nullptr, *q_x = nullptr, *q_h = nullptr, *att = nullptr, *o3 = nullptr, *pd = nullptr;
-    ShapeTermArgs *prep_terms = nullptr; VnShapeArgs *prep_vn = nullptr; int n_prep_terms = 0;   // argument blocks of run_prep's two batched launches
+    int n_prep_terms = 0;       // shape terms of a ShapePrep (its `terms` block)
     int2 *mol_span = nullptr;   // [N] molecule span of every atom
     float *xsum = nullptr;      // [N][3] per-atom sum of the h2x attention rows (folded coordinate update)
     float *part_rows = nullptr, *part_ms = nullptr;   // k > 16: rows [2N][H] and softmax state [2N][heads][2] of the half-atom tiles
@@ -118,6 +127,7 @@ struct shapemol_ctx {
                                    // 231 of 12 -- x2h 26.7 -> 25.6 us, h2x 24.7 -> 23.9; B = 1024, 43 instead of 44: unchanged)
     int lin_fuse = 0;           // 1: per-node products of the next attentions inside node_chain16_kernel instead of a node_linear
     int bn_eval = 0;            // 1: evaluation-mode batch-norm (running statistics, shapemol_set_bn_running) instead of the batch's
+    DevList mem_bn;             // the two below
     float *bn_run = nullptr;    // [2][L][heads] running mean | running variance (device)
     double *bn_eval_acc = nullptr;   // [L][kBnReplicas][2][heads] sums that reproduce them for the current batch size
     int ddpm_fold = 1;          // 1: the last layer's coordinate update inside the DDPM kernel (chains without guidance)
@@ -139,26 +149,25 @@ struct shapemol_ctx {
     int num_cu = 256;
     // shape guidance of the predicted x0: the installed point-cloud set and mesh set (the mesh takes precedence when both are set),
     // the per-workgroup table of whichever guides (sized by the chain) and the mesh's per-step lists (one block; counters: 4 per group)
-    CloudSet cs; MeshSet ms;
-    int2 *wg_table = nullptr; int64_t wg_table_cap = 0;
+    CloudSet cs; MeshSet ms; DevList mem_cs, mem_ms;
+    int2 *wg_table = nullptr; int64_t wg_table_cap = 0; DevList mem_wg;
     // gradient shape guidance (shapemol_set_field_guidance): the borrowed decoder context, whose per-shape workspace the chain's
     // prep fills from the chain's own shapes
     shapemol_sd_ctx *field_sd = nullptr; double field_lr = 0.0; int field_step = 0;
-    float4 *m_within = nullptr; int *m_out = nullptr, *m_cnt = nullptr; int64_t m_cap = 0, m_cnt_cap = 0;
+    float4 *m_within = nullptr; int *m_out = nullptr, *m_cnt = nullptr; int64_t m_cap = 0, m_cnt_cap = 0; DevList mem_mesh;
     int64_t m_flag_groups = 0;      // groups of the last chain / pass with a mesh set (debug_read "mesh_group_flags")
     // classifier-free guidance (shapemol_set_cfg): a second score evaluation per step on a zeroed shape, whose prepared shape
-    // data (invariant embedding, shape terms, VN shape part) lives in the parallel *_u buffers; swap_uncond() exchanges the sets
+    // data is prep[1] and whose outputs are pred_pos_u / pred_v_u
     double cfg_w = 0.0, cfg_p = 0.0; int cfg_type = 0, cfg_has_bounds = 0; float cfg_lo[3] = {}, cfg_hi[3] = {};
     float *cfg_tr_pos_u = nullptr, *cfg_tr_v_u = nullptr;      // caller's uncond trajectories (or nullptr)
-    float *inv_u = nullptr, *add0_u = nullptr, *addp_u = nullptr, *ps_u = nullptr, *pred_pos_u = nullptr, *pred_v_u = nullptr;
+    float *pred_pos_u = nullptr, *pred_v_u = nullptr;
     float *shape_zero = nullptr;      // [B][S][3] zeros (never written)
-    ShapeTermArgs *prep_terms_u = nullptr; VnShapeArgs *prep_vn_u = nullptr;
     float *cfg_stat = nullptr; double *cfg_part = nullptr; unsigned *cfg_hist = nullptr;
     CfgGroupSet cgs;            // per-group strengths and boxes (takes the place of the scalar form while installed)
     int *cfg_mol_grp = nullptr; int2 *cfg_blk_tab = nullptr; double *cfg_gpart = nullptr; int64_t cfg_tab_stride = 0;
     int first_step = 0;         // option "first_step": the next chains start at reverse step first_step (t = T-1-first_step)
     // diagnostic: neighbour lists pinned at given (reverse step, atom) pairs (shapemol_set_knn_pins)
-    int *pin_off = nullptr, *pin_atom = nullptr, *pin_nbr = nullptr; int64_t n_pins = 0; int pin_steps = 0, pin_k = 0;
+    int *pin_off = nullptr, *pin_atom = nullptr, *pin_nbr = nullptr; int64_t n_pins = 0; int pin_steps = 0, pin_k = 0; DevList mem_pins;
     // profiling
     bool prof_on = false;
     std::vector<ProfRec> prof;
@@ -228,69 +237,69 @@ int launch(shapemol_ctx *c, const char *name, hipStream_t s, F &&f) {
 }
 #define LAUNCH(name, ...) do { if (launch(c, name, s, [&]() { __VA_ARGS__; })) return 1; } while (0)
 
-int ensure_workspace(shapemol_ctx *c, int64_t N, int64_t B) {
-    if (N <= c->capN && B <= c->capB) return 0;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipDeviceSynchronize());
-    for (void *p : c->allocs) hipFree(p);
-    c->allocs.clear();
-    c->drop_graphs();
-    const int64_t capN = std::max<int64_t>(N, c->capN), capB = std::max<int64_t>(B, c->capB);
+// The workspace buffers for capN atoms in capB molecules, into the released list c->ws: one allocation per buffer, in this order
+int workspace_alloc(shapemol_ctx *c, int64_t capN, int64_t capB) {
     const shapemol_config &g = c->cfg;
     const int H = g.hidden_dim, L = g.num_layers, hd = g.n_heads;
-    auto A = [&](auto **p, size_t n) -> int {
-        void *q = nullptr;
-        HIPCHK(hipMalloc(&q, n * sizeof(**p) + 256));
-        HIPCHK(hipMemset(q, 0, n * sizeof(**p) + 256));
-        c->allocs.push_back(q);
-        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
-        return 0;
+    hipError_t e = hipSuccess;
+    auto A = [&](auto **p, size_t n) -> int { return (e = c->ws.alloc(p, n * sizeof(**p), true)) != hipSuccess; };
+    auto prep_data = [&](ShapePrep &p) -> int {
+        return A(&p.inv, capB * g.shape_latent_dim) || A(&p.add0, (size_t)capB * 4 * H) || A(&p.addp, (size_t)L * capB * 8 * H) || A(&p.ps, (size_t)L * capB * 2 * hd * 3);
     };
+    auto prep_args = [&](ShapePrep &p) -> int { return A(&p.terms, 2 * L + 1) || A(&p.vn, L); };
+    // per-group classifier-free guidance: workgroup tables and partials for the largest launch bound of this capacity
+    // (elements / 2048 + groups per tensor, cfg_group_blocks), molecule -> group
+    const int64_t stride = capN * std::max(g.num_classes, 3) / 2048 + kCfgMaxGroups + 1;
     if (A(&c->mol_of, capN) || A(&c->mol_off, capB + 1) || A(&c->t_mol, capB) || A(&c->nbr, capN * c->KP) ||
-        A(&c->steps, 4) || A(&c->temb, capB * g.time_emb_dim) || A(&c->inv, capB * g.shape_latent_dim) ||
-        A(&c->add0, (size_t)capB * 4 * H) || A(&c->addp, (size_t)L * capB * 8 * H) || A(&c->ps, (size_t)L * capB * 2 * hd * 3) || A(&c->ew, capN * c->KP) ||
+        A(&c->steps, 4) || A(&c->temb, capB * g.time_emb_dim) || prep_data(c->prep[0]) || A(&c->ew, capN * c->KP) ||
         A(&c->h_a, capN * H) || A(&c->h_b, capN * H) || A(&c->pre0, capN * 4 * H) || A(&c->preAB, capN * 8 * H) || A(&c->q_x, capN * H) || A(&c->q_h, capN * H) ||
         A(&c->att, capN * H) || A(&c->o3, capN * 48) || A(&c->xsum, capN * 3) || A(&c->mol_span, capN) || A(&c->alpha, capN * c->KP * 2 * (H / 16)) || A(&c->pd, capN * hd * 6) || A(&c->x_a, capN * 3) ||
         A(&c->x_b, capN * 3) || A(&c->x_state, capN * 3) || A(&c->pred_pos, capN * 3) ||
         A(&c->pred_v, capN * g.num_classes) || A(&c->v_state, capN) || A(&c->stamps, 2048) || A(&c->kstamps, 8 * 16 * 4096) || A(&c->bn_acc, (size_t)L * kBnReplicas * 2 * hd + L + 1) ||
         (c->KP > 16 && (A(&c->part_rows, (size_t)2 * capN * H) || A(&c->part_ms, (size_t)2 * capN * hd * 2))) ||
-        A(&c->status, 8) || A(&c->chain_params, 1) || A(&c->prep_terms, 2 * L + 1) || A(&c->prep_vn, L) ||
-        A(&c->inv_u, capB * g.shape_latent_dim) || A(&c->add0_u, (size_t)capB * 4 * H) || A(&c->addp_u, (size_t)L * capB * 8 * H) ||
-        A(&c->ps_u, (size_t)L * capB * 2 * hd * 3) || A(&c->pred_pos_u, capN * 3) || A(&c->pred_v_u, capN * g.num_classes) ||
-        A(&c->shape_zero, (size_t)capB * g.shape_dim * 3) || A(&c->prep_terms_u, 2 * L + 1) || A(&c->prep_vn_u, L) ||
-        A(&c->cfg_stat, 4) || A(&c->cfg_part, (size_t)2 * kCfgMaxBlocks * 4) || A(&c->cfg_hist, (size_t)2 * kCfgHistWords))
-        return 1;
-    // per-group classifier-free guidance: workgroup tables and partials for the largest launch bound of this capacity
-    // (elements / 2048 + groups per tensor, cfg_group_blocks), molecule -> group
-    const int64_t stride = capN * std::max(g.num_classes, 3) / 2048 + kCfgMaxGroups + 1;
-    if (A(&c->cfg_mol_grp, capB) || A(&c->cfg_blk_tab, (size_t)2 * stride) || A(&c->cfg_gpart, (size_t)2 * stride * 4)) return 1;
+        A(&c->status, 8) || A(&c->chain_params, 1) || prep_args(c->prep[0]) ||
+        prep_data(c->prep[1]) || A(&c->pred_pos_u, capN * 3) || A(&c->pred_v_u, capN * g.num_classes) ||
+        A(&c->shape_zero, (size_t)capB * g.shape_dim * 3) || prep_args(c->prep[1]) ||
+        A(&c->cfg_stat, 4) || A(&c->cfg_part, (size_t)2 * kCfgMaxBlocks * 4) || A(&c->cfg_hist, (size_t)2 * kCfgHistWords) ||
+        A(&c->cfg_mol_grp, capB) || A(&c->cfg_blk_tab, (size_t)2 * stride) || A(&c->cfg_gpart, (size_t)2 * stride * 4))
+        return hip_fail("workspace allocation", e);
     c->cfg_tab_stride = stride;
-    c->capN = capN; c->capB = capB;
-    // argument blocks of the batched prep launches (they point into the workspace just allocated): the conditional set and
-    // the unconditional one of classifier-free guidance
-    auto prep_blocks = [&](float *inv, float *add0, float *addp_all, float *ps, ShapeTermArgs *d_terms, VnShapeArgs *d_vn) -> int {
+    // argument blocks of the batched prep launches (they point into the workspace just allocated), one per set of shape data
+    for (ShapePrep &p : c->prep) {
         const int SL = g.shape_latent_dim, S = g.shape_dim;
         std::vector<ShapeTermArgs> terms;
         std::vector<VnShapeArgs> vns;
         const DevLayer &D0 = c->dm.layer[0];
-        terms.push_back(ShapeTermArgs{inv, c->P(D0.sk_x2h), c->P(D0.bk_x2h), c->P(D0.sv_x2h), c->P(D0.bv_x2h), add0, SL, H, SL, 4 * H});
+        terms.push_back(ShapeTermArgs{p.inv, c->P(D0.sk_x2h), c->P(D0.bk_x2h), c->P(D0.sv_x2h), c->P(D0.bv_x2h), p.add0, SL, H, SL, 4 * H});
         for (int l = 0; l < L; ++l) {
             const DevLayer &D = c->dm.layer[l];
-            float *addp = addp_all + (size_t)l * c->capB * 8 * H;      // [B][8H]: this layer's h2x | the next layer's x2h
-            terms.push_back(ShapeTermArgs{inv, c->P(D.sk_h2x), c->P(D.bk_h2x), c->P(D.sv_h2x), c->P(D.bv_h2x), addp, SL, H, SL, 8 * H});
+            float *addp = p.addp + (size_t)l * capB * 8 * H;      // [B][8H]: this layer's h2x | the next layer's x2h
+            terms.push_back(ShapeTermArgs{p.inv, c->P(D.sk_h2x), c->P(D.bk_h2x), c->P(D.sv_h2x), c->P(D.bv_h2x), addp, SL, H, SL, 8 * H});
             if (l + 1 < L) {
                 const DevLayer &Dn = c->dm.layer[l + 1];
-                terms.push_back(ShapeTermArgs{inv, c->P(Dn.sk_x2h), c->P(Dn.bk_x2h), c->P(Dn.sv_x2h), c->P(Dn.bv_x2h), addp + 4 * H, SL, H, SL, 8 * H});
+                terms.push_back(ShapeTermArgs{p.inv, c->P(Dn.sk_x2h), c->P(Dn.bk_x2h), c->P(Dn.sv_x2h), c->P(Dn.bv_x2h), addp + 4 * H, SL, H, SL, 8 * H});
             }
-            vns.push_back(VnShapeArgs{nullptr, c->P(D.vn_f), c->P(D.vn_d), ps + (size_t)l * c->capB * 2 * hd * 3, S, hd});
+            vns.push_back(VnShapeArgs{nullptr, c->P(D.vn_f), c->P(D.vn_d), p.ps + (size_t)l * capB * 2 * hd * 3, S, hd});
         }
         c->n_prep_terms = (int)terms.size();
-        HIPCHK(hipMemcpy(d_terms, terms.data(), terms.size() * sizeof(ShapeTermArgs), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_vn, vns.data(), vns.size() * sizeof(VnShapeArgs), hipMemcpyHostToDevice));
-        return 0;
-    };
-    if (prep_blocks(c->inv, c->add0, c->addp, c->ps, c->prep_terms, c->prep_vn) ||
-        prep_blocks(c->inv_u, c->add0_u, c->addp_u, c->ps_u, c->prep_terms_u, c->prep_vn_u)) return 1;
+        HIPCHK(hipMemcpy(p.terms, terms.data(), terms.size() * sizeof(ShapeTermArgs), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p.vn, vns.data(), vns.size() * sizeof(VnShapeArgs), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// The workspace only grows.  While it is rebuilt the context has none: capacities 0, every workspace pointer null (the list's
+// release), nothing of a last evaluation to read and no captured step -- which is also the state a failed growth leaves
+int ensure_workspace(shapemol_ctx *c, int64_t N, int64_t B) {
+    if (N <= c->capN && B <= c->capB) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    c->drop_graphs();
+    const int64_t capN = std::max<int64_t>(N, c->capN), capB = std::max<int64_t>(B, c->capB);
+    c->ws.release();
+    c->capN = c->capB = 0; c->lastN = c->lastB = 0; c->last_h = c->last_x = nullptr;
+    if (workspace_alloc(c, capN, capB)) { c->ws.release(); return 1; }
+    c->capN = capN; c->capB = capB;
     return 0;
 }
 
@@ -600,13 +609,7 @@ __global__ void knn_pin_kernel(const int *off, int n_steps, const int *atom, con
 }
 
 template <int H>
-int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape);
-
-// exchange the conditional and the unconditional sets of prepared shape data and score outputs
-void swap_uncond(shapemol_ctx *c) {
-    std::swap(c->inv, c->inv_u); std::swap(c->add0, c->add0_u); std::swap(c->addp, c->addp_u); std::swap(c->ps, c->ps_u);
-    std::swap(c->prep_terms, c->prep_terms_u); std::swap(c->prep_vn, c->prep_vn_u);
-}
+int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape, const ShapePrep &sp);
 
 // the launch bound of the per-group statistic kernels for a tensor of n elements: the sum over the groups of
 // min(kCfgMaxBlocks, max(1, ceil(n_g / 2048))) is at most n / 2048 + G
@@ -662,24 +665,24 @@ int run_cfg_stats(shapemol_ctx *c, hipStream_t s, const CfgArgs &a) {
 }
 
 template <int H>
-int run_prep(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int64_t B, const float *d_shape) {
+int run_prep(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int64_t B, const float *d_shape, const ShapePrep &sp) {
     LAUNCH("prep", SMK(mol_index_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_batch, (int)N, (int)B, c->mol_of, c->mol_off, c->status));
     LAUNCH("prep", SMK(mol_span_kernel, dim3((N + 255) / 256), dim3(256), 0, s, c->mol_of, c->mol_off, (int)N, c->mol_span));
-    return run_prep_shape<H>(c, s, B, d_shape);
+    return run_prep_shape<H>(c, s, B, d_shape, sp);
 }
 
-// the shape-dependent part of run_prep (into the buffer set in use: swap_uncond)
+// the shape-dependent part of run_prep, into the set sp
 template <int H>
-int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape) {
+int run_prep_shape(shapemol_ctx *c, hipStream_t s, int64_t B, const float *d_shape, const ShapePrep &sp) {
     const shapemol_config &g = c->cfg;
     const int L = g.num_layers, SL = g.shape_latent_dim, S = g.shape_dim;
     ShapeInvArgs si{d_shape, c->P(c->dm.inv.w1), c->P(c->dm.inv.b1), c->P(c->dm.inv.g), c->P(c->dm.inv.be),
-                    c->P(c->dm.inv.w2), c->P(c->dm.inv.b2), c->inv, S, SL};
+                    c->P(c->dm.inv.w2), c->P(c->dm.inv.b2), sp.inv, S, SL};
     LAUNCH("prep", SMK(shape_invariant_kernel, dim3(B), dim3(64), 0, s, si));
     // every step-invariant shape term (layer-0 x2h; per layer h2x | next x2h) and the shape part of every VN-linear: two launches
-    if (SL == 32) LAUNCH("prep", SMK(shape_term_multi_tiled_kernel<32>, dim3((unsigned)((B + kShapeTermMols - 1) / kShapeTermMols), (unsigned)c->n_prep_terms), dim3(256), 0, s, c->prep_terms, (int)B));
-    else LAUNCH("prep", SMK(shape_term_multi_kernel, dim3((unsigned)B, (unsigned)c->n_prep_terms), dim3(256), 0, s, c->prep_terms));
-    LAUNCH("prep", SMK(vn_shape_multi_kernel, dim3((unsigned)B, (unsigned)L), dim3(128), 0, s, d_shape, c->prep_vn));
+    if (SL == 32) LAUNCH("prep", SMK(shape_term_multi_tiled_kernel<32>, dim3((unsigned)((B + kShapeTermMols - 1) / kShapeTermMols), (unsigned)c->n_prep_terms), dim3(256), 0, s, sp.terms, (int)B));
+    else LAUNCH("prep", SMK(shape_term_multi_kernel, dim3((unsigned)B, (unsigned)c->n_prep_terms), dim3(256), 0, s, sp.terms));
+    LAUNCH("prep", SMK(vn_shape_multi_kernel, dim3((unsigned)B, (unsigned)L), dim3(128), 0, s, d_shape, sp.vn));
     return 0;
 }
 
@@ -692,10 +695,10 @@ void fill_edge(A &a, const shapemol_ctx *c, const float *pre, int ld_pre, const 
 }
 
 // VN-linear + batch statistics (enable = 2) or the whole coordinate update (1) of layer l behind its h2x attention
-EdgeFusedArgs::VnFuse vn_fuse_args(const shapemol_ctx *c, int l, float *x_next, unsigned *arrive, int enable) {
+EdgeFusedArgs::VnFuse vn_fuse_args(const shapemol_ctx *c, const ShapePrep &sp, int l, float *x_next, unsigned *arrive, int enable) {
     const DevLayer &D = c->dm.layer[l];
     const int hd = c->cfg.n_heads;
-    return {c->ps + (size_t)l * c->capB * 2 * hd * 3, c->P(D.wf_x), c->P(D.wd_x), c->P(D.wf_o), c->P(D.wd_o), c->P(D.bn_g), c->P(D.bn_b),
+    return {sp.ps + (size_t)l * c->capB * 2 * hd * 3, c->P(D.wf_x), c->P(D.wd_x), c->P(D.wf_o), c->P(D.wd_o), c->P(D.bn_g), c->P(D.bn_b),
             c->mol_of, c->pd, c->bn_acc + (size_t)l * kBnReplicas * 2 * hd, arrive, c->status + ST_VN_BARRIER, x_next, enable};
 }
 
@@ -704,14 +707,14 @@ EdgeFusedArgs::VnFuse vn_fuse_args(const shapemol_ctx *c, int l, float *x_next, 
 // (`ddpm`: the model's last layer in a chain step whose predicted x0 nobody reads before: no guidance, no CFG), or, with neither,
 // the vn_apply launch (vn_done = false; vn_stats too unless stats_done)
 struct H2xPlan { EdgeFusedArgs::VnFuse vn{}; float *xsum = nullptr; VnFold pending{}; DdpmFold ddpm{}; bool stats_done = false, vn_done = false; };
-H2xPlan h2x_plan(const shapemol_ctx *c, int l, bool fold, bool has_next, bool half_tiles, const double *stat_acc, const float *cur_x,
+H2xPlan h2x_plan(const shapemol_ctx *c, const ShapePrep &sp, int l, bool fold, bool has_next, bool half_tiles, const double *stat_acc, const float *cur_x,
                  float *x_next, float *out_pos) {
     H2xPlan p;
     if (!c->vn_fuse || half_tiles) return p;
     const DevLayer &D = c->dm.layer[l];
     const int hd = c->cfg.n_heads;
     const double *acc = stat_acc + (size_t)l * kBnReplicas * 2 * hd;
-    p.vn = vn_fuse_args(c, l, x_next, nullptr, 2);
+    p.vn = vn_fuse_args(c, sp, l, x_next, nullptr, 2);
     p.stats_done = true;
     const bool to_ddpm = !has_next && l == c->cfg.num_layers - 1 && out_pos && c->ddpm_fold && chain_guide(c) == Guide::None &&
                          c->cfg.num_classes <= 16 && hd <= 16;
@@ -763,9 +766,8 @@ int ensure_prologue_tables(shapemol_ctx *c, hipStream_t s) {
     const int T = c->cfg.num_timesteps, C = c->cfg.num_classes;
     const size_t rows = (size_t)T * C;
     if (!c->q_tab) {
-        void *blk = nullptr;
-        HIPCHK(hipMalloc(&blk, rows * 5 * H * sizeof(float) + rows * (sizeof(int64_t) + sizeof(int)) + ((size_t)T + 1) * sizeof(int)));
-        c->q_tab = static_cast<float *>(blk); c->pre_tab = c->q_tab + rows * H;
+        HIPCHK(c->mem_tab.alloc(&c->q_tab, rows * 5 * H * sizeof(float) + rows * (sizeof(int64_t) + sizeof(int)) + ((size_t)T + 1) * sizeof(int)));
+        c->pre_tab = c->q_tab + rows * H;
         c->tab_v = reinterpret_cast<int64_t *>(c->pre_tab + rows * 4 * H);
         c->tab_mol_of = reinterpret_cast<int *>(c->tab_v + rows); c->tab_t_mol = c->tab_mol_of + rows; c->tab_flag = c->tab_t_mol + T;
     }
@@ -777,9 +779,9 @@ int ensure_prologue_tables(shapemol_ctx *c, hipStream_t s) {
     return 0;
 }
 
-// One score evaluation on prepared batch data.  x_in/v_in: current state; outputs as given.
+// One score evaluation on prepared batch data and the prepared shape data sp.  x_in/v_in: current state; outputs as given.
 template <int H>
-int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *v_in, int64_t N, int64_t B,
+int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *x_in, const int64_t *v_in, int64_t N, int64_t B,
               bool sampling, int t_first, float *out_pos, float *out_h, float *out_v, bool reuse_graph = false) {
     // reuse_graph: the second (unconditional) evaluation of a guided step on the same positions keeps the step's kNN graph
     // and edge weights (nbr, ew)
@@ -793,10 +795,10 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
     if (fused_prologue && c->prologue_tab) {      // the same three outputs, gathered from the per-(timestep, type) tables
         if (c->tab_key != prologue_tab_key(c)) return fail("run_score: the prologue tables are not built for this precision mode");
         PrologueTabArgs ta{c->etab, c->q_tab, c->pre_tab, c->tab_flag, v_in, c->mol_of, c->t_mol, ae.step_ptr, ae.step_cur, c->bn_acc,
-                           c->add0, c->h_a, c->q_x, c->pre0, c->status + ST_RANGE, n, C, g.num_timesteps, t_first, ae.bn_acc_len};
+                           sp.add0, c->h_a, c->q_x, c->pre0, c->status + ST_RANGE, n, C, g.num_timesteps, t_first, ae.bn_acc_len};
         LAUNCH("node_prologue", SMK(node_prologue_tab_kernel<H>, dim3((unsigned)((N * 16 + kProTabThreads - 1) / kProTabThreads)), dim3(kProTabThreads), 0, s, ta));
     } else if (fused_prologue) {
-        NodePrologueArgs pa = prologue_args<H>(c, v_in, c->mol_of, c->t_mol, c->add0, c->h_a, c->q_x, c->pre0, n);
+        NodePrologueArgs pa = prologue_args<H>(c, v_in, c->mol_of, c->t_mol, sp.add0, c->h_a, c->q_x, c->pre0, n);
         pa.step_ptr = ae.step_ptr; pa.step_cur = ae.step_cur; pa.bn_acc = c->bn_acc; pa.bn_acc_len = ae.bn_acc_len; pa.t_first = t_first;
         if (nlay == 0) pa.n_lin_tiles = 0;
         pa.stamps = c->kstamp_sel == 5 ? c->kstamps : nullptr;
@@ -832,7 +834,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
     bool v_done = false;
     if (nlay > 0 && !fused_prologue) {   // prologue: per-node products and queries of the first x2h attention
         const DevLayer &D0 = c->dm.layer[0];
-        if (launch_linear<H>(c, s, "node_pre", cur_h, c->P(D0.pre_x2h), c->P(D0.pre6_x2h), c->P(D0.pre16_x2h), c->add0, 4 * H, c->pre0, 4 * H, 4 * NT, n,
+        if (launch_linear<H>(c, s, "node_pre", cur_h, c->P(D0.pre_x2h), c->P(D0.pre6_x2h), c->P(D0.pre16_x2h), sp.add0, 4 * H, c->pre0, 4 * H, 4 * NT, n,
                              c->kstamp_sel == 0 ? c->kstamps : nullptr)) return 1;
         if (launch_mlp2<H, 1>(c, s, "node_q", D0.q_x2h, cur_h, nullptr, NODE_LN_RELU, nullptr, c->q_x, H, H, n)) return 1;
     }
@@ -900,11 +902,11 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
             const int lin_tiles = (has_next && l + 1 < L ? 8 : 4) * NT;
             const bool lin_fused = c->chain_bf16 && c->lin_bf16 && c->node_f16 && c->lin_fuse;
             if (lin_fused) {
-                na.lin_img16 = c->P(Dl.lin16_img); na.add_mol = c->addp + (size_t)l * c->capB * 8 * H; na.mol_of = c->mol_of;
+                na.lin_img16 = c->P(Dl.lin16_img); na.add_mol = sp.addp + (size_t)l * c->capB * 8 * H; na.mol_of = c->mol_of;
                 na.pre_out = c->preAB; na.n_lin_tiles = lin_tiles; na.ld_add = 8 * H; na.ld_out = 8 * H;
             }
             const bool levels = c->node_levels && c->chain_bf16 && c->lin_bf16 && !c->node_f16 && !lin_fused;
-            float *lin_add = c->addp + (size_t)l * c->capB * 8 * H;
+            float *lin_add = sp.addp + (size_t)l * c->capB * 8 * H;
             if (levels) { if (launch_node_levels<H>(c, s, na, c->P(Dl.lin6_img), lin_add, 8 * H, c->preAB, 8 * H, lin_tiles)) return 1; }
             else if (xc_fused) { rec[4] = 1; if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
             else if (c->chain_bf16 && c->node_f16 && c->feat_f16) LAUNCH("node_chain", SMK((node_chain16_kernel<H, true>), dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
@@ -920,7 +922,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
         bool vn_done = false, stats_done = false;
         unsigned long long *stamps_h = (c->kstamp_sel == 2 && l == 0) ? c->kstamps : nullptr;
         if ((f16 || stream) && c->vn_fuse != 1) {   // h2x attention (+ VN-linear and batch statistics when vn_fuse = 2)
-            const H2xPlan plan = h2x_plan(c, l, fold, has_next, half_tiles, stat_acc, cur_x, x_next, out_pos);
+            const H2xPlan plan = h2x_plan(c, sp, l, fold, has_next, half_tiles, stat_acc, cur_x, x_next, out_pos);
             pending = plan.pending; stats_done = plan.stats_done; vn_done = plan.vn_done;
             if (plan.ddpm.enable) c->ddpm_vf = plan.ddpm;
             rec[2] |= plan.pending.enable; rec[3] |= plan.ddpm.enable;
@@ -943,7 +945,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
             EdgeFusedArgs fa{c->P(Dl.img_kh), c->P(Dl.img_vh), c->preAB, c->q_h, cur_x, c->nbr, c->ew, c->alpha, c->o3, n, 8 * H, stamps_h};
             if (c->vn_fuse) {   // VN-linear + batch statistics (2) or the whole coordinate update (1: grid barrier inside) behind the attention
                 double *tail = c->bn_acc + (size_t)L * kBnReplicas * 2 * hd;
-                fa.vn = vn_fuse_args(c, l, x_next, reinterpret_cast<unsigned *>(tail + l), c->vn_fuse == 1 ? 1 : 2);
+                fa.vn = vn_fuse_args(c, sp, l, x_next, reinterpret_cast<unsigned *>(tail + l), c->vn_fuse == 1 ? 1 : 2);
                 if (c->vn_fuse == 1) vn_done = true; else stats_done = true;
             }
             if (launch_fused<H, true>(c, s, fa)) return 1;
@@ -951,7 +953,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const float *x_in, const int64_t *
             EdgeArgs e{c->P(Dl.blob_h2x), c->preAB, c->q_h, cur_x, c->nbr, c->ew, c->o3, n, 8 * H, stamps_h};
             if (launch_edge<H, true>(c, s, e)) return 1;
         }
-        VnArgs va{cur_x, c->o3, c->ps + (size_t)l * c->capB * 2 * hd * 3, c->P(Dl.wf_x), c->P(Dl.wd_x), c->P(Dl.wf_o),
+        VnArgs va{cur_x, c->o3, sp.ps + (size_t)l * c->capB * 2 * hd * 3, c->P(Dl.wf_x), c->P(Dl.wd_x), c->P(Dl.wf_o),
                   c->P(Dl.wd_o), c->P(Dl.bn_g), c->P(Dl.bn_b), c->mol_of, c->pd, c->bn_acc + (size_t)l * kBnReplicas * 2 * hd, x_next, n, hd};
         const int per_blk = 256 / hd;
         if (!vn_done) {
@@ -1025,31 +1027,30 @@ int shapemol_create(const shapemol_config *cfg, const float *weights, size_t n_w
     if (device < 0 || device >= ndev) return fail("shapemol_create: no such HIP device");
     HIPCHK(hipSetDevice(device));
     auto *c = new shapemol_ctx();
+    auto drop = [&](int rc) { shapemol_destroy(c); return rc; };     // every pointer starts null: a partly built context is destroyed like a whole one
     c->cfg = *cfg; c->device = device;
     c->KP = cfg->knn <= 8 ? 8 : (cfg->knn <= 16 ? 16 : 32);
     hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) return drop(hip_fail("hipGetDeviceProperties", e));
     c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 
     Image im;
-    if (build_model_image(*cfg, hm, im, c->dm, c->hid_max)) { delete c; return 1; }
+    if (build_model_image(*cfg, hm, im, c->dm, c->hid_max)) return drop(1);
     const DevModel &dm = c->dm;
-    const int H = cfg->hidden_dim, T = cfg->num_timesteps;
-    if (hipMalloc((void **)&c->d_img, im.d.size() * sizeof(float)) != hipSuccess) { delete c; return fail("hipMalloc(weights) failed"); }
-    if (hipMemcpy(c->d_img, im.d.data(), im.d.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { hipFree(c->d_img); delete c; return fail("hipMemcpy(weights) failed"); }
-    if (H == 128 ? set_edge_attr<128>(c->KP) : set_edge_attr<32>(c->KP)) { hipFree(c->d_img); delete c; return 1; }
-    {   // time-embedding table over all timesteps
-        if (hipMalloc((void **)&c->ttab, (size_t)T * cfg->time_emb_dim * sizeof(float)) != hipSuccess) { hipFree(c->d_img); delete c; return fail("hipMalloc(time table) failed"); }
-        TimeTableArgs ta{c->P(dm.te1w), c->P(dm.te1b), c->P(dm.te2w), c->P(dm.te2b), c->ttab, T, cfg->time_emb_dim};
-        hipLaunchKernelGGL(time_table_kernel, dim3((T + 63) / 64), dim3(64), 0, nullptr, ta);
-        if (hipDeviceSynchronize() != hipSuccess) { hipFree(c->ttab); hipFree(c->d_img); delete c; return fail("time table kernel failed"); }
-        // ... and the atom embedding of every (timestep, atom type) pair
-        const int C = cfg->num_classes;
-        if (hipMalloc((void **)&c->etab, (size_t)T * C * H * sizeof(float)) != hipSuccess) { hipFree(c->ttab); hipFree(c->d_img); delete c; return fail("hipMalloc(embedding table) failed"); }
-        const int items = T * C * (H / 4);
-        hipLaunchKernelGGL(emb_table_kernel, dim3((items + 255) / 256), dim3(256), 0, nullptr, c->P(dm.embwT), c->P(dm.embb), c->ttab, c->etab, T, C, cfg->time_emb_dim, H);
-        if (hipDeviceSynchronize() != hipSuccess) { hipFree(c->etab); hipFree(c->ttab); hipFree(c->d_img); delete c; return fail("embedding table kernel failed"); }
-    }
+    const int H = cfg->hidden_dim, T = cfg->num_timesteps, C = cfg->num_classes;
+    if ((e = c->mem_model.alloc(&c->d_img, im.d.size() * sizeof(float))) != hipSuccess) return drop(hip_fail("shapemol_create: weights", e));
+    if ((e = hipMemcpy(c->d_img, im.d.data(), im.d.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return drop(hip_fail("hipMemcpy(weights)", e));
+    if (H == 128 ? set_edge_attr<128>(c->KP) : set_edge_attr<32>(c->KP)) return drop(1);
+    // time-embedding table over all timesteps, and the atom embedding of every (timestep, atom type) pair
+    if ((e = c->mem_model.alloc(&c->ttab, (size_t)T * cfg->time_emb_dim * sizeof(float))) != hipSuccess) return drop(hip_fail("shapemol_create: time table", e));
+    if ((e = c->mem_model.alloc(&c->etab, (size_t)T * C * H * sizeof(float))) != hipSuccess) return drop(hip_fail("shapemol_create: embedding table", e));
+    TimeTableArgs ta{c->P(dm.te1w), c->P(dm.te1b), c->P(dm.te2w), c->P(dm.te2b), c->ttab, T, cfg->time_emb_dim};
+    hipLaunchKernelGGL(time_table_kernel, dim3((T + 63) / 64), dim3(64), 0, nullptr, ta);
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return drop(hip_fail("time table kernel", e));
+    const int items = T * C * (H / 4);
+    hipLaunchKernelGGL(emb_table_kernel, dim3((items + 255) / 256), dim3(256), 0, nullptr, c->P(dm.embwT), c->P(dm.embb), c->ttab, c->etab, T, C, cfg->time_emb_dim, H);
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return drop(hip_fail("embedding table kernel", e));
     // (the default kernels split every operand into bf16 pieces, which have the fp32 exponent range: no bound on the weights.  The
     //  optional two-piece f16 kernels, edge_bf16 = 3, refuse weights whose LayerNorm outputs could leave the fp16 range: hid_max)
     *out = c;
@@ -1062,20 +1063,7 @@ void shapemol_destroy(shapemol_ctx *c) {
     hipDeviceSynchronize();
     c->drop_graphs();
     for (auto &r : c->prof) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
-    for (void *p : c->allocs) hipFree(p);
-    hipFree(c->ttab);
-    hipFree(c->etab);
-    hipFree(c->q_tab);
-    hipFree(c->d_img);
-    cloud_set_clear(c->cs);
-    mesh_set_clear(c->ms);
-    if (c->wg_table) hipFree(c->wg_table);
-    if (c->cgs.rows) hipFree(c->cgs.rows);
-    if (c->m_within) hipFree(c->m_within);
-    if (c->bn_run) hipFree(c->bn_run);
-    if (c->bn_eval_acc) hipFree(c->bn_eval_acc);
-    if (c->pin_off) { hipFree(c->pin_off); hipFree(c->pin_atom); hipFree(c->pin_nbr); }
-    delete c;
+    delete c;                 // its lists release what they own
 }
 
 int shapemol_set_bn_running(shapemol_ctx *c, const float *h_mean, const float *h_var, int64_t count) {
@@ -1086,9 +1074,9 @@ int shapemol_set_bn_running(shapemol_ctx *c, const float *h_mean, const float *h
         if (!(h_var[i] >= 0.f) || !std::isfinite(h_mean[i]) || !std::isfinite(h_var[i])) return fail("shapemol_set_bn_running: statistics must be finite, variance >= 0");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
-    if (!c->bn_run) {
-        HIPCHK(hipMalloc(&c->bn_run, 2 * count * sizeof(float)));
-        HIPCHK(hipMalloc(&c->bn_eval_acc, (size_t)L * kBnReplicas * 2 * hd * sizeof(double)));
+    if (!c->bn_run) {      // (a failed second allocation releases the first: both or neither)
+        HIPCHK(c->mem_bn.alloc(&c->bn_run, 2 * count * sizeof(float)));
+        HIPCHK(c->mem_bn.alloc(&c->bn_eval_acc, (size_t)L * kBnReplicas * 2 * hd * sizeof(double)));
     }
     HIPCHK(hipMemcpy(c->bn_run, h_mean, count * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->bn_run + count, h_var, count * sizeof(float), hipMemcpyHostToDevice));
@@ -1111,11 +1099,11 @@ int shapemol_score(shapemol_ctx *c, const float *d_pos, const int64_t *d_v, cons
     c->lastN = N; c->lastB = B;
     if (DISPATCH_H(c, ensure_prologue_tables<128>(c, s), ensure_prologue_tables<32>(c, s))) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
-    if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
+    if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape, c->prep[0]), run_prep<32>(c, s, d_batch, N, B, d_shape, c->prep[0]))) return 1;
     LAUNCH("prep", SMK(t_convert_kernel, dim3((B + 255) / 256), dim3(256), 0, s, d_t, (int)B, c->cfg.num_timesteps, c->t_mol, c->status));
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_v, (int)N, c->cfg.num_classes, c->status));
-    return DISPATCH_H(c, run_score<128>(c, s, d_pos, d_v, N, B, false, 0, out_pos, out_h, out_v),
-                      run_score<32>(c, s, d_pos, d_v, N, B, false, 0, out_pos, out_h, out_v));
+    return DISPATCH_H(c, run_score<128>(c, s, c->prep[0], d_pos, d_v, N, B, false, 0, out_pos, out_h, out_v),
+                      run_score<32>(c, s, c->prep[0], d_pos, d_v, N, B, false, 0, out_pos, out_h, out_v));
 }
 
 int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_init_v, const int64_t *d_batch,
@@ -1144,16 +1132,13 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     if (mesh && groups_table(c, s, c->ms.whole ? nullptr : d_batch, N, c->ms.ints, c->ms.groups)) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
     if (mesh && mesh_counters_clear(c, s, c->ms.groups)) return 1;
-    if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape), run_prep<32>(c, s, d_batch, N, B, d_shape))) return 1;
+    if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape, c->prep[0]), run_prep<32>(c, s, d_batch, N, B, d_shape, c->prep[0]))) return 1;
     uint64_t field_gen = 0;
     if (kind == Guide::Field) {      // the decoder's per-shape prologue of the chain's own shapes, once per chain
         if (shapemol_sd_chain_prepare_(c->field_sd, d_shape, B, s, &field_gen)) return 1;      // (not a profiled launch: no event pair)
     }
     if (cfg) {      // classifier-free guidance: the unconditional evaluation's shape data, from a zeroed shape, once per chain
-        swap_uncond(c);
-        const int rc = DISPATCH_H(c, run_prep_shape<128>(c, s, B, c->shape_zero), run_prep_shape<32>(c, s, B, c->shape_zero));
-        swap_uncond(c);
-        if (rc) return 1;
+        if (DISPATCH_H(c, run_prep_shape<128>(c, s, B, c->shape_zero, c->prep[1]), run_prep_shape<32>(c, s, B, c->shape_zero, c->prep[1]))) return 1;
         HIPCHK(hipMemsetAsync(c->cfg_hist, 0, (size_t)2 * kCfgHistWords * sizeof(unsigned), s));
         if (c->cgs.groups > 0) {      // the groups' element ranges, workgroups and ranks, from the batch vector (once per chain)
             const CfgArgs ca = cfg_args(c, N);
@@ -1176,14 +1161,12 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     HIPCHK(hipMemcpyAsync(c->x_state, d_init_pos, N * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->v_state, d_init_v, N * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     auto one_step = [&]() -> int {
-        if (DISPATCH_H(c, run_score<128>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v),
-                       run_score<32>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v))) return 1;
+        if (DISPATCH_H(c, run_score<128>(c, s, c->prep[0], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v),
+                       run_score<32>(c, s, c->prep[0], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v))) return 1;
         if (cfg) {        // the same step on a zeroed shape: same positions, graph and step index; own batch statistics and outputs
-            swap_uncond(c);
-            const int rc = DISPATCH_H(c, run_score<128>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true),
-                                      run_score<32>(c, s, c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true));
-            swap_uncond(c);
-            if (rc || run_cfg_stats(c, s, cfg_args(c, N))) return 1;
+            if (DISPATCH_H(c, run_score<128>(c, s, c->prep[1], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true),
+                           run_score<32>(c, s, c->prep[1], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true)) ||
+                run_cfg_stats(c, s, cfg_args(c, N))) return 1;
         }
         if (enqueue_guidance(c, s, kind, c->pred_pos, N, c->steps + 1, t_first)) return 1;     // shape guidance of the predicted x0 (steps with t > grad_step)
         return DISPATCH_H(c, run_ddpm<128>(c, s, N), run_ddpm<32>(c, s, N));
@@ -1318,7 +1301,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     else if (k == "h0") { src = c->h_a; bytes = N * g.hidden_dim * 4; }                   // the prologue's outputs: intact after an
     else if (k == "q_x") { src = c->q_x; bytes = N * g.hidden_dim * 4; }                  // evaluation with stop_layer = 1
     else if (k == "pre0") { src = c->pre0; bytes = N * 4 * g.hidden_dim * 4; }
-    else if (k == "add0") { src = c->add0; bytes = (size_t)c->lastB * 4 * g.hidden_dim * 4; }
+    else if (k == "add0") { src = c->prep[0].add0; bytes = (size_t)c->lastB * 4 * g.hidden_dim * 4; }
     else if (k == "pre") { src = c->preAB; bytes = N * 8 * g.hidden_dim * 4; }
     else if (k == "q") { src = c->q_h; bytes = N * g.hidden_dim * 4; }
     else if (k == "att") { src = c->att; bytes = N * g.hidden_dim * 4; }
@@ -1350,13 +1333,14 @@ int shapemol_set_knn_pins(shapemol_ctx *c, const int32_t *h_off, int32_t n_steps
     HIPCHK(hipSetDevice(c->device));
     c->drop_graphs();
     HIPCHK(hipDeviceSynchronize());
-    if (c->pin_off) { hipFree(c->pin_off); hipFree(c->pin_atom); hipFree(c->pin_nbr); c->pin_off = c->pin_atom = c->pin_nbr = nullptr; }
+    c->mem_pins.release();
     c->n_pins = 0; c->pin_steps = 0; c->pin_k = 0;
     if (n_pins <= 0) return 0;
     if (!h_off || !h_atom || !h_nbr || n_steps < 1 || k < 1 || k > c->KP) return fail("shapemol_set_knn_pins: bad arguments");
     if (h_off[0] != 0 || h_off[n_steps] != n_pins) return fail("shapemol_set_knn_pins: offsets do not cover the pins");
     for (int i = 0; i < n_steps; ++i) if (h_off[i + 1] < h_off[i]) return fail("shapemol_set_knn_pins: offsets must not decrease");
-    HIPCHK(hipMalloc(&c->pin_off, (size_t)(n_steps + 1) * 4)); HIPCHK(hipMalloc(&c->pin_atom, (size_t)n_pins * 4)); HIPCHK(hipMalloc(&c->pin_nbr, (size_t)n_pins * k * 4));
+    HIPCHK(c->mem_pins.alloc(&c->pin_off, (size_t)(n_steps + 1) * 4)); HIPCHK(c->mem_pins.alloc(&c->pin_atom, (size_t)n_pins * 4));
+    HIPCHK(c->mem_pins.alloc(&c->pin_nbr, (size_t)n_pins * k * 4));
     HIPCHK(hipMemcpy(c->pin_off, h_off, (size_t)(n_steps + 1) * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->pin_atom, h_atom, (size_t)n_pins * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->pin_nbr, h_nbr, (size_t)n_pins * k * 4, hipMemcpyHostToDevice));
@@ -1418,13 +1402,11 @@ int shapemol_set_cfg_groups(shapemol_ctx *c, int32_t n_groups, const int64_t *h_
     if (gs.stream_set && hipStreamSynchronize(gs.stream) != hipSuccess) hipDeviceSynchronize();
     if (n_groups > gs.cap) {
         c->drop_graphs();                        // the captured steps point into the old block
-        HIPCHK(hipDeviceSynchronize());
-        if (gs.rows) { hipFree(gs.rows); gs.rows = nullptr; gs.stat = nullptr; gs.hist = nullptr; gs.cap = 0; gs.last_groups = 0; }
+        gs.stat = nullptr; gs.hist = nullptr; gs.last_groups = 0;
         const size_t rb = ((size_t)(n_groups + 1) * sizeof(CfgGroup) + 255) / 256 * 256, sb = ((size_t)n_groups * 2 * sizeof(float) + 255) / 256 * 256;
-        unsigned char *blk = nullptr;
-        HIPCHK(hipMalloc((void **)&blk, rb + sb + (size_t)n_groups * 2 * kCfgHistWords * sizeof(unsigned)));
-        gs.rows = reinterpret_cast<CfgGroup *>(blk); gs.stat = reinterpret_cast<float *>(blk + rb); gs.hist = reinterpret_cast<unsigned *>(blk + rb + sb);
-        gs.cap = n_groups;
+        HIPCHK(grow(gs.mem, {dev_buf(&gs.rows, rb + sb + (size_t)n_groups * 2 * kCfgHistWords * sizeof(unsigned))}, gs.cap, n_groups));
+        unsigned char *blk = reinterpret_cast<unsigned char *>(gs.rows);
+        gs.stat = reinterpret_cast<float *>(blk + rb); gs.hist = reinterpret_cast<unsigned *>(blk + rb + sb);
     }
     HIPCHK(hipMemcpy(gs.rows, rows.data(), rows.size() * sizeof(CfgGroup), hipMemcpyHostToDevice));
     gs.groups = n_groups; gs.mols = h_mol_off[n_groups];

@@ -66,13 +66,8 @@ MeshGroupsArgs mesh_args(const MeshSet &ms, const int2 *table, float4 *within, i
 // or mesh groups: one table serves whichever guides)
 int groups_table(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int *ints, int n_groups) {
     const int64_t n_wg = groups_grid(N, n_groups);
-    if (n_wg > c->wg_table_cap) {
-        c->drop_graphs();                        // a captured step holds the table's address
-        if (c->wg_table) { hipFree(c->wg_table); c->wg_table = nullptr; }
-        c->wg_table_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->wg_table, (size_t)n_wg * sizeof(int2)));
-        c->wg_table_cap = n_wg;
-    }
+    if (n_wg > c->wg_table_cap) c->drop_graphs();      // a captured step holds the table's address
+    HIPCHK(grow(c->mem_wg, {dev_buf(&c->wg_table, (size_t)n_wg * sizeof(int2))}, c->wg_table_cap, n_wg));
     const int G1 = n_groups + 1;
     LAUNCH("prep", SMK(pc_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, ints, ints + G1, n_groups,
                        ints + 2 * G1, ints + 3 * G1, c->wg_table, (int)n_wg));
@@ -80,14 +75,12 @@ int groups_table(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t
 }
 
 // ---- point-cloud guidance: host side
-void cloud_set_clear(CloudSet &cs) {
-    if (cs.clouds) hipFree(cs.clouds);
-    cs = CloudSet{};
-}
+template <typename Set>          // CloudSet or MeshSet with the list that owns its block: nothing installed
+void set_clear(DevList &mem, Set &set) { mem.release(); set = Set{}; }
 
-// Installs groups that the caller has validated: one device block [clouds | radii | mol_off, cloud_off, atom_off, wg_off
-// (G + 1 ints each)], rounded up to 256 bytes, and `tail_bytes` more behind it for the caller (*tail).
-int cloud_set_install(CloudSet &cs, int n_groups, const int64_t *h_mol_off, const double *h_clouds, const int64_t *h_cloud_off,
+// Installs groups that the caller has validated into a cleared set: one device block of `mem` [clouds | radii | mol_off,
+// cloud_off, atom_off, wg_off (G + 1 ints each)], rounded up to 256 bytes, and `tail_bytes` more behind it for the caller (*tail).
+int cloud_set_install(DevList &mem, CloudSet &cs, int n_groups, const int64_t *h_mol_off, const double *h_clouds, const int64_t *h_cloud_off,
                       const double *h_radius, bool whole, int grad_step, const double *d_draws, size_t tail_bytes = 0,
                       unsigned char **tail = nullptr) {
     const int G1 = n_groups + 1;
@@ -100,10 +93,10 @@ int cloud_set_install(CloudSet &cs, int n_groups, const int64_t *h_mol_off, cons
     for (int g = 0; g < G1; ++g) { hi[g] = (int)h_mol_off[g]; hi[G1 + g] = (int)h_cloud_off[g]; }
     for (int g = 0; g < n_groups; ++g) max_points = std::max(max_points, hi[G1 + g + 1] - hi[G1 + g]);
     const size_t bytes_d = hd.size() * sizeof(double), bytes_i = hi.size() * sizeof(int), bytes = (bytes_d + bytes_i + 255) / 256 * 256;
-    HIPCHK(hipMalloc((void **)&cs.clouds, bytes + tail_bytes));
+    HIPCHK(mem.alloc(&cs.clouds, bytes + tail_bytes));
     hipError_t e = hipMemcpy(cs.clouds, hd.data(), bytes_d, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy((char *)cs.clouds + bytes_d, hi.data(), bytes_i, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { cloud_set_clear(cs); return fail(std::string("guidance clouds: hipMemcpy: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) { set_clear(mem, cs); return hip_fail("guidance clouds: hipMemcpy", e); }
     cs.radius = cs.clouds + P * 3; cs.ints = (int *)((char *)cs.clouds + bytes_d);
     cs.groups = n_groups; cs.max_points = max_points; cs.mols = h_mol_off[n_groups]; cs.points = P; cs.whole = whole;
     cs.grad_step = grad_step; cs.draws = d_draws;
@@ -112,10 +105,10 @@ int cloud_set_install(CloudSet &cs, int n_groups, const int64_t *h_mol_off, cons
 }
 
 // the single-cloud entry points: ONE group of n_points that spans whatever batch comes (`whole`: no molecule count)
-int cloud_set_install_whole(CloudSet &cs, const double *h_cloud, int64_t n_points, double radius, int grad_step, const double *d_draws,
+int cloud_set_install_whole(DevList &mem, CloudSet &cs, const double *h_cloud, int64_t n_points, double radius, int grad_step, const double *d_draws,
                             size_t tail_bytes = 0, unsigned char **tail = nullptr) {
     const int64_t mol_off[2] = {0, 0}, cloud_off[2] = {0, n_points};
-    return cloud_set_install(cs, 1, mol_off, h_cloud, cloud_off, &radius, true, grad_step, d_draws, tail_bytes, tail);
+    return cloud_set_install(mem, cs, 1, mol_off, h_cloud, cloud_off, &radius, true, grad_step, d_draws, tail_bytes, tail);
 }
 
 // ---- mesh shape guidance: host side
@@ -224,20 +217,14 @@ int mesh_set_image_whole(const std::string &me, const double *h_verts, int64_t n
     return mesh_set_image(me, true, 1, mol_off, h_verts, vert_off, h_faces, face_off, h_cloud, cloud_off, out);
 }
 
-void mesh_set_clear(MeshSet &ms) {
-    if (ms.faces) hipFree(ms.faces);
-    ms = MeshSet{};
-}
-
-// one device block: the image, rounded up to 256 bytes, and `tail_bytes` more behind it for the caller (*tail)
-int mesh_set_install(MeshSet &ms, const MeshSetImage &im, int grad_step, const double *d_draws, size_t tail_bytes = 0, unsigned char **tail = nullptr) {
+// into a cleared set: one device block of `mem`, the image, rounded up to 256 bytes, and `tail_bytes` more behind it for the caller (*tail)
+int mesh_set_install(DevList &mem, MeshSet &ms, const MeshSetImage &im, int grad_step, const double *d_draws, size_t tail_bytes = 0, unsigned char **tail = nullptr) {
     const size_t fb = (size_t)im.F * sizeof(MeshFace), bb = (size_t)im.F * sizeof(double4), cb = (size_t)im.P * 24, nb = (size_t)im.groups * 5 * sizeof(double);
     const size_t bytes = (im.bytes.size() + 255) / 256 * 256;
-    unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, bytes + tail_bytes));
+    HIPCHK(mem.alloc(&ms.faces, bytes + tail_bytes));
+    unsigned char *blk = reinterpret_cast<unsigned char *>(ms.faces);
     const hipError_t e = hipMemcpy(blk, im.bytes.data(), im.bytes.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(blk); return fail(std::string("guidance meshes: hipMemcpy: ") + hipGetErrorString(e)); }
-    ms.faces = reinterpret_cast<MeshFace *>(blk);
+    if (e != hipSuccess) { set_clear(mem, ms); return hip_fail("guidance meshes: hipMemcpy", e); }
     ms.fbox = reinterpret_cast<double4 *>(blk + fb);
     ms.clouds = reinterpret_cast<double *>(blk + fb + bb);
     ms.bounds = reinterpret_cast<double *>(blk + fb + bb + cb);
@@ -255,10 +242,10 @@ int mesh_workspace(shapemol_ctx *c, int64_t N, int64_t n_groups) {
     N = std::max(N, c->m_cap); n_groups = std::max(n_groups, c->m_cnt_cap);
     c->drop_graphs();                            // the captured steps point into the old block
     HIPCHK(hipDeviceSynchronize());
-    if (c->m_within) { hipFree(c->m_within); c->m_within = nullptr; c->m_out = c->m_cnt = nullptr; c->m_cap = c->m_cnt_cap = 0; }
-    unsigned char *blk = nullptr;
-    HIPCHK(hipMalloc((void **)&blk, (size_t)N * 20 + (size_t)n_groups * 20));
-    c->m_within = reinterpret_cast<float4 *>(blk);
+    c->mem_mesh.release();
+    c->m_out = c->m_cnt = nullptr; c->m_cap = c->m_cnt_cap = 0;
+    HIPCHK(c->mem_mesh.alloc(&c->m_within, (size_t)N * 20 + (size_t)n_groups * 20));
+    unsigned char *blk = reinterpret_cast<unsigned char *>(c->m_within);
     c->m_out = reinterpret_cast<int *>(blk + (size_t)N * 16);
     c->m_cnt = reinterpret_cast<int *>(blk + (size_t)N * 20);
     c->m_cap = N; c->m_cnt_cap = n_groups;
@@ -338,9 +325,9 @@ int shapemol_set_guidance(shapemol_ctx *c, const double *h_cloud, int64_t n_poin
     if (n_points > 0 && (!h_cloud || !(radius > 0.0))) return fail("shapemol_set_guidance: cloud / radius missing");
     HIPCHK(hipSetDevice(c->device));
     c->drop_graphs();                            // also drains the device: the old clouds may still be in use
-    cloud_set_clear(c->cs);
+    set_clear(c->mem_cs, c->cs);
     if (n_points == 0) return 0;
-    return cloud_set_install_whole(c->cs, h_cloud, n_points, radius, grad_step, d_draws);
+    return cloud_set_install_whole(c->mem_cs, c->cs, h_cloud, n_points, radius, grad_step, d_draws);
 }
 
 int shapemol_set_guidance_groups(shapemol_ctx *c, int32_t n_groups, const int64_t *h_mol_off, const double *h_clouds, const int64_t *h_cloud_off,
@@ -364,9 +351,9 @@ int shapemol_set_guidance_groups(shapemol_ctx *c, int32_t n_groups, const int64_
     }
     HIPCHK(hipSetDevice(c->device));
     c->drop_graphs();                            // also drains the device: the old clouds may still be in use
-    cloud_set_clear(c->cs);
+    set_clear(c->mem_cs, c->cs);
     if (n_groups == 0) return 0;
-    return cloud_set_install(c->cs, n_groups, h_mol_off, h_clouds, h_cloud_off, h_radius, false, grad_step, d_draws);
+    return cloud_set_install(c->mem_cs, c->cs, n_groups, h_mol_off, h_clouds, h_cloud_off, h_radius, false, grad_step, d_draws);
 }
 
 int shapemol_guide_points_groups(shapemol_ctx *c, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws, uint64_t seed,
@@ -387,9 +374,9 @@ int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_points, double
     hipStream_t s = (hipStream_t)stream;
     const unsigned n_wg = groups_grid(N, 1);
     const size_t o_step = (sizeof(ChainParams) + 15) / 16 * 16, o_table = o_step + 16;
-    CloudSet cs;                                        // a set of its own, and behind it [ChainParams | step counter | workgroup table]
+    DevList mem; CloudSet cs;                           // a set of its own, and behind it [ChainParams | step counter | workgroup table]
     unsigned char *tail = nullptr;
-    if (cloud_set_install_whole(cs, h_cloud, n_points, radius, 0, nullptr, o_table + n_wg * sizeof(int2), &tail)) return 1;
+    if (cloud_set_install_whole(mem, cs, h_cloud, n_points, radius, 0, nullptr, o_table + n_wg * sizeof(int2), &tail)) return 1;
     ChainParams *d_cp = reinterpret_cast<ChainParams *>(tail);
     int2 *d_table = reinterpret_cast<int2 *>(tail + o_table);
     hipLaunchKernelGGL(set_chain_params_kernel, dim3(1), dim3(1), 0, s, d_cp, guide_alone_params(seed, d_draws), reinterpret_cast<int *>(tail + o_step));
@@ -400,7 +387,7 @@ int shapemol_pointcloud_guidance(const double *h_cloud, int64_t n_points, double
     hipLaunchKernelGGL(pc_guidance_kernel, dim3(n_wg), dim3(256), cloud_lds_bytes(n_points), s, ga);
     const hipError_t e = hipGetLastError();
     const hipError_t e2 = hipStreamSynchronize(s);       // the block is freed below; the reference's function is synchronous too
-    cloud_set_clear(cs);
+    set_clear(mem, cs);
     if (e != hipSuccess) return fail(std::string("shapemol_pointcloud_guidance: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(std::string("shapemol_pointcloud_guidance: ") + hipGetErrorString(e2));
     return 0;
@@ -430,9 +417,9 @@ int shapemol_set_mesh_guidance(shapemol_ctx *c, const double *h_verts, int64_t n
     if (n_faces > 0 && mesh_set_image_whole("shapemol_set_mesh_guidance", h_verts, n_verts, h_faces, n_faces, h_cloud, n_cloud, img)) return 1;
     HIPCHK(hipSetDevice(c->device));
     c->drop_graphs();                            // also drains the device: the old meshes may still be in use
-    mesh_set_clear(c->ms);
+    set_clear(c->mem_ms, c->ms);
     if (n_faces == 0) return 0;
-    return mesh_set_install(c->ms, img, grad_step, d_draws);
+    return mesh_set_install(c->mem_ms, c->ms, img, grad_step, d_draws);
 }
 
 int shapemol_guide_points_mesh(shapemol_ctx *c, float *d_pos, int64_t N, const double *d_draws, uint64_t seed, void *stream) {
@@ -449,9 +436,9 @@ int shapemol_set_mesh_guidance_groups(shapemol_ctx *c, int32_t n_groups, const i
     if (n_groups > 0 && mesh_set_image(me, false, n_groups, h_mol_off, h_verts, h_vert_off, h_faces, h_face_off, h_clouds, h_cloud_off, img)) return 1;
     HIPCHK(hipSetDevice(c->device));
     c->drop_graphs();                            // also drains the device: the old meshes may still be in use
-    mesh_set_clear(c->ms);
+    set_clear(c->mem_ms, c->ms);
     if (n_groups == 0) return 0;
-    return mesh_set_install(c->ms, img, grad_step, d_draws);
+    return mesh_set_install(c->mem_ms, c->ms, img, grad_step, d_draws);
 }
 
 int shapemol_guide_points_mesh_groups(shapemol_ctx *c, float *d_pos, const int64_t *d_batch, int64_t N, const double *d_draws, uint64_t seed,
@@ -472,9 +459,9 @@ int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t
     const unsigned n_wg = groups_grid(N, 1);
     const size_t o_misc = (sizeof(ChainParams) + 255) / 256 * 256, o_table = o_misc + 256;
     const size_t o_in = o_table + ((size_t)n_wg * sizeof(int2) + 255) / 256 * 256, o_out = o_in + (size_t)N * 16;
-    MeshSet ms;
+    DevList mem; MeshSet ms;
     unsigned char *tail = nullptr;
-    if (mesh_set_install(ms, img, 0, nullptr, o_out + (size_t)N * 4, &tail)) return 1;
+    if (mesh_set_install(mem, ms, img, 0, nullptr, o_out + (size_t)N * 4, &tail)) return 1;
     int *d_misc = reinterpret_cast<int *>(tail + o_misc);        // [0] step counter, [4 .. 11] status, [16 .. 19] counters, [20] unguided steps
     hipError_t e = hipMemsetAsync(d_misc, 0, 256, s);
     int32_t flag = 0;
@@ -492,7 +479,7 @@ int shapemol_mesh_guidance(const double *h_verts, int64_t n_verts, const int32_t
         if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_misc + 4 + ST_MESH, sizeof(int32_t), hipMemcpyDeviceToHost, s);
     }
     const hipError_t e2 = hipStreamSynchronize(s);       // the block is freed below; the reference's function is synchronous too
-    mesh_set_clear(ms);
+    set_clear(mem, ms);
     if (e != hipSuccess) return fail(std::string("shapemol_mesh_guidance: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(std::string("shapemol_mesh_guidance: ") + hipGetErrorString(e2));
     if (flag) {
