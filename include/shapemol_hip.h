@@ -486,6 +486,10 @@ int shapemol_seg_attention_backward(const float *d_q, const float *d_k, const fl
  *          "edge_waves" (waves per workgroup of the edge kernels, 1..12; 0 = automatic: ceil(jobs / CUs) [default]; a
  *                        value other than 0 also selects the separate launches),
  *          "lin_waves"  (1..16 waves per workgroup of node_linear_kernel, tuning),
+ *          "x2h_out_fuse" (exact streaming mode with the two-level node form, k <= 16: 1 = h' = h + MLP_out([att | h]) in the tail of the
+ *          x2h kernel instead of a node_out6_kernel launch while a workgroup owns at most 96 atoms [default], 2 = whatever it owns,
+ *          0 = node_out6_kernel; same bits), "stream_chunk" (tiles per workgroup of the streaming edge kernels, 0 = automatic
+ *          [default]; for tests),
  *          "node_levels" (exact-mode node kernels: 1 = the node stage of a layer by dependency level -- node_out6_kernel (h' only),
  *                        then node_after6_kernel (follow-up MLPs and per-node products of h' side by side in one grid) [default];
  *                        0 = node_chain6_kernel + node_linear6_kernel.  Same results to the bit; tuning / A/B),

@@ -137,6 +137,9 @@ struct shapemol_ctx {
                                 // launch (measured: 28.5 us against 15.3 + 11.1 us, eight dependent weight blocks per wave)
     int node_levels = 1;        // 1: the exact-mode node stage as node_out6_kernel (h' only) + node_after6_kernel (follow-up MLPs and per-node products
                                 // side by side); 0: node_chain6_kernel + node_linear6_kernel
+    int x2h_out_fuse = 1;       // 1: h' inside the x2h streaming kernel's tail (stream_node_out_epilogue) instead of a node_out6_kernel launch, while a
+                                // workgroup owns at most kX2hOutFuseAtoms (96) atoms; 2: whatever it owns (measurements); 0: node_out6_kernel
+    int stream_chunk_opt = 0;   // option "stream_chunk": tiles per workgroup of the streaming kernels (tests); 0 = automatic
     int after_order = 2;        // node_after6_kernel's grid: 0 follow-up jobs first, 1 interleaved with the linear jobs, 2 linear jobs first
     int after_waves = 16;       // ... waves of its linear jobs (the workgroup has max(H / 16, after_waves) waves)
     int after_lin_wgs = 0;      // ... workgroups aimed at for its linear jobs (0 = automatic)
@@ -182,6 +185,9 @@ struct shapemol_ctx {
     // the node stage of the last layer the most recent run_score issued (debug_read "launch_node"): {two-level form used, follow-up
     // jobs, linear jobs, waves per workgroup, job order, column tiles per linear job, linear staging chunk, dynamic LDS bytes}
     int64_t node_rec[8] = {};
+    // the x2h kernel's fused tail in that layer (debug_read "launch_x2h_out"): {fused form used, atoms per workgroup, 16-atom column
+    // tiles per workgroup, dynamic LDS bytes of the x2h launch}
+    int64_t x2h_out_rec[4] = {};
     // the captured step depends on the batch geometry only: seed, noise and trajectory pointers live in chain_params
     // what a captured step depends on besides the options (which drop the graphs when set): sizes, guidance, and the two
     // launch decisions taken from the max_mol_atoms hint (folded coordinate update, fused graph kernel)
@@ -467,9 +473,20 @@ static int stream_jobs(const shapemol_ctx *c, int n_atoms) {      // a job = one
 }
 static int stream_chunk(const shapemol_ctx *c, int n_atoms) {
     const int njobs = stream_jobs(c, n_atoms);
+    if (c->stream_chunk_opt > 0) return c->KP <= 16 ? c->stream_chunk_opt : (c->stream_chunk_opt + kStreamTPR - 1) / kStreamTPR * kStreamTPR;
     const int per_cu = (njobs + c->num_cu - 1) / c->num_cu;
     if (!c->stream_whole_rounds && c->KP <= 16) return std::max(1, per_cu);
     return std::max(kStreamTPR, (per_cu + kStreamTPR - 1) / kStreamTPR * kStreamTPR);
+}
+
+// h' in the x2h kernel's tail (sm_edge_stream.h: stream_node_out_epilogue) instead of a node_out6_kernel launch?  Only where the
+// two-level node form follows a streaming x2h kernel of whole-atom tiles.  The tail walks a workgroup's atoms 32 at a time and
+// streams the output MLP's weights again for every pass; it won at every size measured, up to the 88 atoms (three passes) of
+// B = 1024, so the boundary is three passes: beyond that nothing is measured and node_out6_kernel stays
+constexpr int kX2hOutFuseAtoms = 3 * CHAIN_COLS * 16;
+static bool x2h_out_fuse_ok(const shapemol_ctx *c, int n_atoms, bool levels) {
+    if (!c->x2h_out_fuse || c->edge_bf16 != 2 || !levels || c->KP > 16) return false;
+    return c->x2h_out_fuse == 2 || stream_chunk(c, n_atoms) * (16 / c->KP) <= kX2hOutFuseAtoms;
 }
 
 template <int H, bool H2X>
@@ -481,6 +498,11 @@ int launch_stream(shapemol_ctx *c, hipStream_t s, EdgeStreamArgs a) {
     constexpr int NWAVE = H / 16 + kStreamProducers;
     const size_t shm = (size_t)M::O_TAIL * 4 + (H2X ? (size_t)NWAVE * 64 * 2 * 8 : (a.vf.enable ? (size_t)kVnFoldBytes : 0));
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
+    if (!H2X) {
+        const int64_t apw = KP <= 16 ? (int64_t)a.chunk * (16 / KP) : 0;
+        const int64_t rec[4] = {a.no.h_out != nullptr, apw, (apw + 15) / 16, (int64_t)shm};
+        std::copy(rec, rec + 4, c->x2h_out_rec);
+    }
     DISPATCH_KP(nm, edge_stream_kernel, (, H2X), dim3(grid), dim3(NWAVE * 64), shm, s, a);
     return 0;
 }
@@ -559,10 +581,10 @@ int launch_linear(shapemol_ctx *c, hipStream_t s, const char *name, const float 
 constexpr int kAfterChunk = 6;      // linear staging chunk of 8-wave workgroups: 6 * 3 * H * 32 = 72 KB at H = 128, two workgroups per CU
 template <int H>
 int launch_node_levels(shapemol_ctx *c, hipStream_t s, const NodeChainArgs &na, const float *lin_img6, const float *add_mol, int ld_add,
-                       float *out, int ld_out, int lin_tiles) {
+                       float *out, int ld_out, int lin_tiles, bool out_done) {
     constexpr int NT = H / 16;
     const int n = na.n_atoms, n_ct = (n + 15) / 16, n_pairs = (n_ct + CHAIN_COLS - 1) / CHAIN_COLS;
-    LAUNCH("node_chain", SMK(node_out6_kernel<H>, dim3(n_pairs), dim3(H * 4), Out6Lds<H>::BYTES, s, na));
+    if (!out_done) LAUNCH("node_chain", SMK(node_out6_kernel<H>, dim3(n_pairs), dim3(H * 4), Out6Lds<H>::BYTES, s, na));      // (else: the x2h kernel's tail wrote h')
     const int lw = c->after_waves, bw = std::max(lw, NT);
     const int per_cu = bw <= 8 ? 2 : 1;                   // workgroups that share a CU (128 VGPRs per lane; LDS: kAfterChunk)
     const int slots = c->num_cu * per_cu;
@@ -811,6 +833,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
     int64_t (&rec)[8] = c->launch_rec;
     std::fill(rec, rec + 8, 0);
     std::fill(c->node_rec, c->node_rec + 8, 0);
+    std::fill(c->x2h_out_rec, c->x2h_out_rec + 4, 0);
     rec[0] = sampling; rec[1] = graph_fused; rec[7] = c->num_cu;
     if (c->edge_bf16 == 2 && nlay > 0) { rec[5] = stream_chunk(c, n); rec[6] = (stream_jobs(c, n) + rec[5] - 1) / rec[5]; }
     if (reuse_graph) {
@@ -860,6 +883,10 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
         const float *pre_x = l == 0 ? c->pre0 : c->preAB + 4 * H;      // node pre-products of this x2h attention
         const int ld_pre_x = l == 0 ? 4 * H : 8 * H;
         unsigned long long *stamps_x = (c->kstamp_sel == 1 && l == 0) ? c->kstamps : nullptr;
+        float *h_dst = (last && out_h) ? out_h : (cur_h == c->h_a ? c->h_b : c->h_a);      // h' of this layer
+        const bool lin_fused = c->chain_bf16 && c->lin_bf16 && c->node_f16 && c->lin_fuse;
+        const bool levels = c->node_levels && c->chain_bf16 && c->lin_bf16 && !c->node_f16 && !lin_fused;
+        const bool out_fused = stream && x2h_out_fuse_ok(c, n, levels);      // ... computed by the x2h kernel's tail
         Edge16Args xea{};
         if (f16 || stream) {   // x2h attention: two-piece f16 operands, both MLP images resident (sm_edge16.h), or exactly split bf16
                                // operands, producer / consumer waves (sm_edge_stream.h); `pending`: the previous layer's coordinate update
@@ -875,6 +902,8 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
                 sa.b2v = c->P(Dl.sb2_vx);
                 fill_edge(sa, c, pre_x, ld_pre_x, c->q_x, cur_x, c->att, n, half_tiles, stamps_x);
                 sa.vf = pending;
+                if (out_fused) sa.no = NodeOutArgs{c->att, cur_h, c->P(Dl.no.b1), c->P(Dl.no.g), c->P(Dl.no.be), c->P(Dl.no.b2),
+                                                   c->P(Dl.no.w1img6), c->P(Dl.no.w2img6), h_dst};
                 if (launch_stream<H, false>(c, s, sa)) return 1;
             }
             pending = VnFold{};
@@ -887,7 +916,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
             if (launch_edge<H, false>(c, s, e)) return 1;
         }
         {   // node side: h' = h + MLP([att | h]); queries of h2x (this layer) and x2h (next layer) or the v head
-            float *dst = (last && out_h) ? out_h : (cur_h == c->h_a ? c->h_b : c->h_a);
+            float *dst = h_dst;
             NodeChainArgs na{};
             na.att = c->att; na.h = cur_h; na.h_out = dst; na.n_atoms = n;
             na.stamps = (c->kstamp_sel == 3 && l == 0) ? c->kstamps : nullptr;
@@ -900,14 +929,12 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
             else if (out_v) { na.f[1] = follow_of(c, c->dm.vhead, NODE_SSP, out_v, C, C); na.n_follow = 2; v_done = true; }
             const int n_ct = (n + 15) / 16;
             const int lin_tiles = (has_next && l + 1 < L ? 8 : 4) * NT;
-            const bool lin_fused = c->chain_bf16 && c->lin_bf16 && c->node_f16 && c->lin_fuse;
             if (lin_fused) {
                 na.lin_img16 = c->P(Dl.lin16_img); na.add_mol = sp.addp + (size_t)l * c->capB * 8 * H; na.mol_of = c->mol_of;
                 na.pre_out = c->preAB; na.n_lin_tiles = lin_tiles; na.ld_add = 8 * H; na.ld_out = 8 * H;
             }
-            const bool levels = c->node_levels && c->chain_bf16 && c->lin_bf16 && !c->node_f16 && !lin_fused;
             float *lin_add = sp.addp + (size_t)l * c->capB * 8 * H;
-            if (levels) { if (launch_node_levels<H>(c, s, na, c->P(Dl.lin6_img), lin_add, 8 * H, c->preAB, 8 * H, lin_tiles)) return 1; }
+            if (levels) { if (launch_node_levels<H>(c, s, na, c->P(Dl.lin6_img), lin_add, 8 * H, c->preAB, 8 * H, lin_tiles, out_fused)) return 1; }
             else if (xc_fused) { rec[4] = 1; if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
             else if (c->chain_bf16 && c->node_f16 && c->feat_f16) LAUNCH("node_chain", SMK((node_chain16_kernel<H, true>), dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
             else if (c->chain_bf16 && c->node_f16) LAUNCH("node_chain", SMK(node_chain16_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
@@ -1270,6 +1297,8 @@ int shapemol_set_option(shapemol_ctx *c, const char *name, int64_t value) {
     else if (k == "chain_bf16") c->chain_bf16 = (int)value;
     else if (k == "vn_fuse") c->vn_fuse = (int)value;
     else if (k == "node_levels") c->node_levels = value != 0;
+    else if (k == "x2h_out_fuse") { if (value < 0 || value > 2) return fail("x2h_out_fuse must be 0 (node_out6_kernel), 1 (x2h tail inside its boundary) or 2 (x2h tail always)"); c->x2h_out_fuse = (int)value; }
+    else if (k == "stream_chunk") { if (value < 0 || value > 4096) return fail("stream_chunk must be 0 (automatic) .. 4096"); c->stream_chunk_opt = (int)value; }
     else if (k == "after_order") { if (value < 0 || value > 2) return fail("after_order must be 0 (follow-up jobs first), 1 (interleaved) or 2 (linear jobs first)"); c->after_order = (int)value; }
     else if (k == "after_waves") { if (value < 1 || value > 16) return fail("after_waves must be 1..16"); c->after_waves = (int)value; }
     else if (k == "after_lin_wgs") { if (value < 0 || value > 4096) return fail("after_lin_wgs must be 0 (automatic) .. 4096"); c->after_lin_wgs = (int)value; }
@@ -1293,6 +1322,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     if (k == "dims") { if (max_bytes < sizeof(dims)) return -1; std::memcpy(dst, dims, sizeof(dims)); return sizeof(dims); }
     if (k == "captures") { if (max_bytes < 8) return -1; std::memcpy(dst, &c->n_captures, 8); return 8; }
     if (k == "launch") { if (max_bytes < sizeof(c->launch_rec)) return -1; std::memcpy(dst, c->launch_rec, sizeof(c->launch_rec)); return sizeof(c->launch_rec); }
+    if (k == "launch_x2h_out") { if (max_bytes < sizeof(c->x2h_out_rec)) return -1; std::memcpy(dst, c->x2h_out_rec, sizeof(c->x2h_out_rec)); return sizeof(c->x2h_out_rec); }
     if (k == "launch_node") { if (max_bytes < sizeof(c->node_rec)) return -1; std::memcpy(dst, c->node_rec, sizeof(c->node_rec)); return sizeof(c->node_rec); }
     if (k == "nbr") { src = c->nbr; bytes = N * c->KP * 4; }
     else if (k == "ew") { src = c->ew; bytes = N * c->KP * 4; }

@@ -28,6 +28,7 @@
 // The same launch serves any batch size: a workgroup owns `chunk` consecutive tiles and loops over them.
 #pragma once
 #include "sm_edge16.h"
+#include "sm_node.h"
 #include <type_traits>
 
 struct EdgeStreamArgs {
@@ -47,6 +48,7 @@ struct EdgeStreamArgs {
     float *xsum;                      // h2x with vn.enable: [N][3] sum of the attention rows per atom (for a following fold), or nullptr
     VnFold vf;                        // x2h: coordinate update of the previous layer in the prologue
     float *part_ms;                   // KP = 32: [2 N][heads][2] running max and sum of every half-atom tile's softmax (sm_edge16.h)
+    NodeOutArgs no;                   // x2h, KP <= 16: the node output MLP behind the attention (no.h_out = nullptr: not fused; no.att = out)
 };
 
 constexpr int kStreamProducers = 4, kStreamTPR = 2;      // producer waves; tiles per round
@@ -311,6 +313,24 @@ SM_DEV void stream_vn_epilogue(const EdgeStreamArgs &a, const StreamGeo<H, KP, t
         double *acc = a.vn.acc + (size_t)(blockIdx.x % kVnReplicas) * 2 * HD;
         atomicAdd(acc + threadIdx.x, s1);
         atomicAdd(acc + HD + threadIdx.x, s2);
+    }
+}
+
+// x2h epilogue (option x2h_out_fuse): h' = h + MLP_out([att | h]) of the workgroup's own atoms -- node_out6_kernel's work without
+// its launch.  The attention rows never cross a workgroup: the consumers stored them before the last round's barrier and they
+// come back through L2, as the h2x rows do above.  The H / 16 consumer waves are node_out6_kernel's team (wave = output row block)
+// and walk the atoms 32 at a time through node_out6_pair, in the edge tiles' LDS (dead after the round loop); the producers
+// leave (a barrier counts the waves still running).  The weights are requested one Linear at a time: with both in flight, as in
+// node_out6_kernel, the kernel would need 195 registers instead of the 168 that keep three waves per SIMD.
+template <int H, int KP>
+SM_DEV void stream_node_out_epilogue(const EdgeStreamArgs &a, const StreamGeo<H, KP, false> &G, float *lds) {
+    using GE = StreamGeo<H, KP, false>;
+    static_assert(Out6Lds<H>::BYTES <= (size_t)StreamMap<H, false>::O_TAIL * 4, "the tail works inside the edge tiles' LDS");
+    if (a.no.h_out == nullptr || G.wave >= GE::NCONS) return;
+    const int first_atom = G.wg_first * GE::APJ, end_atom = min(a.n_atoms, G.wg_end * GE::APJ);
+    for (int atom0 = first_atom; atom0 < end_atom; atom0 += CHAIN_COLS * 16) {
+        if (atom0 != first_atom) __syncthreads();          // the previous pair's hidden tile has been read
+        node_out6_pair<H, false>(a.no, atom0, end_atom, reinterpret_cast<unsigned char *>(lds));
     }
 }
 
@@ -630,4 +650,5 @@ edge_stream_kernel(EdgeStreamArgs a) {
     else if (((G.wave - G.NCONS) & 1) == 0) stream_producer<H, KP, H2X, 0>(a, G, lds, (G.wave - G.NCONS) >> 1);
     else stream_producer<H, KP, H2X, 1>(a, G, lds, (G.wave - G.NCONS) >> 1);
     if constexpr (H2X && KP <= 16) stream_vn_epilogue<H, KP>(a, G, lds);      // (k > 16: vn_stats / vn_apply follow the combine)
+    if constexpr (!H2X && KP <= 16) stream_node_out_epilogue<H, KP>(a, G, lds);
 }

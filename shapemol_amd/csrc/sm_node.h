@@ -951,6 +951,16 @@ struct Team6 {       // the steps of node_chain6_kernel's team of H / 16 waves o
 #pragma unroll
         for (int p = 0; p < 3; ++p) load_piece(img, p, w);
     }
+    // load_w with one running address instead of 3 * KB precomputed ones (two VGPRs each: the blocks lie 1 KB apart, beyond the
+    // immediate offset of a load), for callers with a tight register budget
+    template <int KB>
+    SM_DEV void load_w_seq(const float *img, u32x4 (&w)[3][KB]) const {
+        const u32x4 *wi = reinterpret_cast<const u32x4 *>(img) + (size_t)ot * 3 * KB * 64 + lane;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int b = 0; b < KB; ++b) { w[p][b] = *wi; wi += 64; asm volatile("" : "+v"(wi)); }
+    }
     // acc[c] += W * X_c over KB k-steps; fragments at f[((piece * KB + b) * CC + c) * 64 + slot]
     template <int KB>
     SM_DEV void gemm6(const u32x4 (&w)[3][KB], const u32x4 *f, f32x4 (&acc)[CC]) const {
@@ -1024,18 +1034,26 @@ struct Out6Lds {     // one K = 2H fragment buffer (later the hidden tile) + one
     static constexpr size_t BYTES = (size_t)2 * Chain6Lds<H>::FRAG * 16 + (size_t)Chain6Lds<H>::PRE * 4;
 };
 
-template <int H>
-__global__ void __launch_bounds__(H * 4)
-node_out6_kernel(NodeChainArgs a) {
+// h' = h + MLP_out([att | h]) for the (up to) 32 atoms atom0 .. atom0 + 31 below atom_end, as two 16-atom column tiles of the
+// team's H / 16 waves: stages 0-1 of node_chain6_kernel.  lds: Out6Lds<H>::BYTES.  A column's arithmetic does not depend on
+// which column of which tile the atom sits in, so h' has the same bits for any atom0.
+// AHEAD: the second Linear's block and the residual rows are requested with the first's (node_out6_kernel: 195 VGPRs); without
+// it they are requested once the first product has freed its registers (the x2h kernel's tail, sm_edge_stream.h: 168).
+struct NodeOutArgs {
+    const float *att, *h;                                 // [N][H] each
+    const float *b1, *ln_g, *ln_b, *b2, *w1img6, *w2img6; // node_output MLP (K = 2H), split bf16 images
+    float *h_out;                                         // [N][H]
+};
+
+template <int H, bool AHEAD>
+SM_DEV void node_out6_pair(const NodeOutArgs &a, int atom0, int atom_end, unsigned char *lds) {
     using L = Chain6Lds<H>;
     constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS;
-    extern __shared__ __attribute__((aligned(16))) unsigned char out6_lds[];
-    u32x4 *fin = reinterpret_cast<u32x4 *>(out6_lds);      // [att | h] fragments (K = 2H); later the hidden tile
+    u32x4 *fin = reinterpret_cast<u32x4 *>(lds);           // [att | h] fragments (K = 2H); later the hidden tile
     float *pre0 = reinterpret_cast<float *>(fin + 2 * L::FRAG);
     const Team6<H> t;
-    const int ct0 = blockIdx.x * CC;
-    auto atom_of = [&](int c) { return min((ct0 + c) * 16 + t.n, a.n_atoms - 1); };
-    auto atom_ok = [&](int c) { return (ct0 + c) * 16 + t.n < a.n_atoms; };
+    auto atom_of = [&](int c) { return min(atom0 + c * 16 + t.n, atom_end - 1); };
+    auto atom_ok = [&](int c) { return atom0 + c * 16 + t.n < atom_end; };
 
     // ---- stage 0: weights of the output MLP; [att | h] tiles -> fragments (activation rows requested before the weights,
     // as in node_chain6_kernel) ------------------------------------------------------------------------
@@ -1046,15 +1064,18 @@ node_out6_kernel(NodeChainArgs a) {
     for (int it = 0; it < SITER; ++it) {
         const int idx = threadIdx.x + it * NT * 64;
         const int sl = idx & 63, sb = (idx >> 6) % (2 * NB), sc = idx / (64 * 2 * NB);
-        const int at = min((ct0 + sc) * 16 + (sl & 15), a.n_atoms - 1);
+        const int at = min(atom0 + sc * 16 + (sl & 15), atom_end - 1);
         const float *src = (sb < NB ? a.att + (size_t)at * H + 32 * sb : a.h + (size_t)at * H + 32 * (sb - NB)) + 4 * (sl >> 4);
         sv0[it] = ldg4(src); sv1[it] = ldg4(src + 16);
     }
-    float4 hres[CC];
+    float4 hres[CC], b2;
+    if constexpr (AHEAD) {
 #pragma unroll
-    for (int c = 0; c < CC; ++c) hres[c] = ldg4(a.h + (size_t)atom_of(c) * H + t.f0);    // residual
-    const float4 b1 = ldg4(a.b1 + t.f0), b2 = ldg4(a.b2 + t.f0);
-    t.load_w(a.w1img6, w1);
+        for (int c = 0; c < CC; ++c) hres[c] = ldg4(a.h + (size_t)atom_of(c) * H + t.f0);    // residual
+    }
+    const float4 b1 = ldg4(a.b1 + t.f0);
+    if constexpr (AHEAD) b2 = ldg4(a.b2 + t.f0);
+    if constexpr (AHEAD) t.load_w(a.w1img6, w1); else t.load_w_seq(a.w1img6, w1);
 #pragma unroll
     for (int it = 0; it < SITER; ++it) {
         const int idx = threadIdx.x + it * NT * 64;
@@ -1062,7 +1083,7 @@ node_out6_kernel(NodeChainArgs a) {
         const float v[8] = {sv0[it].x, sv0[it].y, sv0[it].z, sv0[it].w, sv1[it].x, sv1[it].y, sv1[it].z, sv1[it].w};
         t.template put_frag<2 * NB>(fin, sb, sc, sl, v);
     }
-    t.load_w(a.w2img6, w2);
+    if constexpr (AHEAD) t.load_w(a.w2img6, w2);
     __syncthreads();
 
     // ---- stage 1: h' = h + W2 relu(LN(W1 [att | h] + b1)) + b2 ---------------------------------------
@@ -1072,6 +1093,12 @@ node_out6_kernel(NodeChainArgs a) {
         for (int c = 0; c < CC; ++c) acc[c] = f32x4{b1.x, b1.y, b1.z, b1.w};
         t.gemm6(w1, fin, acc);
         t.store_pre(pre0, acc);
+    }
+    if constexpr (!AHEAD) {
+        t.load_w_seq(a.w2img6, w2);
+#pragma unroll
+        for (int c = 0; c < CC; ++c) hres[c] = ldg4(a.h + (size_t)atom_of(c) * H + t.f0);
+        b2 = ldg4(a.b2 + t.f0);
     }
     __syncthreads();                                       // (every wave has also finished reading fin)
     t.normalise(pre0, NODE_LN_RELU, a.ln_g, a.ln_b, fin);
@@ -1085,6 +1112,14 @@ node_out6_kernel(NodeChainArgs a) {
         const float4 hn = {acc[c][0] + hres[c].x, acc[c][1] + hres[c].y, acc[c][2] + hres[c].z, acc[c][3] + hres[c].w};
         if (atom_ok(c)) stg4(a.h_out + (size_t)atom_of(c) * H + t.f0, hn);
     }
+}
+
+template <int H>
+__global__ void __launch_bounds__(H * 4)
+node_out6_kernel(NodeChainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char out6_lds[];
+    const NodeOutArgs o{a.att, a.h, a.b1, a.ln_g, a.ln_b, a.b2, a.w1img6, a.w2img6, a.h_out};
+    node_out6_pair<H, true>(o, blockIdx.x * CHAIN_COLS * 16, a.n_atoms, out6_lds);
 }
 
 struct NodeAfterArgs {
