@@ -532,6 +532,39 @@ void shapemol_debug_split_exact(float x, uint16_t *pieces);
  *        left unguided for want of within-atoms (status flag 6 says that some group was, this says which and how often).
  * Returns the number of bytes written, or -1. */
 int64_t shapemol_debug_read(shapemol_ctx *ctx, const char *name, void *host_dst, size_t max_bytes);
+/* ---- shape auto-encoder batches from triangle meshes ---------------------------------------------------------------
+ * The reference's ShapeData / collate_fn (datasets/shape_data.py:106-187) and the mesh half of get_pointAE_shape_emb
+ * (utils/shape.py:240-284) on the device.  A batch is n_shapes meshes back to back: HOST h_vert_off / h_face_off (n_shapes + 1,
+ * starting at 0), h_verts (sum V, 3) float64, h_faces (sum F, 3) int32 with indices relative to the mesh's own vertices.  Per
+ * mesh: n_cloud surface points, area-weighted (pytorch3d's rule), rounded to float32; 3 * n_samples uniform candidates in the
+ * bounding box grown by 1 on every side; containment by this library's ray parity (the rule of mesh guidance, not trimesh's;
+ * meshes are not checked for closedness) and the float64 distance to the nearest cloud point; the FIRST min(n_samples / 2,
+ * #inside) inside candidates followed by the first outside ones up to n_samples rows; everything centred on the float32 mean of
+ * the cloud.  Limits, refused with a message: n_shapes 1..65535, every mesh >= 1 face, face indices inside the mesh's
+ * vertices, finite vertices, n_cloud 1..2048 (the cloud is staged in LDS), n_samples >= 2 -- or 0: clouds, centres and bounds
+ * only, d_points / d_values / h_counts may then be null --, loss_type SHAPEMOL_SD_SIGNEDDIST or SHAPEMOL_SD_OCCUPANCY.
+ * The check alone touches no device. */
+typedef struct shapemol_sdata_ctx shapemol_sdata_ctx;
+int shapemol_sdata_check(int64_t n_shapes, const int64_t *h_vert_off, const double *h_verts, const int64_t *h_face_off,
+                         const int32_t *h_faces, int64_t n_cloud, int64_t n_samples, int32_t loss_type);
+int shapemol_sdata_create(int device, shapemol_sdata_ctx **out);
+void shapemol_sdata_destroy(shapemol_sdata_ctx *ctx);
+/* Uniforms: DEVICE float64 tables d_cloud_draws (n_shapes, n_cloud, 3) and d_query_draws (n_shapes, 3 * n_samples, 3), each
+ * optional; without a table the kernels draw from Philox keyed by (seed, shape, point).  DEVICE float32 outputs: d_cloud
+ * (n_shapes, n_cloud, 3) centred, d_points (n_shapes, n_samples, 3) centred, d_values (n_shapes, n_samples) = +d inside / -d
+ * outside (signed distance) or 1 / 0 (occupancy), d_centres (n_shapes, 3), d_bounds (n_shapes, 3, 2) = the vertex bounding
+ * box minus the centre.  HOST h_counts (n_shapes, 2) int32 = (inside, outside) candidates of every shape.  Optional DEVICE
+ * int32 outputs for tests: d_face_idx (n_shapes, n_cloud) the face of every cloud point, d_flags (n_shapes, 3 * n_samples)
+ * the containment of every candidate, d_sel (n_shapes, n_samples) the candidate of every row.
+ * The call synchronises the stream.  Returns 0; 1 on an error; 2 when some shape has too few outside candidates to fill
+ * its rows (the reference's torch.stack fails there): the message names the shapes, h_counts is valid, the rows of those
+ * shapes are incomplete, and the context stays usable.  A context serves one stream at a time. */
+int shapemol_sdata_build(shapemol_sdata_ctx *ctx, int64_t n_shapes, const int64_t *h_vert_off, const double *h_verts,
+                         const int64_t *h_face_off, const int32_t *h_faces, int64_t n_cloud, int64_t n_samples, int32_t loss_type,
+                         const double *d_cloud_draws, const double *d_query_draws, uint64_t seed, float *d_cloud, float *d_points,
+                         float *d_values, float *d_centres, float *d_bounds, int32_t *h_counts, int32_t *d_face_idx,
+                         int32_t *d_flags, int32_t *d_sel, void *stream);
+
 /* Per-kernel launch-time accounting with HIP events on the launch stream (bench only).
  * shapemol_profile_begin() arms it for the following _score/_sample calls (forces eager launches);
  * shapemol_profile_end() synchronises and writes, for each of up to `cap` kernel classes,

@@ -6,11 +6,15 @@ and, outside it, the frozen shape encoder that produces the conditioning (models
     VN_DGCNN_Encoder
 and the auto-encoder it is half of, with the decoder that evaluates the field a latent encodes:
     PointCloud_AE, DecoderInner      (training: DecoderInner.train_field, PointCloud_AE.get_generator_train_loss)
+and the builder of its training batches and of the sampling script's shape conditions, from molecule meshes (datasets/shape_data.py,
+utils/shape.py):
+    ShapeData, collate_fn, get_pointAE_shape_emb
 plus helpers: synthetic weights/inputs (synth), schedules (diffusion), the C-ABI binding (_lib).
 """
 from .molopt_score_model import ScorePosNet3D, log_sample_categorical, pointcloud_shape_guidance, mesh_shape_guidance  # noqa: F401
 from .packing import pack_state_dict  # noqa: F401
 from .shape_encoder import VN_DGCNN_Encoder  # noqa: F401
 from .shape_autoencoder import PointCloud_AE, DecoderInner  # noqa: F401
+from .shape_data import ShapeData, collate_fn, get_pointAE_shape_emb  # noqa: F401
 
 __version__ = "0.3.0"

@@ -32,6 +32,7 @@ EXPORTS = (
     "shapemol_sd_weight_count", "shapemol_sd_create", "shapemol_sd_destroy", "shapemol_sd_decode",
     "shapemol_sd_tile", "shapemol_sd_debug_read", "shapemol_field_decode_grad", "shapemol_field_guide", "shapemol_field_grad_tile",
     "shapemol_set_field_guidance", "shapemol_field_train", "shapemol_field_load_weights", "shapemol_field_train_tile",
+    "shapemol_sdata_check", "shapemol_sdata_create", "shapemol_sdata_destroy", "shapemol_sdata_build",
 )
 
 
@@ -165,6 +166,11 @@ def load():
     lib.shapemol_field_train_tile.restype = i64
     lib.shapemol_set_field_guidance.argtypes = [vp, vp, C.c_double, i32]
     lib.shapemol_sd_debug_read.argtypes = [vp, i32, vp, C.c_size_t]
+    lib.shapemol_sdata_check.argtypes = [i64, vp, vp, vp, vp, i64, i64, i32]
+    lib.shapemol_sdata_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.shapemol_sdata_destroy.argtypes = [vp]
+    lib.shapemol_sdata_destroy.restype = None
+    lib.shapemol_sdata_build.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, i32, vp, vp, u64] + [vp] * 10
     lib.shapemol_profile_begin.argtypes = [vp]
     lib.shapemol_profile_end.argtypes = [vp, vp, vp, vp, C.c_int]
     if lib.shapemol_abi_version() != ABI_VERSION:
