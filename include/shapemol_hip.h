@@ -565,6 +565,40 @@ int shapemol_sdata_build(shapemol_sdata_ctx *ctx, int64_t n_shapes, const int64_
                          float *d_values, float *d_centres, float *d_bounds, int32_t *h_counts, int32_t *d_face_idx,
                          int32_t *d_flags, int32_t *d_sel, void *stream);
 
+/* ---- molecular surface meshes from atoms and radii ------------------------------------------------------------------
+ * What the reference's get_mesh (utils/shape.py:153-162) asks of oddt, under THIS library's rule (not
+ * oddt's marching cubes, which is not available to compare with).  A batch is n_mols molecules back to back: HOST h_atom_off
+ * (n_mols + 1, starting at 0), centres (sum N, 3) and radii (sum N) float64.  Centres, radii and the probe radius are
+ * multiplied by `scaling`; `spacing` h is the grid spacing in those scaled units.  Per molecule, float64 throughout: a grid
+ * that reaches 2h beyond every inflated sphere; fA = min_i(|x - c_i| - (r_i + p)) on its nodes; for p > 0 the eroded field
+ * g = p - min(d, p + h), d the distance to the nearest node with fA >= 0, else g = fA; the zero level of g (g >= 0: outside) by
+ * marching tetrahedra on the six Kuhn tetrahedra of every cell, vertices at t = g0 / (g0 - g1) in (node, edge class) order,
+ * faces in (cell, tetrahedron, triangle) order with normals pointing outwards.  The mesh is closed and the same in every run.
+ * Limits, refused with a message before any kernel runs: n_mols 1..65535; 1..1024 atoms per molecule; radii > 0, probe_radius
+ * >= 0, spacing > 0, scaling > 0, everything finite; ceil((p + h) / h) <= 16; at most 128^3 grid nodes per molecule (so that
+ * int32 holds every vertex and face index) and 2^26 per call.  shapemol_msurf_sizes writes up to n of (nodes per molecule,
+ * nodes per call, atoms per molecule, stencil, erosion tile edge, nodes per scan block, molecules per call, scan blocks per pass
+ * of the per-molecule scan) and returns 8.
+ * The check alone touches no device. */
+typedef struct shapemol_msurf_ctx shapemol_msurf_ctx;
+int shapemol_msurf_sizes(int64_t *out, int32_t n);
+int shapemol_msurf_check(int64_t n_mols, const int64_t *h_atom_off, const double *h_centres, const double *h_radii,
+                         double probe_radius, double spacing, double scaling);
+int shapemol_msurf_create(int device, shapemol_msurf_ctx **out);
+void shapemol_msurf_destroy(shapemol_msurf_ctx *ctx);
+/* centres / radii: HOST, or DEVICE with inputs_on_device != 0 (they are fetched: the grids are laid out on the host).  HOST
+ * outputs: h_counts (n_mols, 2) int32 = (vertices, faces) of every molecule; optional h_lo (n_mols, 3) float64 and h_dims
+ * (n_mols, 3) int32 = every grid's corner and node counts; optional h_stage_ms (6) = milliseconds of field, erosion, counting,
+ * scan with its host round trip, vertices, faces.  The meshes stay in the context until its next build, back to back in
+ * molecule order: float64 vertices (sum V, 3) and int32 faces (sum F, 3) with indices relative to the molecule's own vertices.
+ * The call synchronises the stream.  Returns 0, or 1 with a message; a refused batch leaves the context usable. */
+int shapemol_msurf_build(shapemol_msurf_ctx *ctx, int64_t n_mols, const int64_t *h_atom_off, const double *centres,
+                         const double *radii, int32_t inputs_on_device, double probe_radius, double spacing, double scaling,
+                         int32_t *h_counts, double *h_lo, int32_t *h_dims, double *h_stage_ms, void *stream);
+/* Copy the first n_items scalars of the last build's vertices (which = 0, float64), faces (1, int32) or node field g (2,
+ * float64, the grids back to back) to dst, HOST or DEVICE.  Synchronises the stream. */
+int shapemol_msurf_copy(shapemol_msurf_ctx *ctx, int32_t which, void *dst, int64_t n_items, void *stream);
+
 /* Per-kernel launch-time accounting with HIP events on the launch stream (bench only).
  * shapemol_profile_begin() arms it for the following _score/_sample calls (forces eager launches);
  * shapemol_profile_end() synchronises and writes, for each of up to `cap` kernel classes,

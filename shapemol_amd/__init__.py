@@ -9,6 +9,8 @@ and the auto-encoder it is half of, with the decoder that evaluates the field a 
 and the builder of its training batches and of the sampling script's shape conditions, from molecule meshes (datasets/shape_data.py,
 utils/shape.py):
     ShapeData, collate_fn, get_pointAE_shape_emb
+and the molecule meshes themselves, from atom coordinates and radii (utils/shape.py get_mesh; the surface rule is this package's):
+    get_mesh, get_mesh_batch
 plus helpers: synthetic weights/inputs (synth), schedules (diffusion), the C-ABI binding (_lib).
 """
 from .molopt_score_model import ScorePosNet3D, log_sample_categorical, pointcloud_shape_guidance, mesh_shape_guidance  # noqa: F401
@@ -16,5 +18,6 @@ from .packing import pack_state_dict  # noqa: F401
 from .shape_encoder import VN_DGCNN_Encoder  # noqa: F401
 from .shape_autoencoder import PointCloud_AE, DecoderInner  # noqa: F401
 from .shape_data import ShapeData, collate_fn, get_pointAE_shape_emb  # noqa: F401
+from .mol_surface import get_mesh, get_mesh_batch  # noqa: F401
 
 __version__ = "0.3.0"

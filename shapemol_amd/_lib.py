@@ -33,6 +33,8 @@ EXPORTS = (
     "shapemol_sd_tile", "shapemol_sd_debug_read", "shapemol_field_decode_grad", "shapemol_field_guide", "shapemol_field_grad_tile",
     "shapemol_set_field_guidance", "shapemol_field_train", "shapemol_field_load_weights", "shapemol_field_train_tile",
     "shapemol_sdata_check", "shapemol_sdata_create", "shapemol_sdata_destroy", "shapemol_sdata_build",
+    "shapemol_msurf_sizes", "shapemol_msurf_check", "shapemol_msurf_create", "shapemol_msurf_destroy", "shapemol_msurf_build",
+    "shapemol_msurf_copy",
 )
 
 
@@ -171,6 +173,13 @@ def load():
     lib.shapemol_sdata_destroy.argtypes = [vp]
     lib.shapemol_sdata_destroy.restype = None
     lib.shapemol_sdata_build.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, i32, vp, vp, u64] + [vp] * 10
+    lib.shapemol_msurf_sizes.argtypes = [vp, i32]
+    lib.shapemol_msurf_check.argtypes = [i64, vp, vp, vp, C.c_double, C.c_double, C.c_double]
+    lib.shapemol_msurf_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.shapemol_msurf_destroy.argtypes = [vp]
+    lib.shapemol_msurf_destroy.restype = None
+    lib.shapemol_msurf_build.argtypes = [vp, i64, vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    lib.shapemol_msurf_copy.argtypes = [vp, i32, vp, i64, vp]
     lib.shapemol_profile_begin.argtypes = [vp]
     lib.shapemol_profile_end.argtypes = [vp, vp, vp, vp, C.c_int]
     if lib.shapemol_abi_version() != ABI_VERSION:
