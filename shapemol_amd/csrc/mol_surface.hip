@@ -3,20 +3,13 @@
 #include "../../include/shapemol_hip.h"
 #include "sm_mol_surface.h"
 #include "sm_devmem.h"
+#include "sm_host.h"
 
 #include <cstring>
 #include <string>
 #include <vector>
 
-extern "C" void shapemol_set_error_(const char *msg);     // shapemol_hip.hip: stores the thread's last error
-
 namespace {
-int msurf_fail(const std::string &m) { shapemol_set_error_(m.c_str()); return 1; }
-#define MSURFCHK(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return msurf_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 constexpr int kMsurfStages = 6;           // field, erode, count, scan, verts, faces
 }  // namespace
 
@@ -50,22 +43,19 @@ int shapemol_msurf_sizes(int64_t *out, int32_t n) {
 int shapemol_msurf_check(int64_t n_mols, const int64_t *h_atom_off, const double *h_centres, const double *h_radii, double probe_radius,
                          double spacing, double scaling) {
     const std::string e = msurf_plan(n_mols, h_atom_off, h_centres, h_radii, probe_radius, spacing, scaling, nullptr);
-    return e.empty() ? 0 : msurf_fail(e);
+    return e.empty() ? 0 : sm_fail(e);
 }
 
 int shapemol_msurf_create(int device, shapemol_msurf_ctx **out) {
-    if (!out) return msurf_fail("shapemol_msurf_create: null argument");
-    int ndev = 0;
-    MSURFCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return msurf_fail("shapemol_msurf_create: no such HIP device");
-    MSURFCHK(hipSetDevice(device));
+    if (!out) return sm_fail("shapemol_msurf_create: null argument");
+    if (sm_open_device(device, "shapemol_msurf_create")) return 1;
     shapemol_msurf_ctx *c = new shapemol_msurf_ctx;
     c->device = device;
     for (hipEvent_t &e : c->ev)
         if (hipEventCreate(&e) != hipSuccess) {
             for (hipEvent_t &d : c->ev) if (d) (void)hipEventDestroy(d);
             delete c;
-            return msurf_fail("shapemol_msurf_create: hipEventCreate failed");
+            return sm_fail("shapemol_msurf_create: hipEventCreate failed");
         }
     *out = c;
     return 0;
@@ -73,8 +63,7 @@ int shapemol_msurf_create(int device, shapemol_msurf_ctx **out) {
 
 void shapemol_msurf_destroy(shapemol_msurf_ctx *c) {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
+    sm_close_device(c->device);
     for (hipEvent_t &e : c->ev) (void)hipEventDestroy(e);
     delete c;                              // the lists free their buffers
 }
@@ -82,26 +71,26 @@ void shapemol_msurf_destroy(shapemol_msurf_ctx *c) {
 int shapemol_msurf_build(shapemol_msurf_ctx *c, int64_t n_mols, const int64_t *h_atom_off, const double *centres, const double *radii,
                          int32_t inputs_on_device, double probe_radius, double spacing, double scaling, int32_t *h_counts, double *h_lo,
                          int32_t *h_dims, double *h_stage_ms, void *stream) {
-    if (!c) return msurf_fail("shapemol_msurf_build: null context");
-    if (!h_counts) return msurf_fail("shapemol_msurf_build: h_counts is missing");
+    if (!c) return sm_fail("shapemol_msurf_build: null context");
+    if (!h_counts) return sm_fail("shapemol_msurf_build: h_counts is missing");
     c->n_verts = c->n_faces = 0;
     c->built = false;
-    MSURFCHK(hipSetDevice(c->device));
+    SMCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     if (inputs_on_device) {               // the grids are laid out on the host
         if (n_mols < 1 || n_mols > kMsurfMaxMols || !h_atom_off || !centres || !radii || h_atom_off[0] != 0 || h_atom_off[n_mols] < 1 ||
             h_atom_off[n_mols] > (int64_t)kMsurfMaxMols * kMsurfMaxAtoms)
-            return msurf_fail("molecular surface: bad molecule count, offsets or input pointers");
+            return sm_fail("molecular surface: bad molecule count, offsets or input pointers");
         const size_t N = (size_t)h_atom_off[n_mols];
         c->h_centres.resize(3 * N); c->h_radii.resize(N);
-        MSURFCHK(hipMemcpyAsync(c->h_centres.data(), centres, 24 * N, hipMemcpyDeviceToHost, s));
-        MSURFCHK(hipMemcpyAsync(c->h_radii.data(), radii, 8 * N, hipMemcpyDeviceToHost, s));
-        MSURFCHK(hipStreamSynchronize(s));
+        SMCHK(hipMemcpyAsync(c->h_centres.data(), centres, 24 * N, hipMemcpyDeviceToHost, s));
+        SMCHK(hipMemcpyAsync(c->h_radii.data(), radii, 8 * N, hipMemcpyDeviceToHost, s));
+        SMCHK(hipStreamSynchronize(s));
         centres = c->h_centres.data(); radii = c->h_radii.data();
     }
     // a build before this one has synchronised its stream before it returned: the host image is free to be rewritten
     const std::string err = msurf_plan(n_mols, h_atom_off, centres, radii, probe_radius, spacing, scaling, &c->plan);
-    if (!err.empty()) return msurf_fail(err);
+    if (!err.empty()) return sm_fail(err);
     MsurfPlan &pl = c->plan;
     const int B = (int)n_mols;
     const size_t o_mol = 0, o_atoms = (sizeof(MsurfMol) * B + 31) / 32 * 32, o_dtab = o_atoms + pl.atoms.size() * 8;
@@ -110,12 +99,12 @@ int shapemol_msurf_build(shapemol_msurf_ctx *c, int64_t n_mols, const int64_t *h
     std::memcpy(c->up.data() + o_atoms, pl.atoms.data(), pl.atoms.size() * 8);
     std::memcpy(c->up.data() + o_dtab, pl.dtab.data(), pl.dtab.size() * 8);
     std::memcpy(c->up.data() + o_mol, pl.mol.data(), sizeof(MsurfMol) * B);
-    MSURFCHK(grow(c->mem_in, {dev_buf(&c->d_in, bytes)}, c->cap_in, (int64_t)bytes));
-    MSURFCHK(grow(c->mem_n, {dev_buf(&c->g, (size_t)pl.nodes * 8), dev_buf(&c->outside, (size_t)pl.nodes), dev_buf(&c->emask, (size_t)pl.nodes),
+    SMCHK(grow(c->mem_in, {dev_buf(&c->d_in, bytes)}, c->cap_in, (int64_t)bytes));
+    SMCHK(grow(c->mem_n, {dev_buf(&c->g, (size_t)pl.nodes * 8), dev_buf(&c->outside, (size_t)pl.nodes), dev_buf(&c->emask, (size_t)pl.nodes),
                              dev_buf(&c->ntri, (size_t)pl.nodes), dev_buf(&c->vbase, (size_t)pl.nodes * 4)}, c->cap_n, pl.nodes));
-    MSURFCHK(grow(c->mem_c, {dev_buf(&c->chunk, (size_t)pl.chunks * 8)}, c->cap_c, pl.chunks));
-    MSURFCHK(grow(c->mem_b, {dev_buf(&c->d_counts, (size_t)B * 8)}, c->cap_b, B));
-    MSURFCHK(hipMemcpyAsync(c->d_in, c->up.data(), bytes, hipMemcpyHostToDevice, s));
+    SMCHK(grow(c->mem_c, {dev_buf(&c->chunk, (size_t)pl.chunks * 8)}, c->cap_c, pl.chunks));
+    SMCHK(grow(c->mem_b, {dev_buf(&c->d_counts, (size_t)B * 8)}, c->cap_b, B));
+    SMCHK(hipMemcpyAsync(c->d_in, c->up.data(), bytes, hipMemcpyHostToDevice, s));
     MsurfArgs a{};
     a.mol = reinterpret_cast<const MsurfMol *>(c->d_in + o_mol);
     a.atoms = reinterpret_cast<const double4 *>(c->d_in + o_atoms);
@@ -125,21 +114,21 @@ int shapemol_msurf_build(shapemol_msurf_ctx *c, int64_t n_mols, const int64_t *h
     const bool timed = h_stage_ms != nullptr;
     int stage = 0;
     auto mark = [&]() { return timed ? hipEventRecord(c->ev[stage++], s) : hipSuccess; };
-    MSURFCHK(mark());
+    SMCHK(mark());
     hipLaunchKernelGGL(msurf_field_kernel, dim3((unsigned)((pl.max_nodes + 255) / 256), (unsigned)B), dim3(256), 0, s, a);
-    MSURFCHK(mark());
+    SMCHK(mark());
     if (pl.R > 0) {
         const int W = kMsurfTile + 2 * pl.R;
         hipLaunchKernelGGL(msurf_erode_kernel, dim3((unsigned)pl.max_tiles, (unsigned)B), dim3(512), (size_t)W * W * W, s, a);
     }
-    MSURFCHK(mark());
+    SMCHK(mark());
     hipLaunchKernelGGL(msurf_count_kernel, dim3((unsigned)pl.max_chunks, (unsigned)B), dim3(256), 0, s, a);
-    MSURFCHK(mark());
+    SMCHK(mark());
     hipLaunchKernelGGL(msurf_scan_kernel, dim3((unsigned)B), dim3(kMsurfScanWidth), 0, s, a);
-    MSURFCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     c->counts.resize(2 * (size_t)B);
-    MSURFCHK(hipMemcpyAsync(c->counts.data(), c->d_counts, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    MSURFCHK(hipStreamSynchronize(s));
+    SMCHK(hipMemcpyAsync(c->counts.data(), c->d_counts, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    SMCHK(hipStreamSynchronize(s));
     long long nv = 0, nf = 0;
     for (int b = 0; b < B; ++b) {
         pl.mol[b].vert_off = nv; pl.mol[b].face_off = nf;
@@ -150,22 +139,22 @@ int shapemol_msurf_build(shapemol_msurf_ctx *c, int64_t n_mols, const int64_t *h
             if (h_dims) h_dims[3 * b + k] = pl.mol[b].n[k];
         }
     }
-    MSURFCHK(grow(c->mem_v, {dev_buf(&c->verts, (size_t)std::max(nv, 1ll) * 24)}, c->cap_v, std::max(nv, 1ll)));
-    MSURFCHK(grow(c->mem_f, {dev_buf(&c->faces, (size_t)std::max(nf, 1ll) * 12)}, c->cap_f, std::max(nf, 1ll)));
+    SMCHK(grow(c->mem_v, {dev_buf(&c->verts, (size_t)std::max(nv, 1ll) * 24)}, c->cap_v, std::max(nv, 1ll)));
+    SMCHK(grow(c->mem_f, {dev_buf(&c->faces, (size_t)std::max(nf, 1ll) * 12)}, c->cap_f, std::max(nf, 1ll)));
     a.verts = c->verts; a.faces = c->faces;
     std::memcpy(c->up.data() + o_mol, pl.mol.data(), sizeof(MsurfMol) * B);      // now with the output offsets
-    MSURFCHK(hipMemcpyAsync(c->d_in + o_mol, c->up.data() + o_mol, sizeof(MsurfMol) * B, hipMemcpyHostToDevice, s));
-    MSURFCHK(mark());
+    SMCHK(hipMemcpyAsync(c->d_in + o_mol, c->up.data() + o_mol, sizeof(MsurfMol) * B, hipMemcpyHostToDevice, s));
+    SMCHK(mark());
     hipLaunchKernelGGL(msurf_verts_kernel, dim3((unsigned)pl.max_chunks, (unsigned)B), dim3(256), 0, s, a);
-    MSURFCHK(mark());
+    SMCHK(mark());
     hipLaunchKernelGGL(msurf_faces_kernel, dim3((unsigned)pl.max_chunks, (unsigned)B), dim3(256), 0, s, a);
-    MSURFCHK(mark());
-    MSURFCHK(hipGetLastError());
-    MSURFCHK(hipStreamSynchronize(s));
+    SMCHK(mark());
+    SMCHK(hipGetLastError());
+    SMCHK(hipStreamSynchronize(s));
     if (timed)
         for (int i = 0; i < kMsurfStages; ++i) {
             float ms = 0;
-            MSURFCHK(hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
+            SMCHK(hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
             h_stage_ms[i] = ms;
         }
     c->n_verts = nv; c->n_faces = nf;
@@ -174,14 +163,14 @@ int shapemol_msurf_build(shapemol_msurf_ctx *c, int64_t n_mols, const int64_t *h
 }
 
 int shapemol_msurf_copy(shapemol_msurf_ctx *c, int32_t which, void *dst, int64_t n_items, void *stream) {
-    if (!c || !dst) return msurf_fail("shapemol_msurf_copy: null argument");
+    if (!c || !dst) return sm_fail("shapemol_msurf_copy: null argument");
     const void *src = which == 0 ? (const void *)c->verts : which == 1 ? (const void *)c->faces : which == 2 ? (const void *)c->g : nullptr;
     const long long have = which == 0 ? c->n_verts * 3 : which == 1 ? c->n_faces * 3 : c->plan.nodes;
     const size_t size = which == 1 ? 4 : 8;
-    if (!c->built || !src || n_items < 0 || n_items > have) return msurf_fail("shapemol_msurf_copy: nothing of that kind and size from the last build");
-    MSURFCHK(hipSetDevice(c->device));
-    if (n_items) MSURFCHK(hipMemcpyAsync(dst, src, (size_t)n_items * size, hipMemcpyDefault, (hipStream_t)stream));
-    MSURFCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (!c->built || !src || n_items < 0 || n_items > have) return sm_fail("shapemol_msurf_copy: nothing of that kind and size from the last build");
+    SMCHK(hipSetDevice(c->device));
+    if (n_items) SMCHK(hipMemcpyAsync(dst, src, (size_t)n_items * size, hipMemcpyDefault, (hipStream_t)stream));
+    SMCHK(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }
 

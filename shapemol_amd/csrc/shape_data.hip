@@ -3,20 +3,10 @@
 #include "../../include/shapemol_hip.h"
 #include "sm_shape_data.h"
 #include "sm_devmem.h"
+#include "sm_host.h"
 
 #include <string>
 #include <vector>
-
-extern "C" void shapemol_set_error_(const char *msg);     // shapemol_hip.hip: stores the thread's last error
-
-namespace {
-int sdata_fail(const std::string &m) { shapemol_set_error_(m.c_str()); return 1; }
-#define SDATACHK(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return sdata_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-}  // namespace
 
 struct shapemol_sdata_ctx {
     int device = 0;
@@ -35,14 +25,12 @@ extern "C" {
 int shapemol_sdata_check(int64_t n_shapes, const int64_t *h_vert_off, const double *h_verts, const int64_t *h_face_off, const int32_t *h_faces,
                          int64_t n_cloud, int64_t n_samples, int32_t loss_type) {
     const std::string e = sdata_check(n_shapes, h_vert_off, h_verts, h_face_off, h_faces, n_cloud, n_samples, loss_type);
-    return e.empty() ? 0 : sdata_fail(e);
+    return e.empty() ? 0 : sm_fail(e);
 }
 
 int shapemol_sdata_create(int device, shapemol_sdata_ctx **out) {
-    if (!out) return sdata_fail("shapemol_sdata_create: null argument");
-    int ndev = 0;
-    SDATACHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return sdata_fail("shapemol_sdata_create: no such HIP device");
+    if (!out) return sm_fail("shapemol_sdata_create: null argument");
+    if (sm_open_device(device, "shapemol_sdata_create")) return 1;
     shapemol_sdata_ctx *c = new shapemol_sdata_ctx;
     c->device = device;
     *out = c;
@@ -51,8 +39,7 @@ int shapemol_sdata_create(int device, shapemol_sdata_ctx **out) {
 
 void shapemol_sdata_destroy(shapemol_sdata_ctx *c) {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
+    sm_close_device(c->device);
     delete c;                              // the lists free their buffers
 }
 
@@ -60,26 +47,26 @@ int shapemol_sdata_build(shapemol_sdata_ctx *c, int64_t n_shapes, const int64_t 
                          const int32_t *h_faces, int64_t n_cloud, int64_t n_samples, int32_t loss_type, const double *d_cloud_draws,
                          const double *d_query_draws, uint64_t seed, float *d_cloud, float *d_points, float *d_values, float *d_centres,
                          float *d_bounds, int32_t *h_counts, int32_t *d_face_idx, int32_t *d_flags, int32_t *d_sel, void *stream) {
-    if (!c) return sdata_fail("shapemol_sdata_build: null context");
+    if (!c) return sm_fail("shapemol_sdata_build: null context");
     if (shapemol_sdata_check(n_shapes, h_vert_off, h_verts, h_face_off, h_faces, n_cloud, n_samples, loss_type)) return 1;
     if (!d_cloud || !d_centres || !d_bounds || (n_samples > 0 && (!d_points || !d_values || !h_counts)))
-        return sdata_fail("shapemol_sdata_build: an output pointer is missing");
-    SDATACHK(hipSetDevice(c->device));
+        return sm_fail("shapemol_sdata_build: an output pointer is missing");
+    SMCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int B = (int)n_shapes, P = (int)n_cloud, T = (int)n_samples;
     const int64_t Q = 3 * (int64_t)T;
     // a build before this one has synchronised its stream before it returned: the host image is free to be rewritten
     sdata_image(B, h_vert_off, h_verts, h_face_off, h_faces, c->im);
     const int64_t bytes = (int64_t)c->im.bytes.size();
-    SDATACHK(grow(c->mem_in, {dev_buf(&c->d_in, (size_t)bytes)}, c->cap_in, bytes));
-    SDATACHK(grow(c->mem_p, {dev_buf(&c->cloud32, (size_t)B * P * 12)}, c->cap_p, (int64_t)B * P));
+    SMCHK(grow(c->mem_in, {dev_buf(&c->d_in, (size_t)bytes)}, c->cap_in, bytes));
+    SMCHK(grow(c->mem_p, {dev_buf(&c->cloud32, (size_t)B * P * 12)}, c->cap_p, (int64_t)B * P));
     if (T > 0) {
-        SDATACHK(grow(c->mem_f, {dev_buf(&c->faces, (size_t)c->im.F * sizeof(MeshFace)), dev_buf(&c->fbox, (size_t)c->im.F * sizeof(double4))}, c->cap_f, c->im.F));
-        SDATACHK(grow(c->mem_q, {dev_buf(&c->cand, (size_t)B * Q * 24), dev_buf(&c->dist, (size_t)B * Q * 8), dev_buf(&c->flag, (size_t)B * Q * 4)},
+        SMCHK(grow(c->mem_f, {dev_buf(&c->faces, (size_t)c->im.F * sizeof(MeshFace)), dev_buf(&c->fbox, (size_t)c->im.F * sizeof(double4))}, c->cap_f, c->im.F));
+        SMCHK(grow(c->mem_q, {dev_buf(&c->cand, (size_t)B * Q * 24), dev_buf(&c->dist, (size_t)B * Q * 8), dev_buf(&c->flag, (size_t)B * Q * 4)},
                       c->cap_q, (int64_t)B * Q));
     }
-    SDATACHK(grow(c->mem_b, {dev_buf(&c->counts, (size_t)B * 8)}, c->cap_b, (int64_t)B));
-    SDATACHK(hipMemcpyAsync(c->d_in, c->im.bytes.data(), (size_t)bytes, hipMemcpyHostToDevice, s));
+    SMCHK(grow(c->mem_b, {dev_buf(&c->counts, (size_t)B * 8)}, c->cap_b, (int64_t)B));
+    SMCHK(hipMemcpyAsync(c->d_in, c->im.bytes.data(), (size_t)bytes, hipMemcpyHostToDevice, s));
     SdataArgs a{};
     const SdataImage &im = c->im;
     a.verts = reinterpret_cast<const double *>(c->d_in + im.o_verts); a.face_ix = reinterpret_cast<const int *>(c->d_in + im.o_ix);
@@ -98,9 +85,9 @@ int shapemol_sdata_build(shapemol_sdata_ctx *c, int64_t n_shapes, const int64_t 
         hipLaunchKernelGGL(sdata_classify_kernel, dim3((unsigned)((Q + 15) / 16), (unsigned)B), dim3(256), mesh_lds_bytes(P), s, a);
     }
     hipLaunchKernelGGL(sdata_finish_kernel, dim3((unsigned)B), dim3(256), 0, s, a);
-    SDATACHK(hipGetLastError());
-    if (T > 0) SDATACHK(hipMemcpyAsync(h_counts, c->counts, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    SDATACHK(hipStreamSynchronize(s));
+    SMCHK(hipGetLastError());
+    if (T > 0) SMCHK(hipMemcpyAsync(h_counts, c->counts, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    SMCHK(hipStreamSynchronize(s));
     if (T > 0) {
         std::string shy;
         for (int b = 0; b < B; ++b) {
@@ -110,7 +97,7 @@ int shapemol_sdata_build(shapemol_sdata_ctx *c, int64_t n_shapes, const int64_t 
                        " outside of " + std::to_string(Q) + " candidates; " + std::to_string(T - n_in) + " outside rows needed)";
         }
         if (!shy.empty()) {
-            sdata_fail("shape data: too few candidates outside the mesh to fill num_samples rows (the reference's torch.stack fails there) for shape " + shy);
+            sm_fail("shape data: too few candidates outside the mesh to fill num_samples rows (the reference's torch.stack fails there) for shape " + shy);
             return 2;
         }
     }

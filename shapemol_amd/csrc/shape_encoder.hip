@@ -3,21 +3,14 @@
 #include "../../include/shapemol_hip.h"
 #include "sm_shape.h"
 #include "sm_devmem.h"
+#include "sm_host.h"
 
 #include <cstring>
 #include <string>
 #include <vector>
 
-extern "C" void shapemol_set_error_(const char *msg);     // shapemol_hip.hip: stores the thread's last error
-
 namespace {
-int se_fail(const std::string &m) { shapemol_set_error_(m.c_str()); return 1; }
-#define SECHK(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return se_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-constexpr int kC = 128;           // hidden_dim of the shipped shape auto-encoder (se_model.pt: config.model.hidden_dim)
+constexpr int kC = 128;          // hidden_dim of the shipped shape auto-encoder (se_model.pt: config.model.hidden_dim)
 }  // namespace
 
 struct shapemol_se_ctx {
@@ -44,20 +37,17 @@ size_t shapemol_se_weight_count(int32_t hidden_dim, int32_t latent_dim, int32_t 
 
 int shapemol_se_create(int32_t hidden_dim, int32_t latent_dim, int32_t layer_num, int32_t num_k, const float *w, size_t n_weights,
                        int device, shapemol_se_ctx **out) {
-    if (!w || !out) return se_fail("shapemol_se_create: null argument");
-    if (hidden_dim != kC) return se_fail("shapemol_se_create: hidden_dim must be 128");
-    if (num_k != kSeK) return se_fail("shapemol_se_create: num_k must be 20");
-    if (latent_dim < 1 || latent_dim > 256 || layer_num < 1 || layer_num > 8) return se_fail("shapemol_se_create: latent_dim / layer_num out of range");
-    if (n_weights != shapemol_se_weight_count(hidden_dim, latent_dim, layer_num)) return se_fail("shapemol_se_create: weight count mismatch");
-    int ndev = 0;
-    SECHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return se_fail("shapemol_se_create: no such HIP device");
-    SECHK(hipSetDevice(device));
+    if (!w || !out) return sm_fail("shapemol_se_create: null argument");
+    if (hidden_dim != kC) return sm_fail("shapemol_se_create: hidden_dim must be 128");
+    if (num_k != kSeK) return sm_fail("shapemol_se_create: num_k must be 20");
+    if (latent_dim < 1 || latent_dim > 256 || layer_num < 1 || layer_num > 8) return sm_fail("shapemol_se_create: latent_dim / layer_num out of range");
+    if (n_weights != shapemol_se_weight_count(hidden_dim, latent_dim, layer_num)) return sm_fail("shapemol_se_create: weight count mismatch");
+    if (sm_open_device(device, "shapemol_se_create")) return 1;
     // se_knn_kernel keeps the 16 x N distances of its row block in dynamic LDS: the device's limit per workgroup bounds N
     int lds = 0;
-    SECHK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    SMCHK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
     const int max_n = lds / (16 * (int)sizeof(float)) / 16 * 16;
-    if (max_n < 32) return se_fail("shapemol_se_create: the device has less than 2 KB of LDS per workgroup");
+    if (max_n < 32) return sm_fail("shapemol_se_create: the device has less than 2 KB of LDS per workgroup");
     auto *c = new shapemol_se_ctx();
     c->LAT = latent_dim; c->L = layer_num; c->device = device; c->lds_limit = lds; c->max_n = max_n;
     const int C = kC;
@@ -95,7 +85,7 @@ int shapemol_se_create(int32_t hidden_dim, int32_t latent_dim, int32_t layer_num
     c->o_c_b = put(p, latent_dim); p += latent_dim;
     c->o_c_wd = put(p, (size_t)layer_num * C); p += (size_t)layer_num * C;
     if (c->mem_w.alloc(&c->d_w, img.size() * 4) != hipSuccess || hipMemcpy(c->d_w, img.data(), img.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        delete c; return se_fail("shapemol_se_create: device allocation failed");
+        delete c; return sm_fail("shapemol_se_create: device allocation failed");
     }
     *out = c;
     return 0;
@@ -103,28 +93,27 @@ int shapemol_se_create(int32_t hidden_dim, int32_t latent_dim, int32_t layer_num
 
 void shapemol_se_destroy(shapemol_se_ctx *c) {
     if (!c) return;
-    hipSetDevice(c->device);
-    hipDeviceSynchronize();
-    delete c;                 // its lists release what they own
+    sm_close_device(c->device);
+    delete c;                // its lists release what they own
 }
 
 int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int64_t N, float *d_out, void *stream) {
-    if (!c || !d_points || !d_out) return se_fail("shapemol_se_encode: null argument");
+    if (!c || !d_points || !d_out) return sm_fail("shapemol_se_encode: null argument");
     if (B < 1 || B > 65535 || N < 32 || (N % 16) != 0 || N > c->max_n || B * N > (1 << 24))
-        return se_fail("shapemol_se_encode: need 1 <= B <= 65535, N a multiple of 16 in [32, " + std::to_string(c->max_n) + "] (16 * N * 4 bytes of the " +
+        return sm_fail("shapemol_se_encode: need 1 <= B <= 65535, N a multiple of 16 in [32, " + std::to_string(c->max_n) + "] (16 * N * 4 bytes of the " +
                        std::to_string(c->lds_limit) + " bytes of LDS a workgroup can have on this device) and B * N <= 2^24; got B = " +
                        std::to_string(B) + ", N = " + std::to_string(N));
-    SECHK(hipSetDevice(c->device));
+    SMCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int C = c->C, L = c->L, LAT = c->LAT;
     const int64_t P = B * N;
-    SECHK(grow(c->mem_P, {dev_buf(&c->h0, P * C * 3 * 4), dev_buf(&c->hcat, P * L * C * 3 * 4), dev_buf(&c->y, P * 4 * C * 3 * 4), dev_buf(&c->xx, P * 4),
+    SMCHK(grow(c->mem_P, {dev_buf(&c->h0, P * C * 3 * 4), dev_buf(&c->hcat, P * L * C * 3 * 4), dev_buf(&c->y, P * 4 * C * 3 * 4), dev_buf(&c->xx, P * 4),
                           dev_buf(&c->pd, P * (LAT + 1) * 3 * 4), dev_buf(&c->idx, P * kSeK * 4), dev_buf(&c->acc, (size_t)kSeReplicas * 2 * 256 * 8)},
                c->capP, P));
     c->lastP = P;
     const size_t knn_lds = (size_t)16 * N * sizeof(float);      // <= lds_limit (N <= max_n)
-    SECHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
-    SECHK(hipFuncSetAttribute((const void *)se_knn_kernel<3 * kC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
+    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
+    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3 * kC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
     const int n_blocks = c->stop_after < 0 ? L : (c->stop_after < L ? c->stop_after : L);
     const float *W = c->d_w;
     const dim3 knn_grid((unsigned)(N / 16), (unsigned)B);
@@ -133,7 +122,7 @@ int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int
     SeEdgeArgs e{};
     e.x = d_points; e.w0f = W + c->o_pos_wf; e.w0d = W + c->o_pos_wd; e.idx = c->idx; e.bn_g = W + c->o_pos_g; e.bn_b = W + c->o_pos_b;
     e.acc = c->acc; e.h_out = c->h0; e.n_total = (int)P; e.N = (int)N; e.C = C; e.h_ld = 3 * C; e.h_off = 0;
-    SECHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
+    SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
     hipLaunchKernelGGL(se_edge_stats_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
     hipLaunchKernelGGL(se_edge_apply_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
     // DGCNN blocks
@@ -146,32 +135,32 @@ int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int
         SeEdgeArgs b{};
         b.y = c->y; b.idx = c->idx; b.bn_g = W + c->o_g[l]; b.bn_b = W + c->o_b[l]; b.acc = c->acc; b.h_out = c->hcat;
         b.n_total = (int)P; b.N = (int)N; b.C = C; b.h_ld = L * 3 * C; b.h_off = l * 3 * C;
-        SECHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
+        SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
         hipLaunchKernelGGL(se_edge_stats_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
         hipLaunchKernelGGL(se_edge_apply_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
     }
-    if (c->stop_after >= 0) { SECHK(hipGetLastError()); return 0; }
+    if (c->stop_after >= 0) { SMCHK(hipGetLastError()); return 0; }
     // conv_c + mean over the points
     SeHeadArgs ha{c->hcat, W + c->o_c_wf, W + c->o_c_wd, W + c->o_c_g, W + c->o_c_b, c->pd, c->acc, d_out, (int)P, (int)N, L * C, LAT};
-    SECHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
+    SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
     hipLaunchKernelGGL(se_head_linear_kernel, dim3((unsigned)((P * (LAT + 1) + 3) / 4)), dim3(256), 0, s, ha);
     hipLaunchKernelGGL(se_head_apply_kernel, dim3((unsigned)(B * LAT)), dim3(256), 0, s, ha);
-    SECHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return 0;
 }
 
 int64_t shapemol_se_max_points(const shapemol_se_ctx *c) { return c ? c->max_n : 0; }
 
 int shapemol_se_debug_stop_after(shapemol_se_ctx *c, int32_t n_blocks) {
-    if (!c) return se_fail("shapemol_se_debug_stop_after: null argument");
-    if (n_blocks < -1 || n_blocks > c->L) return se_fail("shapemol_se_debug_stop_after: n_blocks must be -1 (off) or in [0, layer_num]");
+    if (!c) return sm_fail("shapemol_se_debug_stop_after: null argument");
+    if (n_blocks < -1 || n_blocks > c->L) return sm_fail("shapemol_se_debug_stop_after: n_blocks must be -1 (off) or in [0, layer_num]");
     c->stop_after = n_blocks;
     return 0;
 }
 
 int shapemol_se_debug_read(shapemol_se_ctx *c, int32_t what, void *h_dst, size_t n_bytes) {
-    if (!c || !h_dst) return se_fail("shapemol_se_debug_read: null argument");
-    if (c->lastP == 0) return se_fail("shapemol_se_debug_read: no shapemol_se_encode has run on this context");
+    if (!c || !h_dst) return sm_fail("shapemol_se_debug_read: null argument");
+    if (c->lastP == 0) return sm_fail("shapemol_se_debug_read: no shapemol_se_encode has run on this context");
     const size_t P = (size_t)c->lastP, C = c->C, L = c->L, LAT = c->LAT;
     const void *src = nullptr; size_t need = 0;
     switch (what) {
@@ -181,12 +170,12 @@ int shapemol_se_debug_read(shapemol_se_ctx *c, int32_t what, void *h_dst, size_t
         case SHAPEMOL_SE_Y:    src = c->y;    need = P * 4 * C * 3 * 4; break;
         case SHAPEMOL_SE_XX:   src = c->xx;   need = P * 4; break;
         case SHAPEMOL_SE_PD:   src = c->pd;   need = P * (LAT + 1) * 3 * 4; break;
-        default: return se_fail("shapemol_se_debug_read: what must be one of SHAPEMOL_SE_IDX .. SHAPEMOL_SE_PD (0 .. 5), got " + std::to_string(what));
+        default: return sm_fail("shapemol_se_debug_read: what must be one of SHAPEMOL_SE_IDX .. SHAPEMOL_SE_PD (0 .. 5), got " + std::to_string(what));
     }
-    if (n_bytes != need) return se_fail("shapemol_se_debug_read: buffer " + std::to_string(what) + " of the last encode has " + std::to_string(need) + " bytes, n_bytes is " + std::to_string(n_bytes));
-    SECHK(hipSetDevice(c->device));
-    SECHK(hipDeviceSynchronize());
-    SECHK(hipMemcpy(h_dst, src, need, hipMemcpyDeviceToHost));
+    if (n_bytes != need) return sm_fail("shapemol_se_debug_read: buffer " + std::to_string(what) + " of the last encode has " + std::to_string(need) + " bytes, n_bytes is " + std::to_string(n_bytes));
+    SMCHK(hipSetDevice(c->device));
+    SMCHK(hipDeviceSynchronize());
+    SMCHK(hipMemcpy(h_dst, src, need, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -26,15 +26,11 @@
 
 #include "sm_pack.h"
 #include "sm_devmem.h"
+#include "sm_host.h"
 
 namespace {
 
-#define HIPCHK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-    } while (0)
+#define HIPCHK SMCHK      // (sm_fail stores the message through shapemol_set_error_, below, where fail of sm_pack.h assigns g_err)
 int hip_fail(const char *what, hipError_t e) { return fail(std::string(what) + ": " + hipGetErrorString(e)); }
 
 constexpr int kEdgeThreadsDefault = 768;

@@ -1,7 +1,7 @@
 // The one place of the library that allocates and frees device memory (host only; included by every translation unit).
 // Invariant: a capacity is non-zero only while every pointer of its group is valid; a failed growth leaves capacity 0 and
 // null pointers; destroy frees through the same lists growth uses.  Errors come back as hipError_t for the caller's
-// HIPCHK / SDCHK / SECHK.  The raw operations are the four dm_* functions; a host test defines SM_DEVMEM_STUB and supplies its own.
+// SMCHK (sm_host.h).  The raw operations are the four dm_* functions; a host test defines SM_DEVMEM_STUB and supplies its own.
 #pragma once
 #include <hip/hip_runtime.h>
 

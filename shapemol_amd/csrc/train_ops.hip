@@ -2,21 +2,14 @@
 // Linear -> LayerNorm -> ReLU -> Linear (/root/reference/models/common.py:47-67).  Kernels: sm_train.h.
 #include "../../include/shapemol_hip.h"
 #include "sm_train.h"
+#include "sm_host.h"
 
 #include <algorithm>
 #include <cstdint>
 #include <string>
 
-extern "C" void shapemol_set_error_(const char *msg);     // shapemol_hip.hip: stores the thread's last error
-
 namespace {
 constexpr int kMaxHidden = 256;      // ln_relu_bwd_kernel keeps 16 waves x 3 hidden floats in LDS (48 KB at 256)
-int tr_fail(const std::string &m) { shapemol_set_error_(m.c_str()); return 1; }
-#define TRCHK(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return tr_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // C[M][N] = A B (+ bias); see GemmArgs.  splits > 1: partial tiles C + z * M * ldc
 int gemm(hipStream_t s, const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, const float *bias,
@@ -36,14 +29,14 @@ int gemm(hipStream_t s, const float *A, long long sam, long long sak, const floa
     else if (am == 1) hipLaunchKernelGGL((gemm_f32_vec_kernel<true, false>), grid, dim3(256), 0, s, g);
     else if (bm == 1) hipLaunchKernelGGL((gemm_f32_vec_kernel<false, true>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((gemm_f32_vec_kernel<false, false>), grid, dim3(256), 0, s, g);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return 0;
 }
 int reduce_parts(hipStream_t s, const float *part, int n_parts, long long n, float *out, int cols = 0, int ldo = 0) {
     if (cols < 1) { cols = (int)std::min<long long>(n, 1 << 30); ldo = cols; }      // a plain vector
     if (n_parts > 32) hipLaunchKernelGGL(reduce_partials_kernel<32>, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, s, part, n_parts, n, ReduceOut{{out, nullptr, nullptr}, 0, cols, ldo});
     else hipLaunchKernelGGL(reduce_partials_kernel<8>, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, part, n_parts, n, ReduceOut{{out, nullptr, nullptr}, 0, cols, ldo});
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return 0;
 }
 // the same into up to three separate arrays of seg outputs each
@@ -51,7 +44,7 @@ int reduce_parts3(hipStream_t s, const float *part, int n_parts, long long seg, 
     const long long n = seg * (o2 ? 3 : o1 ? 2 : 1);
     if (n_parts > 32) hipLaunchKernelGGL(reduce_partials_kernel<32>, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, s, part, n_parts, n, ReduceOut{{o0, o1, o2}, seg, 0, 0});
     else hipLaunchKernelGGL(reduce_partials_kernel<8>, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, part, n_parts, n, ReduceOut{{o0, o1, o2}, seg, 0, 0});
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return 0;
 }
 // row-reduction splits of the two weight-gradient products: many short splits (the strided GEMM is latency-bound per workgroup:
@@ -68,7 +61,7 @@ int real_splits(int64_t rows) {
 int ln_backward(hipStream_t s, float *dz, const float *xhat, const float *rstd, const float *gamma, const float *beta, int64_t rows, int H, int nwg,
                 float *pln, float *dgamma, float *dbeta, float *db1) {
     hipLaunchKernelGGL(ln_relu_bwd_kernel, dim3(nwg), dim3(kLnBwdWaves * 64), (size_t)kLnBwdWaves * 3 * H * sizeof(float), s, dz, xhat, rstd, gamma, beta, (long long)rows, H, pln);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return reduce_parts3(s, pln, nwg, H, dgamma, dbeta, db1);
 }
 bool bad_dims(int64_t rows, int k_in, int hidden, int n_out) {
@@ -92,14 +85,14 @@ int shapemol_mlp_forward(const float *d_x, int64_t rows, int32_t k_in, int32_t h
                          const float *d_b1, const float *d_gamma, const float *d_beta, const float *d_w2, const float *d_b2,
                          float *d_y, float *d_xhat, float *d_rstd, float *d_act, void *stream) {
     if (!d_x || !d_w1 || !d_b1 || !d_gamma || !d_beta || !d_w2 || !d_b2 || !d_y || !d_xhat || !d_rstd || !d_act)
-        return tr_fail("shapemol_mlp_forward: null argument");
-    if (bad_dims(rows, k_in, hidden, n_out)) return tr_fail("shapemol_mlp_forward: dimensions out of range (hidden <= 256)");
+        return sm_fail("shapemol_mlp_forward: null argument");
+    if (bad_dims(rows, k_in, hidden, n_out)) return sm_fail("shapemol_mlp_forward: dimensions out of range (hidden <= 256)");
     hipStream_t s = (hipStream_t)stream;
     // z = x W1^T + b1  (B(k, n) = W1[n][k])
     if (gemm(s, d_x, k_in, 1, d_w1, 1, k_in, d_b1, d_act, hidden, (int)rows, hidden, k_in, 1)) return 1;
     hipLaunchKernelGGL(ln_relu_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, d_act, d_gamma, d_beta, d_xhat, d_rstd, (long long)rows, hidden,
                        (const float *)nullptr, (const float *)nullptr, (const long long *)nullptr, (const long long *)nullptr);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     // y = a W2^T + b2
     return gemm(s, d_act, hidden, 1, d_w2, 1, hidden, d_b2, d_y, n_out, (int)rows, n_out, hidden, 1);
 }
@@ -110,9 +103,9 @@ int shapemol_mlp_backward(const float *d_x, const float *d_dy, int64_t rows, int
                           float *d_dw2, float *d_db2, float *d_work, size_t work_floats, void *stream) {
     if (!d_x || !d_dy || !d_w1 || !d_gamma || !d_beta || !d_w2 || !d_xhat || !d_rstd || !d_dw1 || !d_db1 || !d_dgamma || !d_dbeta ||
         !d_dw2 || !d_db2 || !d_work)
-        return tr_fail("shapemol_mlp_backward: null argument (only d_dx and d_act may be NULL)");
-    if (bad_dims(rows, k_in, hidden, n_out)) return tr_fail("shapemol_mlp_backward: dimensions out of range (hidden <= 256)");
-    if (work_floats < shapemol_mlp_backward_workspace(rows, k_in, hidden, n_out)) return tr_fail("shapemol_mlp_backward: workspace too small");
+        return sm_fail("shapemol_mlp_backward: null argument (only d_dx and d_act may be NULL)");
+    if (bad_dims(rows, k_in, hidden, n_out)) return sm_fail("shapemol_mlp_backward: dimensions out of range (hidden <= 256)");
+    if (work_floats < shapemol_mlp_backward_workspace(rows, k_in, hidden, n_out)) return sm_fail("shapemol_mlp_backward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int R = (int)rows, H = hidden;
     const int nwg = (int)((rows + kLnRows - 1) / kLnRows), sp = row_splits(rows), spr = real_splits(rows);
@@ -122,13 +115,13 @@ int shapemol_mlp_backward(const float *d_x, const float *d_dy, int64_t rows, int
     if (gemm(s, d_dy, n_out, 1, d_w2, H, 1, nullptr, dz, H, R, H, n_out, 1)) return 1;
     // db2 partials (column sums of dy)
     hipLaunchKernelGGL(colsum_partial_kernel, dim3(nwg), dim3(256), 0, s, d_dy, (long long)rows, n_out, pb2);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     if (reduce_parts(s, pb2, nwg, n_out, d_db2)) return 1;
     // the activation a = relu(xhat * gamma + beta): the forward's, when the caller kept it, else recomputed from xhat;
     // dW2 = dy^T a:  A(m, k) = dy[k][m], B(k, n) = a[k][n], reduction over the rows in splits
     if (!d_act) {
         hipLaunchKernelGGL(relu_affine_kernel, dim3((unsigned)(((long long)rows * H + 255) / 256)), dim3(256), 0, s, d_xhat, d_gamma, d_beta, act, (long long)rows, H);
-        TRCHK(hipGetLastError());
+        SMCHK(hipGetLastError());
         d_act = act;
     }
     if (gemm(s, d_dy, 1, n_out, d_act, H, 1, nullptr, pw2, H, n_out, H, R, sp)) return 1;
@@ -182,9 +175,9 @@ int shapemol_edge_mlp_forward(const float *d_r, const float *d_h, const float *d
                               float *d_xhat, float *d_rstd, float *d_act, float *d_pd, float *d_ps, void *stream) {
     if (!d_r || !d_h || !d_dst || !d_src || !d_w1 || !d_b1 || !d_gamma || !d_beta || !d_w2 || !d_b2 || !d_y || !d_xhat || !d_rstd || !d_act || !d_pd || !d_ps ||
         (k_shape > 0 && !d_s))
-        return tr_fail("shapemol_edge_mlp_forward: null argument");
+        return sm_fail("shapemol_edge_mlp_forward: null argument");
     const EdgeDims d{n_edges, n_nodes, k_edge, k_node, k_shape, hidden, n_out, k_edge + 2 * k_node + k_shape};
-    if (bad_edge_dims(d)) return tr_fail("shapemol_edge_mlp_forward: dimensions out of range");
+    if (bad_edge_dims(d)) return sm_fail("shapemol_edge_mlp_forward: dimensions out of range");
     hipStream_t s = (hipStream_t)stream;
     const int N = (int)n_nodes, E = (int)n_edges, K1 = d.K1;
     const float *wr = d_w1, *wd = d_w1 + k_edge, *ws = wd + k_node, *wi = ws + k_node;      // column blocks of W1 [hidden][K1]
@@ -195,7 +188,7 @@ int shapemol_edge_mlp_forward(const float *d_r, const float *d_h, const float *d
     if (gemm(s, d_r, k_edge, 1, wr, 1, K1, nullptr, d_act, hidden, E, hidden, k_edge, 1)) return 1;
     hipLaunchKernelGGL(ln_relu_fwd_kernel, dim3((unsigned)((n_edges + 3) / 4)), dim3(256), 0, s, d_act, d_gamma, d_beta, d_xhat, d_rstd, (long long)n_edges, hidden,
                        (const float *)d_pd, (const float *)d_ps, reinterpret_cast<const long long *>(d_dst), reinterpret_cast<const long long *>(d_src));
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return gemm(s, d_act, hidden, 1, d_w2, 1, hidden, d_b2, d_y, n_out, E, n_out, hidden, 1);
 }
 
@@ -206,11 +199,11 @@ int shapemol_edge_mlp_backward(const float *d_r, const float *d_h, const float *
                                float *d_db1, float *d_dgamma, float *d_dbeta, float *d_dw2, float *d_db2, float *d_work, size_t work_floats, void *stream) {
     if (!d_r || !d_h || !d_ptr_dst || !d_perm_src || !d_ptr_src || !d_dy || !d_w1 || !d_gamma || !d_beta || !d_w2 || !d_xhat || !d_rstd || !d_dr || !d_dh ||
         !d_dw1 || !d_db1 || !d_dgamma || !d_dbeta || !d_dw2 || !d_db2 || !d_work || (k_shape > 0 && (!d_s || !d_ds)))
-        return tr_fail("shapemol_edge_mlp_backward: null argument");
+        return sm_fail("shapemol_edge_mlp_backward: null argument");
     const EdgeDims d{n_edges, n_nodes, k_edge, k_node, k_shape, hidden, n_out, k_edge + 2 * k_node + k_shape};
-    if (bad_edge_dims(d)) return tr_fail("shapemol_edge_mlp_backward: dimensions out of range");
+    if (bad_edge_dims(d)) return sm_fail("shapemol_edge_mlp_backward: dimensions out of range");
     const EdgeWork w = edge_work(d);
-    if (work_floats < w.total) return tr_fail("shapemol_edge_mlp_backward: workspace too small");
+    if (work_floats < w.total) return sm_fail("shapemol_edge_mlp_backward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int N = (int)n_nodes, E = (int)n_edges, K1 = d.K1, Hd = hidden;
     const int nwgE = (int)((n_edges + kLnRows - 1) / kLnRows);
@@ -223,11 +216,11 @@ int shapemol_edge_mlp_backward(const float *d_r, const float *d_h, const float *
     // second Linear and LayerNorm + ReLU: as shapemol_mlp_backward
     if (gemm(s, d_dy, n_out, 1, d_w2, Hd, 1, nullptr, dz, Hd, E, Hd, n_out, 1)) return 1;
     hipLaunchKernelGGL(colsum_partial_kernel, dim3(nwgE), dim3(256), 0, s, d_dy, (long long)n_edges, n_out, pb);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     if (reduce_parts(s, pb, nwgE, n_out, d_db2)) return 1;
     if (!d_act) {
         hipLaunchKernelGGL(relu_affine_kernel, dim3((unsigned)(((long long)n_edges * Hd + 255) / 256)), dim3(256), 0, s, d_xhat, d_gamma, d_beta, act, (long long)n_edges, Hd);
-        TRCHK(hipGetLastError());
+        SMCHK(hipGetLastError());
         d_act = act;
     }
     if (gemm(s, d_dy, 1, n_out, d_act, Hd, 1, nullptr, part, Hd, n_out, Hd, E, spE)) return 1;
@@ -240,7 +233,7 @@ int shapemol_edge_mlp_backward(const float *d_r, const float *d_h, const float *
     // the per-node terms: dz summed over each atom's edges as centre (contiguous) and as neighbour (through perm_src)
     hipLaunchKernelGGL(seg_rowsum_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, s, (const float *)dz, ptr_dst, (const long long *)nullptr, dpd, (long long)n_nodes, Hd);
     hipLaunchKernelGGL(seg_rowsum_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, s, (const float *)dz, ptr_src, perm_src, dps, (long long)n_nodes, Hd);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     if (gemm(s, dpd, 1, Hd, d_h, k_node, 1, nullptr, part, k_node, Hd, k_node, N, spN)) return 1;                 // dWd = dpd^T h
     if (reduce_parts(s, part, sprN, (long long)Hd * k_node, d_dw1 + k_edge, k_node, K1)) return 1;
     if (gemm(s, dps, 1, Hd, d_h, k_node, 1, nullptr, part, k_node, Hd, k_node, N, spN)) return 1;                 // dWs = dps^T h
@@ -274,8 +267,8 @@ int shapemol_vn_forward(const float *d_x, const float *d_o3, const float *d_shap
                         float *d_nrm, void *stream) {
     if (!d_x || !d_batch || !d_wf || !d_wd || !d_bn_w || !d_bn_b || !d_out || !d_pf || !d_dir || !d_stats || !d_nrm || (rows_o > 0 && !d_o3) ||
         (rows_s > 0 && !d_shape) || (!training && (!d_run_mean || !d_run_var)))
-        return tr_fail("shapemol_vn_forward: null argument");
-    if (bad_vn_dims(n_atoms, rows_o, rows_s, channels)) return tr_fail("shapemol_vn_forward: dimensions out of range (channels <= 64)");
+        return sm_fail("shapemol_vn_forward: null argument");
+    if (bad_vn_dims(n_atoms, rows_o, rows_s, channels)) return sm_fail("shapemol_vn_forward: dimensions out of range (channels <= 64)");
     hipStream_t s = (hipStream_t)stream;
     VnTrainArgs a{};
     a.x = d_x; a.o3 = d_o3; a.shape = d_shape; a.batch = reinterpret_cast<const long long *>(d_batch);
@@ -287,7 +280,7 @@ int shapemol_vn_forward(const float *d_x, const float *d_o3, const float *d_shap
     hipLaunchKernelGGL(vn_lin_kernel, dim3(nwg), dim3(256), (size_t)2 * channels * a.Cin * sizeof(float), s, a);
     hipLaunchKernelGGL(vn_bn_stats_kernel, dim3(channels), dim3(256), 0, s, a);
     hipLaunchKernelGGL(vn_act_kernel, dim3(nwg), dim3(256), 0, s, a);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return 0;
 }
 
@@ -297,9 +290,9 @@ int shapemol_vn_backward(const float *d_x, const float *d_o3, const float *d_sha
                          float *d_do3, float *d_dwf, float *d_dwd, float *d_dbn_w, float *d_dbn_b, float *d_work, size_t work_floats, void *stream) {
     if (!d_x || !d_batch || !d_wf || !d_wd || !d_bn_w || !d_bn_b || !d_pf || !d_dir || !d_stats || !d_gout || !d_dx || !d_dwf || !d_dwd || !d_dbn_w || !d_dbn_b ||
         !d_work || (rows_o > 0 && (!d_o3 || !d_do3)) || (rows_s > 0 && !d_shape))
-        return tr_fail("shapemol_vn_backward: null argument");
-    if (bad_vn_dims(n_atoms, rows_o, rows_s, channels)) return tr_fail("shapemol_vn_backward: dimensions out of range (channels <= 64)");
-    if (work_floats < shapemol_vn_backward_workspace(n_atoms, rows_o, rows_s, channels)) return tr_fail("shapemol_vn_backward: workspace too small");
+        return sm_fail("shapemol_vn_backward: null argument");
+    if (bad_vn_dims(n_atoms, rows_o, rows_s, channels)) return sm_fail("shapemol_vn_backward: dimensions out of range (channels <= 64)");
+    if (work_floats < shapemol_vn_backward_workspace(n_atoms, rows_o, rows_s, channels)) return sm_fail("shapemol_vn_backward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t NC = (size_t)n_atoms * channels;
     const int per = 256 / channels, Cin = 1 + rows_o + rows_s;
@@ -315,28 +308,28 @@ int shapemol_vn_backward(const float *d_x, const float *d_o3, const float *d_sha
     hipLaunchKernelGGL(vn_bwd_a_kernel, dim3(nwg), dim3(256), 0, s, a);
     hipLaunchKernelGGL(vn_bwd_stats_kernel, dim3(channels), dim3(256), 0, s, a);
     hipLaunchKernelGGL(vn_bwd_b_kernel, dim3(nwg), dim3(256), ((size_t)2 * channels * Cin + (size_t)2 * per * channels * 3) * sizeof(float), s, a);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return reduce_parts3(s, a.wpart, (int)nwg, (long long)channels * Cin, d_dwf, d_dwd, nullptr);
 }
 
 int shapemol_seg_attention_forward(const float *d_q, const float *d_k, const float *d_vals, const int64_t *d_ptr, int64_t n_atoms,
                                    int32_t heads, int32_t dh, int32_t width, float *d_out, void *stream) {
-    if (!d_q || !d_k || !d_vals || !d_ptr || !d_out) return tr_fail("shapemol_seg_attention_forward: null argument");
-    if (n_atoms < 1 || heads < 1 || dh < 1 || dh > kSegAttnMaxDh || width < 1 || width > kSegAttnMaxW) return tr_fail("shapemol_seg_attention_forward: dimensions out of range (dh, width <= 8)");
+    if (!d_q || !d_k || !d_vals || !d_ptr || !d_out) return sm_fail("shapemol_seg_attention_forward: null argument");
+    if (n_atoms < 1 || heads < 1 || dh < 1 || dh > kSegAttnMaxDh || width < 1 || width > kSegAttnMaxW) return sm_fail("shapemol_seg_attention_forward: dimensions out of range (dh, width <= 8)");
     SegAttnArgs a{d_q, d_k, d_vals, reinterpret_cast<const long long *>(d_ptr), d_out, nullptr, nullptr, nullptr, nullptr, (int)n_atoms, heads, dh, width};
     hipLaunchKernelGGL(seg_attention_kernel<false>, dim3((unsigned)((n_atoms * heads * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return 0;
 }
 
 int shapemol_seg_attention_backward(const float *d_q, const float *d_k, const float *d_vals, const int64_t *d_ptr, const float *d_dout,
                                     int64_t n_atoms, int32_t heads, int32_t dh, int32_t width, float *d_dq, float *d_dk, float *d_dvals,
                                     void *stream) {
-    if (!d_q || !d_k || !d_vals || !d_ptr || !d_dout || !d_dq || !d_dk || !d_dvals) return tr_fail("shapemol_seg_attention_backward: null argument");
-    if (n_atoms < 1 || heads < 1 || dh < 1 || dh > kSegAttnMaxDh || width < 1 || width > kSegAttnMaxW) return tr_fail("shapemol_seg_attention_backward: dimensions out of range (dh, width <= 8)");
+    if (!d_q || !d_k || !d_vals || !d_ptr || !d_dout || !d_dq || !d_dk || !d_dvals) return sm_fail("shapemol_seg_attention_backward: null argument");
+    if (n_atoms < 1 || heads < 1 || dh < 1 || dh > kSegAttnMaxDh || width < 1 || width > kSegAttnMaxW) return sm_fail("shapemol_seg_attention_backward: dimensions out of range (dh, width <= 8)");
     SegAttnArgs a{d_q, d_k, d_vals, reinterpret_cast<const long long *>(d_ptr), nullptr, d_dout, d_dq, d_dk, d_dvals, (int)n_atoms, heads, dh, width};
     hipLaunchKernelGGL(seg_attention_kernel<true>, dim3((unsigned)((n_atoms * heads * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    TRCHK(hipGetLastError());
+    SMCHK(hipGetLastError());
     return 0;
 }
 

@@ -14,7 +14,6 @@ package's choice; oddt takes its radii from its own atom typing.
 Limits (``ValueError`` before any kernel runs): 1..1024 atoms per molecule, at most 128^3 grid nodes per molecule and 2^26 per
 call, ``ceil((probe_radius * scaling + spacing) / spacing) <= 16``.
 """
-import atexit
 import collections
 import ctypes as C
 
@@ -22,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._native import DeviceContexts, hip_device, host, ptr, stream_ptr
 
 # Bondi (1964), Angstrom, by atomic number
 VDW_RADII = {1: 1.20, 6: 1.70, 7: 1.55, 8: 1.52, 9: 1.47, 15: 1.80, 16: 1.80, 17: 1.75, 35: 1.85, 53: 1.98}
@@ -52,29 +52,23 @@ def radii_of(elements=None, atom_types=None, mode="add_aromatic"):
         if mode not in VOCAB_ELEMENTS:
             raise ValueError(f"unknown atom vocabulary {mode!r}")
         table = np.asarray(VOCAB_ELEMENTS[mode])
-        idx = _host(atom_types).astype(np.int64)
+        idx = host(atom_types).astype(np.int64)
         if idx.size and (idx.min() < 0 or idx.max() >= len(table)):
             raise ValueError(f"an atom type lies outside the {len(table)} types of {mode!r}")
         elements = table[idx]
-    z = _host(elements).astype(np.int64).reshape(-1)
+    z = host(elements).astype(np.int64).reshape(-1)
     missing = sorted(set(z.tolist()) - set(VDW_RADII))
     if missing:
         raise ValueError(f"no van-der-Waals radius for atomic number(s) {missing}; give radii")
     return np.array([VDW_RADII[int(k)] for k in z], np.float64)
 
 
-def _host(a):
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.asarray(a)
-
-
 def _pack(mols):
     """[(pos (N,3), radii (N,)), ...] -> host arrays (atom_off int64, centres float64, radii float64)."""
     off, cs, rs = [0], [], []
     for b, (pos, rad) in enumerate(mols):
-        c = _host(pos).astype(np.float64).reshape(-1, 3)
-        r = _host(rad).astype(np.float64).reshape(-1)
+        c = host(pos).astype(np.float64).reshape(-1, 3)
+        r = host(rad).astype(np.float64).reshape(-1)
         if len(r) != len(c):
             raise ValueError(f"molecular surface: molecule {b}: {len(c)} positions and {len(r)} radii")
         cs.append(c)
@@ -84,46 +78,13 @@ def _pack(mols):
     return np.asarray(off, np.int64), cat(cs, (1, 3)), cat(rs, (1,))
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class _Context:
-    """One library context per device (workspaces grow with the largest batch seen)."""
-    _by_device = {}
-
-    def __init__(self, device):
-        self.lib = _lib.load()
-        self.ptr = C.c_void_p()
-        _lib.check(self.lib.shapemol_msurf_create(device.index or 0, C.byref(self.ptr)), "shapemol_msurf_create")
-
-    def close(self):
-        if self.ptr:
-            self.lib.shapemol_msurf_destroy(self.ptr)
-            self.ptr = None
-
-    @classmethod
-    def of(cls, device):
-        key = device.index or 0
-        if key not in cls._by_device:
-            cls._by_device[key] = cls(device)
-        return cls._by_device[key]
-
-
-@atexit.register
-def _close_contexts():
-    for c in _Context._by_device.values():
-        c.close()
-    _Context._by_device.clear()
+_contexts = DeviceContexts("shapemol_msurf_create", "shapemol_msurf_destroy")
 
 
 def _device(device):
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("molecular surfaces are built on a HIP device (shapemol_amd has no CPU path)")
-    return torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
+    return hip_device(device, "molecular surfaces are built on a HIP device")
 
 
 def get_mesh_batch(mols, probe_radius=1.4, scaling=1.0, spacing=None, *, device=None, details=False):
@@ -146,24 +107,24 @@ def get_mesh_batch(mols, probe_radius=1.4, scaling=1.0, spacing=None, *, device=
     h = 1.0 if spacing is None else float(spacing)
     lib = _lib.load()
     B = len(pairs)
-    if lib.shapemol_msurf_check(B, _vp(off), _vp(cen), _vp(rad), float(probe_radius), h, float(scaling)):
+    if lib.shapemol_msurf_check(B, ptr(off), ptr(cen), ptr(rad), float(probe_radius), h, float(scaling)):
         raise ValueError(lib.shapemol_last_error().decode())
     device = _device(device)
     counts = np.zeros((B, 2), np.int32)
     lo, dims, ms = np.zeros((B, 3), np.float64), np.zeros((B, 3), np.int32), np.zeros(6, np.float64)
-    ctx = _Context.of(device)
+    ctx = _contexts.of(device)
     with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.shapemol_msurf_build(ctx.ptr, B, _vp(off), _vp(cen), _vp(rad), 0, float(probe_radius), h, float(scaling), _vp(counts),
-                                            _vp(lo), _vp(dims), _vp(ms) if details else None, stream), "shapemol_msurf_build")
+        stream = stream_ptr(device)
+        _lib.check(lib.shapemol_msurf_build(ctx, B, ptr(off), ptr(cen), ptr(rad), 0, float(probe_radius), h, float(scaling), ptr(counts),
+                                            ptr(lo), ptr(dims), ptr(ms) if details else None, stream), "shapemol_msurf_build")
         nv, nf = int(counts[:, 0].sum()), int(counts[:, 1].sum())
         verts, faces = np.empty((nv, 3), np.float64), np.empty((nf, 3), np.int32)
-        _lib.check(lib.shapemol_msurf_copy(ctx.ptr, 0, _vp(verts), 3 * nv, stream), "shapemol_msurf_copy")
-        _lib.check(lib.shapemol_msurf_copy(ctx.ptr, 1, _vp(faces), 3 * nf, stream), "shapemol_msurf_copy")
+        _lib.check(lib.shapemol_msurf_copy(ctx, 0, ptr(verts), 3 * nv, stream), "shapemol_msurf_copy")
+        _lib.check(lib.shapemol_msurf_copy(ctx, 1, ptr(faces), 3 * nf, stream), "shapemol_msurf_copy")
         field = None
         if details:
             field = np.empty(int(dims.astype(np.int64).prod(1).sum()), np.float64)
-            _lib.check(lib.shapemol_msurf_copy(ctx.ptr, 2, _vp(field), field.size, stream), "shapemol_msurf_copy")
+            _lib.check(lib.shapemol_msurf_copy(ctx, 2, ptr(field), field.size, stream), "shapemol_msurf_copy")
     vo, fo = np.concatenate([[0], np.cumsum(counts[:, 0])]), np.concatenate([[0], np.cumsum(counts[:, 1])])
     meshes = [(verts[vo[b]:vo[b + 1]].copy(), faces[fo[b]:fo[b + 1]].copy()) for b in range(B)]
     if not details:

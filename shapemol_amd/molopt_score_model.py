@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import ptr, stream_ptr
 from .diffusion import build_schedule_tables
 from .packing import pack_state_dict
 from .spec import ModelDims, state_dict_spec, RBF_CENTRES
@@ -50,14 +51,6 @@ def _attach(root, key, tensor, kind):
         mod.register_buffer(leaf, tensor)
     else:
         mod.register_parameter(leaf, nn.Parameter(tensor, requires_grad=(kind != "const")))
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream_ptr(stream):
-    return C.c_void_p(stream.cuda_stream)
 
 
 def _check_device_tensor(name, t, dtype):
@@ -157,11 +150,9 @@ class ScorePosNet3D(nn.Module):
             raise _lib.ShapeMolLibraryError(f"packed weight count {packed.size} != library's {want}")
         ctx = C.c_void_p()
         index = device.index if device.index is not None else torch.cuda.current_device()
-        _lib.check(lib.shapemol_create(C.byref(cfg), packed.ctypes.data_as(C.c_void_p), packed.size, index, C.byref(ctx)),
-                   "shapemol_create")
+        _lib.check(lib.shapemol_create(C.byref(cfg), ptr(packed), packed.size, index, C.byref(ctx)), "shapemol_create")
         mean, var = self._bn_running()
-        _lib.check(lib.shapemol_set_bn_running(ctx, mean.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p), mean.size),
-                   "shapemol_set_bn_running")
+        _lib.check(lib.shapemol_set_bn_running(ctx, ptr(mean), ptr(var), mean.size), "shapemol_set_bn_running")
         # options set through set_option apply to every context; replayed in a dependency-safe order (feat_f16 needs the f16
         # kernels selected first), and a context that cannot take them is destroyed, not leaked
         opts = self.__dict__.get("_options", {})
@@ -233,12 +224,12 @@ class ScorePosNet3D(nn.Module):
         off = np.zeros(n_steps + 1, np.int32)
         np.add.at(off, step + 1, 1)
         off = np.ascontiguousarray(np.cumsum(off).astype(np.int32))
-        _lib.check(lib.shapemol_set_knn_pins(ctx, off.ctypes.data_as(C.c_void_p), n_steps, atom.ctypes.data_as(C.c_void_p),
-                                             nbr.ctypes.data_as(C.c_void_p), len(atom), nbr.shape[1]), "shapemol_set_knn_pins")
+        _lib.check(lib.shapemol_set_knn_pins(ctx, ptr(off), n_steps, ptr(atom), ptr(nbr), len(atom), nbr.shape[1]),
+                   "shapemol_set_knn_pins")
 
     def debug_read(self, name, shape, dtype):
         out = np.empty(shape, dtype=dtype)
-        n = _lib.load().shapemol_debug_read(self._ctx, name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
+        n = _lib.load().shapemol_debug_read(self._ctx, name.encode(), ptr(out), out.nbytes)
         if n != out.nbytes:
             raise _lib.ShapeMolLibraryError(f"debug_read({name}): got {n} bytes, want {out.nbytes}")
         return out
@@ -265,9 +256,8 @@ class ScorePosNet3D(nn.Module):
         out_h = torch.empty((n, self.dims.H), dtype=torch.float32, device=dev)
         out_v = torch.empty((n, self.dims.C), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.load().shapemol_score(ctx, _ptr(pos), _ptr(v), _ptr(batch), n, b, _ptr(shape), _ptr(t),
-                                            _ptr(out_pos), _ptr(out_h), _ptr(out_v),
-                                            _stream_ptr(torch.cuda.current_stream(dev)))
+            rc = _lib.load().shapemol_score(ctx, ptr(pos), ptr(v), ptr(batch), n, b, ptr(shape), ptr(t),
+                                            ptr(out_pos), ptr(out_h), ptr(out_v), stream_ptr(dev))
             _lib.check(rc, "shapemol_score")
             preds = {"pred_ligand_pos": out_pos, "pred_ligand_h": out_h, "pred_ligand_v": out_v}
             if return_all:
@@ -278,8 +268,8 @@ class ScorePosNet3D(nn.Module):
                 lib = _lib.load()
                 _lib.check(lib.shapemol_set_option(ctx, b"stop_layer", 0), "shapemol_set_option")
                 try:
-                    rc = lib.shapemol_score(ctx, _ptr(pos), _ptr(v), _ptr(batch), n, b, _ptr(shape), _ptr(t), _ptr(torch.empty_like(out_pos)),
-                                            None, _ptr(out_v0), _stream_ptr(torch.cuda.current_stream(dev)))
+                    rc = lib.shapemol_score(ctx, ptr(pos), ptr(v), ptr(batch), n, b, ptr(shape), ptr(t), ptr(torch.empty_like(out_pos)),
+                                            None, ptr(out_v0), stream_ptr(dev))
                     _lib.check(rc, "shapemol_score")
                 finally:
                     lib.shapemol_set_option(ctx, b"stop_layer", -1)
@@ -570,23 +560,20 @@ class ScorePosNet3D(nn.Module):
                     _lib.check(lib.shapemol_set_option(ctx, b"first_step", int(first_step)), "shapemol_set_option")
                 if cfg and cfg_groups is not None:
                     off, stren, boxes = cfg_groups
-                    _lib.check(lib.shapemol_set_cfg_groups(ctx, len(stren), off.ctypes.data_as(C.c_void_p), stren.ctypes.data_as(C.c_void_p),
-                                                           _lib.CFG_THRESHOLDS[threshold_type], cfg_p,
-                                                           None if boxes is None else boxes.ctypes.data_as(C.c_void_p),
-                                                           _ptr(bufs.get("pos_uncond_traj")), _ptr(bufs.get("v_uncond_traj"))),
+                    _lib.check(lib.shapemol_set_cfg_groups(ctx, len(stren), ptr(off), ptr(stren), _lib.CFG_THRESHOLDS[threshold_type], cfg_p,
+                                                           ptr(boxes), ptr(bufs.get("pos_uncond_traj")), ptr(bufs.get("v_uncond_traj"))),
                                "shapemol_set_cfg_groups")
                 elif cfg:
                     _lib.check(lib.shapemol_set_cfg(ctx, float(guide_stren), _lib.CFG_THRESHOLDS[threshold_type], cfg_p,
-                                                    None if cfg_box is None else cfg_box.ctypes.data_as(C.c_void_p),
-                                                    _ptr(bufs.get("pos_uncond_traj")), _ptr(bufs.get("v_uncond_traj"))),
+                                                    ptr(cfg_box), ptr(bufs.get("pos_uncond_traj")), ptr(bufs.get("v_uncond_traj"))),
                                "shapemol_set_cfg")
                 if field_dec is not None:
                     _lib.check(lib.shapemol_set_field_guidance(ctx, field_dec._context(dev), grad_lr, int(grad_step)),
                                "shapemol_set_field_guidance")
                 try:
-                    rc = lib.shapemol_sample(ctx, _ptr(pos), _ptr(v), _ptr(batch), n, b, _ptr(shape), int(num_steps),
-                                             _ptr(eps), _ptr(u), C.c_uint64(seed), C.byref(tr), _ptr(out_pos), _ptr(out_v),
-                                             1 if use_graph else 0, _stream_ptr(side))
+                    rc = lib.shapemol_sample(ctx, ptr(pos), ptr(v), ptr(batch), n, b, ptr(shape), int(num_steps),
+                                             ptr(eps), ptr(u), C.c_uint64(seed), C.byref(tr), ptr(out_pos), ptr(out_v),
+                                             1 if use_graph else 0, stream_ptr(side))
                 finally:
                     if first_step:
                         lib.shapemol_set_option(ctx, b"first_step", 0)
@@ -623,8 +610,8 @@ class ScorePosNet3D(nn.Module):
         try:
             with torch.cuda.device(pos.device):
                 stream = torch.cuda.current_stream(pos.device)
-                _lib.check(lib.shapemol_guide_points_groups(ctx, _ptr(pos), _ptr(batch), pos.shape[0], _ptr(gd), C.c_uint64(seed),
-                                                            _stream_ptr(stream)), "shapemol_guide_points_groups")
+                _lib.check(lib.shapemol_guide_points_groups(ctx, ptr(pos), ptr(batch), pos.shape[0], ptr(gd), C.c_uint64(seed),
+                                                            stream_ptr(stream)), "shapemol_guide_points_groups")
                 stream.synchronize()
         finally:
             _clear_guidance(lib, ctx, "groups")
@@ -652,9 +639,9 @@ class ScorePosNet3D(nn.Module):
         try:
             with torch.cuda.device(pos.device):
                 stream = torch.cuda.current_stream(pos.device)
-                _lib.check(lib.shapemol_guide_points_mesh_groups(ctx, _ptr(pos), _ptr(batch), pos.shape[0], _ptr(gd), C.c_uint64(seed),
-                                                                 _stream_ptr(stream)), "shapemol_guide_points_mesh_groups")
-                lib.shapemol_status_stream(ctx, flags, _stream_ptr(stream))        # waits for the pass; only the mesh flag is its own
+                _lib.check(lib.shapemol_guide_points_mesh_groups(ctx, ptr(pos), ptr(batch), pos.shape[0], ptr(gd), C.c_uint64(seed),
+                                                                 stream_ptr(stream)), "shapemol_guide_points_mesh_groups")
+                lib.shapemol_status_stream(ctx, flags, stream_ptr(stream))        # waits for the pass; only the mesh flag is its own
         finally:
             _clear_guidance(lib, ctx, "mesh_groups")
         if flags[_lib.ST_MESH]:
@@ -727,7 +714,7 @@ class _PendingChain:
             # the reference returns finished results; also the point where the input flags are read (only this chain's stream
             # is waited for: another slot's chain may be running beside it)
             flags = (C.c_int32 * 8)()
-            rc = _lib.load().shapemol_status_stream(self.ctx, flags, _stream_ptr(self.side))
+            rc = _lib.load().shapemol_status_stream(self.ctx, flags, stream_ptr(self.side))
             if rc and flags[_lib.ST_MESH] and not any(flags[i] for i in range(8) if i != _lib.ST_MESH):
                 if self.n_groups:
                     raise _mesh_groups_error(_lib.load(), self.ctx, self.n_groups)
@@ -797,9 +784,8 @@ def pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=3, ratio=0
     if pos.shape[0] == 0:
         return pred_ligand_pos
     with torch.cuda.device(pos.device):
-        rc = _lib.load().shapemol_pointcloud_guidance(cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], float(use_pointcloud_data[2]),
-                                                      float(ratio), _ptr(pos), pos.shape[0], _ptr(gd), C.c_uint64(seed),
-                                                      _stream_ptr(torch.cuda.current_stream(pos.device)))
+        rc = _lib.load().shapemol_pointcloud_guidance(ptr(cloud), cloud.shape[0], float(use_pointcloud_data[2]),
+                                                      float(ratio), ptr(pos), pos.shape[0], ptr(gd), C.c_uint64(seed), stream_ptr(pos.device))
     _lib.check(rc, "shapemol_pointcloud_guidance")
     return pred_ligand_pos
 
@@ -893,7 +879,7 @@ def _mesh_groups_error(lib, ctx, n_groups):
     """The MeshGuidanceError of a chain / pass with mesh groups: names the groups that were left unguided and in how many steps
     (``.group_steps``: (G,) int32, from the library's per-group count)."""
     steps = np.zeros(n_groups, dtype=np.int32)
-    got = lib.shapemol_debug_read(ctx, b"mesh_group_flags", steps.ctypes.data_as(C.c_void_p), steps.nbytes)
+    got = lib.shapemol_debug_read(ctx, b"mesh_group_flags", ptr(steps), steps.nbytes)
     bad = np.nonzero(steps)[0] if got == steps.nbytes else []
     which = ", ".join(f"group {g} in {int(steps[g])} step(s)" for g in bad[:16]) + (" ..." if len(bad) > 16 else "")
     err = _lib.MeshGuidanceError(
@@ -926,15 +912,14 @@ _GUIDANCE = {"mesh_groups": ("shapemol_set_mesh_guidance_groups", (0, None, None
 
 def _install_guidance(lib, ctx, kind, payload, grad_step, gd):
     """payload -- "mesh_groups": _mesh_guidance_groups' arrays; "groups": _guidance_groups' arrays."""
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)        # noqa: E731
     if kind == "mesh_groups":
         mol_off, verts, vert_off, faces, face_off, clouds, cloud_off = payload
-        opt = lambda a: vp(a) if len(a) else None      # noqa: E731
-        args = (len(mol_off) - 1, vp(mol_off), opt(verts), vp(vert_off), opt(faces), vp(face_off), opt(clouds), vp(cloud_off))
+        opt = lambda a: ptr(a) if len(a) else None      # noqa: E731
+        args = (len(mol_off) - 1, ptr(mol_off), opt(verts), ptr(vert_off), opt(faces), ptr(face_off), opt(clouds), ptr(cloud_off))
     else:
         mol_off, clouds, cloud_off, radii = payload
-        args = (len(radii), vp(mol_off), vp(clouds) if len(clouds) else None, vp(cloud_off), vp(radii))
-    _lib.check(getattr(lib, _GUIDANCE[kind][0])(ctx, *args, int(grad_step), _ptr(gd)), _GUIDANCE[kind][0])
+        args = (len(radii), ptr(mol_off), ptr(clouds) if len(clouds) else None, ptr(cloud_off), ptr(radii))
+    _lib.check(getattr(lib, _GUIDANCE[kind][0])(ctx, *args, int(grad_step), ptr(gd)), _GUIDANCE[kind][0])
 
 
 def _clear_guidance(lib, ctx, kind):
@@ -999,10 +984,8 @@ def mesh_shape_guidance(use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws
         raise _lib.MeshGuidanceError("mesh shape guidance: no atoms inside the mesh (the reference's KDTree of none raises)")
     flag = C.c_int32(0)
     with torch.cuda.device(pos.device):
-        rc = _lib.load().shapemol_mesh_guidance(verts.ctypes.data_as(C.c_void_p), verts.shape[0], faces.ctypes.data_as(C.c_void_p),
-                                                faces.shape[0], cloud.ctypes.data_as(C.c_void_p), cloud.shape[0], _ptr(pos),
-                                                pos.shape[0], _ptr(gd), C.c_uint64(seed), C.byref(flag),
-                                                _stream_ptr(torch.cuda.current_stream(pos.device)))
+        rc = _lib.load().shapemol_mesh_guidance(ptr(verts), verts.shape[0], ptr(faces), faces.shape[0], ptr(cloud), cloud.shape[0],
+                                                ptr(pos), pos.shape[0], ptr(gd), C.c_uint64(seed), C.byref(flag), stream_ptr(pos.device))
     if rc and flag.value:
         raise _lib.MeshGuidanceError(_lib.load().shapemol_last_error().decode())
     _lib.check(rc, "shapemol_mesh_guidance")
@@ -1019,7 +1002,6 @@ def log_sample_categorical(logits, *, u=None, seed=None):
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if u is None else 0
     out = torch.empty((n,), dtype=torch.int64, device=lg.device)
     with torch.cuda.device(lg.device):
-        rc = _lib.load().shapemol_log_sample_categorical(None, _ptr(lg), _ptr(u), n, c, C.c_uint64(seed), _ptr(out),
-                                                         _stream_ptr(torch.cuda.current_stream(lg.device)))
+        rc = _lib.load().shapemol_log_sample_categorical(None, ptr(lg), ptr(u), n, c, C.c_uint64(seed), ptr(out), stream_ptr(lg.device))
     _lib.check(rc, "shapemol_log_sample_categorical")
     return out

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._native import ptr, stream_ptr
 
 
 class ChainRunner:
@@ -65,13 +66,11 @@ class ChainRunner:
             if other is not self and not other.stream.query():
                 raise RuntimeError("another ChainRunner of the same model still has a chain in flight: a context has one workspace; "
                                    "synchronize() it first, or give the second runner its own model (own context)")
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
         self.model._sync_bn_mode(self.ctx)      # module.eval() / .train() since the last call (shared context)
         with torch.cuda.device(self.dev):
-            rc = _lib.load().shapemol_sample(self.ctx, p(self.pos0), p(self.v0), p(self.batch), self.n, self.b, p(self.shape),
-                                             int(num_steps), p(self.eps), p(self.u), C.c_uint64(seed), C.byref(self.traj),
-                                             p(self.out_pos), p(self.out_v), 1 if use_graph else 0,
-                                             C.c_void_p(self.stream.cuda_stream))
+            rc = _lib.load().shapemol_sample(self.ctx, ptr(self.pos0), ptr(self.v0), ptr(self.batch), self.n, self.b, ptr(self.shape),
+                                             int(num_steps), ptr(self.eps), ptr(self.u), C.c_uint64(seed), C.byref(self.traj),
+                                             ptr(self.out_pos), ptr(self.out_v), 1 if use_graph else 0, stream_ptr(self.stream))
         _lib.check(rc, "shapemol_sample")
 
     def synchronize(self):

@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import LOSS_TYPES, get, hip_device, ptr, stream_ptr
 from .shape_encoder import VN_DGCNN_Encoder
 
 __all__ = ["DecoderInner", "PointCloud_AE"]
@@ -81,16 +82,11 @@ class DecoderInner(nn.Module):
     def _load_weights(self, ctx, flat, device):
         """Repack the context's weights from one flat float32 device vector in ``_pack`` order (a kernel on the current stream)."""
         with torch.cuda.device(device):
-            rc = _lib.load().shapemol_field_load_weights(ctx, C.c_void_p(flat.data_ptr()), flat.numel(),
-                                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+            rc = _lib.load().shapemol_field_load_weights(ctx, ptr(flat), flat.numel(), stream_ptr(device))
         _lib.check(rc, "shapemol_field_load_weights")
 
     def _context(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"{device} is not a HIP device (shapemol_amd has no CPU path)")
-        if device.index is None:                           # 'cuda' and 'cuda:<current>' are one context
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = hip_device(device)      # ('cuda' and 'cuda:<current>' are one context)
         key = (str(device), self.loss_type) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._ctx is not None and key == self._key:
             return self._ctx
@@ -103,9 +99,9 @@ class DecoderInner(nn.Module):
         self._release()
         w = self._pack()
         ctx = C.c_void_p()
-        idx = device.index
-        _lib.check(lib.shapemol_sd_create(self.hidden_size, self.z_dim, self.layer_num, 1 if self.loss_type == "occupancy" else 0,
-                                          w.ctypes.data_as(C.c_void_p), w.size, idx, C.byref(ctx)), "shapemol_sd_create")
+        # (as in the reference, every loss_type but 'occupancy' is a signed distance: no sigmoid)
+        _lib.check(lib.shapemol_sd_create(self.hidden_size, self.z_dim, self.layer_num, LOSS_TYPES.get(self.loss_type, 0), ptr(w), w.size,
+                                          device.index, C.byref(ctx)), "shapemol_sd_create")
         self._ctx, self._key = ctx, key
         return ctx
 
@@ -133,7 +129,7 @@ class DecoderInner(nn.Module):
         G (B, H, 3), c (B, H) of fc_in(feature) = w_0 |p|^2 + G p + c."""
         shape = {"z_inv": (n_shapes, self.z_dim), "G": (n_shapes, self.hidden_size, 3), "c": (n_shapes, self.hidden_size)}[name]
         a = np.empty(shape, np.float32)
-        _lib.check(_lib.load().shapemol_sd_debug_read(self._context(device), self._DEBUG[name], a.ctypes.data_as(C.c_void_p), a.nbytes),
+        _lib.check(_lib.load().shapemol_sd_debug_read(self._context(device), self._DEBUG[name], ptr(a), a.nbytes),
                    "shapemol_sd_debug_read")
         return a
 
@@ -149,10 +145,9 @@ class DecoderInner(nn.Module):
         out = torch.empty((n,), dtype=torch.float32, device=dev)
         grad = torch.empty((n, 3), dtype=torch.float32, device=dev) if with_grad else None
         name = "shapemol_field_decode_grad" if with_grad else "shapemol_sd_decode"
-        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None  # noqa: E731
         with torch.cuda.device(dev):
             args = [self._context(dev), ptr(p), ptr(shape_of), n, per_shape, ptr(z), b, ptr(out)] + ([ptr(grad)] if with_grad else [])
-            rc = getattr(_lib.load(), name)(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = getattr(_lib.load(), name)(*args, stream_ptr(dev))
         _lib.check(rc, name)
         return out, grad
 
@@ -246,9 +241,8 @@ class DecoderInner(nn.Module):
         batch = batch.to(torch.int64).contiguous()
         dev = pos.device
         with torch.cuda.device(dev):
-            rc = _lib.load().shapemol_field_guide(self._context(dev), C.c_void_p(out.data_ptr()), C.c_void_p(batch.data_ptr()), n,
-                                               C.c_void_p(z.data_ptr()), z.shape[0], grad_lr,
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = _lib.load().shapemol_field_guide(self._context(dev), ptr(out), ptr(batch), n, ptr(z), z.shape[0], grad_lr,
+                                               stream_ptr(dev))
         _lib.check(rc, "shapemol_field_guide")
         return out
 
@@ -324,9 +318,8 @@ class _TrainField(torch.autograd.Function):
         gz = torch.empty_like(zz)
         gw = torch.empty_like(flat)
         with torch.cuda.device(dev):
-            rc = _lib.load().shapemol_field_train(handle, C.c_void_p(x.data_ptr()), b, t, C.c_void_p(zz.data_ptr()), C.c_void_p(up.data_ptr()),
-                                                  None, C.c_void_p(gp.data_ptr()), C.c_void_p(gz.data_ptr()), C.c_void_p(gw.data_ptr()),
-                                                  ctx.chunk, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = _lib.load().shapemol_field_train(handle, ptr(x), b, t, ptr(zz), ptr(up), None, ptr(gp), ptr(gz), ptr(gw), ctx.chunk,
+                                                  stream_ptr(dev))
         _lib.check(rc, "shapemol_field_train")
         grads, o = [], 0
         for shp in ctx.shapes:
@@ -336,10 +329,6 @@ class _TrainField(torch.autograd.Function):
         return (gp.view(b, t, 3), gz.view(ctx.z_shape), None, None, *grads)
 
 
-def _get(config, name):
-    return config[name] if isinstance(config, dict) else getattr(config, name)
-
-
 class PointCloud_AE(nn.Module):
     """``PointCloud_AE(config)`` of the reference: ``.encoder`` (the device ``VN_DGCNN_Encoder``) and ``.generator`` (the device
     ``DecoderInner``), built from ``config.{encoder, hidden_dim, latent_dim, layer_num, num_k, point_dim, loss_type}``
@@ -347,15 +336,15 @@ class PointCloud_AE(nn.Module):
 
     def __init__(self, config):
         super().__init__()
-        enc = _get(config, "encoder")
+        enc = get(config, "encoder")
         if enc == "VN_Resnet":
             raise NotImplementedError("PointCloud_AE: the VN_Resnet encoder has no device implementation; the shipped model uses VN_DGCNN")
         if enc != "VN_DGCNN":
             raise ValueError(f"PointCloud_AE: unknown encoder {enc!r}")
-        hidden, latent, layers = _get(config, "hidden_dim"), _get(config, "latent_dim"), _get(config, "layer_num")
-        self.encoder = VN_DGCNN_Encoder(hidden, latent, layers, _get(config, "num_k"))
-        self.generator = DecoderInner(_get(config, "point_dim"), latent, hidden, layers, _get(config, "loss_type"))
-        self.loss_type = _get(config, "loss_type")
+        hidden, latent, layers = get(config, "hidden_dim"), get(config, "latent_dim"), get(config, "layer_num")
+        self.encoder = VN_DGCNN_Encoder(hidden, latent, layers, get(config, "num_k"))
+        self.generator = DecoderInner(get(config, "point_dim"), latent, hidden, layers, get(config, "loss_type"))
+        self.loss_type = get(config, "loss_type")
 
     @torch.no_grad()
     def forward(self, inputs, z_vector, point_coord, is_training=False):

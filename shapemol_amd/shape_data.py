@@ -7,27 +7,15 @@ KD-tree, per mesh on the host; here a batch of meshes goes through four kernels 
 package's ray parity (the rule of mesh guidance), not trimesh's, and meshes are not checked for closedness, as the reference
 does not check them either.  Limits: ``point_cloud_samples <= 2048``, int32 face indices.
 """
-import atexit
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._native import LOSS_TYPES, DeviceContexts, get, hip_device, host, ptr, stream_ptr
 
-LOSS_TYPES = {"signed_distance": 0, "occupancy": 1}
 MAX_CLOUD = 2048       # kSdataMaxCloud (csrc/sm_shape_data.h)
-
-
-def _get(config, name):
-    return config[name] if isinstance(config, dict) else getattr(config, name)
-
-
-def _host(a, dtype):
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    a = np.asarray(a)
-    return a if dtype is None else a.astype(dtype, copy=False)
 
 
 def _pack_meshes(meshes):
@@ -38,8 +26,8 @@ def _pack_meshes(meshes):
     for b, m in enumerate(meshes):
         if not isinstance(m, (tuple, list)) or len(m) != 2:
             m = (m.vertices, m.faces)          # a trimesh-like object
-        v = _host(m[0], np.float64).reshape(-1, 3)
-        f = _host(m[1], None).reshape(-1, 3)
+        v = host(m[0], np.float64).reshape(-1, 3)
+        f = host(m[1], None).reshape(-1, 3)
         if f.dtype != np.int32:
             f = f.astype(np.int64)
             if f.size and (f.min() < -2 ** 31 or f.max() >= 2 ** 31):
@@ -53,48 +41,15 @@ def _pack_meshes(meshes):
     return np.asarray(vo, np.int64), cat(verts, np.float64), np.asarray(fo, np.int64), cat(faces, np.int32)
 
 
-def _vp(a):
-    if a is None:
-        return None
-    return C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a.ctypes.data_as(C.c_void_p)
-
-
 def _check(packed, n_cloud, n_samples, loss_code):
     """The library's argument checks (host only): ValueError with its message."""
     vo, v, fo, f = packed
     lib = _lib.load()
-    if lib.shapemol_sdata_check(len(vo) - 1, _vp(vo), _vp(v), _vp(fo), _vp(f), int(n_cloud), int(n_samples), loss_code):
+    if lib.shapemol_sdata_check(len(vo) - 1, ptr(vo), ptr(v), ptr(fo), ptr(f), int(n_cloud), int(n_samples), loss_code):
         raise ValueError(lib.shapemol_last_error().decode())
 
 
-class _Context:
-    """One library context per device (workspaces grow with the largest batch seen)."""
-    _by_device = {}
-
-    def __init__(self, device):
-        self.lib = _lib.load()
-        self.ptr = C.c_void_p()
-        _lib.check(self.lib.shapemol_sdata_create(device.index or 0, C.byref(self.ptr)), "shapemol_sdata_create")
-
-    def close(self):
-        if self.ptr:
-            self.lib.shapemol_sdata_destroy(self.ptr)
-            self.ptr = None
-
-    @classmethod
-    def of(cls, device):
-        key = device.index or 0
-        if key not in cls._by_device:
-            cls._by_device[key] = cls(device)
-        return cls._by_device[key]
-
-
-@atexit.register
-def _close_contexts():
-    """The cached contexts go before the interpreter tears the runtime down (not from a finaliser during it)."""
-    for c in _Context._by_device.values():
-        c.close()
-    _Context._by_device.clear()
+_contexts = DeviceContexts("shapemol_sdata_create", "shapemol_sdata_destroy")
 
 
 def _chunk_seed(seed, chunk):
@@ -106,10 +61,7 @@ def _chunk_seed(seed, chunk):
 
 
 def _device(device):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("shape data is built on a HIP device (shapemol_amd has no CPU path)")
-    return torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
+    return hip_device(device, "shape data is built on a HIP device")
 
 
 def _draws(t, shape, device, name):
@@ -150,17 +102,17 @@ def build_batch(meshes, n_cloud, n_samples, loss_type="signed_distance", *, devi
         if T:
             out.update(flags=torch.empty((B, 3 * T), **i32), sel=torch.full((B, T), -1, **i32))
     vo, v, fo, f = packed
-    ctx = _Context.of(device)
+    lib, ctx = _lib.load(), _contexts.of(device)
     with torch.cuda.device(device):
-        rc = ctx.lib.shapemol_sdata_build(
-            ctx.ptr, B, _vp(vo), _vp(v), _vp(fo), _vp(f), P, T, LOSS_TYPES[loss_type], _vp(cloud_draws), _vp(query_draws),
-            C.c_uint64(int(seed) & (2 ** 64 - 1)), _vp(out["cloud"]), _vp(out.get("points")), _vp(out.get("values")), _vp(out["centres"]),
-            _vp(out["bounds"]), _vp(counts) if T else None, _vp(out.get("face_idx")), _vp(out.get("flags")), _vp(out.get("sel")),
-            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = lib.shapemol_sdata_build(
+            ctx, B, ptr(vo), ptr(v), ptr(fo), ptr(f), P, T, LOSS_TYPES[loss_type], ptr(cloud_draws), ptr(query_draws),
+            C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(out["cloud"]), ptr(out.get("points")), ptr(out.get("values")), ptr(out["centres"]),
+            ptr(out["bounds"]), ptr(counts) if T else None, ptr(out.get("face_idx")), ptr(out.get("flags")), ptr(out.get("sel")),
+            stream_ptr(device))
     if T:
         out["counts"] = counts
     if rc == 2:
-        err = ValueError(ctx.lib.shapemol_last_error().decode())
+        err = ValueError(lib.shapemol_last_error().decode())
         err.counts = counts
         raise err
     _lib.check(rc, "shapemol_sdata_build")
@@ -179,16 +131,16 @@ class ShapeData:
     ``num_samples`` rows raises ValueError naming it (the reference's ``torch.stack`` fails there)."""
 
     def __init__(self, batch_data, config, *, device, seed=None, cloud_draws=None, query_draws=None):
-        shape_type = _get(config, "shape_type")
+        shape_type = get(config, "shape_type")
         if shape_type == "voxel":
             raise NotImplementedError("ShapeData: shape_type 'voxel' has no device implementation; the shipped models use 'point_cloud'")
         if shape_type != "point_cloud":
             raise ValueError(f"ShapeData: unknown shape_type {shape_type!r}")
-        n_samples = int(_get(config, "num_samples"))
+        n_samples = int(get(config, "num_samples"))
         if n_samples < 2:
             raise ValueError(f"ShapeData: num_samples must be >= 2, got {n_samples}")
         meshes = [d["mesh"] for d in batch_data]
-        out = build_batch(meshes, _get(config, "point_cloud_samples"), n_samples, _get(config, "loss_type"), device=device, seed=seed,
+        out = build_batch(meshes, get(config, "point_cloud_samples"), n_samples, get(config, "loss_type"), device=device, seed=seed,
                           cloud_draws=cloud_draws, query_draws=query_draws)
         self._store = {"points": out["points"], "values": out["values"], "point_cloud": out["cloud"], "mesh": meshes,
                        "centres": out["centres"], "bounds": out["bounds"], "counts": out["counts"]}

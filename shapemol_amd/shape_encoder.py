@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import hip_device, ptr, stream_ptr
 
 __all__ = ["VN_DGCNN_Encoder"]
 
@@ -48,6 +49,7 @@ class VN_DGCNN_Encoder(nn.Module):
         return np.concatenate([p.detach().cpu().numpy().astype(np.float32).reshape(-1) for p in parts])
 
     def _context(self, device):
+        device = hip_device(device)      # ('cuda' and 'cuda:<current>' are one context)
         key = (str(device),) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._ctx is not None and key == self._key:
             return self._ctx
@@ -55,9 +57,8 @@ class VN_DGCNN_Encoder(nn.Module):
         self._release()
         w = self._pack()
         ctx = C.c_void_p()
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        _lib.check(lib.shapemol_se_create(self.hidden_dim, self.latent_dim, self.layer_num, self.num_k, w.ctypes.data_as(C.c_void_p),
-                                          w.size, idx, C.byref(ctx)), "shapemol_se_create")
+        _lib.check(lib.shapemol_se_create(self.hidden_dim, self.latent_dim, self.layer_num, self.num_k, ptr(w), w.size, device.index,
+                                          C.byref(ctx)), "shapemol_se_create")
         self._ctx, self._key = ctx, key
         return ctx
 
@@ -75,7 +76,7 @@ class VN_DGCNN_Encoder(nn.Module):
     def max_points(self, device):
         """Largest N the library accepts on `device` (shapemol_se_max_points)."""
         with torch.cuda.device(device):
-            return int(_lib.load().shapemol_se_max_points(self._context(torch.device(device))))
+            return int(_lib.load().shapemol_se_max_points(self._context(device)))
 
     # ---- diagnostics (tests/test_gpu_shape_encoder.py) ----
     _DEBUG = {"idx": (0, np.int32), "h0": (1, np.float32), "hcat": (2, np.float32), "y": (3, np.float32), "xx": (4, np.float32),
@@ -83,7 +84,7 @@ class VN_DGCNN_Encoder(nn.Module):
 
     def debug_stop_after(self, device, n_blocks):
         """Following forwards return after block `n_blocks` (0: after conv_pos; -1: full encode again), leaving the output unset."""
-        _lib.check(_lib.load().shapemol_se_debug_stop_after(self._context(torch.device(device)), n_blocks), "shapemol_se_debug_stop_after")
+        _lib.check(_lib.load().shapemol_se_debug_stop_after(self._context(device), n_blocks), "shapemol_se_debug_stop_after")
 
     def debug_read(self, device, name, n_total):
         """Workspace buffer `name` of the last forward on `device` (n_total = B * N points of it) as a numpy array
@@ -93,7 +94,7 @@ class VN_DGCNN_Encoder(nn.Module):
         shape = {"idx": (n_total, self.num_k), "h0": (n_total, C_, 3), "hcat": (n_total, L, C_, 3), "y": (n_total, 4 * C_, 3), "xx": (n_total,),
                  "pd": (n_total, LAT + 1, 3)}[name]
         a = np.empty(shape, dt)
-        _lib.check(_lib.load().shapemol_se_debug_read(self._context(torch.device(device)), code, a.ctypes.data_as(C.c_void_p), a.nbytes),
+        _lib.check(_lib.load().shapemol_se_debug_read(self._context(device), code, ptr(a), a.nbytes),
                    "shapemol_se_debug_read")
         return a
 
@@ -111,7 +112,6 @@ class VN_DGCNN_Encoder(nn.Module):
         dev = x.device
         out = torch.empty((b, self.latent_dim, 3), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.load().shapemol_se_encode(self._context(dev), C.c_void_p(x.data_ptr()), b, n, C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = _lib.load().shapemol_se_encode(self._context(dev), ptr(x), b, n, ptr(out), stream_ptr(dev))
         _lib.check(rc, "shapemol_se_encode")
         return out

@@ -28,20 +28,16 @@ Reference semantics followed: ``models/molopt_score_model.py:286-320`` (forward)
 train mode, running statistics updated with momentum 0.1 as ``nn.BatchNorm1d`` does), ``models/common.py:19-28,39-45``.
 There is no CPU path here either: tensors must live on a HIP device.
 """
-import ctypes as C
 import math
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._native import ptr as _p, stream_ptr      # (ptr names the CSR offsets here)
 from .spec import RBF_CENTRES
 
 VN_EPS = 1e-6
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class HipMLP(torch.autograd.Function):
@@ -63,7 +59,7 @@ class HipMLP(torch.autograd.Function):
             with torch.cuda.device(x.device):
                 rc = _lib.load().shapemol_mlp_forward(_p(x), rows, k_in, hidden, n_out, _p(ws[0]), _p(ws[1]), _p(ws[2]), _p(ws[3]),
                                                       _p(ws[4]), _p(ws[5]), _p(y), _p(xhat), _p(rstd), _p(act),
-                                                      C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+                                                      stream_ptr(x.device))
             _lib.check(rc, "shapemol_mlp_forward")
         ctx.save_for_backward(x, ws[0], ws[2], ws[3], ws[4], xhat, rstd, act)
         ctx.dims = (rows, k_in, hidden, n_out)
@@ -84,7 +80,7 @@ class HipMLP(torch.autograd.Function):
             with torch.cuda.device(dev):
                 rc = lib.shapemol_mlp_backward(_p(x), _p(dy), rows, k_in, hidden, n_out, _p(w1), _p(gamma), _p(beta), _p(w2), _p(xhat),
                                                _p(rstd), _p(act), _p(dx) if ctx.needs_input_grad[0] else None, _p(dw1), _p(db1), _p(dg), _p(dbe),
-                                               _p(dw2), _p(db2), _p(work), n_work, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                               _p(dw2), _p(db2), _p(work), n_work, stream_ptr(dev))
             _lib.check(rc, "shapemol_mlp_backward")
         return (dx if ctx.needs_input_grad[0] else None), dw1, db1, dg, dbe, dw2, db2
 
@@ -123,7 +119,7 @@ class HipEdgeMLP(torch.autograd.Function):
             with torch.cuda.device(r.device):
                 rc = _lib.load().shapemol_edge_mlp_forward(_p(r), _p(h), _p(s), _p(graph.dst), _p(graph.src), E, n, kr, kn, ks, hidden, n_out,
                                                            *[_p(t) for t in ws], _p(y), _p(xhat), _p(rstd), _p(act), _p(pd), _p(ps),
-                                                           C.c_void_p(torch.cuda.current_stream(r.device).cuda_stream))
+                                                           stream_ptr(r.device))
             _lib.check(rc, "shapemol_edge_mlp_forward")
         ctx.save_for_backward(r, h, s, ws[0], ws[2], ws[3], ws[4], xhat, rstd, act)
         ctx.graph, ctx.dims = graph, (E, n, kr, kn, ks, hidden, n_out)
@@ -145,7 +141,7 @@ class HipEdgeMLP(torch.autograd.Function):
             with torch.cuda.device(dev):
                 rc = lib.shapemol_edge_mlp_backward(_p(r), _p(h), _p(s), _p(g.ptr), _p(g.perm_src), _p(g.ptr_src), _p(dy), E, n, kr, kn, ks, hidden, n_out,
                                                     _p(w1), _p(gamma), _p(beta), _p(w2), _p(xhat), _p(rstd), _p(act), _p(dr), _p(dh), _p(ds), _p(dw1), _p(db1),
-                                                    _p(dg), _p(dbe), _p(dw2), _p(db2), _p(work), n_work, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                                    _p(dg), _p(dbe), _p(dw2), _p(db2), _p(work), n_work, stream_ptr(dev))
             _lib.check(rc, "shapemol_edge_mlp_backward")
         return dr, dh, ds, None, dw1, db1, dg, dbe, dw2, db2
 
@@ -171,7 +167,7 @@ class HipSegAttention(torch.autograd.Function):
         if n > 0 and k.shape[0] > 0:
             with torch.cuda.device(q.device):
                 rc = _lib.load().shapemol_seg_attention_forward(_p(q), _p(k), _p(vals), _p(ptr), n, heads, dh, width, _p(out),
-                                                                C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
+                                                                stream_ptr(q.device))
             _lib.check(rc, "shapemol_seg_attention_forward")
         ctx.save_for_backward(q, k, vals, ptr)
         ctx.dims = (n, heads, dh, width)
@@ -187,7 +183,7 @@ class HipSegAttention(torch.autograd.Function):
             with torch.cuda.device(q.device):
                 rc = _lib.load().shapemol_seg_attention_backward(_p(q), _p(k), _p(vals), _p(ptr), _p(dout), n, heads, dh, width,
                                                                  _p(dq), _p(dk), _p(dvals),
-                                                                 C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
+                                                                 stream_ptr(q.device))
             _lib.check(rc, "shapemol_seg_attention_backward")
         return dq, dk, dvals, None, None
 
@@ -212,7 +208,7 @@ class HipVN(torch.autograd.Function):
         with torch.cuda.device(x.device):
             rc = _lib.load().shapemol_vn_forward(_p(x), _p(o3), _p(shape), _p(batch), n, rows_o, rows_s, ch, *[_p(t) for t in ws], _p(run_mean), _p(run_var),
                                                  int(bool(training)), _p(out), _p(pf), _p(dr), _p(stats), _p(nrm),
-                                                 C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+                                                 stream_ptr(x.device))
         _lib.check(rc, "shapemol_vn_forward")
         if training:      # the kernel wrote the running estimates through raw pointers: bump their version counters, so that whoever
             run_mean.add_(0); run_var.add_(0)      # keys a cache on (data_ptr, _version) -- the validation context of the model -- sees the update
@@ -234,7 +230,7 @@ class HipVN(torch.autograd.Function):
         with torch.cuda.device(dev):
             rc = lib.shapemol_vn_backward(_p(x), _p(o3), _p(shape), _p(batch), n, rows_o, rows_s, ch, _p(wf), _p(wd), _p(bn_w), _p(bn_b), _p(pf), _p(dr),
                                           _p(stats), training, _p(gout), _p(dx), _p(do3), _p(dwf), _p(dwd), _p(dg), _p(db), _p(work), n_work,
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                          stream_ptr(dev))
         _lib.check(rc, "shapemol_vn_backward")
         return dx, do3, None, None, dwf, dwd, dg, db, None, None, None
 
