@@ -22,11 +22,13 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sm_pack.h"
 #include "sm_devmem.h"
 #include "sm_host.h"
+#include "sm_launch.h"
 
 namespace {
 
@@ -88,7 +90,6 @@ struct shapemol_ctx {
     float *pre_tab = nullptr;   // [T][C][4H] per-node halves of layer 0's edge MLPs, without the per-molecule term
     int64_t *tab_v = nullptr; int *tab_mol_of = nullptr, *tab_t_mol = nullptr, *tab_flag = nullptr; DevList mem_tab;
     int tab_key = 0;            // node precision mode the tables were built in (prologue_tab_key), 0 = not built
-    int prologue_tab = 1;       // 1: the per-step node prologue gathers from the tables; 0: the per-atom MLP kernel
     DevModel dm;
     // workspace
     int64_t capN = 0, capB = 0;
@@ -114,36 +115,12 @@ struct shapemol_ctx {
     // last evaluation (debug_read)
     int64_t lastN = 0, lastB = 0;
     const float *last_h = nullptr, *last_x = nullptr;
-    // options
-    int stop_layer = -1, edge_threads = 0 /* 0 = chosen per launch */, lin_waves = 16, edge_bf16 = 2, lin_bf16 = 1, chain_bf16 = 1, vn_fuse = 2;
-    int vn_fold = 1;            // coordinate update of layer l in the prologue of the x2h kernel of layer l + 1 (needs max_mol_atoms)
-    int max_mol_atoms = 0;      // largest molecule of the batches to come (option; 0 = unknown: no fold)
-    int stream_whole_rounds = 0;   // streaming edge kernels: 1 = tiles per workgroup rounded up to whole rounds.  0 (default): as many workgroups as
-                                   // the tiles give; the last round of an odd chunk has one tile (B = 256: 252 workgroups of 11 tiles instead of
-                                   // 231 of 12 -- x2h 26.7 -> 25.6 us, h2x 24.7 -> 23.9; B = 1024, 43 instead of 44: unchanged)
-    int lin_fuse = 0;           // 1: per-node products of the next attentions inside node_chain16_kernel instead of a node_linear
+    lg::Options opt;            // the options that select kernels and shape launches (sm_launch.h)
     int bn_eval = 0;            // 1: evaluation-mode batch-norm (running statistics, shapemol_set_bn_running) instead of the batch's
     DevList mem_bn;             // the two below
     float *bn_run = nullptr;    // [2][L][heads] running mean | running variance (device)
     double *bn_eval_acc = nullptr;   // [L][kBnReplicas][2][heads] sums that reproduce them for the current batch size
-    int ddpm_fold = 1;          // 1: the last layer's coordinate update inside the DDPM kernel (chains without guidance)
-    DdpmFold ddpm_vf{};         // ... handed from run_score to run_ddpm
-    int graph_fuse = 1;         // 1: kNN graph + edge weights in one launch (graph_kernel) when max_mol_atoms <= kGraphCap is known
-    int x2h_chain = 1;          // 1: x2h attention and the node stage of a layer in one launch (x2h_chain16_kernel) when every wave has one job
-                                // launch (measured: 28.5 us against 15.3 + 11.1 us, eight dependent weight blocks per wave)
-    int node_levels = 1;        // 1: the exact-mode node stage as node_out6_kernel (h' only) + node_after6_kernel (follow-up MLPs and per-node products
-                                // side by side); 0: node_chain6_kernel + node_linear6_kernel
-    int x2h_out_fuse = 1;       // 1: h' inside the x2h streaming kernel's tail (stream_node_out_epilogue) instead of a node_out6_kernel launch, while a
-                                // workgroup owns at most kX2hOutFuseAtoms (96) atoms; 2: whatever it owns (measurements); 0: node_out6_kernel
-    int stream_chunk_opt = 0;   // option "stream_chunk": tiles per workgroup of the streaming kernels (tests); 0 = automatic
-    int after_order = 2;        // node_after6_kernel's grid: 0 follow-up jobs first, 1 interleaved with the linear jobs, 2 linear jobs first
-    int after_waves = 16;       // ... waves of its linear jobs (the workgroup has max(H / 16, after_waves) waves)
-    int after_lin_wgs = 0;      // ... workgroups aimed at for its linear jobs (0 = automatic)
-    int node_f16 = 0;           // 1: node kernels on two-piece f16 operands (sm_node16.h) instead of exactly split bf16 (sm_node.h) [default 0]
-    int feat_f16 = 0;           // 1: "f16 features" -- matrix products on the leading f16 piece only (one product per term instead of
-                                // three; accumulation, LayerNorm, softmax, coordinates fp32).  Reduced precision, NOT a parity mode
-    int edge_tiles = -1;        // f16 edge kernels when the waves have several jobs: 0 = sliced launches of the one-job kernel,
-                                // 1 = one looping launch (eight waves per workgroup, next job's rows prefetched), -1 = automatic (= 1) [default]
+    DdpmFold ddpm_vf{};         // the last layer's coordinate update inside the DDPM kernel (option ddpm_fold), handed from run_score to run_ddpm
     float hid_max = 0.f;        // bound of the edge MLPs' hidden activations (LayerNorm outputs): must fit fp16 for edge_bf16 = 3
     int num_cu = 256;
     // shape guidance of the predicted x0: the installed point-cloud set and mesh set (the mesh takes precedence when both are set),
@@ -311,26 +288,13 @@ int ensure_workspace(shapemol_ctx *c, int64_t N, int64_t B) {
 
 namespace {
 
-static int stream_chunk(const shapemol_ctx *c, int n_atoms);
 constexpr int kVnFoldBytes = kVnFoldCap * 3 * 4 + 32 * 8;      // LDS of the folded coordinate update: table + batch sums
 
-// can the coordinate update of a layer be folded into the next x2h kernel?  f16 one-job (or sliced) edge kernels, the
-// VN-linear + statistics epilogue in h2x, and every workgroup's molecule span inside the LDS table
-bool vn_fold_ok(const shapemol_ctx *c, int n_atoms) {
-    if (!c->vn_fold || (c->edge_bf16 != 3 && c->edge_bf16 != 2) || c->KP > 16 || c->vn_fuse != 2 || c->max_mol_atoms <= 0) return false;
-    if (c->edge_bf16 == 2) return stream_chunk(c, n_atoms) * (16 / c->KP) + 2 * (c->max_mol_atoms - 1) <= kVnFoldCap;      // (KP <= 16 here)
-    const int apj = 16 / c->KP, njobs = (n_atoms + apj - 1) / apj;
-    const int waves = std::max(4, std::min(12, (njobs + c->num_cu - 1) / c->num_cu));
-    const int grid = std::max(1, std::min(c->num_cu, (njobs + waves - 1) / waves));
-    if (c->edge_threads > 0) return false;                                 // wave-count sweeps: keep the plain path
-    const int tiles_mode = c->edge_tiles >= 0 ? c->edge_tiles : 1;        // (as launch_edge16)
-    if (njobs > grid * waves && tiles_mode == 1) {                        // looping launches: a workgroup owns `chunk` consecutive jobs
-        const int lwv = 8;
-        const int lgrid = std::max(1, std::min(c->num_cu, (njobs + lwv - 1) / lwv)), chunk = (njobs + lgrid - 1) / lgrid;
-        return chunk * apj + 2 * (c->max_mol_atoms - 1) <= kVnFoldCap;
-    }
-    const int waves_max = std::max(waves, c->cfg.hidden_dim / 16);          // the fused x2h + node-stage launch never uses fewer
-    return waves_max * apj + 2 * (c->max_mol_atoms - 1) <= kVnFoldCap;
+// What sm_launch.h computes every launch geometry and step form from: the options, the kernel headers' constants, the sizes
+template <int H>
+lg::In launch_in(const shapemol_ctx *c, int n_atoms) {
+    constexpr bool chain16_fits = Chain16Lds<H>::BYTES <= 2 * EdgeImage16<H, H / 16>::TOTAL * 4;
+    return {c->opt, {kVnFoldCap, kStreamTPR, CHAIN_COLS, kGraphCap, kLin6Chunk, chain16_fits}, c->KP, c->num_cu, H, n_atoms};
 }
 
 // Largest dynamic LDS of every kernel that needs more than the default: one size per kernel family
@@ -378,40 +342,28 @@ int set_edge_attr(int KP) {
 #define DISPATCH_KP(name, KERNEL, TAIL, ...)                                                        \
     do { if (KP > 16) LAUNCH_KP(name, 32, KERNEL, TAIL, __VA_ARGS__); else DISPATCH_KP16(name, KERNEL, TAIL, __VA_ARGS__); } while (0)
 #define DISPATCH_KP_F16(DISPATCH, name, KERNEL, TAIL, ...)                                          \
-    do { if (c->feat_f16) DISPATCH(name, KERNEL, (SM_ARGS TAIL, true), __VA_ARGS__); else DISPATCH(name, KERNEL, TAIL, __VA_ARGS__); } while (0)
-
-// Waves per workgroup of the single-tile edge kernels: one job per wave while the jobs fit (the launch then lasts
-// one job latency), on as many CUs as possible: ceil(jobs / CUs) waves, at least 4 and at most 12 (the 168-VGPR budget).
-static int edge_waves_for(const shapemol_ctx *c, int njobs) {
-    if (c->edge_threads > 0) return c->edge_threads / 64;
-    return std::max(4, std::min(12, (njobs + c->num_cu - 1) / c->num_cu));
-}
+    do { if (c->opt.feat_f16) DISPATCH(name, KERNEL, (SM_ARGS TAIL, true), __VA_ARGS__); else DISPATCH(name, KERNEL, TAIL, __VA_ARGS__); } while (0)
 
 template <int H, bool H2X>
 int launch_edge(shapemol_ctx *c, hipStream_t s, const EdgeArgs &a) {     // fp32-MFMA edge kernel (option edge_bf16 = 0; k > 16)
     const int KP = c->KP;
-    const int apj = KP >= 16 ? 1 : 16 / KP;
-    const int njobs = (a.n_atoms + apj - 1) / apj;
-    const int waves = c->edge_threads > 0 ? c->edge_threads / 64 : 12;
-    const int grid = std::max(1, std::min(c->num_cu, njobs));
+    const lg::EdgeGeom g = lg::edge_fp32_geom(launch_in<H>(c, a.n_atoms));
     const size_t shm = EdgeBlob<H, H2X>::TOTAL * sizeof(float);
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
     if (KP > 16) return fail("k > 16 runs on the two-piece f16 edge kernels only (option edge_bf16 = 3)");
-    DISPATCH_KP16(nm, edge_attention_kernel, (, H2X), dim3(grid), dim3(waves * 64), shm, s, a);
+    DISPATCH_KP16(nm, edge_attention_kernel, (, H2X), dim3(g.grid), dim3(g.waves * 64), shm, s, a);
     return 0;
 }
 
 template <int H, bool H2X>
 int launch_fused(shapemol_ctx *c, hipStream_t s, const EdgeFusedArgs &a) {
-    const int KP = c->KP, apj = 16 / KP;
-    const int njobs = (a.n_atoms + apj - 1) / apj, waves = edge_waves_for(c, njobs);
-    const int grid = std::max(1, std::min(c->num_cu, (njobs + waves - 1) / waves));
+    const int KP = c->KP;
+    const lg::EdgeGeom g = lg::edge_phase_geom(launch_in<H>(c, a.n_atoms));
     const size_t shm = (EdgePhaseImage<H, H / 16>::TOTAL + (H2X ? EdgePhaseImage<H, 1>::TOTAL : 0)) * sizeof(float)
-                       + (H2X ? (size_t)vn_red_doubles(waves, H / 8) * 8 + (size_t)waves * apj * 48 * 4 : 0);   // + reduction scratch and attention rows of the fused coordinate update
+                       + (H2X ? (size_t)vn_red_doubles(g.waves, H / 8) * 8 + (size_t)g.waves * g.apj * 48 * 4 : 0);   // + reduction scratch and attention rows of the fused coordinate update
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
-    const bool one = njobs <= grid * waves;      // every wave has at most one job: straight-line instantiation
-    if (one) DISPATCH_KP16(nm, edge_fused_kernel, (, H2X, true), dim3(grid), dim3(waves * 64), shm, s, a);
-    else DISPATCH_KP16(nm, edge_fused_kernel, (, H2X, false), dim3(grid), dim3(waves * 64), shm, s, a);
+    if (g.form == lg::Form::One) DISPATCH_KP16(nm, edge_fused_kernel, (, H2X, true), dim3(g.grid), dim3(g.waves * 64), shm, s, a);      // straight-line instantiation
+    else DISPATCH_KP16(nm, edge_fused_kernel, (, H2X, false), dim3(g.grid), dim3(g.waves * 64), shm, s, a);
     return 0;
 }
 
@@ -419,87 +371,38 @@ template <int H, bool H2X>
 int launch_edge16(shapemol_ctx *c, hipStream_t s, const Edge16Args &a) {
     const int KP = c->KP;
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
-    const int tiles_mode = c->edge_tiles >= 0 ? c->edge_tiles : 1;      // -1 = automatic: looping launches
-    {
-        // a job = one 16-slot tile: 16 / KP centre atoms (k <= 16) or half an atom (k > 16: two tiles per atom, merged afterwards)
-        const int apj = KP >= 16 ? 1 : 16 / KP;
-        const int njobs = KP > 16 ? 2 * a.n_atoms : (a.n_atoms + apj - 1) / apj, waves = edge_waves_for(c, njobs);
-        const int grid = std::max(1, std::min(c->num_cu, (njobs + waves - 1) / waves));
-        const bool one = njobs <= grid * waves;      // every wave has at most one job: straight-line instantiation
-        auto shm_for = [&](int w) {
-            return (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, (H2X ? 1 : H / 16)>::TOTAL) * sizeof(float)
-                   + (H2X ? (size_t)vn_red_doubles(w, H / 8) * 8 + (size_t)w * apj * 48 * 4 : (a.vf.enable ? kVnFoldBytes : 0));
-        };
-        if (!one && tiles_mode == 1) {
-            // looping launch: eight waves per workgroup (two per SIMD, 256 VGPRs: a job's state plus the next job's gathered rows
-            // without spilling), every workgroup owns `chunk` consecutive jobs
-            const int lw = c->edge_threads > 0 ? std::min(8, c->edge_threads / 64) : 8;
-            const int lgrid = std::max(1, std::min(c->num_cu, (njobs + lw - 1) / lw));
-            Edge16Args b = a;
-            b.job_base = 0; b.job_end = njobs; b.nwave = lw; b.chunk = (njobs + lgrid - 1) / lgrid;
-            const int g2 = (njobs + b.chunk - 1) / b.chunk;
-            DISPATCH_KP_F16(DISPATCH_KP, nm, edge16_loop_kernel, (, H2X), dim3(g2), dim3(lw * 64), shm_for(lw), s, b);
-            return 0;
-        }
-        // one launch of the straight-line instantiation, or (larger batches, edge_tiles = 0) several, each over a slice of
-        // grid x waves jobs (no spills, full overlap inside a launch; the image fill is paid per slice)
-        // ... of equal size: the jobs are spread evenly over the fewest launches that can hold them (a last slice that
-        // is nearly empty costs a full launch floor)
-        int ws = waves, gs = grid;
-        if (!one && c->edge_threads == 0) {      // (an explicit edge_waves option keeps its wave count)
-            const int nsl = (njobs + c->num_cu * 12 - 1) / (c->num_cu * 12), target = (njobs + nsl - 1) / nsl;
-            ws = std::max(4, std::min(12, (target + c->num_cu - 1) / c->num_cu));
-            gs = std::max(1, std::min(c->num_cu, (target + ws - 1) / ws));
-        }
-        const int per = gs * ws;
-        for (int base = 0; base < njobs; base += per) {
-            Edge16Args b = a;
-            b.job_base = base; b.job_end = std::min(njobs, base + per); b.nwave = ws;
-            const int g2 = std::max(1, std::min(gs, (b.job_end - base + ws - 1) / ws));
-            DISPATCH_KP_F16(DISPATCH_KP, nm, edge16_kernel, (, H2X), dim3(g2), dim3(ws * 64), shm_for(ws), s, b);
-        }
+    const lg::EdgeGeom g = lg::edge16_geom(launch_in<H>(c, a.n_atoms));
+    const size_t shm = (EdgeImage16<H, H / 16>::TOTAL + EdgeImage16<H, (H2X ? 1 : H / 16)>::TOTAL) * sizeof(float)
+                       + (H2X ? (size_t)vn_red_doubles(g.waves, H / 8) * 8 + (size_t)g.waves * g.apj * 48 * 4 : (a.vf.enable ? kVnFoldBytes : 0));
+    Edge16Args b = a;
+    b.nwave = g.waves;
+    if (g.form == lg::Form::Loop) {      // every workgroup owns `chunk` consecutive jobs
+        b.job_base = 0; b.job_end = g.jobs; b.chunk = g.chunk;
+        DISPATCH_KP_F16(DISPATCH_KP, nm, edge16_loop_kernel, (, H2X), dim3(g.grid), dim3(g.waves * 64), shm, s, b);
+        return 0;
+    }
+    // one launch of the straight-line instantiation, or (larger batches, edge_tiles = 0) several, each over a slice of the jobs
+    for (int base = 0; base < g.jobs; base += g.slice) {
+        b.job_base = base; b.job_end = std::min(g.jobs, base + g.slice);
+        DISPATCH_KP_F16(DISPATCH_KP, nm, edge16_kernel, (, H2X), dim3(lg::slice_grid(g, base)), dim3(g.waves * 64), shm, s, b);
     }
     return 0;
 }
 
-// streaming edge kernels (sm_edge_stream.h; option edge_bf16 = 2): consecutive tiles per workgroup -- every CU one workgroup;
-// half-atom tiles (k > 16) in pairs
-static int stream_jobs(const shapemol_ctx *c, int n_atoms) {      // a job = one 16-slot tile: 16 / KP atoms, or half an atom (k > 16)
-    return c->KP > 16 ? 2 * n_atoms : (n_atoms + 16 / c->KP - 1) / (16 / c->KP);
-}
-static int stream_chunk(const shapemol_ctx *c, int n_atoms) {
-    const int njobs = stream_jobs(c, n_atoms);
-    if (c->stream_chunk_opt > 0) return c->KP <= 16 ? c->stream_chunk_opt : (c->stream_chunk_opt + kStreamTPR - 1) / kStreamTPR * kStreamTPR;
-    const int per_cu = (njobs + c->num_cu - 1) / c->num_cu;
-    if (!c->stream_whole_rounds && c->KP <= 16) return std::max(1, per_cu);
-    return std::max(kStreamTPR, (per_cu + kStreamTPR - 1) / kStreamTPR * kStreamTPR);
-}
-
-// h' in the x2h kernel's tail (sm_edge_stream.h: stream_node_out_epilogue) instead of a node_out6_kernel launch?  Only where the
-// two-level node form follows a streaming x2h kernel of whole-atom tiles.  The tail walks a workgroup's atoms 32 at a time and
-// streams the output MLP's weights again for every pass; it won at every size measured, up to the 88 atoms (three passes) of
-// B = 1024, so the boundary is three passes: beyond that nothing is measured and node_out6_kernel stays
-constexpr int kX2hOutFuseAtoms = 3 * CHAIN_COLS * 16;
-static bool x2h_out_fuse_ok(const shapemol_ctx *c, int n_atoms, bool levels) {
-    if (!c->x2h_out_fuse || c->edge_bf16 != 2 || !levels || c->KP > 16) return false;
-    return c->x2h_out_fuse == 2 || stream_chunk(c, n_atoms) * (16 / c->KP) <= kX2hOutFuseAtoms;
-}
-
 template <int H, bool H2X>
-int launch_stream(shapemol_ctx *c, hipStream_t s, EdgeStreamArgs a) {
-    const int KP = c->KP, njobs = stream_jobs(c, a.n_atoms);
-    a.chunk = stream_chunk(c, a.n_atoms);
-    const int grid = (njobs + a.chunk - 1) / a.chunk;
+int launch_stream(shapemol_ctx *c, hipStream_t s, EdgeStreamArgs a) {      // streaming edge kernels (sm_edge_stream.h; option edge_bf16 = 2)
+    const int KP = c->KP;
+    const lg::StreamGeom g = lg::stream_geom(launch_in<H>(c, a.n_atoms));
+    a.chunk = g.chunk;
     using M = StreamMap<H, H2X>;
     constexpr int NWAVE = H / 16 + kStreamProducers;
     const size_t shm = (size_t)M::O_TAIL * 4 + (H2X ? (size_t)NWAVE * 64 * 2 * 8 : (a.vf.enable ? (size_t)kVnFoldBytes : 0));
     const char *nm = H2X ? "edge_h2x" : "edge_x2h";
     if (!H2X) {
-        const int64_t apw = KP <= 16 ? (int64_t)a.chunk * (16 / KP) : 0;
-        const int64_t rec[4] = {a.no.h_out != nullptr, apw, (apw + 15) / 16, (int64_t)shm};
+        const int64_t rec[4] = {a.no.h_out != nullptr, g.atoms_per_wg, (g.atoms_per_wg + 15) / 16, (int64_t)shm};
         std::copy(rec, rec + 4, c->x2h_out_rec);
     }
-    DISPATCH_KP(nm, edge_stream_kernel, (, H2X), dim3(grid), dim3(NWAVE * 64), shm, s, a);
+    DISPATCH_KP(nm, edge_stream_kernel, (, H2X), dim3(g.grid), dim3(NWAVE * 64), shm, s, a);
     return 0;
 }
 
@@ -512,28 +415,14 @@ int launch_combine32(shapemol_ctx *c, hipStream_t s, float *out, int n_atoms) {
     return 0;
 }
 
-// x2h attention + node stage in one launch: possible when the f16 kernels are in use, every wave gets one job in a single
-// launch, and a workgroup has at least H / 16 waves (the node stage's output blocks)
 template <int H>
-bool x2h_chain_ok(const shapemol_ctx *c, int n_atoms) {
-    if (!c->x2h_chain || c->edge_bf16 != 3 || c->KP > 16 || !c->chain_bf16 || !c->node_f16 || c->lin_fuse || c->edge_threads > 0) return false;
-    const int apj = 16 / c->KP, njobs = (n_atoms + apj - 1) / apj;
-    const int waves = std::max(H / 16, edge_waves_for(c, njobs));
-    const int grid = std::max(1, std::min(c->num_cu, (njobs + waves - 1) / waves));
-    // one launch only: in slices (larger batches) the fused kernel loses to the separate ones, whose node stage then has
-    // enough atoms per launch to run at its throughput (B = 1024: 523 against 538 molecules/s)
-    return waves <= 12 && waves * apj <= CHAIN_COLS * 16 && njobs <= grid * waves && Chain16Lds<H>::BYTES <= 2 * EdgeImage16<H, H / 16>::TOTAL * 4;
-}
-
-template <int H>
-int launch_x2h_chain(shapemol_ctx *c, hipStream_t s, const Edge16Args &a, const NodeChainArgs &na) {
-    const int KP = c->KP, apj = 16 / KP;
-    const int njobs = (a.n_atoms + apj - 1) / apj, waves = std::max(H / 16, edge_waves_for(c, njobs));
-    const int grid = std::max(1, std::min(c->num_cu, (njobs + waves - 1) / waves));
+int launch_x2h_chain(shapemol_ctx *c, hipStream_t s, const Edge16Args &a, const NodeChainArgs &na) {      // x2h attention + node stage in one launch
+    const int KP = c->KP;
+    const lg::EdgeGeom g = lg::x2h_chain_geom(launch_in<H>(c, a.n_atoms));
     const size_t shm = 2 * EdgeImage16<H, H / 16>::TOTAL * sizeof(float) + (a.vf.enable ? kVnFoldBytes : 0);
     Edge16Args b = a;
-    b.job_base = 0; b.job_end = njobs; b.nwave = waves;
-    DISPATCH_KP_F16(DISPATCH_KP16, "edge_x2h_chain", x2h_chain16_kernel, (), dim3(grid), dim3(waves * 64), shm, s, b, na, c->status + ST_RANGE);
+    b.job_base = 0; b.job_end = g.jobs; b.nwave = g.waves;
+    DISPATCH_KP_F16(DISPATCH_KP16, "edge_x2h_chain", x2h_chain16_kernel, (), dim3(g.grid), dim3(g.waves * 64), shm, s, b, na, c->status + ST_RANGE);
     return 0;
 }
 
@@ -552,62 +441,46 @@ int launch_mlp2(shapemol_ctx *c, hipStream_t s, const char *name, const DevMlpIm
 template <int H>
 int launch_linear(shapemol_ctx *c, hipStream_t s, const char *name, const float *in, const float *wimg, const float *wimg6, const float *wimg16, const float *add_mol,
                   int ld_add, float *out, int ld_out, int n_out_tiles, int n_atoms, unsigned long long *stamps) {
-    const int nwave = c->lin_waves;
-    const int n_ct = (n_atoms + 15) / 16, ogroups = (n_out_tiles + nwave - 1) / nwave;
-    const int want_groups = std::max(1, c->num_cu / ogroups);
-    const int tpg = std::max(1, (n_ct + want_groups - 1) / want_groups);
-    const int agroups = (n_ct + tpg - 1) / tpg;
-    const bool f16 = c->lin_bf16 && c->node_f16;
-    NodeLinArgs a{in, f16 ? wimg16 : (c->lin_bf16 ? wimg6 : wimg), add_mol, c->mol_of, out, n_atoms, n_out_tiles, tpg, ld_add, ld_out, stamps, nwave};
+    const lg::LinGeom g = lg::linear_geom(launch_in<H>(c, n_atoms), n_out_tiles);
+    const dim3 grid(g.ogroups * g.agroups), block(g.waves * 64);
+    const bool f16 = c->opt.lin_bf16 && c->opt.node_f16;
+    NodeLinArgs a{in, f16 ? wimg16 : (c->opt.lin_bf16 ? wimg6 : wimg), add_mol, c->mol_of, out, n_atoms, n_out_tiles, g.tpg, ld_add, ld_out, stamps, g.waves};
     if (f16) {
-        const size_t shm = (size_t)std::min(tpg, kLin16Chunk) * 2 * H * 32;
-        if (c->feat_f16) LAUNCH(name, SMK((node_linear16_kernel<H, true>), dim3(ogroups * agroups), dim3(nwave * 64), shm, s, a, c->status + ST_RANGE));
-        else LAUNCH(name, SMK(node_linear16_kernel<H>, dim3(ogroups * agroups), dim3(nwave * 64), shm, s, a, c->status + ST_RANGE));
-    } else if (c->lin_bf16) {
-        const size_t shm = (size_t)std::min(tpg, kLin6Chunk) * 3 * H * 32;
-        LAUNCH(name, SMK(node_linear6_kernel<H>, dim3(ogroups * agroups), dim3(nwave * 64), shm, s, a));
+        const size_t shm = (size_t)std::min(g.tpg, kLin16Chunk) * 2 * H * 32;
+        if (c->opt.feat_f16) LAUNCH(name, SMK((node_linear16_kernel<H, true>), grid, block, shm, s, a, c->status + ST_RANGE));
+        else LAUNCH(name, SMK(node_linear16_kernel<H>, grid, block, shm, s, a, c->status + ST_RANGE));
+    } else if (c->opt.lin_bf16) {
+        const size_t shm = (size_t)std::min(g.tpg, kLin6Chunk) * 3 * H * 32;
+        LAUNCH(name, SMK(node_linear6_kernel<H>, grid, block, shm, s, a));
     } else {
-        LAUNCH(name, SMK(node_linear_kernel<H>, dim3(ogroups * agroups), dim3(nwave * 64), 0, s, a));
+        LAUNCH(name, SMK(node_linear_kernel<H>, grid, block, 0, s, a));
     }
     return 0;
 }
 
 // The exact-mode node stage in two dependency levels: h' (node_out6_kernel), then the follow-up MLPs and the per-node products of h'
 // in one launch (node_after6_kernel).  na as for node_chain6_kernel; the products as launch_linear would compute them.
-constexpr int kAfterChunk = 6;      // linear staging chunk of 8-wave workgroups: 6 * 3 * H * 32 = 72 KB at H = 128, two workgroups per CU
 template <int H>
 int launch_node_levels(shapemol_ctx *c, hipStream_t s, const NodeChainArgs &na, const float *lin_img6, const float *add_mol, int ld_add,
                        float *out, int ld_out, int lin_tiles, bool out_done) {
-    constexpr int NT = H / 16;
-    const int n = na.n_atoms, n_ct = (n + 15) / 16, n_pairs = (n_ct + CHAIN_COLS - 1) / CHAIN_COLS;
-    if (!out_done) LAUNCH("node_chain", SMK(node_out6_kernel<H>, dim3(n_pairs), dim3(H * 4), Out6Lds<H>::BYTES, s, na));      // (else: the x2h kernel's tail wrote h')
-    const int lw = c->after_waves, bw = std::max(lw, NT);
-    const int per_cu = bw <= 8 ? 2 : 1;                   // workgroups that share a CU (128 VGPRs per lane; LDS: kAfterChunk)
-    const int slots = c->num_cu * per_cu;
+    const int n = na.n_atoms;
+    const lg::NodeLevelsGeom g = lg::node_levels_geom(launch_in<H>(c, n), na.n_follow, lin_tiles);
+    if (!out_done) LAUNCH("node_chain", SMK(node_out6_kernel<H>, dim3(g.n_pairs), dim3(H * 4), Out6Lds<H>::BYTES, s, na));      // (else: the x2h kernel's tail wrote h')
     NodeAfterArgs a{};
     a.f[0] = na.f[0]; a.f[1] = na.f[1];
-    a.n_pairs = n_pairs; a.n_fjobs = na.n_follow * n_pairs; a.order = c->after_order;
-    int tpg = 1;
-    if (lin_tiles > 0) {      // the linear jobs fill the workgroup slots that the follow-up jobs leave, at least half of all
-        const int ogroups = (lin_tiles + lw - 1) / lw;
-        const int lin_wgs = c->after_lin_wgs > 0 ? c->after_lin_wgs : std::max(slots - a.n_fjobs, slots / 2);
-        const int want_groups = std::max(1, lin_wgs / ogroups);
-        tpg = std::max(1, (n_ct + want_groups - 1) / want_groups);
-        a.n_ljobs = ogroups * ((n_ct + tpg - 1) / tpg);
-    }
-    a.lin_chunk = std::min(tpg, per_cu == 2 ? kAfterChunk : kLin6Chunk);
-    a.lin = NodeLinArgs{na.h_out, lin_img6, add_mol, c->mol_of, out, n, lin_tiles, tpg, ld_add, ld_out, nullptr, lw};
+    a.n_pairs = g.n_pairs; a.n_fjobs = g.n_fjobs; a.n_ljobs = g.n_ljobs; a.order = c->opt.after_order; a.lin_chunk = g.lin_chunk;
+    a.lin = NodeLinArgs{na.h_out, lin_img6, add_mol, c->mol_of, out, n, lin_tiles, g.tpg, ld_add, ld_out, nullptr, g.lw};
     const size_t shm = After6Lds<H>::bytes(a.lin_chunk);
-    const int64_t rec[8] = {1, a.n_fjobs, a.n_ljobs, bw, a.order, tpg, a.lin_chunk, (int64_t)shm};
+    const int64_t rec[8] = {1, a.n_fjobs, a.n_ljobs, g.bw, a.order, g.tpg, a.lin_chunk, (int64_t)shm};
     std::copy(rec, rec + 8, c->node_rec);
-    LAUNCH("node_pre", SMK(node_after6_kernel<H>, dim3(a.n_fjobs + a.n_ljobs), dim3(bw * 64), shm, s, a));
+    LAUNCH("node_pre", SMK(node_after6_kernel<H>, dim3(a.n_fjobs + a.n_ljobs), dim3(g.bw * 64), shm, s, a));
     return 0;
 }
 
 NodeFollow follow_of(const shapemol_ctx *c, const DevMlpImg &m, int mode, float *out, int ld_out, int n_store) {
     NodeFollow f{};
     f.w1img = c->P(m.w1img); f.b1 = c->P(m.b1); f.ln_g = c->P(m.g); f.ln_b = c->P(m.be);
-    f.w1img6 = c->P(c->node_f16 ? m.w1img16 : m.w1img6); f.w2img6 = c->P(c->node_f16 ? m.w2img16 : m.w2img6);
+    f.w1img6 = c->P(c->opt.node_f16 ? m.w1img16 : m.w1img6); f.w2img6 = c->P(c->opt.node_f16 ? m.w2img16 : m.w2img6);
     f.w2img = c->P(m.w2img); f.b2 = c->P(m.b2); f.out = out; f.ld_out = ld_out; f.n_store = n_store; f.mode = mode; f.nt2 = m.nt2;
     return f;
 }
@@ -728,13 +601,13 @@ struct H2xPlan { EdgeFusedArgs::VnFuse vn{}; float *xsum = nullptr; VnFold pendi
 H2xPlan h2x_plan(const shapemol_ctx *c, const ShapePrep &sp, int l, bool fold, bool has_next, bool half_tiles, const double *stat_acc, const float *cur_x,
                  float *x_next, float *out_pos) {
     H2xPlan p;
-    if (!c->vn_fuse || half_tiles) return p;
+    if (!c->opt.vn_fuse || half_tiles) return p;
     const DevLayer &D = c->dm.layer[l];
     const int hd = c->cfg.n_heads;
     const double *acc = stat_acc + (size_t)l * kBnReplicas * 2 * hd;
     p.vn = vn_fuse_args(c, sp, l, x_next, nullptr, 2);
     p.stats_done = true;
-    const bool to_ddpm = !has_next && l == c->cfg.num_layers - 1 && out_pos && c->ddpm_fold && chain_guide(c) == Guide::None &&
+    const bool to_ddpm = !has_next && l == c->cfg.num_layers - 1 && out_pos && c->opt.ddpm_fold && chain_guide(c) == Guide::None &&
                          c->cfg.num_classes <= 16 && hd <= 16;
     if (fold && has_next) p.pending = VnFold{c->pd, acc, c->P(D.bn_g), c->P(D.bn_b), c->xsum, cur_x, x_next, c->mol_span, c->status + ST_SPAN, 1};
     else if (fold && to_ddpm) p.ddpm = DdpmFold{c->pd, acc, c->P(D.bn_g), c->P(D.bn_b), c->xsum, cur_x, out_pos, hd, 1};
@@ -754,7 +627,7 @@ NodePrologueArgs prologue_args(const shapemol_ctx *c, const int64_t *v, const in
     pa.emb_wT = c->P(c->dm.embwT); pa.emb_b = c->P(c->dm.embb); pa.v = v; pa.mol_of = mol_of; pa.ttab = c->ttab; pa.etab = c->etab; pa.t_mol = t_mol;
     pa.h_out = h_out;
     pa.q = follow_of(c, D0.q_x2h, NODE_LN_RELU, q_out, H, H);
-    pa.lin_img6 = c->P(c->node_f16 ? D0.pre16_x2h : D0.pre6_x2h); pa.add_mol = add_mol; pa.pre_out = pre_out;
+    pa.lin_img6 = c->P(c->opt.node_f16 ? D0.pre16_x2h : D0.pre6_x2h); pa.add_mol = add_mol; pa.pre_out = pre_out;
     pa.n_lin_tiles = 4 * (H / 16); pa.ld_add = 4 * H; pa.ld_out = 4 * H;
     pa.n_atoms = n; pa.C = c->cfg.num_classes; pa.D = c->cfg.time_emb_dim;
     return pa;
@@ -765,14 +638,14 @@ int launch_prologue(shapemol_ctx *c, hipStream_t s, const NodePrologueArgs &pa, 
     const int n_ct = (pa.n_atoms + 15) / 16;
     const dim3 grid((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), block(H * 4);
     if (!range_flag) range_flag = c->status + ST_RANGE;
-    if (c->node_f16 && c->feat_f16) LAUNCH("node_prologue", SMK((node_prologue16_kernel<H, true>), grid, block, 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, range_flag));
-    else if (c->node_f16) LAUNCH("node_prologue", SMK(node_prologue16_kernel<H>, grid, block, 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, range_flag));
+    if (c->opt.node_f16 && c->opt.feat_f16) LAUNCH("node_prologue", SMK((node_prologue16_kernel<H, true>), grid, block, 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, range_flag));
+    else if (c->opt.node_f16) LAUNCH("node_prologue", SMK(node_prologue16_kernel<H>, grid, block, 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, range_flag));
     else LAUNCH("node_prologue", SMK(node_prologue6_kernel<H>, grid, block, 2 * Chain6Lds<H>::FRAG * 16 + Chain6Lds<H>::PRE * 4, s, pa));
     return 0;
 }
 
 // which of the three prologue kernels the node precision options select; the tables are keyed by it
-int prologue_tab_key(const shapemol_ctx *c) { return 1 + (c->node_f16 ? 1 + (c->feat_f16 ? 1 : 0) : 0); }
+int prologue_tab_key(const shapemol_ctx *c) { return 1 + (c->opt.node_f16 ? 1 + (c->opt.feat_f16 ? 1 : 0) : 0); }
 
 // q_tab / pre_tab for the precision mode in use, on the stream of the evaluation that needs them (before any graph capture: the
 // first build allocates).  Built with the prologue kernel itself over the pseudo-batch of T x C atoms, atom (t, c) of type c at
@@ -780,7 +653,7 @@ int prologue_tab_key(const shapemol_ctx *c) { return 1 + (c->node_f16 ? 1 + (c->
 // (Its h0 output goes back onto the etab rows it was read from, unchanged.)
 template <int H>
 int ensure_prologue_tables(shapemol_ctx *c, hipStream_t s) {
-    if (!c->prologue_tab || !(c->chain_bf16 && c->lin_bf16) || c->tab_key == prologue_tab_key(c)) return 0;
+    if (!c->opt.prologue_tab || !(c->opt.chain_bf16 && c->opt.lin_bf16) || c->tab_key == prologue_tab_key(c)) return 0;
     const int T = c->cfg.num_timesteps, C = c->cfg.num_classes;
     const size_t rows = (size_t)T * C;
     if (!c->q_tab) {
@@ -808,14 +681,16 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
     const int n = (int)N;
     AtomEmbArgs ae{c->P(c->dm.embw), c->P(c->dm.embb), v_in, c->mol_of, c->ttab, c->t_mol, sampling ? c->steps : nullptr,
                    c->steps + 1, c->bn_acc, c->h_a, n, H, C, D, t_first, L * kBnReplicas * 2 * hd + L};   // + the grid-barrier counters
-    const int nlay = c->stop_layer >= 0 ? std::min(c->stop_layer, L) : L;
-    const bool fused_prologue = c->chain_bf16 && c->lin_bf16;   // embedding + first queries + first per-node products in one launch
-    if (fused_prologue && c->prologue_tab) {      // the same three outputs, gathered from the per-(timestep, type) tables
+    const int nlay = c->opt.stop_layer >= 0 ? std::min(c->opt.stop_layer, L) : L;
+    // every decision that does not depend on the layer, from the geometry of the launches below (sm_launch.h)
+    const lg::In gi = launch_in<H>(c, n);
+    const lg::StepForms sf = lg::step_forms(gi, sampling, c->n_pins > 0);
+    if (sf.fused_prologue && c->opt.prologue_tab) {      // the same three outputs, gathered from the per-(timestep, type) tables
         if (c->tab_key != prologue_tab_key(c)) return fail("run_score: the prologue tables are not built for this precision mode");
         PrologueTabArgs ta{c->etab, c->q_tab, c->pre_tab, c->tab_flag, v_in, c->mol_of, c->t_mol, ae.step_ptr, ae.step_cur, c->bn_acc,
                            sp.add0, c->h_a, c->q_x, c->pre0, c->status + ST_RANGE, n, C, g.num_timesteps, t_first, ae.bn_acc_len};
         LAUNCH("node_prologue", SMK(node_prologue_tab_kernel<H>, dim3((unsigned)((N * 16 + kProTabThreads - 1) / kProTabThreads)), dim3(kProTabThreads), 0, s, ta));
-    } else if (fused_prologue) {
+    } else if (sf.fused_prologue) {
         NodePrologueArgs pa = prologue_args<H>(c, v_in, c->mol_of, c->t_mol, sp.add0, c->h_a, c->q_x, c->pre0, n);
         pa.step_ptr = ae.step_ptr; pa.step_cur = ae.step_cur; pa.bn_acc = c->bn_acc; pa.bn_acc_len = ae.bn_acc_len; pa.t_first = t_first;
         if (nlay == 0) pa.n_lin_tiles = 0;
@@ -824,16 +699,14 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
     } else {
         LAUNCH("embed", SMK(atom_embed_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, ae));
     }
-    // (chains only: the hint is set for the batch of a chain; a score evaluation on other data must not trust a stale one)
-    const bool graph_fused = sampling && c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && KP <= 32 && c->n_pins == 0;
     int64_t (&rec)[8] = c->launch_rec;
     std::fill(rec, rec + 8, 0);
     std::fill(c->node_rec, c->node_rec + 8, 0);
     std::fill(c->x2h_out_rec, c->x2h_out_rec + 4, 0);
-    rec[0] = sampling; rec[1] = graph_fused; rec[7] = c->num_cu;
-    if (c->edge_bf16 == 2 && nlay > 0) { rec[5] = stream_chunk(c, n); rec[6] = (stream_jobs(c, n) + rec[5] - 1) / rec[5]; }
+    rec[0] = sampling; rec[1] = sf.graph_fused; rec[7] = c->num_cu;
+    if (sf.stream && nlay > 0) { const lg::StreamGeom g = lg::stream_geom(gi); rec[5] = g.chunk; rec[6] = g.grid; }
     if (reuse_graph) {
-    } else if (graph_fused) {
+    } else if (sf.graph_fused) {
         GraphArgs ga{x_in, c->mol_span, n, g.knn, KP, c->nbr, c->P(c->dm.ew.w1), c->P(c->dm.ew.b1), c->P(c->dm.ew.g), c->P(c->dm.ew.be),
                      c->P(c->dm.ew.w2), c->P(c->dm.ew.b2), c->ew, c->status + ST_SPAN, c->kstamp_sel == 4 ? c->kstamps : nullptr};
         const int apb = kGraphWaves * (KP >= 16 ? 1 : 16 / KP);      // atoms per workgroup
@@ -843,7 +716,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
         LAUNCH("knn", SMK(knn_pin_kernel, dim3(32), dim3(256), 0, s, c->pin_off, c->pin_steps, c->pin_atom, c->pin_nbr, c->pin_k, KP, c->steps + 1, n, c->nbr));
     EdgeWeightArgs ea{x_in, c->nbr, c->P(c->dm.ew.w1), c->P(c->dm.ew.b1), c->P(c->dm.ew.g), c->P(c->dm.ew.be),
                       c->P(c->dm.ew.w2), c->P(c->dm.ew.b2), c->ew, n * KP, KP};
-    if (!graph_fused && !reuse_graph) {
+    if (!sf.graph_fused && !reuse_graph) {
         const int tiles = (n * KP + 15) / 16;
         LAUNCH("edge_weight", SMK(edge_weight_kernel<H>, dim3((tiles + 3) / 4), dim3(256), 0, s, ea));
     }
@@ -851,60 +724,51 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
     float *cur_h = c->h_a;
     constexpr int NT = H / 16;
     bool v_done = false;
-    if (nlay > 0 && !fused_prologue) {   // prologue: per-node products and queries of the first x2h attention
+    if (nlay > 0 && !sf.fused_prologue) {   // prologue: per-node products and queries of the first x2h attention
         const DevLayer &D0 = c->dm.layer[0];
         if (launch_linear<H>(c, s, "node_pre", cur_h, c->P(D0.pre_x2h), c->P(D0.pre6_x2h), c->P(D0.pre16_x2h), sp.add0, 4 * H, c->pre0, 4 * H, 4 * NT, n,
                              c->kstamp_sel == 0 ? c->kstamps : nullptr)) return 1;
         if (launch_mlp2<H, 1>(c, s, "node_q", D0.q_x2h, cur_h, nullptr, NODE_LN_RELU, nullptr, c->q_x, H, H, n)) return 1;
     }
-    const bool fold = sampling && vn_fold_ok(c, n);       // chains only: coordinate update of layer l inside the x2h kernel of layer l + 1
     // evaluation-mode batch-norm: the consumers of the batch sums read sums that reproduce the running statistics
     double *stat_acc = c->bn_acc;
     if (c->bn_eval) {
         if (!c->bn_run) return fail("bn_eval = 1 needs the running statistics (shapemol_set_bn_running)");
-        if (c->vn_fuse == 1) return fail("bn_eval = 1 is not available with vn_fuse = 1 (coordinate update behind a grid barrier)");
+        if (c->opt.vn_fuse == 1) return fail("bn_eval = 1 is not available with vn_fuse = 1 (coordinate update behind a grid barrier)");
         const int tot = L * kBnReplicas * 2 * hd;
         LAUNCH("prep", SMK(bn_eval_fill_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, c->bn_run, c->bn_run + (size_t)L * hd, L, hd, n, c->bn_eval_acc));
         stat_acc = c->bn_eval_acc;
     }
-    VnFold pending{};                         // ... which then receives this
+    VnFold pending{};                         // fold: the x2h kernel of layer l + 1 receives the coordinate update of layer l
     for (int l = 0; l < nlay; ++l) {
         const DevLayer &Dl = c->dm.layer[l];
         const bool last = (l == nlay - 1), has_next = !last;
-        const bool phases = c->edge_bf16 && KP <= 16;
-        const bool f16 = c->edge_bf16 == 3;         // two-piece f16 operands (sm_edge16.h), the fast optional kernels
-        const bool stream = c->edge_bf16 == 2;      // exactly split bf16 operands, streaming kernels (sm_edge_stream.h), the default
-        const bool xc_fused = f16 && x2h_chain_ok<H>(c, n);
-        const bool half_tiles = (f16 || stream) && KP > 16;          // k > 16: two 16-slot tiles per atom + combine
         const float *pre_x = l == 0 ? c->pre0 : c->preAB + 4 * H;      // node pre-products of this x2h attention
         const int ld_pre_x = l == 0 ? 4 * H : 8 * H;
         unsigned long long *stamps_x = (c->kstamp_sel == 1 && l == 0) ? c->kstamps : nullptr;
         float *h_dst = (last && out_h) ? out_h : (cur_h == c->h_a ? c->h_b : c->h_a);      // h' of this layer
-        const bool lin_fused = c->chain_bf16 && c->lin_bf16 && c->node_f16 && c->lin_fuse;
-        const bool levels = c->node_levels && c->chain_bf16 && c->lin_bf16 && !c->node_f16 && !lin_fused;
-        const bool out_fused = stream && x2h_out_fuse_ok(c, n, levels);      // ... computed by the x2h kernel's tail
         Edge16Args xea{};
-        if (f16 || stream) {   // x2h attention: two-piece f16 operands, both MLP images resident (sm_edge16.h), or exactly split bf16
+        if (sf.f16 || sf.stream) {   // x2h attention: two-piece f16 operands, both MLP images resident (sm_edge16.h), or exactly split bf16
                                // operands, producer / consumer waves (sm_edge_stream.h); `pending`: the previous layer's coordinate update
-            if (f16) {
+            if (sf.f16) {
                 xea.image_k = c->P(Dl.i16_kx); xea.image_v = c->P(Dl.i16_vx);
-                fill_edge(xea, c, pre_x, ld_pre_x, c->q_x, cur_x, c->att, n, half_tiles, stamps_x);
+                fill_edge(xea, c, pre_x, ld_pre_x, c->q_x, cur_x, c->att, n, sf.half_tiles, stamps_x);
                 xea.vf = pending;
-                if (!xc_fused && launch_edge16<H, false>(c, s, xea)) return 1;     // (fused: launched with the node stage below)
+                if (!sf.xc_fused && launch_edge16<H, false>(c, s, xea)) return 1;     // (fused: launched with the node stage below)
             } else {
                 EdgeStreamArgs sa{};
                 sa.part_k = c->P(Dl.st_kx); sa.part_v = c->P(Dl.st_vx);
                 sa.w2k = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_kx)); sa.w2v = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_vx));
                 sa.b2v = c->P(Dl.sb2_vx);
-                fill_edge(sa, c, pre_x, ld_pre_x, c->q_x, cur_x, c->att, n, half_tiles, stamps_x);
+                fill_edge(sa, c, pre_x, ld_pre_x, c->q_x, cur_x, c->att, n, sf.half_tiles, stamps_x);
                 sa.vf = pending;
-                if (out_fused) sa.no = NodeOutArgs{c->att, cur_h, c->P(Dl.no.b1), c->P(Dl.no.g), c->P(Dl.no.be), c->P(Dl.no.b2),
+                if (sf.out_fused) sa.no = NodeOutArgs{c->att, cur_h, c->P(Dl.no.b1), c->P(Dl.no.g), c->P(Dl.no.be), c->P(Dl.no.b2),
                                                    c->P(Dl.no.w1img6), c->P(Dl.no.w2img6), h_dst};
                 if (launch_stream<H, false>(c, s, sa)) return 1;
             }
             pending = VnFold{};
-            if (half_tiles && launch_combine32<false>(c, s, c->att, n)) return 1;
-        } else if (phases && c->edge_bf16 == 1) {   // x2h attention, key and value phase in one launch
+            if (sf.half_tiles && launch_combine32<false>(c, s, c->att, n)) return 1;
+        } else if (sf.phases && c->opt.edge_bf16 == 1) {   // x2h attention, key and value phase in one launch
             EdgeFusedArgs fa{c->P(Dl.img_kx), c->P(Dl.img_vx), pre_x, c->q_x, cur_x, c->nbr, c->ew, c->alpha, c->att, n, ld_pre_x, stamps_x};
             if (launch_fused<H, false>(c, s, fa)) return 1;
         } else {   // x2h attention (fp32 MFMA kernels)
@@ -918,58 +782,58 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
             na.stamps = (c->kstamp_sel == 3 && l == 0) ? c->kstamps : nullptr;
             na.w1img = c->P(Dl.no.w1img); na.b1 = c->P(Dl.no.b1); na.ln_g = c->P(Dl.no.g); na.ln_b = c->P(Dl.no.be);
             na.w2img = c->P(Dl.no.w2img); na.b2 = c->P(Dl.no.b2);
-            na.w1img6 = c->P(c->node_f16 ? Dl.no.w1img16 : Dl.no.w1img6); na.w2img6 = c->P(c->node_f16 ? Dl.no.w2img16 : Dl.no.w2img6);
+            na.w1img6 = c->P(c->opt.node_f16 ? Dl.no.w1img16 : Dl.no.w1img6); na.w2img6 = c->P(c->opt.node_f16 ? Dl.no.w2img16 : Dl.no.w2img6);
             na.f[0] = follow_of(c, Dl.q_h2x, NODE_LN_RELU, c->q_h, H, H);
             na.n_follow = 1;
             if (has_next) { na.f[1] = follow_of(c, c->dm.layer[l + 1].q_x2h, NODE_LN_RELU, c->q_x, H, H); na.n_follow = 2; }
             else if (out_v) { na.f[1] = follow_of(c, c->dm.vhead, NODE_SSP, out_v, C, C); na.n_follow = 2; v_done = true; }
             const int n_ct = (n + 15) / 16;
             const int lin_tiles = (has_next && l + 1 < L ? 8 : 4) * NT;
-            if (lin_fused) {
+            if (sf.lin_fused) {
                 na.lin_img16 = c->P(Dl.lin16_img); na.add_mol = sp.addp + (size_t)l * c->capB * 8 * H; na.mol_of = c->mol_of;
                 na.pre_out = c->preAB; na.n_lin_tiles = lin_tiles; na.ld_add = 8 * H; na.ld_out = 8 * H;
             }
             float *lin_add = sp.addp + (size_t)l * c->capB * 8 * H;
-            if (levels) { if (launch_node_levels<H>(c, s, na, c->P(Dl.lin6_img), lin_add, 8 * H, c->preAB, 8 * H, lin_tiles, out_fused)) return 1; }
-            else if (xc_fused) { rec[4] = 1; if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
-            else if (c->chain_bf16 && c->node_f16 && c->feat_f16) LAUNCH("node_chain", SMK((node_chain16_kernel<H, true>), dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
-            else if (c->chain_bf16 && c->node_f16) LAUNCH("node_chain", SMK(node_chain16_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
-            else if (c->chain_bf16) LAUNCH("node_chain", SMK(node_chain6_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain6Lds<H>::BYTES, s, na));
+            if (sf.levels) { if (launch_node_levels<H>(c, s, na, c->P(Dl.lin6_img), lin_add, 8 * H, c->preAB, 8 * H, lin_tiles, sf.out_fused)) return 1; }
+            else if (sf.xc_fused) { rec[4] = 1; if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
+            else if (c->opt.chain_bf16 && c->opt.node_f16 && c->opt.feat_f16) LAUNCH("node_chain", SMK((node_chain16_kernel<H, true>), dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
+            else if (c->opt.chain_bf16 && c->opt.node_f16) LAUNCH("node_chain", SMK(node_chain16_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
+            else if (c->opt.chain_bf16) LAUNCH("node_chain", SMK(node_chain6_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain6Lds<H>::BYTES, s, na));
             else LAUNCH("node_chain", SMK(node_chain_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), 0, s, na));
             cur_h = dst;
             // per-node halves of the edge MLPs' first Linear: h2x of this layer | x2h of the next one
-            if (!lin_fused && !levels && launch_linear<H>(c, s, "node_pre", cur_h, c->P(Dl.lin_img), c->P(Dl.lin6_img), c->P(Dl.lin16_img), lin_add, 8 * H,
+            if (!sf.lin_fused && !sf.levels && launch_linear<H>(c, s, "node_pre", cur_h, c->P(Dl.lin_img), c->P(Dl.lin6_img), c->P(Dl.lin16_img), lin_add, 8 * H,
                                  c->preAB, 8 * H, lin_tiles, n, (c->kstamp_sel == 0 && l == 0) ? c->kstamps : nullptr)) return 1;
         }
         float *x_next = (last && out_pos) ? out_pos : ((cur_x == c->x_a) ? c->x_b : c->x_a);
         bool vn_done = false, stats_done = false;
         unsigned long long *stamps_h = (c->kstamp_sel == 2 && l == 0) ? c->kstamps : nullptr;
-        if ((f16 || stream) && c->vn_fuse != 1) {   // h2x attention (+ VN-linear and batch statistics when vn_fuse = 2)
-            const H2xPlan plan = h2x_plan(c, sp, l, fold, has_next, half_tiles, stat_acc, cur_x, x_next, out_pos);
+        if ((sf.f16 || sf.stream) && c->opt.vn_fuse != 1) {   // h2x attention (+ VN-linear and batch statistics when vn_fuse = 2)
+            const H2xPlan plan = h2x_plan(c, sp, l, sf.fold, has_next, sf.half_tiles, stat_acc, cur_x, x_next, out_pos);
             pending = plan.pending; stats_done = plan.stats_done; vn_done = plan.vn_done;
             if (plan.ddpm.enable) c->ddpm_vf = plan.ddpm;
             rec[2] |= plan.pending.enable; rec[3] |= plan.ddpm.enable;
-            if (f16) {
+            if (sf.f16) {
                 Edge16Args ea{};
                 ea.image_k = c->P(Dl.i16_kh); ea.image_v = c->P(Dl.i16_vh);
-                fill_edge(ea, c, c->preAB, 8 * H, c->q_h, cur_x, c->o3, n, half_tiles, stamps_h);
+                fill_edge(ea, c, c->preAB, 8 * H, c->q_h, cur_x, c->o3, n, sf.half_tiles, stamps_h);
                 ea.vn = plan.vn; ea.xsum = plan.xsum;
                 if (launch_edge16<H, true>(c, s, ea)) return 1;
             } else {
                 EdgeStreamArgs sa{};
                 sa.part_k = c->P(Dl.st_kh); sa.part_v = c->P(Dl.st_vh);
                 sa.w2k = reinterpret_cast<const unsigned *>(c->P(Dl.sw2_kh));
-                fill_edge(sa, c, c->preAB, 8 * H, c->q_h, cur_x, c->o3, n, half_tiles, stamps_h);
+                fill_edge(sa, c, c->preAB, 8 * H, c->q_h, cur_x, c->o3, n, sf.half_tiles, stamps_h);
                 sa.vn = plan.vn; sa.xsum = plan.xsum;
                 if (launch_stream<H, true>(c, s, sa)) return 1;
             }
-            if (half_tiles && launch_combine32<true>(c, s, c->o3, n)) return 1;
-        } else if (phases) {   // h2x attention, both images resident in LDS (exactly split bf16 operands)
+            if (sf.half_tiles && launch_combine32<true>(c, s, c->o3, n)) return 1;
+        } else if (sf.phases) {   // h2x attention, both images resident in LDS (exactly split bf16 operands)
             EdgeFusedArgs fa{c->P(Dl.img_kh), c->P(Dl.img_vh), c->preAB, c->q_h, cur_x, c->nbr, c->ew, c->alpha, c->o3, n, 8 * H, stamps_h};
-            if (c->vn_fuse) {   // VN-linear + batch statistics (2) or the whole coordinate update (1: grid barrier inside) behind the attention
+            if (c->opt.vn_fuse) {   // VN-linear + batch statistics (2) or the whole coordinate update (1: grid barrier inside) behind the attention
                 double *tail = c->bn_acc + (size_t)L * kBnReplicas * 2 * hd;
-                fa.vn = vn_fuse_args(c, sp, l, x_next, reinterpret_cast<unsigned *>(tail + l), c->vn_fuse == 1 ? 1 : 2);
-                if (c->vn_fuse == 1) vn_done = true; else stats_done = true;
+                fa.vn = vn_fuse_args(c, sp, l, x_next, reinterpret_cast<unsigned *>(tail + l), c->opt.vn_fuse == 1 ? 1 : 2);
+                if (c->opt.vn_fuse == 1) vn_done = true; else stats_done = true;
             }
             if (launch_fused<H, true>(c, s, fa)) return 1;
         } else {   // h2x attention (fp32 MFMA kernels)
@@ -1026,7 +890,11 @@ int check_cfg(const shapemol_config &g) {
     return 0;
 }
 
-#define DISPATCH_H(c, call128, call32) ((c)->cfg.hidden_dim == 128 ? (call128) : (call32))
+// f(std::integral_constant<int, H>) for the context's hidden width: f is a generic lambda that names a template as f<h()>
+template <typename F>
+auto dispatch_h(const shapemol_ctx *c, F &&f) {
+    return c->cfg.hidden_dim == 128 ? f(std::integral_constant<int, 128>{}) : f(std::integral_constant<int, 32>{});
+}
 
 }  // namespace
 
@@ -1064,7 +932,7 @@ int shapemol_create(const shapemol_config *cfg, const float *weights, size_t n_w
     const int H = cfg->hidden_dim, T = cfg->num_timesteps, C = cfg->num_classes;
     if ((e = c->mem_model.alloc(&c->d_img, im.d.size() * sizeof(float))) != hipSuccess) return drop(hip_fail("shapemol_create: weights", e));
     if ((e = hipMemcpy(c->d_img, im.d.data(), im.d.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return drop(hip_fail("hipMemcpy(weights)", e));
-    if (H == 128 ? set_edge_attr<128>(c->KP) : set_edge_attr<32>(c->KP)) return drop(1);
+    if (dispatch_h(c, [&](auto h) { return set_edge_attr<h()>(c->KP); })) return drop(1);
     // time-embedding table over all timesteps, and the atom embedding of every (timestep, atom type) pair
     if ((e = c->mem_model.alloc(&c->ttab, (size_t)T * cfg->time_emb_dim * sizeof(float))) != hipSuccess) return drop(hip_fail("shapemol_create: time table", e));
     if ((e = c->mem_model.alloc(&c->etab, (size_t)T * C * H * sizeof(float))) != hipSuccess) return drop(hip_fail("shapemol_create: embedding table", e));
@@ -1120,13 +988,12 @@ int shapemol_score(shapemol_ctx *c, const float *d_pos, const int64_t *d_v, cons
     if (ensure_workspace(c, N, B)) return 1;
     hipStream_t s = (hipStream_t)stream;
     c->lastN = N; c->lastB = B;
-    if (DISPATCH_H(c, ensure_prologue_tables<128>(c, s), ensure_prologue_tables<32>(c, s))) return 1;
+    if (dispatch_h(c, [&](auto h) { return ensure_prologue_tables<h()>(c, s); })) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
-    if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape, c->prep[0]), run_prep<32>(c, s, d_batch, N, B, d_shape, c->prep[0]))) return 1;
+    if (dispatch_h(c, [&](auto h) { return run_prep<h()>(c, s, d_batch, N, B, d_shape, c->prep[0]); })) return 1;
     LAUNCH("prep", SMK(t_convert_kernel, dim3((B + 255) / 256), dim3(256), 0, s, d_t, (int)B, c->cfg.num_timesteps, c->t_mol, c->status));
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_v, (int)N, c->cfg.num_classes, c->status));
-    return DISPATCH_H(c, run_score<128>(c, s, c->prep[0], d_pos, d_v, N, B, false, 0, out_pos, out_h, out_v),
-                      run_score<32>(c, s, c->prep[0], d_pos, d_v, N, B, false, 0, out_pos, out_h, out_v));
+    return dispatch_h(c, [&](auto h) { return run_score<h()>(c, s, c->prep[0], d_pos, d_v, N, B, false, 0, out_pos, out_h, out_v); });
 }
 
 int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_init_v, const int64_t *d_batch,
@@ -1140,7 +1007,7 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     if (ensure_workspace(c, N, B)) return 1;
     hipStream_t s = (hipStream_t)stream;
     c->lastN = N; c->lastB = B;
-    if (DISPATCH_H(c, ensure_prologue_tables<128>(c, s), ensure_prologue_tables<32>(c, s))) return 1;
+    if (dispatch_h(c, [&](auto h) { return ensure_prologue_tables<h()>(c, s); })) return 1;
     const int t_first = c->cfg.num_timesteps - 1;
     const Guide kind = chain_guide(c);
     const bool mesh = kind == Guide::Mesh, cfg = kind == Guide::Cfg;
@@ -1155,13 +1022,13 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     if (mesh && groups_table(c, s, c->ms.whole ? nullptr : d_batch, N, c->ms.ints, c->ms.groups)) return 1;
     HIPCHK(hipMemsetAsync(c->status, 0, 8 * sizeof(int), s));
     if (mesh && mesh_counters_clear(c, s, c->ms.groups)) return 1;
-    if (DISPATCH_H(c, run_prep<128>(c, s, d_batch, N, B, d_shape, c->prep[0]), run_prep<32>(c, s, d_batch, N, B, d_shape, c->prep[0]))) return 1;
+    if (dispatch_h(c, [&](auto h) { return run_prep<h()>(c, s, d_batch, N, B, d_shape, c->prep[0]); })) return 1;
     uint64_t field_gen = 0;
     if (kind == Guide::Field) {      // the decoder's per-shape prologue of the chain's own shapes, once per chain
         if (shapemol_sd_chain_prepare_(c->field_sd, d_shape, B, s, &field_gen)) return 1;      // (not a profiled launch: no event pair)
     }
     if (cfg) {      // classifier-free guidance: the unconditional evaluation's shape data, from a zeroed shape, once per chain
-        if (DISPATCH_H(c, run_prep_shape<128>(c, s, B, c->shape_zero, c->prep[1]), run_prep_shape<32>(c, s, B, c->shape_zero, c->prep[1]))) return 1;
+        if (dispatch_h(c, [&](auto h) { return run_prep_shape<h()>(c, s, B, c->shape_zero, c->prep[1]); })) return 1;
         HIPCHK(hipMemsetAsync(c->cfg_hist, 0, (size_t)2 * kCfgHistWords * sizeof(unsigned), s));
         if (c->cgs.groups > 0) {      // the groups' element ranges, workgroups and ranks, from the batch vector (once per chain)
             const CfgArgs ca = cfg_args(c, N);
@@ -1184,20 +1051,19 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     HIPCHK(hipMemcpyAsync(c->x_state, d_init_pos, N * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->v_state, d_init_v, N * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     auto one_step = [&]() -> int {
-        if (DISPATCH_H(c, run_score<128>(c, s, c->prep[0], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v),
-                       run_score<32>(c, s, c->prep[0], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v))) return 1;
+        if (dispatch_h(c, [&](auto h) { return run_score<h()>(c, s, c->prep[0], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos, nullptr, c->pred_v); })) return 1;
         if (cfg) {        // the same step on a zeroed shape: same positions, graph and step index; own batch statistics and outputs
-            if (DISPATCH_H(c, run_score<128>(c, s, c->prep[1], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true),
-                           run_score<32>(c, s, c->prep[1], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true)) ||
+            if (dispatch_h(c, [&](auto h) { return run_score<h()>(c, s, c->prep[1], c->x_state, c->v_state, N, B, true, t_first, c->pred_pos_u, nullptr, c->pred_v_u, true); }) ||
                 run_cfg_stats(c, s, cfg_args(c, N))) return 1;
         }
         if (enqueue_guidance(c, s, kind, c->pred_pos, N, c->steps + 1, t_first)) return 1;     // shape guidance of the predicted x0 (steps with t > grad_step)
-        return DISPATCH_H(c, run_ddpm<128>(c, s, N), run_ddpm<32>(c, s, N));
+        return dispatch_h(c, [&](auto h) { return run_ddpm<h()>(c, s, N); });
     };
     if (use_graph && !c->prof_on) {
         shapemol_ctx::GraphKey key{};
-        key.N = N; key.B = B; key.guide = kind; key.fold = vn_fold_ok(c, (int)N);
-        key.gfuse = c->graph_fuse && c->max_mol_atoms > 0 && c->max_mol_atoms <= kGraphCap && c->n_pins == 0;
+        // (the forms run_score will choose: same call, same arguments)
+        const lg::StepForms sf = dispatch_h(c, [&](auto h) { return lg::step_forms(launch_in<h()>(c, (int)N), true, c->n_pins > 0); });
+        key.N = N; key.B = B; key.guide = kind; key.fold = sf.fold; key.gfuse = sf.graph_fused;
         if (kind == Guide::Field) { key.field_gen = field_gen; key.field_lr = c->field_lr; key.field_step = c->field_step; }
         if (cfg && c->cgs.groups > 0) {
             key.cfg = 1 + c->cgs.type; key.cfg_groups = c->cgs.groups; key.cfgv[1] = c->cgs.p;
@@ -1260,7 +1126,7 @@ int shapemol_set_option(shapemol_ctx *c, const char *name, int64_t value) {
     const std::string k(name);
     if (k == "max_mol_atoms") {   // hint for the folded coordinate update; the captured graph is keyed on the resulting decision
         if (value < 0) return fail("max_mol_atoms must be >= 0");
-        c->max_mol_atoms = (int)std::min<int64_t>(value, 1 << 20);
+        c->opt.max_mol_atoms = (int)std::min<int64_t>(value, 1 << 20);
         return 0;
     }
     if (k == "first_step") {      // does not touch the captured graph: the step counter lives in device memory
@@ -1268,40 +1134,40 @@ int shapemol_set_option(shapemol_ctx *c, const char *name, int64_t value) {
         c->first_step = (int)value;
         return 0;
     }
-    if (k == "stop_layer") c->stop_layer = (int)value;
+    if (k == "stop_layer") c->opt.stop_layer = (int)value;
     else if (k == "edge_bf16") {
         if (value < 0 || value > 3) return fail("edge_bf16 must be 0 (fp32 MFMA), 1 (exactly split bf16, phase kernels), 2 (exactly split bf16, streaming kernels) or 3 (two-piece f16)");
         if (value != 3 && value != 2 && c->KP > 16) return fail("k > 16 runs on the streaming (edge_bf16 = 2) or the two-piece f16 (edge_bf16 = 3) edge kernels");
         if (value == 3 && c->hid_max > 6.0e4f) return fail("edge_bf16 = 3: the edge MLPs' LayerNorm outputs may exceed the fp16 range for these weights");
-        c->edge_bf16 = (int)value;
+        c->opt.edge_bf16 = (int)value;
     }
-    else if (k == "edge_tiles") { if (value < -1 || value > 1) return fail("edge_tiles must be -1 (automatic), 0 (sliced one-job launches) or 1 (looping launch)"); c->edge_tiles = (int)value; }
-    else if (k == "node_f16") c->node_f16 = value != 0;
+    else if (k == "edge_tiles") { if (value < -1 || value > 1) return fail("edge_tiles must be -1 (automatic), 0 (sliced one-job launches) or 1 (looping launch)"); c->opt.edge_tiles = (int)value; }
+    else if (k == "node_f16") c->opt.node_f16 = value != 0;
     else if (k == "feat_f16") {
-        if (value && (c->edge_bf16 != 3 || !c->node_f16)) return fail("feat_f16 = 1 needs the f16 kernels (edge_bf16 = 3, node_f16 = 1)");
-        c->feat_f16 = value != 0;
+        if (value && (c->opt.edge_bf16 != 3 || !c->opt.node_f16)) return fail("feat_f16 = 1 needs the f16 kernels (edge_bf16 = 3, node_f16 = 1)");
+        c->opt.feat_f16 = value != 0;
     }
-    else if (k == "lin_fuse") c->lin_fuse = value != 0;
-    else if (k == "stream_whole_rounds") c->stream_whole_rounds = value != 0;
-    else if (k == "x2h_chain") c->x2h_chain = value != 0;
-    else if (k == "graph_fuse") c->graph_fuse = value != 0;
+    else if (k == "lin_fuse") c->opt.lin_fuse = value != 0;
+    else if (k == "stream_whole_rounds") c->opt.stream_whole_rounds = value != 0;
+    else if (k == "x2h_chain") c->opt.x2h_chain = value != 0;
+    else if (k == "graph_fuse") c->opt.graph_fuse = value != 0;
     else if (k == "bn_eval") c->bn_eval = value != 0;
-    else if (k == "ddpm_fold") c->ddpm_fold = value != 0;
-    else if (k == "vn_fold") c->vn_fold = value != 0;
-    else if (k == "prologue_tab") c->prologue_tab = value != 0;      // 0: the per-atom MLP prologue (A/B, equivalence tests)
-    else if (k == "lin_bf16") c->lin_bf16 = (int)value;
-    else if (k == "chain_bf16") c->chain_bf16 = (int)value;
-    else if (k == "vn_fuse") c->vn_fuse = (int)value;
-    else if (k == "node_levels") c->node_levels = value != 0;
-    else if (k == "x2h_out_fuse") { if (value < 0 || value > 2) return fail("x2h_out_fuse must be 0 (node_out6_kernel), 1 (x2h tail inside its boundary) or 2 (x2h tail always)"); c->x2h_out_fuse = (int)value; }
-    else if (k == "stream_chunk") { if (value < 0 || value > 4096) return fail("stream_chunk must be 0 (automatic) .. 4096"); c->stream_chunk_opt = (int)value; }
-    else if (k == "after_order") { if (value < 0 || value > 2) return fail("after_order must be 0 (follow-up jobs first), 1 (interleaved) or 2 (linear jobs first)"); c->after_order = (int)value; }
-    else if (k == "after_waves") { if (value < 1 || value > 16) return fail("after_waves must be 1..16"); c->after_waves = (int)value; }
-    else if (k == "after_lin_wgs") { if (value < 0 || value > 4096) return fail("after_lin_wgs must be 0 (automatic) .. 4096"); c->after_lin_wgs = (int)value; }
-    else if (k == "lin_waves") { if (value < 1 || value > 16) return fail("lin_waves must be 1..16"); c->lin_waves = (int)value; }
+    else if (k == "ddpm_fold") c->opt.ddpm_fold = value != 0;
+    else if (k == "vn_fold") c->opt.vn_fold = value != 0;
+    else if (k == "prologue_tab") c->opt.prologue_tab = value != 0;      // 0: the per-atom MLP prologue (A/B, equivalence tests)
+    else if (k == "lin_bf16") c->opt.lin_bf16 = (int)value;
+    else if (k == "chain_bf16") c->opt.chain_bf16 = (int)value;
+    else if (k == "vn_fuse") c->opt.vn_fuse = (int)value;
+    else if (k == "node_levels") c->opt.node_levels = value != 0;
+    else if (k == "x2h_out_fuse") { if (value < 0 || value > 2) return fail("x2h_out_fuse must be 0 (node_out6_kernel), 1 (x2h tail inside its boundary) or 2 (x2h tail always)"); c->opt.x2h_out_fuse = (int)value; }
+    else if (k == "stream_chunk") { if (value < 0 || value > 4096) return fail("stream_chunk must be 0 (automatic) .. 4096"); c->opt.stream_chunk_opt = (int)value; }
+    else if (k == "after_order") { if (value < 0 || value > 2) return fail("after_order must be 0 (follow-up jobs first), 1 (interleaved) or 2 (linear jobs first)"); c->opt.after_order = (int)value; }
+    else if (k == "after_waves") { if (value < 1 || value > 16) return fail("after_waves must be 1..16"); c->opt.after_waves = (int)value; }
+    else if (k == "after_lin_wgs") { if (value < 0 || value > 4096) return fail("after_lin_wgs must be 0 (automatic) .. 4096"); c->opt.after_lin_wgs = (int)value; }
+    else if (k == "lin_waves") { if (value < 1 || value > 16) return fail("lin_waves must be 1..16"); c->opt.lin_waves = (int)value; }
     else if (k == "stamps") c->stamp_on = (int)value;
     else if (k == "kstamp_sel") c->kstamp_sel = (int)value;
-    else if (k == "edge_waves") { if (value < 0 || value > 12) return fail("edge_waves must be 0 (automatic) .. 12"); c->edge_threads = (int)value * 64; }   // 0 = automatic
+    else if (k == "edge_waves") { if (value < 0 || value > 12) return fail("edge_waves must be 0 (automatic) .. 12"); c->opt.edge_threads = (int)value * 64; }   // 0 = automatic
     else return fail("unknown option " + k);
     hipSetDevice(c->device);
     c->drop_graphs();

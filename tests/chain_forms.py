@@ -2,8 +2,9 @@
 tests/test_gpu_chain_forms.py): the kernels that only a reverse step launches -- graph_kernel, the coordinate update folded into
 the next x2h kernel (VnFold) or into the posterior kernel (DdpmFold), x2h_chain16_kernel -- and the streaming edge kernels'
 tails, at the shapes where those forms switch or fill up.  No GPU code here: the formulas below restate the host's launch
-decisions (shapemol_hip.hip: stream_chunk, vn_fold_ok, the graph_fused condition) so that the shapes follow from the device's
-CU count, and the GPU tests check them against the library's own record (debug_read "launch")."""
+decisions (csrc/sm_launch.h: stream_geom, and step_forms' fold and graph_fused) so that the shapes follow from the device's
+CU count; tests/test_launch_geom_cpu.py holds them to that header over a sweep of sizes and CU counts, and the GPU tests check
+them against the library's own record (debug_read "launch")."""
 import numpy as np
 import torch
 
@@ -45,7 +46,7 @@ def stream_grid(n, kp, num_cu):
 
 
 def fold_atoms(mode, n, kp, num_cu, hidden=128):
-    """Atoms of one workgroup as vn_fold_ok counts them (None: no fold on this path): the exact mode's streaming kernels own
+    """Atoms of one workgroup as step_forms' fold counts them (None: no fold on this path): the exact mode's streaming kernels own
     `chunk` tiles; the f16x2 kernels one tile per wave of max(waves, H / 16) waves, or `chunk` tiles when they loop."""
     if kp > 16:
         return None
@@ -62,7 +63,7 @@ def fold_atoms(mode, n, kp, num_cu, hidden=128):
 
 
 def fold_expected(mode, counts, k, num_cu):
-    """vn_fold_ok for a chain on this batch with the true max_mol_atoms hint."""
+    """step_forms' fold for a chain on this batch with the true max_mol_atoms hint."""
     a = fold_atoms(mode, int(np.sum(counts)), kp_of(k), num_cu)
     return a is not None and a + 2 * (int(np.max(counts)) - 1) <= FOLD_CAP
 

@@ -23,7 +23,7 @@ DEV = "cuda:0"
 MODELS = {128: dict(num_layers=2), 32: dict(hidden_dim=32, n_heads=4, num_layers=2)}
 REC = ("fused", "atoms_per_wg", "col_tiles_per_wg", "lds_bytes")
 OPTION_DEFAULTS = {"x2h_out_fuse": 1, "stream_chunk": 0, "stop_layer": -1}
-BOUNDARY = 96       # atoms per workgroup up to which the fused form is used (kX2hOutFuseAtoms)
+BOUNDARY = 96       # atoms per workgroup up to which the fused form is used (3 * CHAIN_COLS * 16: step_forms, csrc/sm_launch.h)
 # (k, N, forced chunk): atoms per workgroup = chunk * 16 / KP
 CASES = [(8, 1, 0), (8, 2, 0), (8, 3, 0), (8, 17, 1), (8, 33, 1), (8, 37, 8), (8, 37, 9), (8, 49, 11), (8, 44, 11), (8, 45, 16),
          (12, 35, 16), (12, 35, 17), (12, 3, 0)]
