@@ -48,6 +48,14 @@ def hip_device(device, what=None):
     return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
 
 
+def _check_device_tensor(name, t, dtype):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a tensor on a HIP device (shapemol_amd has no CPU path)")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must have dtype {dtype}, got {t.dtype}")
+    return t.contiguous()
+
+
 class DeviceContexts:
     """One library context per device, made by ``<create_name>(device index, &handle)`` at the first ``of(device)`` and
     destroyed by ``<destroy_name>(handle)`` before the interpreter tears the runtime down (not from a finaliser during it).

@@ -20,14 +20,19 @@ the state dict; the running statistics are read, never updated.
 There is no CPU path: tensors must live on a HIP device and the library must be built.
 """
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import ptr, stream_ptr
+from ._native import _check_device_tensor, ptr, stream_ptr
 from .diffusion import build_schedule_tables
+from .guidance import (_GUIDANCE, _ChainSettings, _clear_guidance, _guidance_groups, _install_guidance, _mesh_groups_error, _mesh_guidance_groups,
+                       _resolve_chain, _standalone_inputs, mesh_shape_guidance, pointcloud_shape_guidance)
+# not used here: every helper that moved to guidance.py stays importable from this module
+from .guidance import _cfg_groups, _cloud_array, _field_decoder, _mesh_arrays, _one_group  # noqa: F401
 from .packing import pack_state_dict
 from .spec import ModelDims, state_dict_spec, RBF_CENTRES
 
@@ -53,12 +58,15 @@ def _attach(root, key, tensor, kind):
         mod.register_parameter(leaf, nn.Parameter(tensor, requires_grad=(kind != "const")))
 
 
-def _check_device_tensor(name, t, dtype):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name} must be a tensor on a HIP device (shapemol_amd has no CPU path)")
-    if t.dtype != dtype:
-        raise TypeError(f"{name} must have dtype {dtype}, got {t.dtype}")
-    return t.contiguous()
+@dataclass
+class _Slot:
+    """One library context of the model and what the host caches about it: the context, the weights key it was made from, the
+    batch-norm mode it is in, and the side stream its chains run on.  Slot 0 is the model's own context; slots > 0 are further
+    contexts over the same weights."""
+    ctx: C.c_void_p = None
+    key: tuple = None
+    bn_eval: bool = False
+    stream: torch.cuda.Stream = None
 
 
 # library defaults of the options the precision modes touch (shapemol_set_option; include/shapemol_hip.h)
@@ -105,10 +113,14 @@ class ScorePosNet3D(nn.Module):
                 t = (torch.rand(shape, generator=gen) * 2 - 1) * bound
             _attach(self, key, t, kind)
         self.num_timesteps = self.dims.T
-        self._ctx = None
-        self._ctx_key = None
+        self._slots = {}         # slot -> _Slot
 
     # ------------------------------------------------------------------ library context
+    @property
+    def _ctx(self):
+        """Slot 0's context, or None."""
+        return self._slots[0].ctx if 0 in self._slots else None
+
     def _weights_key(self, device):
         return (str(device),) + tuple((p.data_ptr(), p._version) for p in self.parameters()) \
             + tuple((b.data_ptr(), b._version) for n, b in self.named_buffers() if n.endswith(("running_mean", "running_var")))
@@ -125,20 +137,13 @@ class ScorePosNet3D(nn.Module):
         same weights (own workspace and captured graphs each), so that independent chains can be in flight side by side
         (shapemol_amd.sampling keeps two)."""
         key = self._weights_key(device)
-        if slot != 0:
-            extra = self.__dict__.setdefault("_ctx_extra", {})
-            ent = extra.get(slot)
-            if ent is not None and ent["key"] == key:
-                return ent["ctx"]
-            if ent is not None:
-                _lib.load().shapemol_destroy(ent["ctx"])
-            extra[slot] = {"ctx": self._new_context(device), "key": key, "bn_eval": False}
-            return extra[slot]["ctx"]
-        if self._ctx is not None and key == self._ctx_key:
-            return self._ctx
-        self._release(extra=False)
-        self._ctx, self._ctx_key, self._bn_eval_set = self._new_context(device), key, False
-        return self._ctx
+        s = self._slots.setdefault(slot, _Slot())
+        if s.ctx is None or s.key != key:
+            if s.ctx is not None:
+                _lib.load().shapemol_destroy(s.ctx)
+                s.ctx = None
+            s.ctx, s.key, s.bn_eval = self._new_context(device), key, False
+        return s.ctx
 
     def _new_context(self, device):
         lib = _lib.load()
@@ -169,25 +174,16 @@ class ScorePosNet3D(nn.Module):
         """module.eval() / .train() -> the library's batch-norm mode (running statistics / the batch's), as nn.BatchNorm1d
         switches with the module's flag (models/shape_vn_layers.py:45-61).  Sampling in the reference runs in train mode
         (the scripts never call .eval() before sample_diffusion); validate() switches to eval."""
-        want = not self.training
-        if slot != 0:
-            ent = self.__dict__["_ctx_extra"][slot]
-            if want != ent["bn_eval"]:
-                _lib.check(_lib.load().shapemol_set_option(ctx, b"bn_eval", int(want)), "shapemol_set_option")
-                ent["bn_eval"] = want
-            return
-        if want != getattr(self, "_bn_eval_set", False):
+        want, s = not self.training, self._slots[slot]
+        if want != s.bn_eval:
             _lib.check(_lib.load().shapemol_set_option(ctx, b"bn_eval", int(want)), "shapemol_set_option")
-            self._bn_eval_set = want
+            s.bn_eval = want
 
-    def _release(self, extra=True):
-        if getattr(self, "_ctx", None) is not None:
-            _lib.load().shapemol_destroy(self._ctx)
-            self._ctx = None
-        if extra:
-            for ent in self.__dict__.get("_ctx_extra", {}).values():
-                _lib.load().shapemol_destroy(ent["ctx"])
-            self.__dict__["_ctx_extra"] = {}
+    def _release(self):
+        for s in self._slots.values():
+            if s.ctx is not None:
+                _lib.load().shapemol_destroy(s.ctx)
+                s.ctx = None
 
     def __del__(self):
         try:
@@ -197,16 +193,15 @@ class ScorePosNet3D(nn.Module):
 
     def set_option(self, name, value):
         """Library tuning / diagnostics knob (see shapemol_set_option)."""
-        dev = next(self.parameters()).device
-        _lib.check(_lib.load().shapemol_set_option(self._context(dev), name.encode(), int(value)), "shapemol_set_option")
-        if name == "bn_eval":           # keep the cache of _sync_bn_mode truthful
-            self._bn_eval_set = bool(value)
-        else:                           # (the batch-norm mode follows module.training; everything else is remembered for contexts
+        self._context(next(self.parameters()).device)
+        for slot in sorted(self._slots):         # slot 0 first: what it refuses reaches no other context and is not remembered
+            s = self._slots[slot]
+            if s.ctx is not None:
+                _lib.check(_lib.load().shapemol_set_option(s.ctx, name.encode(), int(value)), "shapemol_set_option")
+                if name == "bn_eval":            # keep the cache of _sync_bn_mode truthful
+                    s.bn_eval = bool(value)
+        if name != "bn_eval":           # (the batch-norm mode follows module.training; everything else is remembered for contexts
             self.__dict__.setdefault("_options", {})[name] = int(value)      #  created later: weight reloads, extra slots)
-        for slot, ent in self.__dict__.get("_ctx_extra", {}).items():
-            _lib.check(_lib.load().shapemol_set_option(ent["ctx"], name.encode(), int(value)), "shapemol_set_option")
-            if name == "bn_eval":
-                ent["bn_eval"] = bool(value)
 
     def set_knn_pins(self, step=None, atom=None, nbr=None, num_steps=None):
         """Diagnostic of the parity tests (shapemol_set_knn_pins): pin the kNN graph of the following sample_diffusion calls at
@@ -436,54 +431,9 @@ class ScorePosNet3D(nn.Module):
         builds the dict (chains on different slots then run side by side, and a finished chain's trajectories are
         unbatched and copied while the next one runs).
         """
-        # gradient shape guidance: behind a mesh and a point cloud in the reference's if / elif, so with either it is not looked at
-        field_dec = None
-        if use_grad and use_mesh_data is None and use_pointcloud_data is None:
-            field_dec = _field_decoder(shape_AE)
-            grad_lr = float(grad_lr)
-            if not np.isfinite(grad_lr):
-                raise ValueError(f"grad_lr must be finite, got {grad_lr}")
-        groups = mesh_groups = None
-        if isinstance(use_pointcloud_data, list):
-            if isinstance(use_mesh_data, list):
-                raise NotImplementedError("mesh groups and point-cloud groups in one chain are not supported: give one kind of list")
-            if use_mesh_data is not None:
-                raise NotImplementedError("mesh guidance takes one mesh per chain")
-            groups = _guidance_groups(use_pointcloud_data, int(ligand_shape.shape[0]))
-        elif isinstance(use_mesh_data, list):        # (with a single point cloud beside: the mesh wins, the reference's if / elif)
-            mesh_groups = _mesh_guidance_groups(use_mesh_data, int(ligand_shape.shape[0]))
-        cfg_groups = None
-        if isinstance(guide_stren, list):
-            cfg_groups = _cfg_groups(guide_stren, bounds, int(ligand_shape.shape[0]))
-            if self.cond_mask_prob == 0:
-                assert not cfg_groups[1].any()
-            guide_stren = float(np.abs(cfg_groups[1]).max()) if cfg_groups[1].any() else 0.0      # (> 0: some group is guided)
-        elif self.cond_mask_prob == 0:
-            assert guide_stren == 0
-        # classifier-free guidance: the reference's branch order (:561-642) -- mesh, point cloud, then CFG
-        cfg = use_mesh_data is None and use_pointcloud_data is None and field_dec is None and (self.cond_mask_prob or 0) > 0 and guide_stren > 0.0
-        cfg_p, cfg_box = 0.0, None
-        if cfg:
-            if threshold_type not in _lib.CFG_THRESHOLDS:
-                raise ValueError("undefined thresholding strategy: expect one of (reference_threshold, dynamic_threshold, rescale, none) "
-                                 + "but get %s" % (threshold_type))
-            if threshold_type is not None:
-                cfg_p = float((threshold_args or {}).get("p", _lib.CFG_DEFAULT_P[threshold_type]))
-            if threshold_type == "dynamic_threshold" and not 0.0 <= cfg_p <= 1.0:
-                raise RuntimeError(f"quantile() q must be in the range [0, 1] but got {cfg_p}")     # torch.quantile's check
-            if bounds is not None and cfg_groups is None:
-                bx = bounds.detach().cpu().numpy() if isinstance(bounds, torch.Tensor) else np.asarray(bounds)
-                bx = np.asarray(bx, dtype=np.float64)
-                if bx.ndim == 3:
-                    bx = bx[0]               # the box of molecule 0 clamps every atom, as the reference's bounds[0]
-                if bx.shape != (3, 2):
-                    raise ValueError("bounds must be a (B, 3, 2) or (3, 2) box")
-                cfg_box = np.ascontiguousarray(bx)
-        if center_pos_mode not in (None, "none", "center"):
-            raise NotImplementedError(center_pos_mode)       # as center_pos() of the reference (:52-60)
-        if num_steps is None:
-            num_steps = self.num_timesteps
-        print('sample center pos mode: ', center_pos_mode)
+        plan = _resolve_chain(self, ligand_shape, threshold_type, threshold_args, num_steps, center_pos_mode, use_grad, grad_lr, shape_AE,
+                              use_mesh_data, use_pointcloud_data, grad_step, guide_stren, bounds, first_step)
+        num_steps, guided = plan.num_steps, plan.kind if plan.kind in _GUIDANCE else None     # guided: the kind of set, if any
 
         pos = _check_device_tensor("init_ligand_pos", init_ligand_pos, torch.float32)
         v = _check_device_tensor("init_ligand_v", init_ligand_v, torch.int64)
@@ -491,7 +441,7 @@ class ScorePosNet3D(nn.Module):
         shape = _check_device_tensor("ligand_shape", ligand_shape, torch.float32).view(-1, self.dims.S, 3)
         n, b, cc, dev = pos.shape[0], shape.shape[0], self.dims.C, pos.device
         offset = None
-        if center_pos_mode == "center":
+        if plan.center_pos_mode == "center":
             # the chain runs on coordinates centred per molecule; the offset goes back onto `pos` and `pos_traj` (reference :547,
             # :675-684; `pos_cond_traj`, the raw network outputs, stays in the centred frame there too)
             cnt = torch.bincount(batch, minlength=b).clamp(min=1).to(torch.float32)
@@ -506,10 +456,8 @@ class ScorePosNet3D(nn.Module):
             u = _check_device_tensor("noise[1]", noise[1], torch.float32)
             if tuple(eps.shape) != (num_steps, n, 3) or tuple(u.shape) != (num_steps, n, cc):
                 raise ValueError("noise must be (eps (S,N,3), u (S,N,C))")
-        # the kind of set the chain installs (the names of _GUIDANCE's two rows); the mesh wins, as the reference's if / elif
-        guided = "mesh_groups" if use_mesh_data is not None else ("groups" if use_pointcloud_data is not None else None)
-        if guided == "mesh_groups" and mesh_groups is None:
-            mesh_groups = _one_group(guided, use_mesh_data, b)
+        if guided == "mesh_groups":
+            plan.one_group(b)
         if seed is None:
             if noise is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -520,18 +468,14 @@ class ScorePosNet3D(nn.Module):
                 seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64))
             else:
                 seed = 0
-        # the largest molecule of the batch lets the library fold the per-layer coordinate update into the next attention
-        # kernel (one tiny synchronising reduction per chain; the reference synchronises at every step)
-        _lib.check(lib.shapemol_set_option(ctx, b"max_mol_atoms", int(torch.bincount(batch).max().item()) if n else 0), "shapemol_set_option")
+        self._set_max_mol_atoms(ctx, batch, n)
         gd = None
         if guided and guide_draws is not None:
             gd = _check_device_tensor("guide_draws", guide_draws, torch.float64)
             if tuple(gd.shape) != (num_steps, 5, n):
                 raise ValueError("guide_draws must be (S, 5, N) float64")
-        if guided == "groups" and groups is None:
-            groups = _one_group(guided, use_pointcloud_data, b)
-        if guided:      # (taken out of the context again by _PendingChain._drop_guidance)
-            _install_guidance(lib, ctx, guided, mesh_groups if guided == "mesh_groups" else groups, grad_step, gd)
+        if guided == "groups":
+            plan.one_group(b)
         tr = _lib.Traj()
         bufs = {}
         if return_traj:
@@ -541,48 +485,27 @@ class ScorePosNet3D(nn.Module):
                                   ("v_cond_traj", (num_steps, n, cc), torch.float32)):
                 bufs[name] = torch.empty(shp, dtype=dt, device=dev)
                 setattr(tr, name, bufs[name].data_ptr())
-            if cfg:
+            if plan.kind == "cfg":
                 bufs["pos_uncond_traj"] = torch.empty((num_steps, n, 3), dtype=torch.float32, device=dev)
                 bufs["v_uncond_traj"] = torch.empty((num_steps, n, cc), dtype=torch.float32, device=dev)
         out_pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
         out_v = torch.empty((n,), dtype=torch.int64, device=dev)
-        pending = _PendingChain(self, ctx, dev, guided, bufs, out_pos, out_v, return_traj, _reuse_host_buffers,
+        settings = _ChainSettings(plan, bufs, gd)
+        pending = _PendingChain(self, ctx, dev, settings, bufs, out_pos, out_v, return_traj, _reuse_host_buffers,
                                 keep=(pos, v, batch, shape, eps, u, gd), offset=offset)
-        pending.field_dec = field_dec            # (the chain borrows the decoder's library context)
-        pending.n_groups = len(mesh_groups[0]) - 1 if isinstance(use_mesh_data, list) else 0
-        try:
+        try:        # (nothing is installed before this line: _ChainSettings' rule)
             with torch.cuda.device(dev):
                 cur = torch.cuda.current_stream(dev)
                 # hipGraph capture is not allowed on the legacy default stream: run the chain on a side stream
                 side = self._side_stream(dev, _slot)
                 side.wait_stream(cur)
-                if first_step:
-                    _lib.check(lib.shapemol_set_option(ctx, b"first_step", int(first_step)), "shapemol_set_option")
-                if cfg and cfg_groups is not None:
-                    off, stren, boxes = cfg_groups
-                    _lib.check(lib.shapemol_set_cfg_groups(ctx, len(stren), ptr(off), ptr(stren), _lib.CFG_THRESHOLDS[threshold_type], cfg_p,
-                                                           ptr(boxes), ptr(bufs.get("pos_uncond_traj")), ptr(bufs.get("v_uncond_traj"))),
-                               "shapemol_set_cfg_groups")
-                elif cfg:
-                    _lib.check(lib.shapemol_set_cfg(ctx, float(guide_stren), _lib.CFG_THRESHOLDS[threshold_type], cfg_p,
-                                                    ptr(cfg_box), ptr(bufs.get("pos_uncond_traj")), ptr(bufs.get("v_uncond_traj"))),
-                               "shapemol_set_cfg")
-                if field_dec is not None:
-                    _lib.check(lib.shapemol_set_field_guidance(ctx, field_dec._context(dev), grad_lr, int(grad_step)),
-                               "shapemol_set_field_guidance")
                 try:
+                    settings.install(lib, ctx, dev)
                     rc = lib.shapemol_sample(ctx, ptr(pos), ptr(v), ptr(batch), n, b, ptr(shape), int(num_steps),
                                              ptr(eps), ptr(u), C.c_uint64(seed), C.byref(tr), ptr(out_pos), ptr(out_v),
                                              1 if use_graph else 0, stream_ptr(side))
                 finally:
-                    if first_step:
-                        lib.shapemol_set_option(ctx, b"first_step", 0)
-                    if field_dec is not None:    # read when the chain is enqueued, like the classifier-free settings below
-                        lib.shapemol_set_field_guidance(ctx, None, 0.0, 0)
-                    if cfg and cfg_groups is not None:      # (the rows stay in device memory for the chain in flight)
-                        lib.shapemol_set_cfg_groups(ctx, 0, None, None, 0, 0.0, None, None, None)
-                    elif cfg:    # read when the chain is enqueued: the context goes back to unguided chains at once
-                        lib.shapemol_set_cfg(ctx, 0.0, 0, 0.0, None, None, None)
+                    settings.clear_enqueued(lib, ctx)
                 pending.side, pending.cur = side, cur
             _lib.check(rc, "shapemol_sample")
         except BaseException:
@@ -675,37 +598,35 @@ class ScorePosNet3D(nn.Module):
         torch.cuda.current_stream(t.device).synchronize()
         return h
 
+    @staticmethod
+    def _set_max_mol_atoms(ctx, batch, n):
+        """The largest molecule of the batch lets the library fold the per-layer coordinate update into the next attention
+        kernel (one tiny synchronising reduction per chain; the reference synchronises at every step)."""
+        most = int(torch.bincount(batch).max().item()) if n else 0
+        _lib.check(_lib.load().shapemol_set_option(ctx, b"max_mol_atoms", most), "shapemol_set_option")
+
     def _side_stream(self, dev, slot=0):
-        streams = self.__dict__.setdefault("_streams", {})
-        s = streams.get(slot)
-        if s is None or s.device != dev:
-            s = torch.cuda.Stream(device=dev)
-            streams[slot] = s
-        return s
+        s = self._slots[slot]
+        if s.stream is None or s.stream.device != dev:
+            s.stream = torch.cuda.Stream(device=dev)
+        return s.stream
 
 
 class _PendingChain:
     """A reverse chain that has been enqueued on its context's side stream (ScorePosNet3D.sample_diffusion(_async=True));
     result() waits for it, reads the status flags and builds the reference's result dict."""
 
-    def __init__(self, model, ctx, dev, guided, bufs, out_pos, out_v, return_traj, reuse, keep, offset=None):
+    def __init__(self, model, ctx, dev, settings, bufs, out_pos, out_v, return_traj, reuse, keep, offset=None):
         self.offset = offset                 # (N, 3) per-atom centre of its molecule (center_pos_mode='center') or None
-        self.model, self.ctx, self.dev, self.guided, self.bufs = model, ctx, dev, guided, bufs
+        # settings: the chain's _ChainSettings (its plan keeps the decoder of a field-guided chain alive until the chain is done)
+        self.model, self.ctx, self.dev, self.settings, self.bufs = model, ctx, dev, settings, bufs
         self.out_pos, self.out_v, self.return_traj, self.reuse, self.keep = out_pos, out_v, return_traj, reuse, keep
         self.side = self.cur = None
         self.done = False
-        self.n_groups = 0                    # mesh groups of a list-form chain (their unguided steps go into a MeshGuidanceError)
-        self.field_dec = None                # the decoder of a field-guided chain: kept alive until the chain is done
-
-    def _drop_guidance(self):
-        if self.guided:      # whatever happened, the context must not keep the cloud / mesh (and the caller-owned draws pointer) installed
-            kind, self.guided = self.guided, None
-            torch.cuda.synchronize(self.dev)
-            _clear_guidance(_lib.load(), self.ctx, kind)
 
     def abandon(self):
-        self.done = True
-        self._drop_guidance()
+        self.done = True     # whatever happened, the context must not keep the cloud / mesh (and the caller-owned draws pointer) installed
+        self.settings.clear_finished(_lib.load(), self.ctx, self.dev)
 
     def result(self):
         assert not self.done, "result() of a chain can be taken once"
@@ -716,12 +637,12 @@ class _PendingChain:
             flags = (C.c_int32 * 8)()
             rc = _lib.load().shapemol_status_stream(self.ctx, flags, stream_ptr(self.side))
             if rc and flags[_lib.ST_MESH] and not any(flags[i] for i in range(8) if i != _lib.ST_MESH):
-                if self.n_groups:
-                    raise _mesh_groups_error(_lib.load(), self.ctx, self.n_groups)
+                if self.settings.plan.n_mesh_groups:
+                    raise _mesh_groups_error(_lib.load(), self.ctx, self.settings.plan.n_mesh_groups)
                 raise _lib.MeshGuidanceError(f"mesh shape guidance: {_lib.load().shapemol_last_error().decode()}")
             _lib.check(rc, "input check")
         finally:
-            self._drop_guidance()
+            self.settings.clear_finished(_lib.load(), self.ctx, self.dev)
         self.cur.wait_stream(self.side)
         m, bufs = self.model, self.bufs
         for t_ in (*self.keep, self.out_pos, self.out_v, *bufs.values()):
@@ -754,242 +675,6 @@ class _PendingChain:
         else:
             res.update(pos_traj=[], v_traj=[], v0_traj=[], vt_traj=[], pos_cond_traj=[], v_cond_traj=[])
         return res
-
-
-def _field_decoder(shape_AE):
-    """The device ``DecoderInner`` behind ``sample_diffusion(shape_AE=...)``."""
-    from .shape_autoencoder import DecoderInner, PointCloud_AE
-    if shape_AE is None:
-        raise ValueError("use_grad=True needs shape_AE: a shapemol_amd.shape_autoencoder.PointCloud_AE or DecoderInner")
-    if isinstance(shape_AE, PointCloud_AE):
-        return shape_AE.generator
-    if isinstance(shape_AE, DecoderInner):
-        return shape_AE
-    raise TypeError(f"shape_AE is a {type(shape_AE).__module__}.{type(shape_AE).__name__}: gradient shape guidance runs on the device "
-                    "auto-encoder -- load its state dict into shapemol_amd.shape_autoencoder.PointCloud_AE and pass that")
-
-
-def pointcloud_shape_guidance(use_pointcloud_data, pred_ligand_pos, k=3, ratio=0.2, *, draws=None, seed=None):
-    """``pointcloud_shape_guidance`` of the reference (module level there too, ``models/molopt_score_model.py:699-740``) as
-    one device kernel: atoms of ``pred_ligand_pos`` (N,3) whose ``k`` = 3 nearest cloud points are on average farther than
-    ``radius`` are pulled towards their mean by ``u * (0.8 - ratio) + ratio``, up to five times; the tensor is updated in
-    place and returned.  ``use_pointcloud_data = (point_clouds, kdtree, radius)`` as there (the KD-tree is not used:
-    brute-force float64 search on the device).
-    Extensions (keyword-only): ``draws`` (5,N) float64 device tensor = the uniform of every (iteration, atom) (parity
-    mode); otherwise device Philox keyed by ``seed`` (default: drawn from numpy's global generator, which the reference's
-    function draws its uniforms from)."""
-    if k != 3:
-        raise NotImplementedError("the device kernel searches the reference's default k = 3 nearest cloud points")
-    pos, _, cloud, gd, seed = _standalone_inputs(pred_ligand_pos, draws, seed, lambda: _cloud_array(use_pointcloud_data[0]))
-    if pos.shape[0] == 0:
-        return pred_ligand_pos
-    with torch.cuda.device(pos.device):
-        rc = _lib.load().shapemol_pointcloud_guidance(ptr(cloud), cloud.shape[0], float(use_pointcloud_data[2]),
-                                                      float(ratio), ptr(pos), pos.shape[0], ptr(gd), C.c_uint64(seed), stream_ptr(pos.device))
-    _lib.check(rc, "shapemol_pointcloud_guidance")
-    return pred_ligand_pos
-
-
-def _cfg_groups(entries, bounds, n_mols):
-    """The list form of classifier-free guidance, ``[(guide_stren, n_mols), ...]`` with ``bounds`` (B,3,2), (3,2) or None, as the
-    arrays shapemol_set_cfg_groups takes: molecule offsets (G+1) int64, strengths (G) float64 and boxes (G,3,2) float64 or None
-    (each group's box is the row of its first molecule; a group without molecules gets a NaN row: no clamp).  Host logic only."""
-    if not entries:
-        raise ValueError("guide_stren: the list of groups is empty")
-    off, stren = [0], []
-    for i, e in enumerate(entries):
-        if not isinstance(e, (tuple, list)) or len(e) != 2:
-            raise ValueError(f"guide_stren[{i}] must be (guide_stren, n_mols)")
-        w, cnt = float(e[0]), int(e[1])
-        if cnt < 0:
-            raise ValueError(f"guide_stren[{i}]: n_mols must be >= 0")
-        if not np.isfinite(w):
-            raise ValueError(f"guide_stren[{i}]: the guidance strength must be finite")
-        stren.append(w)
-        off.append(off[-1] + cnt)
-    if off[-1] != n_mols:
-        raise ValueError(f"guide_stren: the groups hold {off[-1]} molecules, the batch has {n_mols}")
-    if len(stren) > _lib.CFG_MAX_GROUPS:
-        raise ValueError(f"guide_stren: {len(stren)} groups, a chain takes at most {_lib.CFG_MAX_GROUPS}")
-    boxes = None
-    if bounds is not None:
-        bx = bounds.detach().cpu().numpy() if isinstance(bounds, torch.Tensor) else np.asarray(bounds)
-        bx = np.asarray(bx, dtype=np.float64)
-        if bx.shape == (3, 2):
-            boxes = np.ascontiguousarray(np.broadcast_to(bx, (len(stren), 3, 2)))
-        elif bx.shape == (n_mols, 3, 2):
-            boxes = np.full((len(stren), 3, 2), np.nan)
-            for g in range(len(stren)):
-                if off[g + 1] > off[g]:
-                    boxes[g] = bx[off[g]]
-        else:
-            raise ValueError("bounds must be a (B, 3, 2) or (3, 2) box")
-    return np.asarray(off, dtype=np.int64), np.asarray(stren, dtype=np.float64), boxes
-
-
-def _guidance_groups(entries, n_mols):
-    """``[(point_clouds or None, kdtree, radius, n_mols), ...]`` -> (mol_off (G+1,) int64, clouds (sum P_g, 3) float64, cloud_off
-    (G+1,) int64, radii (G,) float64), host arrays for ``shapemol_set_guidance_groups``.  The groups' molecule counts must sum to
-    ``n_mols``.  Host logic only: the clouds' sizes and the radii are checked by the library, which names the offending group."""
-    if len(entries) == 0:
-        raise ValueError("use_pointcloud_data: the list of groups is empty")
-    counts, clouds, radii = [], [], []
-    for g, e in enumerate(entries):
-        if not isinstance(e, (tuple, list)) or len(e) != 4:
-            raise ValueError(f"use_pointcloud_data[{g}] must be (point_clouds, kdtree, radius, n_mols)")
-        cnt = int(e[3])
-        if cnt < 0:
-            raise ValueError(f"use_pointcloud_data[{g}]: n_mols < 0")
-        counts.append(cnt)
-        clouds.append(np.zeros((0, 3)) if e[0] is None else np.asarray(e[0], dtype=np.float64).reshape(-1, 3))
-        radii.append(1.0 if e[0] is None else float(e[2]))          # an unguided group's radius is not used
-    if sum(counts) != n_mols:
-        raise ValueError(f"use_pointcloud_data: the groups hold {sum(counts)} molecules, the batch has {n_mols}")
-    mol_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    cloud_off = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
-    return mol_off, np.ascontiguousarray(np.concatenate(clouds)), cloud_off, np.asarray(radii, dtype=np.float64)
-
-
-def _mesh_guidance_groups(entries, n_mols):
-    """``[(mesh or None, point_clouds, kdtree, n_mols), ...]`` -> (mol_off, verts (sum V_g, 3) float64, vert_off, faces (sum F_g, 3)
-    int32 with indices relative to the group's own vertices, face_off, clouds (sum P_g, 3) float64, cloud_off), offsets (G+1,)
-    int64: host arrays for ``shapemol_set_mesh_guidance_groups``.  The groups' molecule counts must sum to ``n_mols``.  Host logic
-    only; the library checks the meshes and clouds again and names the offending group."""
-    if len(entries) == 0:
-        raise ValueError("use_mesh_data: the list of groups is empty")
-    counts, verts, faces, clouds = [], [], [], []
-    for g, e in enumerate(entries):
-        if not isinstance(e, (tuple, list)) or len(e) != 4:
-            raise ValueError(f"use_mesh_data[{g}] must be (mesh, point_clouds, kdtree, n_mols)")
-        cnt = int(e[3])
-        if cnt < 0:
-            raise ValueError(f"use_mesh_data[{g}]: n_mols < 0")
-        counts.append(cnt)
-        v, f, c = (np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int32), np.zeros((0, 3))) if e[0] is None else _mesh_arrays(tuple(e[:3]))
-        verts.append(v), faces.append(f), clouds.append(c)
-    if sum(counts) != n_mols:
-        raise ValueError(f"use_mesh_data: the groups hold {sum(counts)} molecules, the batch has {n_mols}")
-    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)        # noqa: E731
-    return (np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), np.ascontiguousarray(np.concatenate(verts)), off(verts),
-            np.ascontiguousarray(np.concatenate(faces).astype(np.int32)), off(faces), np.ascontiguousarray(np.concatenate(clouds)),
-            off(clouds))
-
-
-def _mesh_groups_error(lib, ctx, n_groups):
-    """The MeshGuidanceError of a chain / pass with mesh groups: names the groups that were left unguided and in how many steps
-    (``.group_steps``: (G,) int32, from the library's per-group count)."""
-    steps = np.zeros(n_groups, dtype=np.int32)
-    got = lib.shapemol_debug_read(ctx, b"mesh_group_flags", ptr(steps), steps.nbytes)
-    bad = np.nonzero(steps)[0] if got == steps.nbytes else []
-    which = ", ".join(f"group {g} in {int(steps[g])} step(s)" for g in bad[:16]) + (" ..." if len(bad) > 16 else "")
-    err = _lib.MeshGuidanceError(
-        "mesh shape guidance per group of molecules: " + (which or "a group") + " had fewer than 3 atoms inside its mesh and > 0.4 "
-        "from its cloud (none at all, or fewer than 3 while atoms are to be pulled) and was left unguided there; the reference "
-        "raises ValueError from its KD-tree here.  The other groups were guided; the chain's result is not returned")
-    err.group_steps = steps if got == steps.nbytes else None
-    return err
-
-
-def _cloud_array(points):
-    return np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
-
-
-def _one_group(kind, data, n_mols):
-    """The tuple form ``(mesh, point_clouds, kdtree)`` / ``(point_clouds, kdtree, radius)`` as the payload of a set of ONE group
-    that spans the batch: the only place where the reference's form becomes the form the library runs.  The tuple's own argument
-    checks (and their texts) come first.  What the library itself rejects (a cloud of fewer than 3 or more than 2048 points, a
-    radius <= 0, a face that repeats a vertex, a non-finite vertex) is then reported by the groups setter, as "group 0"."""
-    if kind == "mesh_groups":
-        verts, faces, cloud = _mesh_arrays(data)
-        return _mesh_guidance_groups([((verts, faces), cloud, None, n_mols)], n_mols)
-    return _guidance_groups([(_cloud_array(data[0]), None, float(data[2]), n_mols)], n_mols)
-
-
-# setter of each kind of guidance, and the arguments that take the guidance out of the context again
-_GUIDANCE = {"mesh_groups": ("shapemol_set_mesh_guidance_groups", (0, None, None, None, None, None, None, None, 0, None)),
-             "groups": ("shapemol_set_guidance_groups", (0, None, None, None, None, 0, None))}
-
-
-def _install_guidance(lib, ctx, kind, payload, grad_step, gd):
-    """payload -- "mesh_groups": _mesh_guidance_groups' arrays; "groups": _guidance_groups' arrays."""
-    if kind == "mesh_groups":
-        mol_off, verts, vert_off, faces, face_off, clouds, cloud_off = payload
-        opt = lambda a: ptr(a) if len(a) else None      # noqa: E731
-        args = (len(mol_off) - 1, ptr(mol_off), opt(verts), ptr(vert_off), opt(faces), ptr(face_off), opt(clouds), ptr(cloud_off))
-    else:
-        mol_off, clouds, cloud_off, radii = payload
-        args = (len(radii), ptr(mol_off), ptr(clouds) if len(clouds) else None, ptr(cloud_off), ptr(radii))
-    _lib.check(getattr(lib, _GUIDANCE[kind][0])(ctx, *args, int(grad_step), ptr(gd)), _GUIDANCE[kind][0])
-
-
-def _clear_guidance(lib, ctx, kind):
-    name, off = _GUIDANCE[kind]
-    _lib.check(getattr(lib, name)(ctx, *off), name)
-
-
-def _standalone_inputs(pred_ligand_pos, draws, seed, payload, batch_ligand=None):
-    """Shared head of the stand-alone guidance functions, in the order their errors are raised: the (N, 3) tensor updated in place,
-    the batch vector (groups only), ``payload()``'s host arrays, the (5, N) draws, the default seed (numpy's global generator)."""
-    pos = _check_device_tensor("pred_ligand_pos", pred_ligand_pos, torch.float32)
-    if pos.data_ptr() != pred_ligand_pos.data_ptr() or pos.dim() != 2 or pos.shape[1] != 3:
-        raise ValueError("pred_ligand_pos must be a contiguous (N, 3) tensor (it is updated in place)")
-    batch = None if batch_ligand is None else _check_device_tensor("batch_ligand", batch_ligand, torch.int64)
-    arrays = payload()
-    gd = None if draws is None else _check_device_tensor("draws", draws, torch.float64)
-    bad_draws = gd is not None and tuple(gd.shape) != (5, pos.shape[0])
-    if bad_draws or (batch is not None and batch.shape != (pos.shape[0],)):
-        raise ValueError("draws must be (5, N) float64" if batch is None else "batch_ligand must be (N,) and draws (5, N) float64")
-    if seed is None:
-        seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64)) if gd is None else 0
-    return pos, batch, arrays, gd, seed
-
-
-def _mesh_arrays(use_mesh_data):
-    """(mesh, point_clouds, kdtree) -> contiguous (V,3) float64 vertices, (F,3) int32 faces, (P,3) float64 cloud.  The mesh is
-    duck-typed: ``.vertices`` / ``.faces`` (a ``trimesh.Trimesh``) or a ``(vertices, faces)`` pair."""
-    if not isinstance(use_mesh_data, (tuple, list)) or len(use_mesh_data) != 3:
-        raise NotImplementedError("use_mesh_data must be (mesh, point_clouds, kdtree), as the reference's sampling script builds it")
-    mesh, cloud = use_mesh_data[0], use_mesh_data[1]
-    if hasattr(mesh, "vertices") and hasattr(mesh, "faces"):
-        verts, faces = mesh.vertices, mesh.faces
-    elif isinstance(mesh, (tuple, list)) and len(mesh) == 2:
-        verts, faces = mesh
-    else:
-        raise NotImplementedError(f"a mesh of type {type(mesh).__name__}: give one with .vertices / .faces or a (vertices, faces) pair")
-    verts = np.ascontiguousarray(np.asarray(verts, dtype=np.float64))
-    faces = np.asarray(faces)
-    if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3 or len(faces) == 0:
-        raise ValueError("the mesh must have (V, 3) vertices and (F >= 1, 3) faces")
-    if faces.min() < 0 or faces.max() >= len(verts):
-        raise ValueError("a face names a vertex outside [0, V)")
-    faces = np.ascontiguousarray(faces.astype(np.int32))
-    cloud = cloud.detach().cpu().numpy() if isinstance(cloud, torch.Tensor) else cloud
-    return verts, faces, _cloud_array(cloud)
-
-
-def mesh_shape_guidance(use_mesh_data, pred_ligand_pos, k=3, ratio=0.5, *, draws=None, seed=None):
-    """``mesh_shape_guidance`` of the reference (``models/molopt_score_model.py:742-775``) as two device kernels: the atoms of
-    ``pred_ligand_pos`` (N,3) inside the mesh and > 0.4 from the cloud anchor the pull; every atom outside the mesh or < 0.2
-    from the cloud moves away from the mean of its 3 nearest anchors by ``u * 0.8 + 0.2`` and is accepted once inside the mesh
-    and > 0.2 from the cloud, up to five times; atoms never accepted keep their position.  The tensor is updated in place and
-    returned.  ``use_mesh_data = (mesh, point_clouds, kdtree)`` as there; the mesh is anything with ``.vertices`` / ``.faces``
-    or a ``(vertices, faces)`` pair, the KD-tree is not used (brute-force float64 searches on the device), and ``k`` / ``ratio``
-    are ignored, as the reference ignores them.  Containment is the parity of a fixed ray (``csrc/sm_mesh.h``), not trimesh's
-    code.  Raises ``ValueError`` (``_lib.MeshGuidanceError``) when fewer than 3 atoms are inside, as the reference's KD-tree.
-    Extensions (keyword-only): ``draws`` (5,N) float64 device tensor = the uniform of every (iteration, atom) (parity mode);
-    otherwise device Philox keyed by ``seed`` (default: drawn from numpy's global generator)."""
-    del k, ratio                 # the reference hard-codes 3 neighbours and the fraction u * 0.8 + 0.2
-    pos, _, (verts, faces, cloud), gd, seed = _standalone_inputs(pred_ligand_pos, draws, seed, lambda: _mesh_arrays(use_mesh_data))
-    if pos.shape[0] == 0:
-        raise _lib.MeshGuidanceError("mesh shape guidance: no atoms inside the mesh (the reference's KDTree of none raises)")
-    flag = C.c_int32(0)
-    with torch.cuda.device(pos.device):
-        rc = _lib.load().shapemol_mesh_guidance(ptr(verts), verts.shape[0], ptr(faces), faces.shape[0], ptr(cloud), cloud.shape[0],
-                                                ptr(pos), pos.shape[0], ptr(gd), C.c_uint64(seed), C.byref(flag), stream_ptr(pos.device))
-    if rc and flag.value:
-        raise _lib.MeshGuidanceError(_lib.load().shapemol_last_error().decode())
-    _lib.check(rc, "shapemol_mesh_guidance")
-    return pred_ligand_pos
 
 
 def log_sample_categorical(logits, *, u=None, seed=None):

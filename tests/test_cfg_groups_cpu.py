@@ -65,7 +65,7 @@ def test_fixture_groups_differ_and_clamp(tag):
 
 
 def test_cfg_groups_host_arrays():
-    from shapemol_amd.molopt_score_model import _cfg_groups
+    from shapemol_amd.guidance import _cfg_groups
     bounds = np.arange(6 * 6, dtype=np.float64).reshape(6, 3, 2)
     off, w, boxes = _cfg_groups([(0.7, 2), (1.5, 3), (0.0, 1)], bounds, 6)
     assert off.dtype == np.int64 and list(off) == [0, 2, 5, 6] and list(w) == [0.7, 1.5, 0.0]

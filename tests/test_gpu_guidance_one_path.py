@@ -133,6 +133,35 @@ def test_single_mesh_with_odd_cloud_sizes(points):
     _same(got, ref, pred)
 
 
+@pytest.mark.parametrize("slot", (0, 1))
+def test_a_refused_guided_chain_leaves_the_context_unguided(slot):
+    """A tuple-form mesh chain that the library refuses AFTER its set (and the caller's draws pointer) has been installed --
+    num_steps = T + 1 is an error return of shapemol_sample, before any launch -- takes the set out again: the same unguided
+    chain before and after it is bit-equal on that context, and runs the same launch forms."""
+    from shapemol_amd import _lib
+    m = hip_model()
+    bb = synth.synthetic_batch(2, seed=11)
+    n, steps_max = len(bb["batch"]), int(m.num_timesteps)
+    args = (T(bb["init_pos"], DEV), T(bb["init_v"], DEV), T(bb["batch"], DEV), T(bb["shape"], DEV).view(2, -1))
+    plain = dict(num_steps=2, center_pos_mode="none", seed=9, _slot=slot)
+
+    def forms():
+        rec = np.zeros(8, np.int64)
+        assert _lib.load().shapemol_debug_read(m._context(torch.device(DEV), slot), b"launch", _vp(rec), rec.nbytes) == rec.nbytes
+        return rec.tolist()
+    first = m.sample_diffusion(*args, **plain)
+    first_forms = forms()
+    verts, faces, cloud, _, _ = _mesh_case()
+    draws = torch.zeros((steps_max + 1, 5, n), dtype=torch.float64, device=DEV)
+    with pytest.raises(_lib.ShapeMolLibraryError, match="num_steps out of range"):
+        m.sample_diffusion(*args, num_steps=steps_max + 1, center_pos_mode="none", seed=9, _slot=slot, return_traj=False,
+                           use_mesh_data=((verts, faces), cloud, None), guide_draws=draws)
+    del draws
+    again = m.sample_diffusion(*args, **plain)
+    assert torch.equal(again["pos"], first["pos"]) and torch.equal(again["v"], first["v"])
+    assert forms() == first_forms
+
+
 def _chain_inputs(name, n_mols=None):
     """The fixture's batch, or its first n_mols molecules as a batch of their own (with their per-atom noise)."""
     c = golden(name)

@@ -228,7 +228,7 @@ def test_group_without_atoms_inside_raises_mesh_guidance_error():
     bad[2], bad[1] = groups[2], ((groups[1][0][0], f_bad), groups[1][1], None, 3)
     with pytest.raises(_lib.ShapeMolLibraryError, match=r"group 1: face 7 repeats a vertex"):
         run(m, bb, eps, u, B, S, use_mesh_data=bad, grad_step=990)
-    from shapemol_amd.molopt_score_model import _clear_guidance, _install_guidance, _mesh_guidance_groups
+    from shapemol_amd.guidance import _clear_guidance, _install_guidance, _mesh_guidance_groups
     lib, ctx = _lib.load(), m._context(torch.device(DEV))
     _install_guidance(lib, ctx, "mesh_groups", _mesh_guidance_groups([(groups[0][0], groups[0][1], None, 5)], 5), 990, None)
     try:

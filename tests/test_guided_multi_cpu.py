@@ -130,7 +130,7 @@ def test_argument_checks_raise_before_the_library_is_loaded(monkeypatch):
 
 
 def test_group_arrays():
-    from shapemol_amd.molopt_score_model import _guidance_groups
+    from shapemol_amd.guidance import _guidance_groups
     a, b = np.arange(12.0).reshape(4, 3), np.arange(9.0).reshape(3, 3) + 100
     mol_off, clouds, cloud_off, radii = _guidance_groups([(a, None, 0.2, 2), (None, None, None, 1), (b, "tree", 0.3, 4)], 7)
     assert mol_off.tolist() == [0, 2, 3, 7] and mol_off.dtype == np.int64

@@ -188,7 +188,7 @@ def test_argument_checks_raise_before_the_library_is_loaded(monkeypatch):
 
 
 def test_group_arrays():
-    from shapemol_amd.molopt_score_model import _mesh_guidance_groups
+    from shapemol_amd.guidance import _mesh_guidance_groups
     (v0, f0, c0), (v1, f1, c1), _ = meshes()
 
     class TrimeshLike:

@@ -86,7 +86,7 @@ def test_fragile_caps_of_the_gpu_cases():
 
 
 def test_host_side_refusals():
-    from shapemol_amd.molopt_score_model import _field_decoder
+    from shapemol_amd.guidance import _field_decoder
     from shapemol_amd.shape_autoencoder import DecoderInner
     with pytest.raises(ValueError, match="shape_AE"):
         _field_decoder(None)
