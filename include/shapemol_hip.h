@@ -287,6 +287,30 @@ int64_t shapemol_se_max_points(const shapemol_se_ctx *ctx);
 enum { SHAPEMOL_SE_IDX = 0, SHAPEMOL_SE_H0 = 1, SHAPEMOL_SE_HCAT = 2, SHAPEMOL_SE_Y = 3, SHAPEMOL_SE_XX = 4, SHAPEMOL_SE_PD = 5 };
 int shapemol_se_debug_stop_after(shapemol_se_ctx *ctx, int32_t n_blocks);
 int shapemol_se_debug_read(shapemol_se_ctx *ctx, int32_t what, void *h_dst, size_t n_bytes);
+/* Training the encoder: every parameter's gradient; none to the points, none through the neighbour lists.
+ * Deterministic: no floating-point atomics, the latent and every gradient are bit-identical from run to run.
+ * _load_weights repacks the context's weights from d_weights (DEVICE, the flat vector in the order of _create's `weights`) with a
+ * kernel on `stream`: after an optimiser step no host packing and no new context.
+ * _train_forward is _encode with batch statistics summed in a fixed order, and leaves what the backward needs in CALLER-OWNED
+ * device buffers (a later forward on the context cannot touch them), L = layer_num, P = B*N:
+ *   d_idx (L+1,P,20) i32 the neighbour lists of conv_pos and of every block; d_h0 (P,C,3); d_hcat (P,L,C,3); d_pd (P,latent+1,3);
+ *   d_stats (L+2,2,256) f64: per stage (conv_pos, the blocks, conv_c) the batch mean and the biased batch variance per channel.
+ * _train_backward takes them back with the latent's gradient d_grad_out (B,latent,3) -- or, for a staged check, d_grad_hcat (P,L,C,3),
+ * the gradient at conv_c's input, with conv_c skipped and its gradients zero; exactly one of the two is non-NULL -- and writes
+ * d_grad_w, shapemol_se_weight_count floats in the weights' order.  Y = W' h is recomputed per block, not saved.
+ * d_masks (diagnostic, may be NULL): (L+2,P,256) i32, per stage the leaky-ReLU branches the backward took: for conv_pos and the blocks
+ * bit kk of [i][c] is set where edge (i, kk) of channel c had dot < 0, for conv_c [p][m] is 1 where row m had; written only by
+ * the stages that run.  The training calls do not feed _debug_read, which keeps referring to the last _encode.
+ * Both calls work in d_ws, a caller-owned device buffer of at least _train_workspace(ctx, B, N) bytes aligned to 256 bytes, whose
+ * contents mean nothing between calls.  Shapes as _encode; refusals come with a message before any launch. */
+int shapemol_se_load_weights(shapemol_se_ctx *ctx, const float *d_weights, size_t n_weights, void *stream);
+size_t shapemol_se_train_workspace(const shapemol_se_ctx *ctx, int64_t n_shapes, int64_t n_points);
+int shapemol_se_train_forward(shapemol_se_ctx *ctx, const float *d_points, int64_t n_shapes, int64_t n_points, int32_t *d_idx, float *d_h0,
+                              float *d_hcat, double *d_stats, float *d_pd, float *d_out, void *d_ws, size_t ws_bytes, void *stream);
+int shapemol_se_train_backward(shapemol_se_ctx *ctx, const float *d_points, int64_t n_shapes, int64_t n_points, const int32_t *d_idx,
+                               const float *d_h0, const float *d_hcat, const double *d_stats, const float *d_pd, const float *d_grad_out,
+                               const float *d_grad_hcat, float *d_grad_w, int32_t *d_masks, void *d_ws, size_t ws_bytes,
+                               void *stream);
 
 /* ---- shape decoder: the auto-encoder's implicit field --------------------------------------------------------------
  * DecoderInner.forward (models/shape_pointcloud_modelAE.py:21-103, blocks: ResnetBlockFC, models/shape_vn_layers.py:210-252):

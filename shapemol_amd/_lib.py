@@ -29,6 +29,7 @@ EXPORTS = (
     "shapemol_set_bn_running",
     "shapemol_se_weight_count", "shapemol_se_create", "shapemol_se_destroy", "shapemol_se_encode",
     "shapemol_se_max_points", "shapemol_se_debug_stop_after", "shapemol_se_debug_read",
+    "shapemol_se_load_weights", "shapemol_se_train_workspace", "shapemol_se_train_forward", "shapemol_se_train_backward",
     "shapemol_sd_weight_count", "shapemol_sd_create", "shapemol_sd_destroy", "shapemol_sd_decode",
     "shapemol_sd_tile", "shapemol_sd_debug_read", "shapemol_field_decode_grad", "shapemol_field_guide", "shapemol_field_grad_tile",
     "shapemol_set_field_guidance", "shapemol_field_train", "shapemol_field_load_weights", "shapemol_field_train_tile",
@@ -150,6 +151,11 @@ def load():
     lib.shapemol_se_max_points.restype = i64
     lib.shapemol_se_debug_stop_after.argtypes = [vp, i32]
     lib.shapemol_se_debug_read.argtypes = [vp, i32, vp, C.c_size_t]
+    lib.shapemol_se_load_weights.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.shapemol_se_train_workspace.restype = C.c_size_t
+    lib.shapemol_se_train_workspace.argtypes = [vp, i64, i64]
+    lib.shapemol_se_train_forward.argtypes = [vp, vp, i64, i64] + [vp] * 7 + [C.c_size_t, vp]
+    lib.shapemol_se_train_backward.argtypes = [vp, vp, i64, i64] + [vp] * 10 + [C.c_size_t, vp]
     lib.shapemol_sd_weight_count.restype = C.c_size_t
     lib.shapemol_sd_weight_count.argtypes = [i32, i32, i32]
     lib.shapemol_sd_create.argtypes = [i32, i32, i32, i32, vp, C.c_size_t, C.c_int, C.POINTER(vp)]

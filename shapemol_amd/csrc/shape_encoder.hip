@@ -1,7 +1,8 @@
 // C ABI of the device shape encoder (include/shapemol_hip.h, shapemol_se_*): VN_DGCNN_Encoder.forward of the reference
-// (models/shape_pointcloud_modelAE.py:207-255).  Kernels: sm_shape.h.
+// (models/shape_pointcloud_modelAE.py:207-255), its training variant and its backward.  Kernels: sm_shape.h, sm_shape_train.h.
 #include "../../include/shapemol_hip.h"
 #include "sm_shape.h"
+#include "sm_shape_train.h"
 #include "sm_devmem.h"
 #include "sm_host.h"
 
@@ -27,6 +28,57 @@ struct shapemol_se_ctx {
     int *idx = nullptr;
     double *acc = nullptr;
 };
+
+namespace {
+// the workspace of an encode of P points (the context's; shapemol_se_encode and shapemol_se_train_forward share it)
+int se_grow(shapemol_se_ctx *c, int64_t P) {
+    const int C = c->C, L = c->L, LAT = c->LAT;
+    SMCHK(grow(c->mem_P, {dev_buf(&c->h0, P * C * 3 * 4), dev_buf(&c->hcat, P * L * C * 3 * 4), dev_buf(&c->y, P * 4 * C * 3 * 4), dev_buf(&c->xx, P * 4),
+                          dev_buf(&c->pd, P * (LAT + 1) * 3 * 4), dev_buf(&c->idx, P * kSeK * 4), dev_buf(&c->acc, (size_t)kSeReplicas * 2 * 256 * 8)},
+               c->capP, P));
+    return 0;
+}
+
+// the caller's workspace of a training call on P points: byte offsets of its parts, and the split geometry of the two weight products
+struct SeTrainWs {
+    size_t y, dY, dhcat, dh0, gpd, deg, rowptr, rev, part, S, wT, pw, total;
+    int parts, n_groups, dw_splits, dw_per, head_splits, head_per;
+};
+SeTrainWs se_train_ws(const shapemol_se_ctx *c, int64_t P) {
+    const size_t C = c->C, L = c->L, LAT = c->LAT, p = (size_t)P;
+    SeTrainWs w{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
+    w.parts = (int)(P < kSeParts ? P : kSeParts);
+    w.n_groups = (int)(P / 16);
+    int s = w.n_groups / 8; s = s < 1 ? 1 : (s > kSeDwMaxSplits ? kSeDwMaxSplits : s);
+    w.dw_per = (w.n_groups + s - 1) / s; w.dw_splits = (w.n_groups + w.dw_per - 1) / w.dw_per;
+    int hs = (int)(P / 128); hs = hs < 1 ? 1 : (hs > 32 ? 32 : hs);
+    w.head_per = (int)((P + hs - 1) / hs); w.head_splits = (int)((P + w.head_per - 1) / w.head_per);
+    w.y = take(p * 4 * C * 3 * 4); w.dY = take(p * 4 * C * 3 * 4); w.dhcat = take(p * L * C * 3 * 4); w.dh0 = take(p * C * 3 * 4);
+    w.gpd = take(p * (LAT + 1) * 3 * 4); w.deg = take(p * 4); w.rowptr = take(p * 4); w.rev = take(p * kSeK * 4);
+    w.part = take((size_t)kSeParts * kSePartQ * kSeCh * 8); w.S = take((size_t)kSePartQ * kSeCh * 8); w.wT = take(4 * C * C * 4);
+    const size_t pw_edge = (size_t)4 * w.dw_splits * C * C * 4, pw_head = (size_t)w.head_splits * (LAT + 1) * L * C * 8;
+    w.pw = take(pw_edge > pw_head ? pw_edge : pw_head);
+    w.total = o;
+    return w;
+}
+
+// the shape limits of shapemol_se_encode, for the training calls
+int se_check_shape(const shapemol_se_ctx *c, const char *who, int64_t B, int64_t N) {
+    if (B < 1 || B > 65535 || N < 32 || (N % 16) != 0 || N > c->max_n || B * N > (1 << 24))
+        return sm_fail(std::string(who) + ": need 1 <= B <= 65535, N a multiple of 16 in [32, " + std::to_string(c->max_n) + "] (16 * N * 4 bytes of the " +
+                       std::to_string(c->lds_limit) + " bytes of LDS a workgroup can have on this device) and B * N <= 2^24; got B = " +
+                       std::to_string(B) + ", N = " + std::to_string(N));
+    return 0;
+}
+int se_check_ws(const SeTrainWs &w, const char *who, const void *d_ws, size_t ws_bytes) {
+    if (!d_ws || ((uintptr_t)d_ws & 255) != 0) return sm_fail(std::string(who) + ": the workspace must be a device buffer aligned to 256 bytes");
+    if (ws_bytes < w.total)
+        return sm_fail(std::string(who) + ": the workspace has " + std::to_string(ws_bytes) + " bytes, shapemol_se_train_workspace asks for " + std::to_string(w.total));
+    return 0;
+}
+}  // namespace
 
 extern "C" {
 
@@ -107,9 +159,7 @@ int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int
     hipStream_t s = (hipStream_t)stream;
     const int C = c->C, L = c->L, LAT = c->LAT;
     const int64_t P = B * N;
-    SMCHK(grow(c->mem_P, {dev_buf(&c->h0, P * C * 3 * 4), dev_buf(&c->hcat, P * L * C * 3 * 4), dev_buf(&c->y, P * 4 * C * 3 * 4), dev_buf(&c->xx, P * 4),
-                          dev_buf(&c->pd, P * (LAT + 1) * 3 * 4), dev_buf(&c->idx, P * kSeK * 4), dev_buf(&c->acc, (size_t)kSeReplicas * 2 * 256 * 8)},
-               c->capP, P));
+    if (se_grow(c, P)) return 1;
     c->lastP = P;
     const size_t knn_lds = (size_t)16 * N * sizeof(float);      // <= lds_limit (N <= max_n)
     SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
@@ -150,6 +200,163 @@ int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int
 }
 
 int64_t shapemol_se_max_points(const shapemol_se_ctx *c) { return c ? c->max_n : 0; }
+
+int shapemol_se_load_weights(shapemol_se_ctx *c, const float *d_weights, size_t n_weights, void *stream) {
+    if (!c || !d_weights) return sm_fail("shapemol_se_load_weights: null argument");
+    if (n_weights != shapemol_se_weight_count(c->C, c->LAT, c->L))
+        return sm_fail("shapemol_se_load_weights: weight count mismatch: the context holds " + std::to_string(shapemol_se_weight_count(c->C, c->LAT, c->L)) +
+                       " weights, got " + std::to_string(n_weights));
+    SMCHK(hipSetDevice(c->device));
+    SeLoadArgs a{};
+    a.src = d_weights; a.dst = c->d_w; a.L = c->L; a.LAT = c->LAT;
+    a.o_pos_wf = (unsigned)c->o_pos_wf; a.o_pos_g = (unsigned)c->o_pos_g; a.o_pos_b = (unsigned)c->o_pos_b; a.o_pos_wd = (unsigned)c->o_pos_wd;
+    a.o_c_wf = (unsigned)c->o_c_wf; a.o_c_g = (unsigned)c->o_c_g; a.o_c_b = (unsigned)c->o_c_b; a.o_c_wd = (unsigned)c->o_c_wd;
+    for (int l = 0; l < c->L; ++l) { a.o_img[l] = (unsigned)c->o_img[l]; a.o_g[l] = (unsigned)c->o_g[l]; a.o_b[l] = (unsigned)c->o_b[l]; }
+    hipLaunchKernelGGL(se_load_weights_kernel, dim3((unsigned)((n_weights + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    SMCHK(hipGetLastError());
+    return 0;
+}
+
+size_t shapemol_se_train_workspace(const shapemol_se_ctx *c, int64_t B, int64_t N) {
+    if (!c || B < 1 || N < 1 || B * N > (1 << 24)) return 0;
+    return se_train_ws(c, B * N).total;
+}
+
+int shapemol_se_train_forward(shapemol_se_ctx *c, const float *d_points, int64_t B, int64_t N, int32_t *d_idx, float *d_h0, float *d_hcat,
+                              double *d_stats, float *d_pd, float *d_out, void *d_ws, size_t ws_bytes, void *stream) {
+    const char *who = "shapemol_se_train_forward";
+    if (!c || !d_points || !d_idx || !d_h0 || !d_hcat || !d_stats || !d_pd || !d_out) return sm_fail(std::string(who) + ": null argument");
+    if (se_check_shape(c, who, B, N)) return 1;
+    const int64_t P = B * N;
+    const SeTrainWs ws = se_train_ws(c, P);
+    if (se_check_ws(ws, who, d_ws, ws_bytes)) return 1;
+    SMCHK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int C = c->C, L = c->L, LAT = c->LAT;
+    if (se_grow(c, P)) return 1;
+    double *part = (double *)((char *)d_ws + ws.part);
+    const size_t knn_lds = (size_t)16 * N * sizeof(float);      // <= lds_limit (N <= max_n)
+    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
+    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3 * kC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
+    const float *W = c->d_w;
+    const dim3 knn_grid((unsigned)(N / 16), (unsigned)B);
+    const double edges = (double)P * kSeK;
+    // conv_pos on the raw points
+    hipLaunchKernelGGL(se_knn_kernel<3>, knn_grid, dim3(256), knn_lds, s, d_points, 3, nullptr, (int)N, d_idx);
+    SeEdgeArgs e{};
+    e.x = d_points; e.w0f = W + c->o_pos_wf; e.w0d = W + c->o_pos_wd; e.idx = d_idx; e.bn_g = W + c->o_pos_g; e.bn_b = W + c->o_pos_b;
+    e.acc = c->acc; e.h_out = d_h0; e.n_total = (int)P; e.N = (int)N; e.C = C; e.h_ld = 3 * C; e.h_off = 0;
+    hipLaunchKernelGGL(se_edge_stats_part_kernel<true>, dim3(ws.parts), dim3(C), 0, s, e, part);
+    hipLaunchKernelGGL(se_stats_reduce_kernel, dim3(1), dim3(256), 0, s, part, ws.parts, C, edges, c->acc, d_stats);
+    hipLaunchKernelGGL(se_edge_apply_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
+    for (int l = 0; l < L; ++l) {
+        const float *hin = l == 0 ? d_h0 : d_hcat + (size_t)(l - 1) * 3 * C;
+        const int ld = l == 0 ? 3 * C : L * 3 * C;
+        int32_t *idx = d_idx + (size_t)(l + 1) * P * kSeK;
+        hipLaunchKernelGGL(se_sqnorm_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s, hin, (int)P, 3 * C, ld, c->xx);
+        hipLaunchKernelGGL(se_knn_kernel<3 * kC>, knn_grid, dim3(256), knn_lds, s, hin, ld, c->xx, (int)N, idx);
+        hipLaunchKernelGGL(se_point_linear_kernel<kC>, dim3((unsigned)((P * 3 + 15) / 16)), dim3(256), 0, s, hin, ld, W + c->o_img[l], (int)(P * 3), 4 * C, c->y);
+        SeEdgeArgs b{};
+        b.y = c->y; b.idx = idx; b.bn_g = W + c->o_g[l]; b.bn_b = W + c->o_b[l]; b.acc = c->acc; b.h_out = d_hcat;
+        b.n_total = (int)P; b.N = (int)N; b.C = C; b.h_ld = L * 3 * C; b.h_off = l * 3 * C;
+        hipLaunchKernelGGL(se_edge_stats_part_kernel<false>, dim3(ws.parts), dim3(C), 0, s, b, part);
+        hipLaunchKernelGGL(se_stats_reduce_kernel, dim3(1), dim3(256), 0, s, part, ws.parts, C, edges, c->acc, d_stats + (size_t)(l + 1) * 2 * kSeCh);
+        hipLaunchKernelGGL(se_edge_apply_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
+    }
+    // conv_c + mean over the points (se_head_linear_kernel's own sums go into the accumulator the reducer then overwrites)
+    SeHeadArgs ha{d_hcat, W + c->o_c_wf, W + c->o_c_wd, W + c->o_c_g, W + c->o_c_b, d_pd, c->acc, d_out, (int)P, (int)N, L * C, LAT};
+    SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
+    hipLaunchKernelGGL(se_head_linear_kernel, dim3((unsigned)((P * (LAT + 1) + 3) / 4)), dim3(256), 0, s, ha);
+    hipLaunchKernelGGL(se_head_stats_part_kernel, dim3(ws.parts), dim3(256), 0, s, d_pd, (int)P, LAT, part);
+    hipLaunchKernelGGL(se_stats_reduce_kernel, dim3(1), dim3(256), 0, s, part, ws.parts, LAT, (double)P, c->acc, d_stats + (size_t)(L + 1) * 2 * kSeCh);
+    hipLaunchKernelGGL(se_head_apply_kernel, dim3((unsigned)(B * LAT)), dim3(256), 0, s, ha);
+    SMCHK(hipGetLastError());
+    return 0;
+}
+
+int shapemol_se_train_backward(shapemol_se_ctx *c, const float *d_points, int64_t B, int64_t N, const int32_t *d_idx, const float *d_h0,
+                               const float *d_hcat, const double *d_stats, const float *d_pd, const float *d_grad_out, const float *d_grad_hcat,
+                               float *d_grad_w, int32_t *d_masks, void *d_ws, size_t ws_bytes, void *stream) {
+    const char *who = "shapemol_se_train_backward";
+    if (!c || !d_points || !d_idx || !d_h0 || !d_hcat || !d_stats || !d_pd || !d_grad_w) return sm_fail(std::string(who) + ": null argument");
+    if ((d_grad_out == nullptr) == (d_grad_hcat == nullptr)) return sm_fail(std::string(who) + ": give the latent's gradient or hcat's, not both");
+    if (se_check_shape(c, who, B, N)) return 1;
+    const int64_t P = B * N;
+    const SeTrainWs ws = se_train_ws(c, P);
+    if (se_check_ws(ws, who, d_ws, ws_bytes)) return 1;
+    SMCHK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int C = c->C, L = c->L, LAT = c->LAT, KC = L * C;
+    char *wb = (char *)d_ws;
+    float *y = (float *)(wb + ws.y), *dY = (float *)(wb + ws.dY), *dhcat = (float *)(wb + ws.dhcat), *dh0 = (float *)(wb + ws.dh0), *gpd = (float *)(wb + ws.gpd);
+    int *deg = (int *)(wb + ws.deg), *rowptr = (int *)(wb + ws.rowptr), *rev = (int *)(wb + ws.rev);
+    double *part = (double *)(wb + ws.part), *S = (double *)(wb + ws.S);
+    float *wT = (float *)(wb + ws.wT), *pw = (float *)(wb + ws.pw);
+    const float *W = c->d_w;
+    // the gradient vector, in the weights' order
+    const size_t blk = (size_t)4 * C * C + 2 * C, n_cwf = (size_t)LAT * KC;
+    float *g_pos = d_grad_w, *g_blocks = d_grad_w + 6 * C, *g_c = g_blocks + L * blk;
+    const double *st_c = d_stats + (size_t)(L + 1) * 2 * kSeCh;
+    if (d_grad_hcat) {
+        SMCHK(hipMemcpyAsync(dhcat, d_grad_hcat, (size_t)P * KC * 3 * 4, hipMemcpyDeviceToDevice, s));
+        SMCHK(hipMemsetAsync(g_c, 0, (n_cwf + 2 * LAT + KC) * 4, s));
+    } else {
+        SeHeadBwdArgs hb{d_hcat, W + c->o_c_wf, W + c->o_c_wd, W + c->o_c_g, W + c->o_c_b, d_pd, st_c, S, d_grad_out, gpd, dhcat,
+                         d_masks ? d_masks + (size_t)(L + 1) * P * kSeCh : nullptr, (int)P, (int)N, KC, LAT};
+        hipLaunchKernelGGL(se_head_bwd_sums_kernel, dim3(ws.parts), dim3(256), 0, s, hb, part);
+        SeSumDst o{};
+        o.dst[0] = g_c + n_cwf + LAT; o.stride[0] = 1; o.dst[1] = g_c + n_cwf; o.stride[1] = 1;          // S1 = dbeta, S2 = dgamma
+        hipLaunchKernelGGL(se_part_reduce_kernel, dim3(2), dim3(256), 0, s, part, ws.parts, 2, LAT, S, o);
+        hipLaunchKernelGGL(se_head_bwd_point_kernel, dim3((unsigned)P), dim3(256), 0, s, hb);
+        const unsigned eb = (unsigned)(((size_t)(LAT + 1) * KC + 255) / 256);
+        hipLaunchKernelGGL(se_head_bwd_dw_kernel, dim3(eb, ws.head_splits), dim3(256), 0, s, hb, ws.head_per, (double *)pw);
+        hipLaunchKernelGGL(se_head_bwd_dw_finish_kernel, dim3(eb), dim3(256), 0, s, (const double *)pw, ws.head_splits, LAT, KC, g_c, g_c + n_cwf + 2 * LAT);
+    }
+    for (int l = L - 1; l >= 0; --l) {
+        const float *hin = l == 0 ? d_h0 : d_hcat + (size_t)(l - 1) * 3 * C;
+        const int ld = l == 0 ? 3 * C : L * 3 * C;
+        const int32_t *idx = d_idx + (size_t)(l + 1) * P * kSeK;
+        float *gl = g_blocks + l * blk;
+        SMCHK(hipMemsetAsync(deg, 0, (size_t)P * 4, s));
+        hipLaunchKernelGGL(se_deg_kernel, dim3((unsigned)((P * kSeK + 255) / 256)), dim3(256), 0, s, idx, (int)P, (int)N, deg);
+        hipLaunchKernelGGL(se_rowptr_kernel, dim3((unsigned)B), dim3(256), 0, s, deg, (int)N, rowptr);
+        hipLaunchKernelGGL(se_rev_fill_kernel, dim3((unsigned)(N / 16), (unsigned)B), dim3(256), 0, s, idx, (int)N, rowptr, rev);
+        hipLaunchKernelGGL(se_point_linear_kernel<kC>, dim3((unsigned)((P * 3 + 15) / 16)), dim3(256), 0, s, hin, ld, W + c->o_img[l], (int)(P * 3), 4 * C, y);
+        SeBwdArgs a{};
+        a.e.y = y; a.e.idx = idx; a.e.bn_g = W + c->o_g[l]; a.e.bn_b = W + c->o_b[l]; a.e.n_total = (int)P; a.e.N = (int)N; a.e.C = C;
+        a.stats = d_stats + (size_t)(l + 1) * 2 * kSeCh; a.dH = dhcat; a.dh_ld = L * 3 * C; a.dh_off = l * 3 * C;
+        a.deg = deg; a.rowptr = rowptr; a.rev = rev; a.dY = dY; a.mask = d_masks ? d_masks + (size_t)(l + 1) * P * kSeCh : nullptr;
+        hipLaunchKernelGGL((se_edge_bwd_sums_kernel<false, 0>), dim3(ws.parts), dim3(C), 0, s, a, part);
+        SeSumDst o{};
+        o.dst[0] = gl + 2 * C * C + C; o.stride[0] = 1; o.dst[1] = gl + 2 * C * C; o.stride[1] = 1;
+        hipLaunchKernelGGL(se_part_reduce_kernel, dim3(2), dim3(256), 0, s, part, ws.parts, 2, C, S, o);
+        a.S = S;
+        hipLaunchKernelGGL(se_edge_bwd_gather_kernel, dim3((unsigned)P), dim3(C), 0, s, a);
+        hipLaunchKernelGGL(se_wimg_transpose_kernel<kC>, dim3(4 * C * C / 256), dim3(256), 0, s, W + c->o_img[l], wT);
+        hipLaunchKernelGGL(se_dhin_kernel<kC>, dim3((unsigned)((P * 3 + 15) / 16)), dim3(256), 0, s, dY, wT, (int)(P * 3), l == 0 ? dh0 : dhcat,
+                           l == 0 ? 3 * C : L * 3 * C, l == 0 ? 0 : (l - 1) * 3 * C, l == 0 ? 0 : 1);
+        hipLaunchKernelGGL(se_dw_kernel, dim3(4, ws.dw_splits), dim3(256), 0, s, dY, hin, ld, ws.n_groups, ws.dw_per, pw);
+        hipLaunchKernelGGL(se_dw_finish_kernel, dim3(C * C / 256), dim3(256), 0, s, pw, ws.dw_splits, gl, gl + 2 * C * C + 2 * C);
+    }
+    {   // conv_pos: one input channel, its weight gradients are direct sums over the edges
+        SeBwdArgs a{};
+        a.e.x = d_points; a.e.w0f = W + c->o_pos_wf; a.e.w0d = W + c->o_pos_wd; a.e.idx = d_idx; a.e.bn_g = W + c->o_pos_g; a.e.bn_b = W + c->o_pos_b;
+        a.e.n_total = (int)P; a.e.N = (int)N; a.e.C = C;
+        a.stats = d_stats; a.dH = dh0; a.dh_ld = 3 * C; a.dh_off = 0; a.mask = d_masks;
+        hipLaunchKernelGGL((se_edge_bwd_sums_kernel<true, 0>), dim3(ws.parts), dim3(C), 0, s, a, part);
+        SeSumDst o{};
+        o.dst[0] = g_pos + 3 * C; o.stride[0] = 1; o.dst[1] = g_pos + 2 * C; o.stride[1] = 1;
+        hipLaunchKernelGGL(se_part_reduce_kernel, dim3(2), dim3(256), 0, s, part, ws.parts, 2, C, S, o);
+        a.S = S;
+        hipLaunchKernelGGL((se_edge_bwd_sums_kernel<true, 1>), dim3(ws.parts), dim3(C), 0, s, a, part);
+        SeSumDst w{};
+        w.dst[0] = g_pos; w.dst[1] = g_pos + 1; w.dst[2] = g_pos + 4 * C; w.dst[3] = g_pos + 4 * C + 1;
+        w.stride[0] = w.stride[1] = w.stride[2] = w.stride[3] = 2;
+        hipLaunchKernelGGL(se_part_reduce_kernel, dim3(4), dim3(256), 0, s, part, ws.parts, 4, C, S + 2 * kSeCh, w);
+    }
+    SMCHK(hipGetLastError());
+    return 0;
+}
 
 int shapemol_se_debug_stop_after(shapemol_se_ctx *c, int32_t n_blocks) {
     if (!c) return sm_fail("shapemol_se_debug_stop_after: null argument");

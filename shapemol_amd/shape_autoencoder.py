@@ -13,7 +13,8 @@ Inference has one derivative, the field's gradient with respect to the query poi
 autograd function ``field`` and the guidance pass ``guide_atoms`` built on it).  Training goes through ``DecoderInner.train_field``
 (dense form only): the field as an autograd function differentiable in ``p``, ``z`` and every decoder parameter, whose backward is
 one deterministic library call (``shapemol_field_train``); ``PointCloud_AE.get_generator_train_loss`` is the reference's training
-loss on it.  The encoder has no backward, so a latent that comes from the encoder is a constant of that loss.
+loss on it, with the latent a constant when it comes from the encoder; ``PointCloud_AE.get_autoencoder_train_loss`` is the same
+loss through ``VN_DGCNN_Encoder.encode_train``, differentiable in every encoder and generator parameter.
 Once a module has a context, changed parameters that live on the context's device are repacked there by a kernel
 (``shapemol_field_load_weights``) -- an optimiser step costs no host packing and no new context.
 A module owns one library context whose per-shape workspace every call rewrites: calls of one module on different streams must
@@ -372,8 +373,17 @@ class PointCloud_AE(nn.Module):
         return mse, hit.sum() / hit.numel(), (hit & occupied).sum() / n_occupied
 
     def get_train_loss(self, point_clouds, sample_points, sample_values):
-        raise NotImplementedError("PointCloud_AE.get_train_loss: the device encoder has no backward (kNN graph features, VN batch norm); "
+        raise NotImplementedError("PointCloud_AE.get_train_loss keeps refusing (the name stays bound to the frozen encoder): "
+                                  "get_autoencoder_train_loss is the same loss with gradients for the encoder and the generator; "
                                   "get_generator_train_loss trains the generator (and a given latent) on the same loss")
+
+    def get_autoencoder_train_loss(self, point_clouds, sample_points, sample_values):
+        """The reference's ``get_train_loss`` (``models/shape_pointcloud_modelAE.py:146-150``): ``encode_train`` of ``point_clouds (B, N, 3)``,
+        ``generator.train_field`` at ``sample_points (B, T, 3)``, ``mean((net_out - sample_values) ** 2)``.  Differentiable in every
+        parameter of the encoder and of the generator; the clouds and the sample points are data."""
+        latent = self.encoder.encode_train(point_clouds[:, None])
+        net_out = self.generator.train_field(sample_points, latent)
+        return torch.mean((net_out - sample_values) ** 2)
 
     def get_generator_train_loss(self, point_clouds, sample_points, sample_values, z_vector=None):
         """The reference's ``get_train_loss`` formula, ``mean((net_out - sample_values) ** 2)``, differentiable in the generator's
