@@ -623,6 +623,44 @@ int shapemol_msurf_build(shapemol_msurf_ctx *ctx, int64_t n_mols, const int64_t 
  * float64, the grids back to back) to dst, HOST or DEVICE.  Synchronises the stream. */
 int shapemol_msurf_copy(shapemol_msurf_ctx *ctx, int32_t which, void *dst, int64_t n_items, void *stream);
 
+/* ---- geometry scores of sampled molecules: stability and pair distances ------------------------------------------------
+ * What the reference's evaluation script asks of analyze.check_stability and eval_bond_length.pair_distance_from_pos_v /
+ * get_pair_length_profile, for n_frames frames of one packed batch: n_mols molecules back to back,
+ * HOST h_off (n_mols + 1, starting at 0, shared by all frames), N = h_off[n_mols] atoms per frame.  The rule is data:
+ * h_thresholds (3, E, E) float64 = bondsK + marginK in pm, formed by the caller in float64; h_allowed (E) the valences;
+ * h_class_slot (n_classes) int32 the row of the rule (0 .. E - 1) of every atom class; carbon_slot the row of atomic number 6
+ * (-1: the rule has none, no C-C pair); the two histograms' ascending bin edges and cut-offs.  All arithmetic is float64 in
+ * the reference's order, d = sqrt((dx*dx + dy*dy) + dz*dz) without FMA contraction; a pair's bond order is 3, 2, 1 or 0 by the
+ * nested strict tests 100 * d < threshold1, < threshold2, < threshold3; a pair i < j with d < cut-off adds 1 to the bin
+ * np.searchsorted(edges, d, side='left') (C-C: both atoms of the carbon slot).  NaN distances give order 0 and no entry.
+ * Molecules of at most 64 atoms take the wave form (form 0), larger ones the block form (1); shapemol_eval_sizes writes up to
+ * n of (atoms of the wave form, atoms per molecule, elements, classes, edges per histogram, threads per workgroup) and
+ * returns 6.  Limits, refused with a message before any kernel runs: 1..1024 atoms per molecule, n_elements 1..16, n_classes
+ * 1..32, class slots inside the rule, 1..255 finite ascending edges per histogram, n_frames and n_mols 1..2^20.
+ * shapemol_eval_check touches no device; it writes the form of every molecule to the optional h_forms (n_mols). */
+typedef struct shapemol_eval_ctx shapemol_eval_ctx;
+int shapemol_eval_sizes(int64_t *out, int32_t n);
+int shapemol_eval_check(int64_t n_frames, int64_t n_mols, const int64_t *h_off, int32_t n_elements, int32_t n_classes,
+                        const int32_t *h_class_slot, const double *h_cc_edges, int32_t n_cc, double cc_cut,
+                        const double *h_all_edges, int32_t n_all, double all_cut, int32_t *h_forms);
+int shapemol_eval_create(int device, shapemol_eval_ctx **out);
+void shapemol_eval_destroy(shapemol_eval_ctx *ctx);
+/* DEVICE inputs: d_pos (n_frames, N, 3) float32, d_classes (n_frames, N) int32, or int64 with classes_int64 != 0.  DEVICE
+ * outputs, all written by the call: d_nr_bonds (n_frames, N) int32 the bond orders summed per atom; d_n_stable (n_frames,
+ * n_mols) int32 the atoms whose sum s has valence >= s > 0 (hs != 0: valence == s); d_mol_stable (n_frames, n_mols) uint8
+ * whether all atoms are; d_hist_cc (n_frames, n_cc + 1), d_hist_all (n_frames, n_all + 1) and d_class_counts (n_frames,
+ * n_classes) int64.  The same in every run.  The call synchronises the stream.  Returns 0, or 1 with a message: a refused
+ * call launches nothing; a class outside [0, n_classes) found on the device makes the outputs invalid.  Either way the
+ * context stays usable.  A context serves one stream at a time. */
+int shapemol_eval_run(shapemol_eval_ctx *ctx, int64_t n_frames, int64_t n_mols, const int64_t *h_off, const float *d_pos,
+                      const void *d_classes, int32_t classes_int64, int32_t n_elements, const double *h_thresholds,
+                      const double *h_allowed, int32_t carbon_slot, int32_t n_classes, const int32_t *h_class_slot,
+                      const double *h_cc_edges, int32_t n_cc, double cc_cut, const double *h_all_edges, int32_t n_all,
+                      double all_cut, int32_t hs, int32_t *d_nr_bonds, int32_t *d_n_stable, uint8_t *d_mol_stable,
+                      int64_t *d_hist_cc, int64_t *d_hist_all, int64_t *d_class_counts, void *stream);
+/* Tests only: fill the context's device workspace with `byte`. */
+int shapemol_eval_debug_fill(shapemol_eval_ctx *ctx, int32_t byte, void *stream);
+
 /* Per-kernel launch-time accounting with HIP events on the launch stream (bench only).
  * shapemol_profile_begin() arms it for the following _score/_sample calls (forces eager launches);
  * shapemol_profile_end() synchronises and writes, for each of up to `cap` kernel classes,

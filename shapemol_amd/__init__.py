@@ -11,6 +11,9 @@ utils/shape.py):
     ShapeData, collate_fn, get_pointAE_shape_emb
 and the molecule meshes themselves, from atom coordinates and radii (utils/shape.py get_mesh; the surface rule is this package's):
     get_mesh, get_mesh_batch
+and, after the chain, the scores of sampled molecules that need no chemistry toolkit (utils/evaluation analyze.check_stability,
+eval_bond_length pair-distance profiles), for one frame or every recorded frame, with the rule given as data:
+    StabilityRule, GeometryReport, check_stability, evaluate_geometry, evaluate_trajectory, evaluate_samples
 plus helpers: synthetic weights/inputs (synth), schedules (diffusion), the C-ABI binding (_lib).
 """
 from .molopt_score_model import ScorePosNet3D, log_sample_categorical, pointcloud_shape_guidance, mesh_shape_guidance  # noqa: F401
@@ -19,5 +22,7 @@ from .shape_encoder import VN_DGCNN_Encoder  # noqa: F401
 from .shape_autoencoder import PointCloud_AE, DecoderInner  # noqa: F401
 from .shape_data import ShapeData, collate_fn, get_pointAE_shape_emb  # noqa: F401
 from .mol_surface import get_mesh, get_mesh_batch  # noqa: F401
+from .evaluation import (StabilityRule, GeometryReport, check_stability, evaluate_geometry, evaluate_trajectory,  # noqa: F401
+                         evaluate_samples)
 
 __version__ = "0.3.0"

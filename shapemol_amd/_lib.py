@@ -36,6 +36,8 @@ EXPORTS = (
     "shapemol_sdata_check", "shapemol_sdata_create", "shapemol_sdata_destroy", "shapemol_sdata_build",
     "shapemol_msurf_sizes", "shapemol_msurf_check", "shapemol_msurf_create", "shapemol_msurf_destroy", "shapemol_msurf_build",
     "shapemol_msurf_copy",
+    "shapemol_eval_sizes", "shapemol_eval_check", "shapemol_eval_create", "shapemol_eval_destroy", "shapemol_eval_run",
+    "shapemol_eval_debug_fill",
 )
 
 
@@ -186,6 +188,14 @@ def load():
     lib.shapemol_msurf_destroy.restype = None
     lib.shapemol_msurf_build.argtypes = [vp, i64, vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp]
     lib.shapemol_msurf_copy.argtypes = [vp, i32, vp, i64, vp]
+    lib.shapemol_eval_sizes.argtypes = [vp, i32]
+    lib.shapemol_eval_check.argtypes = [i64, i64, vp, i32, i32, vp, vp, i32, C.c_double, vp, i32, C.c_double, vp]
+    lib.shapemol_eval_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.shapemol_eval_destroy.argtypes = [vp]
+    lib.shapemol_eval_destroy.restype = None
+    lib.shapemol_eval_run.argtypes = ([vp, i64, i64, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, C.c_double, vp, i32, C.c_double, i32]
+                                      + [vp] * 7)
+    lib.shapemol_eval_debug_fill.argtypes = [vp, i32, vp]
     lib.shapemol_profile_begin.argtypes = [vp]
     lib.shapemol_profile_end.argtypes = [vp, vp, vp, vp, C.c_int]
     if lib.shapemol_abi_version() != ABI_VERSION:
