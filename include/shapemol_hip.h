@@ -300,7 +300,8 @@ int shapemol_se_debug_read(shapemol_se_ctx *ctx, int32_t what, void *h_dst, size
  * d_grad_w, shapemol_se_weight_count floats in the weights' order.  Y = W' h is recomputed per block, not saved.
  * d_masks (diagnostic, may be NULL): (L+2,P,256) i32, per stage the leaky-ReLU branches the backward took: for conv_pos and the blocks
  * bit kk of [i][c] is set where edge (i, kk) of channel c had dot < 0, for conv_c [p][m] is 1 where row m had; written only by
- * the stages that run.  The training calls do not feed _debug_read, which keeps referring to the last _encode.
+ * the stages that run.  The training calls do not feed _debug_read, which keeps referring to the last _encode, and
+ * _debug_stop_after does not shorten them.
  * Both calls work in d_ws, a caller-owned device buffer of at least _train_workspace(ctx, B, N) bytes aligned to 256 bytes, whose
  * contents mean nothing between calls.  Shapes as _encode; refusals come with a message before any launch. */
 int shapemol_se_load_weights(shapemol_se_ctx *ctx, const float *d_weights, size_t n_weights, void *stream);

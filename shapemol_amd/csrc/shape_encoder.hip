@@ -1,12 +1,14 @@
 // C ABI of the device shape encoder (include/shapemol_hip.h, shapemol_se_*): VN_DGCNN_Encoder.forward of the reference
 // (models/shape_pointcloud_modelAE.py:207-255), its training variant and its backward.  Kernels: sm_shape.h, sm_shape_train.h.
+// One forward sweep, se_forward, serves shapemol_se_encode and shapemol_se_train_forward: they differ in where the results go and
+// in how the batch sums are taken (SeForwardDst).  One packer, se_pack_weights, a kernel, builds the weight image for
+// shapemol_se_create and shapemol_se_load_weights.
 #include "../../include/shapemol_hip.h"
 #include "sm_shape.h"
 #include "sm_shape_train.h"
 #include "sm_devmem.h"
 #include "sm_host.h"
 
-#include <cstring>
 #include <string>
 #include <vector>
 
@@ -64,7 +66,7 @@ SeTrainWs se_train_ws(const shapemol_se_ctx *c, int64_t P) {
     return w;
 }
 
-// the shape limits of shapemol_se_encode, for the training calls
+// the shape limits of an encode, for every call that takes a batch of clouds
 int se_check_shape(const shapemol_se_ctx *c, const char *who, int64_t B, int64_t N) {
     if (B < 1 || B > 65535 || N < 32 || (N % 16) != 0 || N > c->max_n || B * N > (1 << 24))
         return sm_fail(std::string(who) + ": need 1 <= B <= 65535, N a multiple of 16 in [32, " + std::to_string(c->max_n) + "] (16 * N * 4 bytes of the " +
@@ -77,6 +79,91 @@ int se_check_ws(const SeTrainWs &w, const char *who, const void *d_ws, size_t ws
     if (ws_bytes < w.total)
         return sm_fail(std::string(who) + ": the workspace has " + std::to_string(ws_bytes) + " bytes, shapemol_se_train_workspace asks for " + std::to_string(w.total));
     return 0;
+}
+
+// Where a forward sweep leaves its results, and how it takes the batch sums of its L + 2 stages (0: conv_pos, l + 1: block l, L + 1: conv_c)
+struct SeForwardDst {
+    int *idx; size_t idx_stride;    // neighbour lists: stage l's [P][k] at idx + l * idx_stride (stride 0: one list, every stage overwrites it)
+    float *h0, *hcat, *pd;
+    float *out;                     // null: the sweep ends after its blocks, conv_c does not run
+    double *part, *stats;           // part null: replicated float64 atomics.  Else fixed-order partials [kSeParts][kSePartQ][kSeCh], and the
+};                                  // stages' mean and variance go to stats [L + 2][2][kSeCh]
+
+// The batch sums of ||p|| of one edge stage into the context's accumulator: the one place that knows the two modes of an edge stage
+template <bool L0>
+int se_edge_stats(shapemol_se_ctx *c, hipStream_t s, const SeEdgeArgs &e, const SeForwardDst &dst, int stage) {
+    if (!dst.part) {
+        SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
+        hipLaunchKernelGGL(se_edge_stats_kernel<L0>, dim3((unsigned)e.n_total), dim3(e.C), 0, s, e);
+    } else {
+        const int parts = e.n_total < kSeParts ? e.n_total : kSeParts;
+        hipLaunchKernelGGL(se_edge_stats_part_kernel<L0>, dim3(parts), dim3(e.C), 0, s, e, dst.part);
+        hipLaunchKernelGGL(se_stats_reduce_kernel, dim3(1), dim3(256), 0, s, dst.part, parts, e.C, (double)e.n_total * kSeK, c->acc, dst.stats + (size_t)stage * 2 * kSeCh);
+    }
+    return 0;
+}
+
+// The forward sweep on B clouds of N points (checked by the caller): kNN, conv_pos, n_blocks x (squared norms, kNN, point product,
+// batch sums, apply), and conv_c with the mean over the points where dst.out is given.  xx, y and the accumulator are the context's
+// (se_grow for B * N points has run).  n_blocks and dst.out are the caller's: shapemol_se_debug_stop_after shortens
+// shapemol_se_encode alone, a training forward always passes L blocks and its output.
+int se_forward(shapemol_se_ctx *c, hipStream_t s, const float *d_points, int64_t B, int64_t N, const SeForwardDst &dst, int n_blocks) {
+    const int C = c->C, L = c->L, LAT = c->LAT;
+    const int64_t P = B * N;
+    const size_t knn_lds = (size_t)16 * N * sizeof(float);      // <= lds_limit (N <= max_n)
+    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
+    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3 * kC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
+    const float *W = c->d_w;
+    const dim3 knn_grid((unsigned)(N / 16), (unsigned)B);
+    auto stage_idx = [&](int stage) { return dst.idx + stage * dst.idx_stride; };
+    auto edge_args = [&](int stage, const float *bn_g, const float *bn_b, float *h_out, int h_ld, int h_off) {
+        SeEdgeArgs e{};
+        e.x = d_points; e.w0f = W + c->o_pos_wf; e.w0d = W + c->o_pos_wd; e.y = c->y;      // (conv_pos reads x and w0, a block y)
+        e.idx = stage_idx(stage); e.bn_g = bn_g; e.bn_b = bn_b; e.acc = c->acc; e.h_out = h_out;
+        e.n_total = (int)P; e.N = (int)N; e.C = C; e.h_ld = h_ld; e.h_off = h_off;
+        return e;
+    };
+    // conv_pos on the raw points
+    const SeEdgeArgs e = edge_args(0, W + c->o_pos_g, W + c->o_pos_b, dst.h0, 3 * C, 0);
+    hipLaunchKernelGGL(se_knn_kernel<3>, knn_grid, dim3(256), knn_lds, s, d_points, 3, nullptr, (int)N, stage_idx(0));
+    if (se_edge_stats<true>(c, s, e, dst, 0)) return 1;
+    hipLaunchKernelGGL(se_edge_apply_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
+    // DGCNN blocks
+    for (int l = 0; l < n_blocks; ++l) {
+        const float *hin = l == 0 ? dst.h0 : dst.hcat + (size_t)(l - 1) * 3 * C;
+        const int ld = l == 0 ? 3 * C : L * 3 * C;
+        const SeEdgeArgs b = edge_args(l + 1, W + c->o_g[l], W + c->o_b[l], dst.hcat, L * 3 * C, l * 3 * C);
+        hipLaunchKernelGGL(se_sqnorm_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s, hin, (int)P, 3 * C, ld, c->xx);
+        hipLaunchKernelGGL(se_knn_kernel<3 * kC>, knn_grid, dim3(256), knn_lds, s, hin, ld, c->xx, (int)N, stage_idx(l + 1));
+        hipLaunchKernelGGL(se_point_linear_kernel<kC>, dim3((unsigned)((P * 3 + 15) / 16)), dim3(256), 0, s, hin, ld, W + c->o_img[l], (int)(P * 3), 4 * C, c->y);
+        if (se_edge_stats<false>(c, s, b, dst, l + 1)) return 1;
+        hipLaunchKernelGGL(se_edge_apply_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
+    }
+    if (dst.out) {
+        // conv_c + mean over the points.  se_head_linear_kernel adds its sums into the accumulator in both modes; with partials the
+        // reducer then overwrites them
+        SeHeadArgs ha{dst.hcat, W + c->o_c_wf, W + c->o_c_wd, W + c->o_c_g, W + c->o_c_b, dst.pd, c->acc, dst.out, (int)P, (int)N, L * C, LAT};
+        SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
+        hipLaunchKernelGGL(se_head_linear_kernel, dim3((unsigned)((P * (LAT + 1) + 3) / 4)), dim3(256), 0, s, ha);
+        if (dst.part) {
+            const int parts = (int)(P < kSeParts ? P : kSeParts);
+            hipLaunchKernelGGL(se_head_stats_part_kernel, dim3(parts), dim3(256), 0, s, dst.pd, (int)P, LAT, dst.part);
+            hipLaunchKernelGGL(se_stats_reduce_kernel, dim3(1), dim3(256), 0, s, dst.part, parts, LAT, (double)P, c->acc, dst.stats + (size_t)(L + 1) * 2 * kSeCh);
+        }
+        hipLaunchKernelGGL(se_head_apply_kernel, dim3((unsigned)(B * LAT)), dim3(256), 0, s, ha);
+    }
+    SMCHK(hipGetLastError());
+    return 0;
+}
+
+// the context's weight image from the flat vector d_flat (DEVICE, the order of shapemol_se_create's weights): one kernel on s
+void se_pack_weights(const shapemol_se_ctx *c, const float *d_flat, hipStream_t s) {
+    SeLoadArgs a{};
+    a.src = d_flat; a.dst = c->d_w; a.L = c->L; a.LAT = c->LAT;
+    a.o_pos_wf = (unsigned)c->o_pos_wf; a.o_pos_g = (unsigned)c->o_pos_g; a.o_pos_b = (unsigned)c->o_pos_b; a.o_pos_wd = (unsigned)c->o_pos_wd;
+    a.o_c_wf = (unsigned)c->o_c_wf; a.o_c_g = (unsigned)c->o_c_g; a.o_c_b = (unsigned)c->o_c_b; a.o_c_wd = (unsigned)c->o_c_wd;
+    for (int l = 0; l < c->L; ++l) { a.o_img[l] = (unsigned)c->o_img[l]; a.o_g[l] = (unsigned)c->o_g[l]; a.o_b[l] = (unsigned)c->o_b[l]; }
+    hipLaunchKernelGGL(se_load_weights_kernel, dim3((unsigned)((shapemol_se_weight_count(c->C, c->LAT, c->L) + 255) / 256)), dim3(256), 0, s, a);
 }
 }  // namespace
 
@@ -102,42 +189,23 @@ int shapemol_se_create(int32_t hidden_dim, int32_t latent_dim, int32_t layer_num
     if (max_n < 32) return sm_fail("shapemol_se_create: the device has less than 2 KB of LDS per workgroup");
     auto *c = new shapemol_se_ctx();
     c->LAT = latent_dim; c->L = layer_num; c->device = device; c->lds_limit = lds; c->max_n = max_n;
-    const int C = kC;
-    std::vector<float> img;
-    auto put = [&](const float *src, size_t n) { const size_t o = (img.size() + 63) & ~size_t(63); img.resize(o + n); std::memcpy(&img[o], src, n * 4); return o; };
-    const float *p = w;
-    c->o_pos_wf = put(p, 2 * C); p += 2 * C;
-    c->o_pos_g = put(p, C); p += C;
-    c->o_pos_b = put(p, C); p += C;
-    c->o_pos_wd = put(p, 2 * C); p += 2 * C;
-    for (int l = 0; l < layer_num; ++l) {
-        const float *wf = p; p += (size_t)C * 2 * C;
-        c->o_g.push_back(put(p, C)); p += C;
-        c->o_b.push_back(put(p, C)); p += C;
-        const float *wd = p; p += (size_t)C * 2 * C;
-        // W' = [Wf1 ; Wf2 - Wf1 ; Wd1 ; Wd2 - Wd1]  (4C x C), as A fragments of se_point_linear_kernel
-        std::vector<float> Wp((size_t)4 * C * C);
-        for (int m = 0; m < C; ++m)
-            for (int k = 0; k < C; ++k) {
-                Wp[(size_t)(0 * C + m) * C + k] = wf[(size_t)m * 2 * C + k];
-                Wp[(size_t)(1 * C + m) * C + k] = wf[(size_t)m * 2 * C + C + k] - wf[(size_t)m * 2 * C + k];
-                Wp[(size_t)(2 * C + m) * C + k] = wd[(size_t)m * 2 * C + k];
-                Wp[(size_t)(3 * C + m) * C + k] = wd[(size_t)m * 2 * C + C + k] - wd[(size_t)m * 2 * C + k];
-            }
-        std::vector<float> im((size_t)4 * C * C);
-        for (int t = 0; t < 4 * C / 16; ++t)
-            for (int s4 = 0; s4 < C / 16; ++s4)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r)
-                        im[((size_t)(t * (C / 16) + s4) * 64 + lane) * 4 + r] = Wp[(size_t)(16 * t + (lane & 15)) * C + 4 * (4 * s4 + r) + (lane >> 4)];
-        c->o_img.push_back(put(im.data(), im.size()));
-    }
-    c->o_c_wf = put(p, (size_t)latent_dim * layer_num * C); p += (size_t)latent_dim * layer_num * C;
-    c->o_c_g = put(p, latent_dim); p += latent_dim;
-    c->o_c_b = put(p, latent_dim); p += latent_dim;
-    c->o_c_wd = put(p, (size_t)layer_num * C); p += (size_t)layer_num * C;
-    if (c->mem_w.alloc(&c->d_w, img.size() * 4) != hipSuccess || hipMemcpy(c->d_w, img.data(), img.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        delete c; return sm_fail("shapemol_se_create: device allocation failed");
+    // the image's parts, each at a multiple of 64 floats: plain copies of the flat vector's, and per block the A fragments of
+    // W' = [Wf1 ; Wf2 - Wf1 ; Wd1 ; Wd2 - Wd1] (4C x C) for se_point_linear_kernel.  se_pack_weights fills it
+    const size_t C = kC, L = layer_num, LAT = latent_dim;
+    size_t n_img = 0;
+    auto take = [&](size_t n) { const size_t o = (n_img + 63) & ~size_t(63); n_img = o + n; return o; };
+    c->o_pos_wf = take(2 * C); c->o_pos_g = take(C); c->o_pos_b = take(C); c->o_pos_wd = take(2 * C);
+    for (size_t l = 0; l < L; ++l) { c->o_g.push_back(take(C)); c->o_b.push_back(take(C)); c->o_img.push_back(take(4 * C * C)); }
+    c->o_c_wf = take(LAT * L * C); c->o_c_g = take(LAT); c->o_c_b = take(LAT); c->o_c_wd = take(L * C);
+    float *stage = nullptr;
+    DevList mem_stage;                                                          // (freed when this function returns)
+    hipError_t e = c->mem_w.alloc(&c->d_w, n_img * 4, true);                    // (zeroed: the alignment gaps behind conv_c's bn vectors)
+    if (e == hipSuccess) e = mem_stage.alloc(&stage, n_weights * 4);
+    if (e == hipSuccess) e = hipMemcpy(stage, w, n_weights * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { se_pack_weights(c, stage, nullptr); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        delete c; return sm_fail(std::string("shapemol_se_create: device allocation failed: ") + hipGetErrorString(e));
     }
     *out = c;
     return 0;
@@ -151,52 +219,15 @@ void shapemol_se_destroy(shapemol_se_ctx *c) {
 
 int shapemol_se_encode(shapemol_se_ctx *c, const float *d_points, int64_t B, int64_t N, float *d_out, void *stream) {
     if (!c || !d_points || !d_out) return sm_fail("shapemol_se_encode: null argument");
-    if (B < 1 || B > 65535 || N < 32 || (N % 16) != 0 || N > c->max_n || B * N > (1 << 24))
-        return sm_fail("shapemol_se_encode: need 1 <= B <= 65535, N a multiple of 16 in [32, " + std::to_string(c->max_n) + "] (16 * N * 4 bytes of the " +
-                       std::to_string(c->lds_limit) + " bytes of LDS a workgroup can have on this device) and B * N <= 2^24; got B = " +
-                       std::to_string(B) + ", N = " + std::to_string(N));
+    if (se_check_shape(c, "shapemol_se_encode", B, N)) return 1;
     SMCHK(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int C = c->C, L = c->L, LAT = c->LAT;
-    const int64_t P = B * N;
-    if (se_grow(c, P)) return 1;
-    c->lastP = P;
-    const size_t knn_lds = (size_t)16 * N * sizeof(float);      // <= lds_limit (N <= max_n)
-    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
-    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3 * kC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
-    const int n_blocks = c->stop_after < 0 ? L : (c->stop_after < L ? c->stop_after : L);
-    const float *W = c->d_w;
-    const dim3 knn_grid((unsigned)(N / 16), (unsigned)B);
-    // conv_pos on the raw points
-    hipLaunchKernelGGL(se_knn_kernel<3>, knn_grid, dim3(256), knn_lds, s, d_points, 3, nullptr, (int)N, c->idx);
-    SeEdgeArgs e{};
-    e.x = d_points; e.w0f = W + c->o_pos_wf; e.w0d = W + c->o_pos_wd; e.idx = c->idx; e.bn_g = W + c->o_pos_g; e.bn_b = W + c->o_pos_b;
-    e.acc = c->acc; e.h_out = c->h0; e.n_total = (int)P; e.N = (int)N; e.C = C; e.h_ld = 3 * C; e.h_off = 0;
-    SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
-    hipLaunchKernelGGL(se_edge_stats_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
-    hipLaunchKernelGGL(se_edge_apply_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
-    // DGCNN blocks
-    for (int l = 0; l < n_blocks; ++l) {
-        const float *hin = l == 0 ? c->h0 : c->hcat + (size_t)(l - 1) * 3 * C;
-        const int ld = l == 0 ? 3 * C : L * 3 * C;
-        hipLaunchKernelGGL(se_sqnorm_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s, hin, (int)P, 3 * C, ld, c->xx);
-        hipLaunchKernelGGL(se_knn_kernel<3 * kC>, knn_grid, dim3(256), knn_lds, s, hin, ld, c->xx, (int)N, c->idx);
-        hipLaunchKernelGGL(se_point_linear_kernel<kC>, dim3((unsigned)((P * 3 + 15) / 16)), dim3(256), 0, s, hin, ld, W + c->o_img[l], (int)(P * 3), 4 * C, c->y);
-        SeEdgeArgs b{};
-        b.y = c->y; b.idx = c->idx; b.bn_g = W + c->o_g[l]; b.bn_b = W + c->o_b[l]; b.acc = c->acc; b.h_out = c->hcat;
-        b.n_total = (int)P; b.N = (int)N; b.C = C; b.h_ld = L * 3 * C; b.h_off = l * 3 * C;
-        SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
-        hipLaunchKernelGGL(se_edge_stats_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
-        hipLaunchKernelGGL(se_edge_apply_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
-    }
-    if (c->stop_after >= 0) { SMCHK(hipGetLastError()); return 0; }
-    // conv_c + mean over the points
-    SeHeadArgs ha{c->hcat, W + c->o_c_wf, W + c->o_c_wd, W + c->o_c_g, W + c->o_c_b, c->pd, c->acc, d_out, (int)P, (int)N, L * C, LAT};
-    SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
-    hipLaunchKernelGGL(se_head_linear_kernel, dim3((unsigned)((P * (LAT + 1) + 3) / 4)), dim3(256), 0, s, ha);
-    hipLaunchKernelGGL(se_head_apply_kernel, dim3((unsigned)(B * LAT)), dim3(256), 0, s, ha);
-    SMCHK(hipGetLastError());
-    return 0;
+    if (se_grow(c, B * N)) return 1;
+    c->lastP = B * N;
+    // into the context's workspace (shapemol_se_debug_read reads it), one neighbour list, atomic sums; shapemol_se_debug_stop_after
+    // ends the sweep after its blocks and leaves d_out alone
+    const bool stop = c->stop_after >= 0;
+    const SeForwardDst dst{c->idx, 0, c->h0, c->hcat, c->pd, stop ? nullptr : d_out, nullptr, nullptr};
+    return se_forward(c, (hipStream_t)stream, d_points, B, N, dst, stop ? c->stop_after : c->L);
 }
 
 int64_t shapemol_se_max_points(const shapemol_se_ctx *c) { return c ? c->max_n : 0; }
@@ -207,12 +238,7 @@ int shapemol_se_load_weights(shapemol_se_ctx *c, const float *d_weights, size_t 
         return sm_fail("shapemol_se_load_weights: weight count mismatch: the context holds " + std::to_string(shapemol_se_weight_count(c->C, c->LAT, c->L)) +
                        " weights, got " + std::to_string(n_weights));
     SMCHK(hipSetDevice(c->device));
-    SeLoadArgs a{};
-    a.src = d_weights; a.dst = c->d_w; a.L = c->L; a.LAT = c->LAT;
-    a.o_pos_wf = (unsigned)c->o_pos_wf; a.o_pos_g = (unsigned)c->o_pos_g; a.o_pos_b = (unsigned)c->o_pos_b; a.o_pos_wd = (unsigned)c->o_pos_wd;
-    a.o_c_wf = (unsigned)c->o_c_wf; a.o_c_g = (unsigned)c->o_c_g; a.o_c_b = (unsigned)c->o_c_b; a.o_c_wd = (unsigned)c->o_c_wd;
-    for (int l = 0; l < c->L; ++l) { a.o_img[l] = (unsigned)c->o_img[l]; a.o_g[l] = (unsigned)c->o_g[l]; a.o_b[l] = (unsigned)c->o_b[l]; }
-    hipLaunchKernelGGL(se_load_weights_kernel, dim3((unsigned)((n_weights + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    se_pack_weights(c, d_weights, (hipStream_t)stream);
     SMCHK(hipGetLastError());
     return 0;
 }
@@ -231,47 +257,10 @@ int shapemol_se_train_forward(shapemol_se_ctx *c, const float *d_points, int64_t
     const SeTrainWs ws = se_train_ws(c, P);
     if (se_check_ws(ws, who, d_ws, ws_bytes)) return 1;
     SMCHK(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int C = c->C, L = c->L, LAT = c->LAT;
     if (se_grow(c, P)) return 1;
-    double *part = (double *)((char *)d_ws + ws.part);
-    const size_t knn_lds = (size_t)16 * N * sizeof(float);      // <= lds_limit (N <= max_n)
-    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
-    SMCHK(hipFuncSetAttribute((const void *)se_knn_kernel<3 * kC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds));
-    const float *W = c->d_w;
-    const dim3 knn_grid((unsigned)(N / 16), (unsigned)B);
-    const double edges = (double)P * kSeK;
-    // conv_pos on the raw points
-    hipLaunchKernelGGL(se_knn_kernel<3>, knn_grid, dim3(256), knn_lds, s, d_points, 3, nullptr, (int)N, d_idx);
-    SeEdgeArgs e{};
-    e.x = d_points; e.w0f = W + c->o_pos_wf; e.w0d = W + c->o_pos_wd; e.idx = d_idx; e.bn_g = W + c->o_pos_g; e.bn_b = W + c->o_pos_b;
-    e.acc = c->acc; e.h_out = d_h0; e.n_total = (int)P; e.N = (int)N; e.C = C; e.h_ld = 3 * C; e.h_off = 0;
-    hipLaunchKernelGGL(se_edge_stats_part_kernel<true>, dim3(ws.parts), dim3(C), 0, s, e, part);
-    hipLaunchKernelGGL(se_stats_reduce_kernel, dim3(1), dim3(256), 0, s, part, ws.parts, C, edges, c->acc, d_stats);
-    hipLaunchKernelGGL(se_edge_apply_kernel<true>, dim3((unsigned)P), dim3(C), 0, s, e);
-    for (int l = 0; l < L; ++l) {
-        const float *hin = l == 0 ? d_h0 : d_hcat + (size_t)(l - 1) * 3 * C;
-        const int ld = l == 0 ? 3 * C : L * 3 * C;
-        int32_t *idx = d_idx + (size_t)(l + 1) * P * kSeK;
-        hipLaunchKernelGGL(se_sqnorm_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s, hin, (int)P, 3 * C, ld, c->xx);
-        hipLaunchKernelGGL(se_knn_kernel<3 * kC>, knn_grid, dim3(256), knn_lds, s, hin, ld, c->xx, (int)N, idx);
-        hipLaunchKernelGGL(se_point_linear_kernel<kC>, dim3((unsigned)((P * 3 + 15) / 16)), dim3(256), 0, s, hin, ld, W + c->o_img[l], (int)(P * 3), 4 * C, c->y);
-        SeEdgeArgs b{};
-        b.y = c->y; b.idx = idx; b.bn_g = W + c->o_g[l]; b.bn_b = W + c->o_b[l]; b.acc = c->acc; b.h_out = d_hcat;
-        b.n_total = (int)P; b.N = (int)N; b.C = C; b.h_ld = L * 3 * C; b.h_off = l * 3 * C;
-        hipLaunchKernelGGL(se_edge_stats_part_kernel<false>, dim3(ws.parts), dim3(C), 0, s, b, part);
-        hipLaunchKernelGGL(se_stats_reduce_kernel, dim3(1), dim3(256), 0, s, part, ws.parts, C, edges, c->acc, d_stats + (size_t)(l + 1) * 2 * kSeCh);
-        hipLaunchKernelGGL(se_edge_apply_kernel<false>, dim3((unsigned)P), dim3(C), 0, s, b);
-    }
-    // conv_c + mean over the points (se_head_linear_kernel's own sums go into the accumulator the reducer then overwrites)
-    SeHeadArgs ha{d_hcat, W + c->o_c_wf, W + c->o_c_wd, W + c->o_c_g, W + c->o_c_b, d_pd, c->acc, d_out, (int)P, (int)N, L * C, LAT};
-    SMCHK(hipMemsetAsync(c->acc, 0, (size_t)kSeReplicas * 2 * 256 * 8, s));
-    hipLaunchKernelGGL(se_head_linear_kernel, dim3((unsigned)((P * (LAT + 1) + 3) / 4)), dim3(256), 0, s, ha);
-    hipLaunchKernelGGL(se_head_stats_part_kernel, dim3(ws.parts), dim3(256), 0, s, d_pd, (int)P, LAT, part);
-    hipLaunchKernelGGL(se_stats_reduce_kernel, dim3(1), dim3(256), 0, s, part, ws.parts, LAT, (double)P, c->acc, d_stats + (size_t)(L + 1) * 2 * kSeCh);
-    hipLaunchKernelGGL(se_head_apply_kernel, dim3((unsigned)(B * LAT)), dim3(256), 0, s, ha);
-    SMCHK(hipGetLastError());
-    return 0;
+    // into the caller's tensors, a neighbour list per stage, fixed-order sums; always the full sweep (shapemol_se_debug_stop_after is shapemol_se_encode's)
+    const SeForwardDst dst{d_idx, (size_t)P * kSeK, d_h0, d_hcat, d_pd, d_out, (double *)((char *)d_ws + ws.part), d_stats};
+    return se_forward(c, (hipStream_t)stream, d_points, B, N, dst, c->L);
 }
 
 int shapemol_se_train_backward(shapemol_se_ctx *c, const float *d_points, int64_t B, int64_t N, const int32_t *d_idx, const float *d_h0,

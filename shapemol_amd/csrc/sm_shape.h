@@ -11,6 +11,9 @@
 //     se_edge_stats      p_ij = Yf1[j] + Yf2[i]; batch sums of ||p|| per channel (train-mode batch-norm)
 //     se_edge_apply      normalise, VN-leaky-ReLU against d_ij = Yd1[j] + Yd2[i], mean over the k neighbours -> next h
 // and se_head_* for conv_c (Linear 4C -> latent, BatchNorm1d, shared direction, mean over the points).
+// Written once, as device functions: an element's ||p|| + EPS and its share of the batch sums (se_norm_sums, se_edge_norm_sums: also
+// the training path's fixed-order sums, sm_shape_train.h), the read of the batch statistics (se_batch_stats over se_mean_var, which
+// the training path's reducer saves from) and the VN batch-norm + leaky-ReLU element (se_vn_act, both apply kernels).
 // Layouts: h [B][N][C][3] fp32; Y [B][N][4 C'][3]; idx [B][N][k] i32.
 #pragma once
 #include "sm_device.h"
@@ -143,19 +146,57 @@ SM_DEV void se_edge_pd(const SeEdgeArgs &a, int i, int j, int c, float (&p)[3], 
     }
 }
 
-// one workgroup of C threads per point; pass 1: batch sums of ||p|| + EPS per channel
+// ||p|| + EPS of one element, and its share of the batch sums
+SM_DEV float se_norm(const float *p) { return sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f; }
+SM_DEV void se_norm_sums(const float *p, double &s1, double &s2) {
+    const float nrm = se_norm(p);
+    s1 += (double)nrm; s2 += (double)nrm * (double)nrm;
+}
+// the same over the 20 edges of point i, in edge order
 template <bool L0>
-__global__ void se_edge_stats_kernel(SeEdgeArgs a) {
-    const int i = blockIdx.x, c = threadIdx.x;
+SM_DEV void se_edge_norm_sums(const SeEdgeArgs &a, int i, int c, double &s1, double &s2) {
     const int base = (i / a.N) * a.N;
-    double s1 = 0.0, s2 = 0.0;
     for (int kk = 0; kk < kSeK; ++kk) {
         const int j = base + a.idx[(size_t)i * kSeK + kk];
         float p[3], d[3];
         se_edge_pd<L0>(a, i, j, c, p, d);
-        const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-        s1 += (double)nrm; s2 += (double)nrm * (double)nrm;
+        se_norm_sums(p, s1, s2);
     }
+}
+
+// batch mean and biased, clamped variance from the sums of cnt elements; then what the apply kernels take from the accumulator
+// acc [kSeReplicas][2][nch] for channel c
+SM_DEV void se_mean_var(double t1, double t2, double cnt, double &mean, double &var) {
+    mean = t1 / cnt;
+    var = t2 / cnt - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+}
+SM_DEV void se_batch_stats(const double *acc, int nch, int c, double cnt, float &meanf, float &rstd) {
+    double t1 = 0.0, t2 = 0.0, mean, var;
+    for (int r = 0; r < kSeReplicas; ++r) { t1 += acc[(size_t)r * 2 * nch + c]; t2 += acc[(size_t)r * 2 * nch + nch + c]; }
+    se_mean_var(t1, t2, cnt, mean, var);
+    meanf = (float)mean; rstd = 1.0f / sqrtf((float)var + 1e-5f);
+}
+
+// VNBatchNorm (train mode) + VN-leaky-ReLU of one element: p is normalised in place, o += its activation against the direction d
+SM_DEV void se_vn_act(float (&p)[3], const float (&d)[3], float meanf, float rstd, float g, float b, float (&o)[3]) {
+    const float nrm = se_norm(p);
+    const float nbn = (nrm - meanf) * rstd * g + b;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = p[k] / nrm * nbn;
+    const float dot = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
+    const float dsq = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    const float coef = dot / (dsq + 1e-6f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] += 0.2f * p[k] + 0.8f * (dot >= 0.f ? p[k] : p[k] - coef * d[k]);
+}
+
+// one workgroup of C threads per point; pass 1: batch sums of ||p|| + EPS per channel
+template <bool L0>
+__global__ void se_edge_stats_kernel(SeEdgeArgs a) {
+    const int c = threadIdx.x;
+    double s1 = 0.0, s2 = 0.0;
+    se_edge_norm_sums<L0>(a, blockIdx.x, c, s1, s2);
     double *acc = a.acc + (size_t)(blockIdx.x % kSeReplicas) * 2 * a.C;
     atomicAdd(acc + c, s1);
     atomicAdd(acc + a.C + c, s2);
@@ -166,27 +207,15 @@ template <bool L0>
 __global__ void se_edge_apply_kernel(SeEdgeArgs a) {
     const int i = blockIdx.x, c = threadIdx.x;
     const int base = (i / a.N) * a.N;
-    double t1 = 0.0, t2 = 0.0;
-    for (int r = 0; r < kSeReplicas; ++r) { t1 += a.acc[(size_t)r * 2 * a.C + c]; t2 += a.acc[(size_t)r * 2 * a.C + a.C + c]; }
-    const double cnt = (double)a.n_total * kSeK;
-    const double mean = t1 / cnt;
-    double var = t2 / cnt - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const float meanf = (float)mean, rstd = 1.0f / sqrtf((float)var + 1e-5f), bg = a.bn_g[c], bb = a.bn_b[c];
+    float meanf, rstd;
+    se_batch_stats(a.acc, a.C, c, (double)a.n_total * kSeK, meanf, rstd);
+    const float bg = a.bn_g[c], bb = a.bn_b[c];
     float o[3] = {0.f, 0.f, 0.f};
     for (int kk = 0; kk < kSeK; ++kk) {
         const int j = base + a.idx[(size_t)i * kSeK + kk];
         float p[3], d[3];
         se_edge_pd<L0>(a, i, j, c, p, d);
-        const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-        const float nbn = (nrm - meanf) * rstd * bg + bb;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p[k] = p[k] / nrm * nbn;
-        const float dot = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
-        const float dsq = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        const float coef = dot / (dsq + 1e-6f);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] += 0.2f * p[k] + 0.8f * (dot >= 0.f ? p[k] : p[k] - coef * d[k]);
+        se_vn_act(p, d, meanf, rstd, bg, bb, o);
     }
     float *ho = a.h_out + (size_t)i * a.h_ld + a.h_off + (size_t)c * 3;
 #pragma unroll
@@ -223,10 +252,11 @@ __global__ void se_head_linear_kernel(SeHeadArgs a) {
         float *o = a.pd + ((size_t)p * (a.LAT + 1) + m) * 3;
         o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
         if (m < a.LAT) {
-            const float nrm = sqrtf(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]) + 1e-6f;
+            double s1 = 0.0, s2 = 0.0;
+            se_norm_sums(s, s1, s2);
             double *acc = a.acc + (size_t)(p % kSeReplicas) * 2 * a.LAT;
-            atomicAdd(acc + m, (double)nrm);
-            atomicAdd(acc + a.LAT + m, (double)nrm * (double)nrm);
+            atomicAdd(acc + m, s1);
+            atomicAdd(acc + a.LAT + m, s2);
         }
     }
 }
@@ -234,27 +264,16 @@ __global__ void se_head_linear_kernel(SeHeadArgs a) {
 __global__ void se_head_apply_kernel(SeHeadArgs a) {
     __shared__ float red[3][256];
     const int b = blockIdx.x / a.LAT, m = blockIdx.x % a.LAT;
-    double t1 = 0.0, t2 = 0.0;
-    for (int r = 0; r < kSeReplicas; ++r) { t1 += a.acc[(size_t)r * 2 * a.LAT + m]; t2 += a.acc[(size_t)r * 2 * a.LAT + a.LAT + m]; }
-    const double cnt = (double)a.n_total, mean = t1 / cnt;
-    double var = t2 / cnt - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const float meanf = (float)mean, rstd = 1.0f / sqrtf((float)var + 1e-5f), bg = a.bn_g[m], bb = a.bn_b[m];
+    float meanf, rstd;
+    se_batch_stats(a.acc, a.LAT, m, (double)a.n_total, meanf, rstd);
+    const float bg = a.bn_g[m], bb = a.bn_b[m];
     float o[3] = {0.f, 0.f, 0.f};
     for (int nn = threadIdx.x; nn < a.N; nn += blockDim.x) {
         const float *pp = a.pd + ((size_t)(b * a.N + nn) * (a.LAT + 1) + m) * 3;
         const float *dd = a.pd + ((size_t)(b * a.N + nn) * (a.LAT + 1) + a.LAT) * 3;
         float p[3] = {pp[0], pp[1], pp[2]};
         const float d[3] = {dd[0], dd[1], dd[2]};
-        const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-        const float nbn = (nrm - meanf) * rstd * bg + bb;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p[k] = p[k] / nrm * nbn;
-        const float dot = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
-        const float dsq = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        const float coef = dot / (dsq + 1e-6f);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] += 0.2f * p[k] + 0.8f * (dot >= 0.f ? p[k] : p[k] - coef * d[k]);
+        se_vn_act(p, d, meanf, rstd, bg, bb, o);
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) red[k][threadIdx.x] = o[k];

@@ -3,10 +3,12 @@
 // neighbour lists.  Nothing here uses a floating-point atomic: every sum that crosses threads is taken in a fixed order, in
 // float64 where partials meet, so the latent and every gradient are bit-identical from run to run.
 //
-// Forward.  The kernels of sm_shape.h, except the two that add the batch sums with atomics: se_*_stats_part_kernel leaves one
-// float64 partial per workgroup (a fixed number of workgroups, each walking its points in order) and se_stats_reduce_kernel adds
-// them in workgroup order.  It writes the totals into replica 0 of the accumulator the apply kernels read (the other replicas
-// zero), so se_edge_apply_kernel / se_head_apply_kernel run unchanged, and the batch mean and variance into the caller's buffer.
+// Forward.  The sweep of sm_shape.h (se_forward of shape_encoder.hip issues it for both paths), except the two kernels that add the
+// batch sums with atomics: se_*_stats_part_kernel leaves one float64 partial per workgroup (a fixed number of workgroups, each
+// walking its points in order, a point's sums by the device function the atomic kernels use) and se_stats_reduce_kernel adds them in
+// workgroup order.  It writes the totals into replica 0 of the accumulator the apply kernels read (the other replicas zero), so
+// se_edge_apply_kernel / se_head_apply_kernel run unchanged, and the batch mean and variance (se_mean_var, as the apply kernels
+// take them) into the caller's buffer.
 //
 // Backward of a VN stage (edge e = (i, j), channel c; M = edges of the batch):
 //     r = |p|, n = r + 1e-6, xh = (n - mean) / sig, s = gamma xh + beta, q = p s / n, dot = q.d, D = d.d + 1e-6,
@@ -36,16 +38,7 @@ template <bool L0>
 __global__ void se_edge_stats_part_kernel(SeEdgeArgs a, double *part) {
     const int c = threadIdx.x;
     double s1 = 0.0, s2 = 0.0;
-    for (int i = blockIdx.x; i < a.n_total; i += gridDim.x) {
-        const int base = (i / a.N) * a.N;
-        for (int kk = 0; kk < kSeK; ++kk) {
-            const int j = base + a.idx[(size_t)i * kSeK + kk];
-            float p[3], d[3];
-            se_edge_pd<L0>(a, i, j, c, p, d);
-            const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-            s1 += (double)nrm; s2 += (double)nrm * (double)nrm;
-        }
-    }
+    for (int i = blockIdx.x; i < a.n_total; i += gridDim.x) se_edge_norm_sums<L0>(a, i, c, s1, s2);
     double *dst = part + (size_t)blockIdx.x * kSePartQ * kSeCh;
     dst[c] = s1; dst[kSeCh + c] = s2;
 }
@@ -54,16 +47,12 @@ __global__ void se_head_stats_part_kernel(const float *pd, int n_total, int LAT,
     const int m = threadIdx.x;
     if (m >= LAT) return;
     double s1 = 0.0, s2 = 0.0;
-    for (int pt = blockIdx.x; pt < n_total; pt += gridDim.x) {
-        const float *p = pd + ((size_t)pt * (LAT + 1) + m) * 3;
-        const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-        s1 += (double)nrm; s2 += (double)nrm * (double)nrm;
-    }
+    for (int pt = blockIdx.x; pt < n_total; pt += gridDim.x) se_norm_sums(pd + ((size_t)pt * (LAT + 1) + m) * 3, s1, s2);
     double *dst = part + (size_t)blockIdx.x * kSePartQ * kSeCh;
     dst[m] = s1; dst[kSeCh + m] = s2;
 }
-// one workgroup, thread c < nch: totals into replica 0 of acc [kSeReplicas][2][nch], mean and biased variance (as the apply
-// kernels compute them) into stats [2][kSeCh]
+// one workgroup, thread c < nch: totals into replica 0 of acc [kSeReplicas][2][nch], mean and biased variance (se_mean_var, the
+// function the apply kernels take theirs from) into stats [2][kSeCh]
 __global__ void se_stats_reduce_kernel(const double *part, int n_parts, int nch, double cnt, double *acc, double *stats) {
     const int c = threadIdx.x;
     if (c >= nch) return;
@@ -71,9 +60,8 @@ __global__ void se_stats_reduce_kernel(const double *part, int n_parts, int nch,
     for (int b = 0; b < n_parts; ++b) { t1 += part[(size_t)b * kSePartQ * kSeCh + c]; t2 += part[(size_t)b * kSePartQ * kSeCh + kSeCh + c]; }
     acc[c] = t1; acc[nch + c] = t2;
     for (int r = 1; r < kSeReplicas; ++r) { acc[(size_t)r * 2 * nch + c] = 0.0; acc[(size_t)r * 2 * nch + nch + c] = 0.0; }
-    const double mean = t1 / cnt;
-    double var = t2 / cnt - mean * mean;
-    var = var > 0.0 ? var : 0.0;
+    double mean, var;
+    se_mean_var(t1, t2, cnt, mean, var);
     stats[c] = mean; stats[kSeCh + c] = var;
 }
 
@@ -456,8 +444,8 @@ __global__ void __launch_bounds__(256) se_head_bwd_dw_finish_kernel(const double
     if (e < (int64_t)LAT * KC) gwf[e] = (float)s; else gwd[e - (int64_t)LAT * KC] = (float)s;
 }
 
-// ---- the weight images from the flat parameter vector (shapemol_se_load_weights) ------------------------------------------------
-// What shapemol_se_create packs on the host: plain copies, and per block W' = [Wf1 ; Wf2 - Wf1 ; Wd1 ; Wd2 - Wd1] as A fragments.
+// ---- the weight images from the flat parameter vector (shapemol_se_create, shapemol_se_load_weights) ----------------------------
+// The library's one packer: plain copies, and per block W' = [Wf1 ; Wf2 - Wf1 ; Wd1 ; Wd2 - Wd1] as A fragments of se_point_linear_kernel.
 struct SeLoadArgs {
     const float *src; float *dst;
     int L, LAT;

@@ -157,6 +157,32 @@ def test_sgd_step_uses_the_device_repack_and_matches_a_fresh_context():
     assert not torch.equal(z, r["out"])
 
 
+def test_debug_stop_after_is_the_frozen_forwards_alone():
+    """The two paths share one sweep; shapemol_se_debug_stop_after belongs to shapemol_se_encode: the training forward stays full."""
+    case = (3, 48, 2, 32)
+    B, N, L, LAT = case
+    r = _run(case)
+    enc = _encoder(L, LAT)
+    full = enc(r["x"])
+    enc.debug_stop_after(DEV, 1)
+    out, saved = enc._train_forward(r["x"])
+    assert torch.equal(out, r["out"]), "the training forward must not stop early"
+    for k in ("idx", "h0", "hcat", "pd"):
+        assert torch.equal(saved[k], r["saved"][k]), k
+    st, ref = saved["stats"], r["saved"]["stats"]          # (a stage writes its own channels: 128 of the edge stages, LAT of conv_c)
+    assert torch.equal(st[:L + 1, :, :128], ref[:L + 1, :, :128]) and torch.equal(st[L + 1, :, :LAT], ref[L + 1, :, :LAT]), "stats"
+    # forward honours the stop: the head has not run (the output is untouched) and the one neighbour list is block 0's, not block 1's
+    from shapemol_amd import _lib
+    from shapemol_amd._native import ptr, stream_ptr
+    z = torch.full((B, LAT, 3), 7.0, device=DEV)
+    _lib.check(_lib.load().shapemol_se_encode(enc._context(DEV), ptr(r["x"]), B, N, ptr(z), stream_ptr(r["x"].device)), "shapemol_se_encode")
+    lists = torch.from_numpy(enc.debug_read(DEV, "idx", B * N)).sort(-1)[0]
+    assert bool((z == 7.0).all()), "a stopped forward must leave the output alone"
+    assert torch.equal(lists, r["idx"][1].sort(-1)[0]) and not torch.equal(lists, r["idx"][2].sort(-1)[0])
+    enc.debug_stop_after(DEV, -1)
+    assert torch.equal(enc(r["x"]), full)
+
+
 def test_backward_of_a_graph_older_than_a_parameter_change():
     """Forward, an in-place change of every parameter, backward: the gradient is the one taken before the change (the node loads its
     own weights into the context), and the module then goes on with the changed ones."""
