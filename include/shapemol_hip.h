@@ -543,6 +543,18 @@ int shapemol_set_knn_pins(shapemol_ctx *ctx, const int32_t *h_off, int32_t n_ste
  * third piece falls under bf16's smallest subnormal and the error is bounded by 2^-133) (fp32 nn.Linear operands of the reference:
  * models/common.py:47-67).  pieces: three bf16 bit patterns.  tests/test_host.py checks the identity over random and edge values. */
 void shapemol_debug_split_exact(float x, uint16_t *pieces);
+/* Diagnostic: the statistic stage of ONE classifier-free guidance step on caller-supplied predictions, under the setting that
+ * shapemol_set_cfg or shapemol_set_cfg_groups installed -- exactly what a chain launches for it: the histograms cleared, with
+ * groups their table from d_batch (n_atoms,) i64 DEVICE, then the partial-sum or the three radix-select launches and the
+ * finalize launch over d_pos_cond / d_pos_uncond (n_atoms,3) and d_v_cond / d_v_uncond (n_atoms,num_classes) f32 DEVICE.  The
+ * result stays where a chain leaves it: shapemol_debug_read "cfg_stat" (2,) f32, with groups "cfg_group_stat" (G,2) f32
+ * (threshold_type 0 has no statistic: nothing is launched).  Enqueued on `stream`, no synchronisation.  Refused before any
+ * launch: a null pointer, n_atoms < 1, n_mols < 1 or > n_atoms, n_atoms * num_classes >= 2^31, no classifier-free setting
+ * installed (or a mesh, a cloud or a field installed, which take precedence), a group set that does not cover n_mols.  The
+ * workspace grows as for _sample (a growth drops the captured steps; the next chain captures again); chains before and after
+ * are otherwise untouched.  tests/test_gpu_cfg_stats.py gates the statistic kernels through it on crafted tensors. */
+int shapemol_debug_cfg_stats(shapemol_ctx *ctx, const float *d_pos_cond, const float *d_pos_uncond, const float *d_v_cond,
+                             const float *d_v_uncond, const int64_t *d_batch, int64_t n_atoms, int64_t n_mols, void *stream);
 /* Copy an internal device buffer of the last _score to HOST memory (synchronises the device).
  * names: "nbr" (N,KP) i32, "ew" (N,KP) f32, "h" (N,H), "x" (N,3), "pre" (N,4H), "q" (N,H),
  *        "h0" (N,H), "q_x" (N,H), "pre0" (N,4H), "add0" (B,4H): the node prologue's outputs and the per-molecule term it adds

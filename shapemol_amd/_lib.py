@@ -22,6 +22,7 @@ EXPORTS = (
     "shapemol_pointcloud_guidance", "shapemol_set_mesh_guidance", "shapemol_guide_points_mesh", "shapemol_mesh_guidance",
     "shapemol_set_mesh_guidance_groups", "shapemol_guide_points_mesh_groups",
     "shapemol_set_cfg", "shapemol_set_cfg_groups", "shapemol_set_knn_pins", "shapemol_debug_split_exact",
+    "shapemol_debug_cfg_stats",
     "shapemol_mlp_backward_workspace", "shapemol_mlp_forward", "shapemol_mlp_backward",
     "shapemol_seg_attention_forward", "shapemol_seg_attention_backward",
     "shapemol_vn_backward_workspace", "shapemol_vn_forward", "shapemol_vn_backward",
@@ -121,6 +122,7 @@ def load():
     lib.shapemol_set_knn_pins.argtypes = [vp, vp, i32, vp, vp, i64, i32]
     lib.shapemol_debug_split_exact.argtypes = [C.c_float, vp]
     lib.shapemol_debug_split_exact.restype = None
+    lib.shapemol_debug_cfg_stats.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, vp]
     lib.shapemol_pointcloud_guidance.argtypes = [vp, i64, C.c_double, C.c_double, vp, i64, vp, u64, vp]
     lib.shapemol_set_mesh_guidance.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp]
     lib.shapemol_guide_points_mesh.argtypes = [vp, vp, i64, vp, u64, vp]

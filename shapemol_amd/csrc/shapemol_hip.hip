@@ -555,6 +555,20 @@ int run_cfg_stats(shapemol_ctx *c, hipStream_t s, const CfgArgs &a) {
     return 0;
 }
 
+// classifier-free guidance, once per chain (and per shapemol_debug_cfg_stats call) before the first statistic stage: cleared
+// histograms and, with groups, their element ranges, workgroups and ranks from the batch vector
+int run_cfg_prep(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int64_t B) {
+    HIPCHK(hipMemsetAsync(c->cfg_hist, 0, (size_t)2 * kCfgHistWords * sizeof(unsigned), s));
+    if (c->cgs.groups > 0) {
+        const CfgArgs ca = cfg_args(c, N);
+        HIPCHK(hipMemsetAsync(c->cgs.hist, 0, (size_t)c->cgs.groups * 2 * kCfgHistWords * sizeof(unsigned), s));
+        LAUNCH("prep", SMK(cfg_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, ca.C, ca.n_groups, (int)B, ca.pf, c->cgs.rows,
+                           c->cfg_mol_grp, c->cfg_blk_tab, ca.tab_stride, ca.blocks[0], ca.blocks[1]));
+        c->cgs.stream = s; c->cgs.stream_set = true; c->cgs.last_groups = c->cgs.groups;
+    }
+    return 0;
+}
+
 template <int H>
 int run_prep(shapemol_ctx *c, hipStream_t s, const int64_t *d_batch, int64_t N, int64_t B, const float *d_shape, const ShapePrep &sp) {
     LAUNCH("prep", SMK(mol_index_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_batch, (int)N, (int)B, c->mol_of, c->mol_off, c->status));
@@ -1029,14 +1043,7 @@ int shapemol_sample(shapemol_ctx *c, const float *d_init_pos, const int64_t *d_i
     }
     if (cfg) {      // classifier-free guidance: the unconditional evaluation's shape data, from a zeroed shape, once per chain
         if (dispatch_h(c, [&](auto h) { return run_prep_shape<h()>(c, s, B, c->shape_zero, c->prep[1]); })) return 1;
-        HIPCHK(hipMemsetAsync(c->cfg_hist, 0, (size_t)2 * kCfgHistWords * sizeof(unsigned), s));
-        if (c->cgs.groups > 0) {      // the groups' element ranges, workgroups and ranks, from the batch vector (once per chain)
-            const CfgArgs ca = cfg_args(c, N);
-            HIPCHK(hipMemsetAsync(c->cgs.hist, 0, (size_t)c->cgs.groups * 2 * kCfgHistWords * sizeof(unsigned), s));
-            LAUNCH("prep", SMK(cfg_groups_table_kernel, dim3(1), dim3(256), 0, s, d_batch, (int)N, ca.C, ca.n_groups, (int)B, ca.pf, c->cgs.rows,
-                               c->cfg_mol_grp, c->cfg_blk_tab, ca.tab_stride, ca.blocks[0], ca.blocks[1]));
-            c->cgs.stream = s; c->cgs.stream_set = true; c->cgs.last_groups = c->cgs.groups;
-        }
+        if (run_cfg_prep(c, s, d_batch, N, B)) return 1;
     }
     LAUNCH("prep", SMK(v_check_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_init_v, (int)N, c->cfg.num_classes, c->status));
     {
@@ -1210,6 +1217,25 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) { fail("shapemol_debug_read: copy failed"); return -1; }
     return (int64_t)bytes;
+}
+
+/* Diagnostic: the statistic stage of one classifier-free guidance step on the caller's four prediction tensors, under the installed
+ * setting: what a chain prepares (run_cfg_prep) and what each of its steps launches (run_cfg_stats on cfg_args), nothing else. */
+int shapemol_debug_cfg_stats(shapemol_ctx *c, const float *d_pos_cond, const float *d_pos_uncond, const float *d_v_cond, const float *d_v_uncond,
+                             const int64_t *d_batch, int64_t N, int64_t B, void *stream) {
+    const std::string me = "shapemol_debug_cfg_stats: ";
+    if (!c || !d_pos_cond || !d_pos_uncond || !d_v_cond || !d_v_uncond || !d_batch) return fail(me + "null argument");
+    if (N < 1 || B < 1 || B > N || N > (1 << 27) || N * c->cfg.num_classes >= (int64_t)1 << 31) return fail(me + "n_atoms / n_mols out of range");
+    if (chain_guide(c) != Guide::Cfg) return fail(me + "no classifier-free guidance setting is installed (or another guidance takes precedence)");
+    if (c->cgs.groups > 0 && c->cgs.mols != B)
+        return fail(me + "n_mols = " + std::to_string(B) + " but the classifier-free guidance groups cover " + std::to_string(c->cgs.mols) + " molecules");
+    HIPCHK(hipSetDevice(c->device));
+    if (ensure_workspace(c, N, B)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (run_cfg_prep(c, s, d_batch, N, B)) return 1;
+    CfgArgs a = cfg_args(c, N);
+    a.pos_c = d_pos_cond; a.pos_u = d_pos_uncond; a.v_c = d_v_cond; a.v_u = d_v_uncond;
+    return run_cfg_stats(c, s, a);
 }
 
 /* Diagnostic: the exact three-way bf16 split the packers apply to every weight (and the kernels, with the same arithmetic, to every

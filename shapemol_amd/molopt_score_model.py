@@ -229,6 +229,32 @@ class ScorePosNet3D(nn.Module):
             raise _lib.ShapeMolLibraryError(f"debug_read({name}): got {n} bytes, want {out.nbytes}")
         return out
 
+    def debug_cfg_stats(self, pos_cond, pos_uncond, v_cond, v_uncond, batch, n_mols, *, guide_stren, threshold_type, p):
+        """Diagnostic (shapemol_debug_cfg_stats): the statistic stage of one classifier-free guidance step on the given
+        predictions, (N,3) / (N,C) float32 and the (N,) int64 batch vector on the device.  ``guide_stren`` is a float (the
+        whole-batch form) or ``[(w, n_mols), ...]`` (one statistic per group); the setting is installed for this call only.
+        Returns threshold_CFG's s or r as float32 numpy, (2,) or (G,2): positions | logits."""
+        dev = pos_cond.device
+        t = [_check_device_tensor(n, x, torch.float32) for n, x in (("pos_cond", pos_cond), ("pos_uncond", pos_uncond), ("v_cond", v_cond), ("v_uncond", v_uncond))]
+        batch = _check_device_tensor("batch", batch, torch.int64)
+        n = batch.shape[0]
+        if any(x.numel() != n * k for x, k in zip(t, (3, 3, self.dims.C, self.dims.C))):
+            raise ValueError("inconsistent input shapes")
+        lib, ctx = _lib.load(), self._context(dev)
+        code = _lib.CFG_THRESHOLDS[threshold_type]
+        groups = _cfg_groups(guide_stren, None, int(n_mols)) if isinstance(guide_stren, (list, tuple)) else None
+        try:
+            if groups is not None:
+                _lib.check(lib.shapemol_set_cfg_groups(ctx, len(groups[1]), ptr(groups[0]), ptr(groups[1]), code, float(p), None, None, None), "shapemol_set_cfg_groups")
+            else:
+                _lib.check(lib.shapemol_set_cfg(ctx, float(guide_stren), code, float(p), None, None, None), "shapemol_set_cfg")
+            with torch.cuda.device(dev):
+                _lib.check(lib.shapemol_debug_cfg_stats(ctx, *(ptr(x) for x in t), ptr(batch), n, int(n_mols), stream_ptr(dev)), "shapemol_debug_cfg_stats")
+            return self.debug_read("cfg_stat", (2,), np.float32) if groups is None else self.debug_read("cfg_group_stat", (len(groups[1]), 2), np.float32)
+        finally:
+            lib.shapemol_set_cfg_groups(ctx, 0, None, None, 0, 0.0, None, None, None)
+            lib.shapemol_set_cfg(ctx, 0.0, 0, 0.0, None, None, None)
+
     # ------------------------------------------------------------------ forward
     def forward(self, ligand_pos_perturbed, ligand_v_perturbed, batch_ligand, ligand_shape, time_step=None,
                 return_all=False):

@@ -152,14 +152,16 @@ def test_cfg_quantile_equals_torch_quantile(B, C):
         record("cfg_quantile_exact", B=B, C=C, p=p, values=got)
 
 
-def recomposed_step_errors(tag, B, S, seed, C=15):
+def recomposed_step_errors(tag, B, S, seed, C=15, p=None, quantiles=None):
     """A CFG chain of S steps with every step recomposed on the host from the device chain's own state -- the model's forward
     with the shape and with zeros, the restated threshold_CFG (torch.quantile on the device), the posterior with the fed noise
-    -- against the chain's v0_traj, vt_traj and positions: (worst absolute differences, atoms)."""
+    -- against the chain's v0_traj, vt_traj and positions: (worst absolute differences, atoms).  p: instead of the tag's own;
+    quantiles: a list that receives every step's (positions', logits') host quantile (dynamic_threshold)."""
     m = hip_model(cond_mask_prob=0.1, num_classes=C)
     args, kw = _batch(B, seed, S, C)
     pos0, v0, batch, shape = args
-    p = {"none": None, "reference_threshold": 1.05, "dynamic_threshold": 0.99, "rescale": 0.6}[tag]
+    if p is None:
+        p = {"none": None, "reference_threshold": 1.05, "dynamic_threshold": 0.99, "rescale": 0.6}[tag]
     targs = {} if p is None else {"p": p}
     box = np.array([[-3.0, 3.5], [-2.5, 3.0], [-3.5, 2.5]])
     r = m.sample_diffusion(*args, **kw, threshold_type=_ttype(tag), threshold_args=targs, guide_stren=1.5,
@@ -178,6 +180,8 @@ def recomposed_step_errors(tag, B, S, seed, C=15):
         gv = O.combine(pc["pred_ligand_v"], pu["pred_ligand_v"], 1.5)
         if tag == "dynamic_threshold":       # the statistic exactly as the reference takes it (torch.quantile on the device)
             sp, sv = torch.quantile(gp.reshape(-1), p), torch.quantile(gv.reshape(-1), p)
+            if quantiles is not None:
+                quantiles.append((sp.item(), sv.item()))
             gp = torch.minimum(torch.maximum(gp, -sp), sp)
             gv = torch.minimum(torch.maximum(gv, -sv), sv)
             bx = torch.as_tensor(box, dtype=torch.float32, device=DEV)
@@ -200,6 +204,17 @@ def test_cfg_step_recomposed_at_size(tag):
     """B = 256 (about 5.5k atoms), 10 steps: every step recomposed on the host (recomposed_step_errors)."""
     worst, n = recomposed_step_errors(tag, 256, 10, 31)
     record("cfg_step_recomposed_at_size", tag=tag, n=n, **worst)
+    assert worst["pos"] <= STEP_TOL and worst["v0"] <= STEP_TOL and worst["vt"] <= STEP_TOL, worst
+
+
+def test_cfg_step_recomposed_negative_quantile():
+    """dynamic_threshold with p = 0.02 at B = 4, 3 steps: the quantile of both tensors is negative in every step, so clip(x, -s, s)
+    has -s > s and collapses every value to s, as torch.clamp with min > max does -- cfg_apply (sm_cfg.h) with a negative
+    statistic, recomposed on the host like the steps above."""
+    quantiles = []
+    worst, n = recomposed_step_errors("dynamic_threshold", 4, 3, 31, p=0.02, quantiles=quantiles)
+    record("cfg_step_recomposed_negative_quantile", n=n, quantiles=quantiles, **worst)
+    assert len(quantiles) == 3 and all(sp < 0 and sv < 0 for sp, sv in quantiles), quantiles
     assert worst["pos"] <= STEP_TOL and worst["v0"] <= STEP_TOL and worst["vt"] <= STEP_TOL, worst
 
 
