@@ -119,7 +119,7 @@ struct shapemol_ctx {
     int bn_eval = 0;            // 1: evaluation-mode batch-norm (running statistics, shapemol_set_bn_running) instead of the batch's
     DevList mem_bn;             // the two below
     float *bn_run = nullptr;    // [2][L][heads] running mean | running variance (device)
-    double *bn_eval_acc = nullptr;   // [L][kBnReplicas][2][heads] sums that reproduce them for the current batch size
+    double *bn_eval_acc = nullptr;   // [L][kVnReplicas][2][heads] sums that reproduce them for the current batch size
     DdpmFold ddpm_vf{};         // the last layer's coordinate update inside the DDPM kernel (option ddpm_fold), handed from run_score to run_ddpm
     float hid_max = 0.f;        // bound of the edge MLPs' hidden activations (LayerNorm outputs): must fit fp16 for edge_bf16 = 3
     int num_cu = 256;
@@ -234,7 +234,7 @@ int workspace_alloc(shapemol_ctx *c, int64_t capN, int64_t capB) {
         A(&c->h_a, capN * H) || A(&c->h_b, capN * H) || A(&c->pre0, capN * 4 * H) || A(&c->preAB, capN * 8 * H) || A(&c->q_x, capN * H) || A(&c->q_h, capN * H) ||
         A(&c->att, capN * H) || A(&c->o3, capN * 48) || A(&c->xsum, capN * 3) || A(&c->mol_span, capN) || A(&c->alpha, capN * c->KP * 2 * (H / 16)) || A(&c->pd, capN * hd * 6) || A(&c->x_a, capN * 3) ||
         A(&c->x_b, capN * 3) || A(&c->x_state, capN * 3) || A(&c->pred_pos, capN * 3) ||
-        A(&c->pred_v, capN * g.num_classes) || A(&c->v_state, capN) || A(&c->stamps, 2048) || A(&c->kstamps, 8 * 16 * 4096) || A(&c->bn_acc, (size_t)L * kBnReplicas * 2 * hd + L + 1) ||
+        A(&c->pred_v, capN * g.num_classes) || A(&c->v_state, capN) || A(&c->stamps, 2048) || A(&c->kstamps, 8 * 16 * 4096) || A(&c->bn_acc, (size_t)L * kVnReplicas * 2 * hd + L + 1) ||
         (c->KP > 16 && (A(&c->part_rows, (size_t)2 * capN * H) || A(&c->part_ms, (size_t)2 * capN * hd * 2))) ||
         A(&c->status, 8) || A(&c->chain_params, 1) || prep_args(c->prep[0]) ||
         prep_data(c->prep[1]) || A(&c->pred_pos_u, capN * 3) || A(&c->pred_v_u, capN * g.num_classes) ||
@@ -604,7 +604,7 @@ EdgeFusedArgs::VnFuse vn_fuse_args(const shapemol_ctx *c, const ShapePrep &sp, i
     const DevLayer &D = c->dm.layer[l];
     const int hd = c->cfg.n_heads;
     return {sp.ps + (size_t)l * c->capB * 2 * hd * 3, c->P(D.wf_x), c->P(D.wd_x), c->P(D.wf_o), c->P(D.wd_o), c->P(D.bn_g), c->P(D.bn_b),
-            c->mol_of, c->pd, c->bn_acc + (size_t)l * kBnReplicas * 2 * hd, arrive, c->status + ST_VN_BARRIER, x_next, enable};
+            c->mol_of, c->pd, c->bn_acc + (size_t)l * kVnReplicas * 2 * hd, arrive, c->status + ST_VN_BARRIER, x_next, enable};
 }
 
 // What follows the h2x attention of layer l on the f16 / streaming kernels (vn_fuse = 0 or 2): the VN-linear + statistics epilogue
@@ -618,7 +618,7 @@ H2xPlan h2x_plan(const shapemol_ctx *c, const ShapePrep &sp, int l, bool fold, b
     if (!c->opt.vn_fuse || half_tiles) return p;
     const DevLayer &D = c->dm.layer[l];
     const int hd = c->cfg.n_heads;
-    const double *acc = stat_acc + (size_t)l * kBnReplicas * 2 * hd;
+    const double *acc = stat_acc + (size_t)l * kVnReplicas * 2 * hd;
     p.vn = vn_fuse_args(c, sp, l, x_next, nullptr, 2);
     p.stats_done = true;
     const bool to_ddpm = !has_next && l == c->cfg.num_layers - 1 && out_pos && c->opt.ddpm_fold && chain_guide(c) == Guide::None &&
@@ -694,7 +694,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
     const int L = g.num_layers, hd = g.n_heads, C = g.num_classes, D = g.time_emb_dim, KP = c->KP;
     const int n = (int)N;
     AtomEmbArgs ae{c->P(c->dm.embw), c->P(c->dm.embb), v_in, c->mol_of, c->ttab, c->t_mol, sampling ? c->steps : nullptr,
-                   c->steps + 1, c->bn_acc, c->h_a, n, H, C, D, t_first, L * kBnReplicas * 2 * hd + L};   // + the grid-barrier counters
+                   c->steps + 1, c->bn_acc, c->h_a, n, H, C, D, t_first, L * kVnReplicas * 2 * hd + L};   // + the grid-barrier counters
     const int nlay = c->opt.stop_layer >= 0 ? std::min(c->opt.stop_layer, L) : L;
     // every decision that does not depend on the layer, from the geometry of the launches below (sm_launch.h)
     const lg::In gi = launch_in<H>(c, n);
@@ -749,7 +749,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
     if (c->bn_eval) {
         if (!c->bn_run) return fail("bn_eval = 1 needs the running statistics (shapemol_set_bn_running)");
         if (c->opt.vn_fuse == 1) return fail("bn_eval = 1 is not available with vn_fuse = 1 (coordinate update behind a grid barrier)");
-        const int tot = L * kBnReplicas * 2 * hd;
+        const int tot = L * kVnReplicas * 2 * hd;
         LAUNCH("prep", SMK(bn_eval_fill_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, c->bn_run, c->bn_run + (size_t)L * hd, L, hd, n, c->bn_eval_acc));
         stat_acc = c->bn_eval_acc;
     }
@@ -845,7 +845,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
         } else if (sf.phases) {   // h2x attention, both images resident in LDS (exactly split bf16 operands)
             EdgeFusedArgs fa{c->P(Dl.img_kh), c->P(Dl.img_vh), c->preAB, c->q_h, cur_x, c->nbr, c->ew, c->alpha, c->o3, n, 8 * H, stamps_h};
             if (c->opt.vn_fuse) {   // VN-linear + batch statistics (2) or the whole coordinate update (1: grid barrier inside) behind the attention
-                double *tail = c->bn_acc + (size_t)L * kBnReplicas * 2 * hd;
+                double *tail = c->bn_acc + (size_t)L * kVnReplicas * 2 * hd;
                 fa.vn = vn_fuse_args(c, sp, l, x_next, reinterpret_cast<unsigned *>(tail + l), c->opt.vn_fuse == 1 ? 1 : 2);
                 if (c->opt.vn_fuse == 1) vn_done = true; else stats_done = true;
             }
@@ -855,11 +855,11 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
             if (launch_edge<H, true>(c, s, e)) return 1;
         }
         VnArgs va{cur_x, c->o3, sp.ps + (size_t)l * c->capB * 2 * hd * 3, c->P(Dl.wf_x), c->P(Dl.wd_x), c->P(Dl.wf_o),
-                  c->P(Dl.wd_o), c->P(Dl.bn_g), c->P(Dl.bn_b), c->mol_of, c->pd, c->bn_acc + (size_t)l * kBnReplicas * 2 * hd, x_next, n, hd};
+                  c->P(Dl.wd_o), c->P(Dl.bn_g), c->P(Dl.bn_b), c->mol_of, c->pd, c->bn_acc + (size_t)l * kVnReplicas * 2 * hd, x_next, n, hd};
         const int per_blk = 256 / hd;
         if (!vn_done) {
             if (!stats_done) LAUNCH("vn_stats", SMK(vn_stats_kernel, dim3((N + per_blk - 1) / per_blk), dim3(kVnThreads), 0, s, va));
-            if (c->bn_eval) va.acc = stat_acc + (size_t)l * kBnReplicas * 2 * hd;      // (the statistics pass wrote the batch's sums elsewhere)
+            if (c->bn_eval) va.acc = stat_acc + (size_t)l * kVnReplicas * 2 * hd;      // (the statistics pass wrote the batch's sums elsewhere)
             LAUNCH("vn_apply", SMK(vn_apply_kernel, dim3((N + per_blk - 1) / per_blk), dim3(256), 0, s, va));
         }
         cur_x = x_next;
@@ -981,7 +981,7 @@ int shapemol_set_bn_running(shapemol_ctx *c, const float *h_mean, const float *h
     HIPCHK(hipDeviceSynchronize());
     if (!c->bn_run) {      // (a failed second allocation releases the first: both or neither)
         HIPCHK(c->mem_bn.alloc(&c->bn_run, 2 * count * sizeof(float)));
-        HIPCHK(c->mem_bn.alloc(&c->bn_eval_acc, (size_t)L * kBnReplicas * 2 * hd * sizeof(double)));
+        HIPCHK(c->mem_bn.alloc(&c->bn_eval_acc, (size_t)L * kVnReplicas * 2 * hd * sizeof(double)));
     }
     HIPCHK(hipMemcpy(c->bn_run, h_mean, count * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->bn_run + count, h_var, count * sizeof(float), hipMemcpyHostToDevice));
@@ -1211,7 +1211,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     else if (k == "mesh_group_flags") { src = c->m_cnt ? c->m_cnt + 4 * c->m_cnt_cap : nullptr; bytes = (size_t)c->m_flag_groups * 4; }
     else if (k == "cfg_stat") { src = c->cfg_stat; bytes = 2 * 4; }
     else if (k == "cfg_group_stat") { src = c->cgs.last_groups > 0 ? c->cgs.stat : nullptr; bytes = (size_t)c->cgs.last_groups * 2 * 4; }
-    else if (k == "bnstat") { src = c->bn_acc; bytes = (size_t)g.num_layers * kBnReplicas * 2 * g.n_heads * 8; }
+    else if (k == "bnstat") { src = c->bn_acc; bytes = (size_t)g.num_layers * kVnReplicas * 2 * g.n_heads * 8; }
     else { fail("shapemol_debug_read: unknown buffer " + k); return -1; }
     if (!src || bytes > max_bytes) { fail("shapemol_debug_read: buffer unavailable or destination too small"); return -1; }
     if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||

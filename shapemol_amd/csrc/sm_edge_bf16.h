@@ -19,6 +19,7 @@
 // the jobs fit; loads of a job are issued before the weight image is copied to LDS.
 #pragma once
 #include "sm_device.h"
+#include "sm_vn.h"
 #ifndef SM_ABLATE
 #define SM_ABLATE 0          // diagnostic builds only (build.sh --ablate MASK): compile-time mask of parts to drop
 #endif
@@ -123,28 +124,11 @@ struct EdgeFusedArgs {
     float *out;             // x2h: [N][H]; h2x: [N][16][3]
     int n_atoms, ld_pre;
     unsigned long long *stamps;   // diagnostic build only
-    // h2x only: the coordinate update that follows the attention (VN-linear + train-mode batch-norm + VN-leaky-ReLU,
-    // shape_vn_layers.py:41-61,95-110; uni_transformer.py:153-162) fused behind it.  enable = 0 leaves it to
-    // vn_stats_kernel / vn_apply_kernel (sm_misc.h), whose arithmetic this follows line by line.
-    struct VnFuse {
-        const float *ps;            // [B][2][heads][3]
-        const float *wf_x, *wd_x;   // [heads]
-        const float *wf_o, *wd_o;   // [heads][16]
-        const float *bn_g, *bn_b;   // [heads]
-        const int *mol_of;
-        float *pd;                  // [N][heads][6]
-        double *acc;                // [kVnReplicas][2][heads], zeroed at the start of the evaluation
-        unsigned *arrive;           // grid-barrier counter of this launch, zeroed likewise
-        int *err;                   // set to 1 if the grid barrier timed out (workgroups not co-resident)
-        float *x_out;               // [N][3]
-        int enable;                 // 0 off, 1 whole update (grid barrier inside), 2 VN-linear + statistics only
-    } vn;
+    // h2x only: the coordinate update that follows the attention (sm_vn.h) fused behind it.  enable = 0 leaves it to
+    // vn_stats_kernel / vn_apply_kernel (sm_misc.h).
+    using VnFuse = ::VnFuse;
+    VnFuse vn;
 };
-constexpr int kVnReplicas = 16;
-// doubles of reduction scratch behind the LDS images of the h2x kernel (host and device use the same formula)
-__host__ __device__ constexpr int vn_red_doubles(int nwave, int hd) {
-    return nwave * 64 > (2 + 2 * kVnReplicas) * hd ? nwave * 64 : (2 + 2 * kVnReplicas) * hd;
-}
 
 // ONE = true: the launch gives every wave at most one job (jobs <= workgroups x waves; the common case up to ~6k atoms):
 // the job loops become straight-line code and no next job's rows are kept in flight (fewer live registers).
@@ -372,6 +356,8 @@ edge_fused_kernel(EdgeFusedArgs a) {
         const int v_al = lane >> 4, v_c = lane & 15;               // lane = (atom of the job, channel)
         const bool v_lane = v_al < APJ && v_c < HD;
         double v_s1 = 0.0, v_s2 = 0.0;
+        // (This kernel keeps the coordinate update of sm_vn.h written out by hand: through the shared functions its results were not
+        //  bit-identical to its own earlier ones, profiles/vn_one_body.)
         // ---- VN-linear of this wave's atoms: p, d per channel from the 16 attention rows (+ x, + shape term);
         //      lane = (atom of the job, channel).  The rows were stored by this wave above (same CU, write-through).
         if (!one_job) __syncthreads();               // rows come back through L2: drain this workgroup's stores first

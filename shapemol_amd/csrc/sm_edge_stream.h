@@ -169,7 +169,7 @@ struct StreamGeo {
 };
 
 // Prologue every wave runs (after its own first requests): the producer parts by LDS-DMA and, for x2h, the coordinate update
-// of the PREVIOUS layer folded in (sm_edge16.h: VnFold): the workgroup recomputes the new coordinates of every atom of the
+// of the PREVIOUS layer folded in (sm_vn.h: VnFold, vn_fold_span): the workgroup recomputes the new coordinates of every atom of the
 // molecules its tiles touch into an LDS table and writes those of its own atoms to global memory.  Ends with the barrier
 // that publishes both.
 template <int H, int KP, bool H2X>
@@ -185,59 +185,7 @@ SM_DEV void stream_prologue(const EdgeStreamArgs &a, const StreamGeo<H, KP, H2X>
         if (a.vf.enable) {
             float *xt = lds + M::O_TAIL;                       // [kVnFoldCap][3] new coordinates of the touched molecules
             double *sred = reinterpret_cast<double *>(xt + 3 * kVnFoldCap);          // [2][16] batch sums
-            const int first_atom = G.wg_first * APJ;
-            const int last_atom = min(a.n_atoms, G.wg_end * APJ) - 1;
-            if (first_atom <= last_atom) {
-                span0 = a.vf.mol_span[first_atom].x;
-                const int span = a.vf.mol_span[last_atom].y - span0;
-                if (span > kVnFoldCap && threadIdx.x == 0) *a.vf.span_flag = 1;      // the max_mol_atoms hint was too small
-                span_n = min(span, kVnFoldCap);
-            }
-            if (threadIdx.x < 32) {
-                const int c = threadIdx.x & 15, which = threadIdx.x >> 4;
-                double t = 0.0;
-                if (c < HD) for (int r = 0; r < kVnReplicas; ++r) t += a.vf.acc[(size_t)r * 2 * HD + which * HD + c];
-                sred[threadIdx.x] = t;
-            }
-            __syncthreads();
-            const int c = lane & 15;
-            float meanf = 0.f, rstd = 0.f, bng = 0.f, bnb = 0.f;
-            if (c < HD) {
-                const double cnt = (double)a.n_atoms;
-                const double mean = sred[c] / cnt;
-                double var = sred[16 + c] / cnt - mean * mean;
-                var = var > 0.0 ? var : 0.0;
-                meanf = (float)mean;
-                rstd = 1.0f / sqrtf((float)var + 1e-5f);
-                bng = a.vf.bn_g[c]; bnb = a.vf.bn_b[c];
-            }
-            for (int it = threadIdx.x; it < span_n * 16; it += NWAVE * 64) {       // item = (atom of the span, channel)
-                const int va = span0 + (it >> 4);
-                float o[3] = {0.f, 0.f, 0.f};
-                if (c < HD) {
-                    const float *pdp = a.vf.pd + ((size_t)va * HD + c) * 6;
-                    float p[3] = {pdp[0], pdp[1], pdp[2]};
-                    const float d[3] = {pdp[3], pdp[4], pdp[5]};
-                    const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-                    const float nbn = (nrm - meanf) * rstd * bng + bnb;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) p[k] = p[k] / nrm * nbn;
-                    const float dot = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
-                    const float dsq = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-                    const float coef = dot / (dsq + 1e-6f);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) o[k] = 0.2f * p[k] + 0.8f * (dot >= 0.f ? p[k] : p[k] - coef * d[k]);
-                }
-                float res[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) res[k] = seg_sum<16>(o[k]);              // over the channels of the atom
-                if (c < 3) {
-                    const float r = c == 0 ? res[0] : (c == 1 ? res[1] : res[2]);
-                    const float xn = a.vf.x_old[va * 3 + c] + (a.vf.xsum[va * 3 + c] / HD + r / HD);
-                    xt[(it >> 4) * 3 + c] = xn;
-                    if (va >= first_atom && va <= last_atom) a.vf.x_new[va * 3 + c] = xn;
-                }
-            }
+            vn_fold_span(a.vf, HD, a.n_atoms, G.wg_first * APJ, min(a.n_atoms, G.wg_end * APJ) - 1, xt, sred, NWAVE * 64, span0, span_n);
         }
     }
     __syncthreads();                       // the images have landed, the coordinate table is complete
@@ -260,60 +208,12 @@ SM_DEV void stream_vn_epilogue(const EdgeStreamArgs &a, const StreamGeo<H, KP, t
     for (int va = first_atom + wave * 4 + v_al; va < end_atom; va += NWAVE * 4) {
         if (v_c >= HD) continue;
         float orow[48];
-        const float *ov = a.out + (size_t)va * 48;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            const float4 t = ldg4(ov + 4 * i);
-            orow[4 * i] = t.x; orow[4 * i + 1] = t.y; orow[4 * i + 2] = t.z; orow[4 * i + 3] = t.w;
-        }
-        float wf[16], wd[16];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 t = ldg4(a.vn.wf_o + v_c * 16 + 4 * i), u = ldg4(a.vn.wd_o + v_c * 16 + 4 * i);
-            wf[4 * i] = t.x; wf[4 * i + 1] = t.y; wf[4 * i + 2] = t.z; wf[4 * i + 3] = t.w;
-            wd[4 * i] = u.x; wd[4 * i + 1] = u.y; wd[4 * i + 2] = u.z; wd[4 * i + 3] = u.w;
-        }
-        const float *psf = a.vn.ps + ((size_t)a.vn.mol_of[va] * 2 * HD + v_c) * 3;
-        const float *psd = psf + HD * 3;
-        const float wfx = a.vn.wf_x[v_c], wdx = a.vn.wd_x[v_c];
-        float p[3], d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float xk = a.x[va * 3 + k];
-            float pp = wfx * xk, dd = wdx * xk;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                pp += wf[rr] * orow[rr * 3 + k];
-                dd += wd[rr] * orow[rr * 3 + k];
-            }
-            p[k] = pp + psf[k];
-            d[k] = dd + psd[k];
-        }
-        float *out = a.vn.pd + ((size_t)va * HD + v_c) * 6;
-        out[0] = p[0]; out[1] = p[1]; out[2] = p[2]; out[3] = d[0]; out[4] = d[1]; out[5] = d[2];
-        if (a.xsum && v_c < 3) {                     // sum over the attention rows (padding rows are zero), r ascending as vn_apply_kernel
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) { a0 += orow[rr * 3]; a1 += orow[rr * 3 + 1]; a2 += orow[rr * 3 + 2]; }
-            a.xsum[va * 3 + v_c] = v_c == 0 ? a0 : (v_c == 1 ? a1 : a2);
-        }
-        const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-        v_s1 += (double)nrm;
-        v_s2 += (double)nrm * (double)nrm;
+        vn_load_rows(a.out + (size_t)va * 48, orow);
+        vn_linear_atom(a.vn, orow, a.x, a.xsum, va, v_c, HD, v_s1, v_s2);
     }
     vn_red[(wave * 64 + lane) * 2] = v_s1; vn_red[(wave * 64 + lane) * 2 + 1] = v_s2;
     __syncthreads();
-    if (threadIdx.x < HD) {
-        double s1 = 0.0, s2 = 0.0;
-        for (int w = 0; w < NWAVE; ++w)
-            for (int al = 0; al < 4; ++al) {
-                s1 += vn_red[(w * 64 + al * 16 + threadIdx.x) * 2];
-                s2 += vn_red[(w * 64 + al * 16 + threadIdx.x) * 2 + 1];
-            }
-        double *acc = a.vn.acc + (size_t)(blockIdx.x % kVnReplicas) * 2 * HD;
-        atomicAdd(acc + threadIdx.x, s1);
-        atomicAdd(acc + HD + threadIdx.x, s2);
-    }
+    vn_sums_commit(vn_red, 64, NWAVE, 4, HD, a.vn.acc);
 }
 
 // x2h epilogue (option x2h_out_fuse): h' = h + MLP_out([att | h]) of the workgroup's own atoms -- node_out6_kernel's work without

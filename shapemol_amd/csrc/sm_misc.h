@@ -4,6 +4,7 @@
 #pragma once
 #include "sm_device.h"
 #include "sm_cfg.h"
+#include "sm_vn.h"
 
 // ---------------------------------------------------------------------------------------------
 // batch (N,) i64 sorted -> mol_of (N,) i32 and mol_off (B+1,) i32
@@ -103,20 +104,6 @@ struct ShapeTermArgs {
     float *add;            // [B][ld] (4H columns written)
     int ldw, H, SL, ld;
 };
-__global__ void shape_term_kernel(ShapeTermArgs a) {
-    const int b = blockIdx.x;
-    for (int f = threadIdx.x; f < 4 * a.H; f += blockDim.x) {
-        const int blk = f / a.H, ff = f % a.H;
-        float v = 0.f;
-        if ((blk & 1) == 0) {
-            const float *w = (blk == 0 ? a.wk : a.wv) + (size_t)ff * a.ldw;
-            v = (blk == 0 ? a.bk : a.bv)[ff];
-            for (int i = 0; i < a.SL; ++i) v += w[i] * a.inv[(size_t)b * a.SL + i];
-        }
-        a.add[(size_t)b * a.ld + f] = v;
-    }
-}
-
 // all shape terms of a chain in one launch: grid (B, n_terms), the argument blocks in device memory
 __global__ void shape_term_multi_kernel(const ShapeTermArgs *terms) {
     const ShapeTermArgs a = terms[blockIdx.y];
@@ -173,17 +160,6 @@ struct VnShapeArgs {
     float *ps;             // [B][2][heads][3]
     int S, heads;
 };
-__global__ void vn_shape_kernel(VnShapeArgs a) {
-    const int b = blockIdx.x, per = a.heads * 3, cin = 1 + a.heads + a.S;
-    for (int idx = threadIdx.x; idx < 2 * per; idx += blockDim.x) {
-        const int which = idx / per, c = (idx % per) / 3, dim = idx % 3;
-        const float *w = (which ? a.wd : a.wf) + (size_t)c * cin + 1 + a.heads;
-        float v = 0.f;
-        for (int s = 0; s < a.S; ++s) v += w[s] * a.shape[((size_t)b * a.S + s) * 3 + dim];
-        a.ps[(size_t)b * 2 * per + idx] = v;
-    }
-}
-
 // all layers in one launch: grid (B, L); `shape` is the call's argument, the rest comes from the device-side blocks
 __global__ void vn_shape_multi_kernel(const float *shape, const VnShapeArgs *layers) {
     VnShapeArgs a = layers[blockIdx.y];
@@ -456,7 +432,7 @@ edge_weight_kernel(EdgeWeightArgs a) {
 // VNLinearLeakyReLU (shape_vn_layers.py:95-110) with VNBatchNorm in TRAIN mode (:50-61):
 // pass 1 computes p = W_f z, d = W_d z per atom and accumulates the batch sums of the vector
 // norms; pass 2 normalises with the batch mean / biased variance and updates x.
-// z = [x_i | o_i (heads vectors) | shape_b (S vectors)]; the shape part is pre-reduced (vn_shape_kernel).
+// z = [x_i | o_i (heads vectors) | shape_b (S vectors)]; the shape part is pre-reduced (vn_shape_multi_kernel).
 // o3 is stored with permuted head rows (row 4g + r, see sm_edge.h); `wf_o`/`wd_o` are permuted to match.
 // ---------------------------------------------------------------------------------------------
 struct VnArgs {
@@ -468,7 +444,7 @@ struct VnArgs {
     const float *bn_g, *bn_b;   // [heads]
     const int *mol_of;
     float *pd;              // [N][heads][6]  p (3) and d (3)
-    double *acc;            // [kBnReplicas][2][heads] sums of norms / squared norms (this layer), spread over
+    double *acc;            // [kVnReplicas][2][heads] sums of norms / squared norms (this layer), spread over
                             // replicas because same-address atomics serialise at the memory side
     float *x_out;           // [N][3]
     int n_atoms, heads;
@@ -478,7 +454,6 @@ struct VnArgs {
 // block's atoms and the VN weights are staged in LDS with coalesced 16-byte loads (each thread used to
 // issue ~150 scalar global loads); the double sums go to global memory with one atomic per block and channel.
 constexpr int kVnThreads = 256;
-constexpr int kBnReplicas = 16;
 __global__ void __launch_bounds__(kVnThreads) vn_stats_kernel(VnArgs a) {
     __shared__ __attribute__((aligned(16))) float s_o[64 * 48];      // up to 64 atoms x 16 rows x 3
     __shared__ __attribute__((aligned(16))) float s_w[2 * 32 * 16];  // wf_o | wd_o, [heads][16]
@@ -497,26 +472,10 @@ __global__ void __launch_bounds__(kVnThreads) vn_stats_kernel(VnArgs a) {
         const float *o = s_o + la * 48;
         const float *wf = s_w + c * 16, *wd = s_w + 32 * 16 + c * 16;
         const float *psf = a.ps + ((size_t)a.mol_of[i] * 2 * heads + c) * 3;
-        const float *psd = psf + heads * 3;
-        const float wfx = a.wf_x[c], wdx = a.wd_x[c];
         float p[3], d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float xk = a.x[i * 3 + k];
-            float pp = wfx * xk, dd = wdx * xk;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                pp += wf[r] * o[r * 3 + k];
-                dd += wd[r] * o[r * 3 + k];
-            }
-            p[k] = pp + psf[k];
-            d[k] = dd + psd[k];
-        }
-        float *out = a.pd + ((size_t)i * heads + c) * 6;
-        out[0] = p[0]; out[1] = p[1]; out[2] = p[2]; out[3] = d[0]; out[4] = d[1]; out[5] = d[2];
-        const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-        nv = (double)nrm;
-        nv2 = (double)nrm * (double)nrm;
+        vn_linear_pd(o, wf, wd, a.wf_x[c], a.wd_x[c], a.x + i * 3, psf, psf + heads * 3, p, d);
+        vn_store_pd(a.pd + ((size_t)i * heads + c) * 6, p, d);
+        vn_norm_sums(p, nv, nv2);
     }
     red[0][threadIdx.x] = nv;
     red[1][threadIdx.x] = nv2;
@@ -524,9 +483,7 @@ __global__ void __launch_bounds__(kVnThreads) vn_stats_kernel(VnArgs a) {
     if (threadIdx.x < heads) {
         double s = 0.0, s2 = 0.0;
         for (int k = 0; k < per_blk; ++k) { s += red[0][k * heads + threadIdx.x]; s2 += red[1][k * heads + threadIdx.x]; }
-        double *acc = a.acc + (size_t)(blockIdx.x % kBnReplicas) * 2 * heads;
-        atomicAdd(acc + threadIdx.x, s);
-        atomicAdd(acc + heads + threadIdx.x, s2);
+        vn_sums_add(a.acc, heads, s, s2);
     }
 }
 
@@ -536,7 +493,7 @@ __global__ void __launch_bounds__(kVnThreads) vn_stats_kernel(VnArgs a) {
 // s1 = mean N, s2 = (var + mean^2) N in replica 0, zeros elsewhere (double: mean and var come back to the last float bit).
 __global__ void bn_eval_fill_kernel(const float *run_mean, const float *run_var, int n_layers, int heads, int n_atoms, double *acc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int per = kBnReplicas * 2 * heads;
+    const int per = kVnReplicas * 2 * heads;
     if (i >= n_layers * per) return;
     const int l = i / per, r = (i % per) / (2 * heads), which = (i % (2 * heads)) / heads, c = i % heads;
     double v = 0.0;
@@ -555,37 +512,19 @@ __global__ void vn_apply_kernel(VnArgs a) {
     const bool ok = la < per_blk && i < a.n_atoms;
     float o[3] = {0.f, 0.f, 0.f};
     if (ok) {
-        const double cnt = (double)a.n_atoms;
+        // both totals in one loop (two calls of vn_replica_total: 64 registers against 35; the same sums, r ascending)
         double s1 = 0.0, s2 = 0.0;
-        for (int r = 0; r < kBnReplicas; ++r) { s1 += a.acc[(size_t)r * 2 * heads + c]; s2 += a.acc[(size_t)r * 2 * heads + heads + c]; }
-        const double mean = s1 / cnt;
-        double var = s2 / cnt - mean * mean;
-        var = var > 0.0 ? var : 0.0;
-        const float meanf = (float)mean;
-        const float rstd = 1.0f / sqrtf((float)var + 1e-5f);
-        const float *pd = a.pd + ((size_t)i * heads + c) * 6;
-        float p[3] = {pd[0], pd[1], pd[2]};
-        const float d[3] = {pd[3], pd[4], pd[5]};
-        const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-        const float nbn = (nrm - meanf) * rstd * a.bn_g[c] + a.bn_b[c];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p[k] = p[k] / nrm * nbn;
-        const float dot = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
-        const float dsq = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        const float coef = dot / (dsq + 1e-6f);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float neg = p[k] - coef * d[k];
-            o[k] = 0.2f * p[k] + 0.8f * (dot >= 0.f ? p[k] : neg);
-        }
+        for (int r = 0; r < kVnReplicas; ++r) { s1 += a.acc[(size_t)r * 2 * heads + c]; s2 += a.acc[(size_t)r * 2 * heads + heads + c]; }
+        float meanf, rstd;
+        vn_batch_stats(s1, s2, (double)a.n_atoms, meanf, rstd);
+        vn_act(a.pd + ((size_t)i * heads + c) * 6, meanf, rstd, a.bn_g[c], a.bn_b[c], o);
     }
     red[threadIdx.x][0] = o[0]; red[threadIdx.x][1] = o[1]; red[threadIdx.x][2] = o[2];
     __syncthreads();
     if (ok && c < 3) {
-        float res = 0.f, att = 0.f;
+        float res = 0.f;
         for (int h = 0; h < heads; ++h) res += red[la * heads + h][c];
-        const float *ob = a.o3 + (size_t)i * 48;
-        for (int r = 0; r < 16; ++r) att += ob[r * 3 + c];          // padding rows are zero
+        const float att = vn_rows_sum(a.o3 + (size_t)i * 48, c);
         a.x_out[i * 3 + c] = a.x[i * 3 + c] + (att / heads + res / heads);
     }
 }
@@ -760,10 +699,10 @@ __global__ void set_chain_params_kernel(ChainParams *dst, ChainParams v, int *st
 
 // The coordinate update of the LAST layer (vn_apply_kernel's work: batch-norm of ||p||, VN-leaky-ReLU, mean over the channels,
 // x += ...) inside the DDPM kernel: 16 lanes per atom there are the 16 channels here, and the predicted position is consumed
-// nowhere else (chains without guidance).  Same arithmetic as the update folded into the x2h kernels (sm_edge16.h, VnFold).
+// nowhere else (chains without guidance): vn_update16, the step of the update folded into the x2h kernels (sm_vn.h).
 struct DdpmFold {
     const float *pd;          // [N][heads][6]
-    const double *acc;        // [kBnReplicas][2][heads] batch sums of the last layer
+    const double *acc;        // [kVnReplicas][2][heads] batch sums of the last layer
     const float *bn_g, *bn_b; // [heads]
     const float *xsum;        // [N][3] sum over the attention rows (h2x epilogue)
     const float *x_old;       // [N][3]
@@ -936,42 +875,14 @@ __global__ void __launch_bounds__(256) ddpm_step16_kernel(DdpmArgs aa, CfgArgs c
     if (a.vf.enable) {
         __shared__ double sred[32];
         const int HD = a.vf.heads;
-        if (threadIdx.x < 32) {
-            const int cc = threadIdx.x & 15, which = threadIdx.x >> 4;
-            double t = 0.0;
-            if (cc < HD) for (int r = 0; r < kBnReplicas; ++r) t += a.vf.acc[(size_t)r * 2 * HD + which * HD + cc];
-            sred[threadIdx.x] = t;
-        }
-        __syncthreads();
-        float o[3] = {0.f, 0.f, 0.f};
+        vn_stage_totals(a.vf.acc, HD, sred);
+        float meanf = 0.f, rstd = 0.f, bng = 0.f, bnb = 0.f;
         if (c < HD) {
-            const double cnt = (double)a.n_atoms;
-            const double mean = sred[c] / cnt;
-            double var = sred[16 + c] / cnt - mean * mean;
-            var = var > 0.0 ? var : 0.0;
-            const float meanf = (float)mean;
-            const float rstd = 1.0f / sqrtf((float)var + 1e-5f);
-            const float *pdp = a.vf.pd + ((size_t)i * HD + c) * 6;
-            float p[3] = {pdp[0], pdp[1], pdp[2]};
-            const float d[3] = {pdp[3], pdp[4], pdp[5]};
-            const float nrm = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) + 1e-6f;
-            const float nbn = (nrm - meanf) * rstd * a.vf.bn_g[c] + a.vf.bn_b[c];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) p[k] = p[k] / nrm * nbn;
-            const float dot = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
-            const float dsq = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-            const float coef = dot / (dsq + 1e-6f);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) o[k] = 0.2f * p[k] + 0.8f * (dot >= 0.f ? p[k] : p[k] - coef * d[k]);
+            vn_batch_stats(sred[c], sred[16 + c], (double)a.n_atoms, meanf, rstd);
+            bng = a.vf.bn_g[c]; bnb = a.vf.bn_b[c];
         }
-        float res[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) res[k] = seg_sum<16>(o[k]);              // over the channels of the atom
-        if (c < 3) {
-            const float r = c == 0 ? res[0] : (c == 1 ? res[1] : res[2]);
-            pp_fold = a.vf.x_old[i * 3 + c] + (a.vf.xsum[i * 3 + c] / HD + r / HD);
-            if (atom_ok) a.vf.pred_out[i * 3 + c] = pp_fold;
-        }
+        pp_fold = vn_update16(a.vf.pd, a.vf.x_old, a.vf.xsum, i, c, HD, meanf, rstd, bng, bnb);
+        if (c < 3 && atom_ok) a.vf.pred_out[i * 3 + c] = pp_fold;
     }
     // classifier-free guidance: the values of the atom's group (or of the whole batch); lanes 0..2 read their side of the box
     CfgLane gl{};
@@ -1052,12 +963,6 @@ __global__ void gumbel_argmax_kernel(const float *logits, const float *u, int n,
         if (sc > bestv) { bestv = sc; best = c; }
     }
     out[i] = best;
-}
-
-__global__ void copy_state_kernel(const float *x_src, const int64_t *v_src, float *x_dst, int64_t *v_dst, int n_atoms) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_atoms * 3 && x_dst) x_dst[i] = x_src[i];
-    if (i < n_atoms && v_dst) v_dst[i] = v_src[i];
 }
 
 // diagnostic: shader-clock / real-time stamp pairs (clock = d(memtime) / d(memrealtime) * 100 MHz)
