@@ -565,6 +565,8 @@ int shapemol_debug_cfg_stats(shapemol_ctx *ctx, const float *d_pos_cond, const f
  *        fused kNN graph + edge-weight kernel, a coordinate update folded into an x2h kernel, the last one folded into the
  *        posterior kernel, x2h attention + node stage in one launch, streaming edge kernels' tiles per workgroup, their grid
  *        (0, 0 on the other edge kernels), CUs}; after a graph replay: the decisions taken when that step was captured,
+ *        "launch_edge" (4,) i64 the edge tiles of that evaluation (host memory): {half-atom tiles used (k > 16), tiles per
+ *        attention, combine32_kernel launches issued, floats of a row of the half-tile buffer},
  *        "mesh_group_flags" (G,) i32: per group of the last chain / pass with mesh groups, the steps in which the group was
  *        left unguided for want of within-atoms (status flag 6 says that some group was, this says which and how often).
  * Returns the number of bytes written, or -1. */

@@ -161,6 +161,9 @@ struct shapemol_ctx {
     // the x2h kernel's fused tail in that layer (debug_read "launch_x2h_out"): {fused form used, atoms per workgroup, 16-atom column
     // tiles per workgroup, dynamic LDS bytes of the x2h launch}
     int64_t x2h_out_rec[4] = {};
+    // the edge tiles of that evaluation (debug_read "launch_edge"): {half-atom tiles used (k > 16), tiles per attention, combine32_kernel
+    // launches issued, floats of a part_rows row}
+    int64_t edge_rec[4] = {};
     // the captured step depends on the batch geometry only: seed, noise and trajectory pointers live in chain_params
     // what a captured step depends on besides the options (which drop the graphs when set): sizes, guidance, and the two
     // launch decisions taken from the max_mol_atoms hint (folded coordinate update, fused graph kernel)
@@ -411,6 +414,7 @@ template <bool H2X>
 int launch_combine32(shapemol_ctx *c, hipStream_t s, float *out, int n_atoms) {
     Combine32Args ca{c->part_rows, c->part_ms, out, n_atoms, c->cfg.n_heads, c->cfg.hidden_dim / 16};
     const int items = n_atoms * (H2X ? 48 : c->cfg.hidden_dim / 4);
+    ++c->edge_rec[2];
     LAUNCH("edge_combine", SMK(combine32_kernel<H2X>, dim3((items + 255) / 256), dim3(256), 0, s, ca));
     return 0;
 }
@@ -718,6 +722,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
     std::fill(c->node_rec, c->node_rec + 8, 0);
     std::fill(c->x2h_out_rec, c->x2h_out_rec + 4, 0);
     rec[0] = sampling; rec[1] = sf.graph_fused; rec[7] = c->num_cu;
+    { const int64_t er[4] = {sf.half_tiles, lg::tile_jobs(KP, n).jobs, 0, sf.half_tiles ? H : 0}; std::copy(er, er + 4, c->edge_rec); }
     if (sf.stream && nlay > 0) { const lg::StreamGeom g = lg::stream_geom(gi); rec[5] = g.chunk; rec[6] = g.grid; }
     if (reuse_graph) {
     } else if (sf.graph_fused) {
@@ -896,6 +901,9 @@ int check_cfg(const shapemol_config &g) {
     if (g.n_heads * 8 != g.hidden_dim) return fail("hidden_dim / n_heads must be 8");
     if (g.num_r_gaussian != 20) return fail("num_r_gaussian must be 20 (fixed RBF centres)");
     if (g.knn < 1 || g.knn > 32) return fail("knn must be in 1..32");
+    // k > 16 runs on half-atom tiles, whose h2x rows are 48 floats wide and are stored into rows of hidden_dim floats (part_rows):
+    // at hidden_dim 32 they do not fit, and a forward of that combination has faulted on the device
+    if (g.knn > 16 && g.hidden_dim < 48) return fail("knn > 16 needs hidden_dim 128 (the reduced model, hidden_dim 32, supports knn 1..16)");
     if (g.shape_dim < 1 || g.shape_dim > 64 || g.shape_latent_dim < 4 || g.shape_latent_dim > 64 || (g.shape_latent_dim & 3))
         return fail("shape_dim must be 1..64, shape_latent_dim a multiple of 4 in 4..64");
     if (g.time_emb_dim < 4 || g.time_emb_dim > 16 || (g.time_emb_dim & 1)) return fail("time_emb_dim must be even, 4..16");
@@ -1192,6 +1200,7 @@ int64_t shapemol_debug_read(shapemol_ctx *c, const char *name, void *dst, size_t
     if (k == "captures") { if (max_bytes < 8) return -1; std::memcpy(dst, &c->n_captures, 8); return 8; }
     if (k == "launch") { if (max_bytes < sizeof(c->launch_rec)) return -1; std::memcpy(dst, c->launch_rec, sizeof(c->launch_rec)); return sizeof(c->launch_rec); }
     if (k == "launch_x2h_out") { if (max_bytes < sizeof(c->x2h_out_rec)) return -1; std::memcpy(dst, c->x2h_out_rec, sizeof(c->x2h_out_rec)); return sizeof(c->x2h_out_rec); }
+    if (k == "launch_edge") { if (max_bytes < sizeof(c->edge_rec)) return -1; std::memcpy(dst, c->edge_rec, sizeof(c->edge_rec)); return sizeof(c->edge_rec); }
     if (k == "launch_node") { if (max_bytes < sizeof(c->node_rec)) return -1; std::memcpy(dst, c->node_rec, sizeof(c->node_rec)); return sizeof(c->node_rec); }
     if (k == "nbr") { src = c->nbr; bytes = N * c->KP * 4; }
     else if (k == "ew") { src = c->ew; bytes = N * c->KP * 4; }

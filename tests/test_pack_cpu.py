@@ -106,3 +106,44 @@ def test_atom_type_head_tiles_and_padding(probe, num_classes, nt2, tmp_path):
     emb = im[int(out["dm.embw"]):int(out["dm.embw"]) + d.H * e].reshape(d.H, e)
     embT = im[int(out["dm.embwT"]):int(out["dm.embwT"]) + d.H * e].reshape(e, d.H)
     assert np.array_equal(emb, sdn["ligand_atom_emb.weight"]) and np.array_equal(embT, emb.T)
+
+
+@pytest.mark.parametrize("case", ["h32_k9", "h128_sl36", "h32_max_k32"])
+def test_shape_time_and_vocabulary_dimensions_in_the_image(probe, case, tmp_path):
+    """Configurations away from S = 32, SL = 32, D = 8, C = 15 (tests/config_space.py), checked structurally against the state
+    dict -- not hashed: a hash recorded from the packer proves nothing about a shape it has never been compared at.  Per layer the
+    split-off shape columns of each edge MLP's first Linear ([H][SL] = columns G + 2H onwards of net.0.weight) and the two
+    VN-linear weights ([heads][1 + heads + S]); the invariant shape MLP ([S][S], [SL][S]), the time MLP ([2D][D], [D][2D]) and the
+    embedding [H][C + D] with its transpose."""
+    import config_space as CS
+    from shapemol_amd.spec import ModelDims
+    C = CS.classes(case)
+    out, image, sdn, _ = probe_image(probe, CS.overrides(case), tmp_path, C)
+    d = ModelDims(CS.config(case), C)
+    im = np.frombuffer(image, np.float32)
+
+    def at(name, *shape):
+        off = int(out[name])
+        return im[off:off + int(np.prod(shape))].reshape(shape)
+
+    assert len(sdn["time_emb.1.weight"]) == 2 * d.temb and sdn["ligand_atom_emb.weight"].shape == (d.H, C + d.temb)
+    for l in range(d.L):
+        base = f"refine_net.base_block.{l}."
+        for dev, key in (("sk_x2h", "x2h_layers.0.hk_func"), ("sv_x2h", "x2h_layers.0.hv_func"), ("sk_h2x", "h2x_layers.0.xk_func"),
+                         ("sv_h2x", "h2x_layers.0.xv_func")):
+            w = sdn[base + key + ".net.0.weight"]
+            assert w.shape == (d.H, d.G + 2 * d.H + d.S_latent)
+            assert np.array_equal(at(f"dm.layer{l}.{dev}", d.H, d.S_latent), w[:, d.G + 2 * d.H:]), (l, dev)
+        for dev, key in (("vn_f", "map_to_feat"), ("vn_d", "map_to_dir")):
+            w = sdn[base + f"h2x_layers.0.shape_linear.{key}.weight"]
+            assert w.shape == (d.heads, 1 + d.heads + d.S)
+            assert np.array_equal(at(f"dm.layer{l}.{dev}", d.heads, 1 + d.heads + d.S), w), (l, dev)
+            assert np.array_equal(at(f"dm.layer{l}.w{dev[-1]}_x", d.heads), w[:, 0]), (l, dev)
+    inv = "refine_net.invariant_shape_layer.hidden_layer.net."
+    assert np.array_equal(at("dm.inv.w1", d.S, d.S), sdn[inv + "0.weight"]) and np.array_equal(at("dm.inv.w2", d.S_latent, d.S), sdn[inv + "3.weight"])
+    assert np.array_equal(at("dm.inv.b2", d.S_latent), sdn[inv + "3.bias"])
+    assert np.array_equal(at("dm.te1w", 2 * d.temb, d.temb), sdn["time_emb.1.weight"]) and np.array_equal(at("dm.te2w", d.temb, 2 * d.temb), sdn["time_emb.3.weight"])
+    e = C + d.temb
+    emb = at("dm.embw", d.H, e)
+    assert np.array_equal(emb, sdn["ligand_atom_emb.weight"]) and np.array_equal(at("dm.embwT", e, d.H), emb.T)
+    assert int(out["dm.vhead.nt2"]) == (C + 15) // 16
