@@ -676,6 +676,62 @@ int shapemol_eval_run(shapemol_eval_ctx *ctx, int64_t n_frames, int64_t n_mols, 
 /* Tests only: fill the context's device workspace with `byte`. */
 int shapemol_eval_debug_fill(shapemol_eval_ctx *ctx, int32_t byte, void *stream);
 
+/* ---- Gaussian similarity of molecules: shape and electrostatic overlap, and the rigid overlay ------------------------------
+ * What the reference's evaluation asks of shaep_utils.get_ROCS / shape_tanimoto / VAB_2nd_order and of espsim's
+ * GetIntegralsViaGaussians / GaussInt / SimilarityMetric, plus a rigid overlay by this library's own rule where the reference
+ * shells out to ShaEP.  Two packed sets of molecules, a and b: n_mols molecules back to back, HOST
+ * h_off (n_mols + 1, starting at 0), DEVICE d_pos (N, 3) float64, HOST per-atom parameters h_u and h_v (N) float64.  HOST
+ * h_pairs (n_pairs, 2) int64 names a molecule of a and one of b per pair, so N-to-1, 1-to-1 and all-pairs are one call.
+ * mode 0 (shape): u = the Gaussian widths alpha, v = the prefactors p; one term per atom pair with s = alpha_i + alpha_j,
+ * A = (pi^1.5 * (p_i * p_j)) / (s * sqrt(s)), B = (alpha_i * alpha_j) / s, w = 1.  mode 1 (esp): u = the charges w, v unused
+ * (may be null); n_terms (1..16) terms with HOST h_term_a = A_k and h_term_b = B_k (GaussInt's b are -B_k).  An integral is
+ * S_xy = sum_{i in x, j in y} w_i w_j sum_k A_k exp(-(B_k * r2)), r2 = (dx*dx + dy*dy) + dz*dz, float64 without FMA
+ * contraction; the thread of atom i sums over j ascending, the threads' sums are added by a fixed binary tree: the same bits
+ * in every run, no atomics.  metric 0: Tanimoto S_ab / ((S_aa + S_bb) - S_ab); metric 1: Carbo S_ab / sqrt(S_aa * S_bb).  A
+ * denominator that equals 0 gives a NaN score and the pair's flag.
+ * A pair whose molecules both have at most 64 atoms takes the wave form (form 0), any other the block form (1);
+ * shapemol_sim_sizes writes up to n of (atoms of the wave form, atoms per molecule, terms, starts of an overlay, largest
+ * iteration cap, pairs per call) and returns 6.  Limits, refused with a message before any kernel runs: 1..256 atoms per
+ * molecule, 1..2^20 molecules per set, 1..2^22 pairs with indices inside their sets, finite parameters, widths > 0.
+ * shapemol_sim_check touches no device; it writes the form of every pair to the optional h_forms (n_pairs). */
+typedef struct shapemol_sim_ctx shapemol_sim_ctx;
+int shapemol_sim_sizes(int64_t *out, int32_t n);
+int shapemol_sim_check(int32_t mode, int64_t n_mols_a, const int64_t *h_off_a, const double *h_u_a, const double *h_v_a,
+                       int64_t n_mols_b, const int64_t *h_off_b, const double *h_u_b, const double *h_v_b, int64_t n_pairs,
+                       const int64_t *h_pairs, int32_t n_terms, const double *h_term_a, const double *h_term_b,
+                       int32_t *h_forms);
+int shapemol_sim_create(int device, shapemol_sim_ctx **out);
+void shapemol_sim_destroy(shapemol_sim_ctx *ctx);
+/* The fixed pose.  DEVICE outputs: d_out (n_pairs, 4) float64 = S_aa, S_bb, S_ab, score; d_flags (n_pairs) int32, 1 where the
+ * denominator is 0.  The call synchronises the stream.  Returns 0, or 1 with a message; a refused call launches nothing and
+ * the context stays usable.  A context serves one stream at a time. */
+int shapemol_sim_score(shapemol_sim_ctx *ctx, int32_t mode, int32_t metric, int64_t n_mols_a, const int64_t *h_off_a,
+                       const double *d_pos_a, const double *h_u_a, const double *h_v_a, int64_t n_mols_b,
+                       const int64_t *h_off_b, const double *d_pos_b, const double *h_u_b, const double *h_v_b,
+                       int64_t n_pairs, const int64_t *h_pairs, int32_t n_terms, const double *h_term_a,
+                       const double *h_term_b, double *d_out, int32_t *d_flags, void *stream);
+/* The overlay (shape mode): per pair, maximise S_ab over rigid motions of molecule a.  Starts 0..3: the proper rotations
+ * Vb diag(1,1,1 | 1,-1,-1 | -1,1,-1 | -1,-1,1) Va^T that map a's principal frame onto b's with the centroids coincident (V:
+ * eigenvectors of the unit-weight inertia tensor by cyclic Jacobi, ascending eigenvalues, third column = first x second);
+ * start 4, with include_given, the pose as given.  From each start BFGS over (translation, rotation about a's centroid) with
+ * the analytic gradient, steps of at most 0.5 (Angstrom, radian) per component, Armijo backtracking (1e-4, halving, at most
+ * 30 times), until the largest gradient component is <= gtol * (S_aa + S_bb) / 2 (converged) or max_iter (0..10000)
+ * iterations are used.  The start with the largest S_ab wins (ties: the lowest index).  The winner's motion is applied to the
+ * coordinates of a as given, x' = ((R0 x + R1 y) + R2 z) + t per row, and the result is scored by the fixed-pose kernel; with
+ * include_given the pose as given replaces it (start 4, identity, 0 iterations) when it scores higher, so the result is never
+ * below it; the converged flag reported then is start 4's own if that start never left the pose as given, else 0.  A start
+ * whose value or gradient is NaN (positions that are not finite) stops at once, not converged.  DEVICE outputs: d_out (n_pairs, 4) float64 = S_aa, S_bb, S_ab, Tanimoto; d_rot (n_pairs, 9) row-major and
+ * d_trans (n_pairs, 3) float64; d_info (n_pairs, 4) int32 = winning start, its iterations, its converged flag, zero
+ * denominator; d_aligned (optional, may be null): the moved copies of a, (sum over the pairs of their a's atoms, 3) float64
+ * in pair order.  Synchronises the stream; errors as for shapemol_sim_score. */
+int shapemol_sim_align(shapemol_sim_ctx *ctx, int64_t n_mols_a, const int64_t *h_off_a, const double *d_pos_a,
+                       const double *h_alpha_a, const double *h_p_a, int64_t n_mols_b, const int64_t *h_off_b,
+                       const double *d_pos_b, const double *h_alpha_b, const double *h_p_b, int64_t n_pairs,
+                       const int64_t *h_pairs, int32_t include_given, int32_t max_iter, double gtol, double *d_out,
+                       double *d_rot, double *d_trans, int32_t *d_info, double *d_aligned, void *stream);
+/* Tests only: fill the context's device workspaces with `byte`. */
+int shapemol_sim_debug_fill(shapemol_sim_ctx *ctx, int32_t byte, void *stream);
+
 /* Per-kernel launch-time accounting with HIP events on the launch stream (bench only).
  * shapemol_profile_begin() arms it for the following _score/_sample calls (forces eager launches);
  * shapemol_profile_end() synchronises and writes, for each of up to `cap` kernel classes,

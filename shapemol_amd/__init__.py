@@ -14,6 +14,9 @@ and the molecule meshes themselves, from atom coordinates and radii (utils/shape
 and, after the chain, the scores of sampled molecules that need no chemistry toolkit (utils/evaluation analyze.check_stability,
 eval_bond_length pair-distance profiles), for one frame or every recorded frame, with the rule given as data:
     StabilityRule, GeometryReport, check_stability, evaluate_geometry, evaluate_trajectory, evaluate_samples
+and how well a sample matches the shape of its condition (utils/evaluation shaep_utils.get_ROCS / shape_tanimoto, espsim's Gaussian
+integrals, calculate_shaep_shape_sim with this package's own overlay in place of the ShaEP executable):
+    shape_tanimoto, get_rocs, esp_similarity, align_shapes, similarity_to_condition
 plus helpers: synthetic weights/inputs (synth), schedules (diffusion), the C-ABI binding (_lib).
 """
 from .molopt_score_model import ScorePosNet3D, log_sample_categorical, pointcloud_shape_guidance, mesh_shape_guidance  # noqa: F401
@@ -24,5 +27,6 @@ from .shape_data import ShapeData, collate_fn, get_pointAE_shape_emb  # noqa: F4
 from .mol_surface import get_mesh, get_mesh_batch  # noqa: F401
 from .evaluation import (StabilityRule, GeometryReport, check_stability, evaluate_geometry, evaluate_trajectory,  # noqa: F401
                          evaluate_samples)
+from .similarity import shape_tanimoto, get_rocs, esp_similarity, align_shapes, similarity_to_condition  # noqa: F401
 
 __version__ = "0.3.0"

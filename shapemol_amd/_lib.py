@@ -39,6 +39,8 @@ EXPORTS = (
     "shapemol_msurf_copy",
     "shapemol_eval_sizes", "shapemol_eval_check", "shapemol_eval_create", "shapemol_eval_destroy", "shapemol_eval_run",
     "shapemol_eval_debug_fill",
+    "shapemol_sim_sizes", "shapemol_sim_check", "shapemol_sim_create", "shapemol_sim_destroy", "shapemol_sim_score",
+    "shapemol_sim_align", "shapemol_sim_debug_fill",
 )
 
 
@@ -198,6 +200,14 @@ def load():
     lib.shapemol_eval_run.argtypes = ([vp, i64, i64, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, C.c_double, vp, i32, C.c_double, i32]
                                       + [vp] * 7)
     lib.shapemol_eval_debug_fill.argtypes = [vp, i32, vp]
+    lib.shapemol_sim_sizes.argtypes = [vp, i32]
+    lib.shapemol_sim_check.argtypes = [i32, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, i32, vp, vp, vp]
+    lib.shapemol_sim_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.shapemol_sim_destroy.argtypes = [vp]
+    lib.shapemol_sim_destroy.restype = None
+    lib.shapemol_sim_score.argtypes = [vp, i32, i32, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    lib.shapemol_sim_align.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, C.c_double] + [vp] * 6
+    lib.shapemol_sim_debug_fill.argtypes = [vp, i32, vp]
     lib.shapemol_profile_begin.argtypes = [vp]
     lib.shapemol_profile_end.argtypes = [vp, vp, vp, vp, C.c_int]
     if lib.shapemol_abi_version() != ABI_VERSION:
