@@ -326,8 +326,8 @@ int set_edge_attr_k() {
 
 template <int H>
 int set_edge_attr(int KP) {
-    constexpr size_t pro6 = 2 * Chain6Lds<H>::FRAG * 16 + Chain6Lds<H>::PRE * 4, pro16 = 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4;
-    ATTR(pro6, node_prologue6_kernel<H>); ATTR(Chain6Lds<H>::BYTES, node_chain6_kernel<H>); ATTR(kLin6Chunk * 3 * H * 32, node_linear6_kernel<H>);
+    constexpr size_t pro16 = Prologue16Lds<H>::BYTES;
+    ATTR(Prologue6Lds<H>::BYTES, node_prologue6_kernel<H>); ATTR(Chain6Lds<H>::BYTES, node_chain6_kernel<H>); ATTR(kLin6Chunk * 3 * H * 32, node_linear6_kernel<H>);
     ATTR(Out6Lds<H>::BYTES, node_out6_kernel<H>); ATTR(After6Lds<H>::bytes(kLin6Chunk), node_after6_kernel<H>);
     ATTR(pro16, node_prologue16_kernel<H>); ATTR(Chain16Lds<H>::BYTES, node_chain16_kernel<H>); ATTR(kLin16Chunk * 2 * H * 32, node_linear16_kernel<H>);
     ATTR(pro16, node_prologue16_kernel<H, true>); ATTR(Chain16Lds<H>::BYTES, node_chain16_kernel<H, true>); ATTR(kLin16Chunk * 2 * H * 32, node_linear16_kernel<H, true>);
@@ -656,9 +656,21 @@ int launch_prologue(shapemol_ctx *c, hipStream_t s, const NodePrologueArgs &pa, 
     const int n_ct = (pa.n_atoms + 15) / 16;
     const dim3 grid((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), block(H * 4);
     if (!range_flag) range_flag = c->status + ST_RANGE;
-    if (c->opt.node_f16 && c->opt.feat_f16) LAUNCH("node_prologue", SMK((node_prologue16_kernel<H, true>), grid, block, 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, range_flag));
-    else if (c->opt.node_f16) LAUNCH("node_prologue", SMK(node_prologue16_kernel<H>, grid, block, 2 * Chain16Lds<H>::FRAG * 16 + Chain16Lds<H>::PRE * 4, s, pa, range_flag));
-    else LAUNCH("node_prologue", SMK(node_prologue6_kernel<H>, grid, block, 2 * Chain6Lds<H>::FRAG * 16 + Chain6Lds<H>::PRE * 4, s, pa));
+    if (c->opt.node_f16 && c->opt.feat_f16) LAUNCH("node_prologue", SMK((node_prologue16_kernel<H, true>), grid, block, Prologue16Lds<H>::BYTES, s, pa, range_flag));
+    else if (c->opt.node_f16) LAUNCH("node_prologue", SMK(node_prologue16_kernel<H>, grid, block, Prologue16Lds<H>::BYTES, s, pa, range_flag));
+    else LAUNCH("node_prologue", SMK(node_prologue6_kernel<H>, grid, block, Prologue6Lds<H>::BYTES, s, pa));
+    return 0;
+}
+
+// The node chain in one launch per pair of column tiles, in the form the node precision options select (chain_bf16, node_f16, feat_f16)
+template <int H>
+int launch_node_chain(shapemol_ctx *c, hipStream_t s, const NodeChainArgs &na) {
+    const int n_ct = (na.n_atoms + 15) / 16;
+    const dim3 grid((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), block(H * 4);
+    if (c->opt.chain_bf16 && c->opt.node_f16 && c->opt.feat_f16) LAUNCH("node_chain", SMK((node_chain16_kernel<H, true>), grid, block, Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
+    else if (c->opt.chain_bf16 && c->opt.node_f16) LAUNCH("node_chain", SMK(node_chain16_kernel<H>, grid, block, Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
+    else if (c->opt.chain_bf16) LAUNCH("node_chain", SMK(node_chain6_kernel<H>, grid, block, Chain6Lds<H>::BYTES, s, na));
+    else LAUNCH("node_chain", SMK(node_chain_kernel<H>, grid, block, 0, s, na));
     return 0;
 }
 
@@ -806,7 +818,6 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
             na.n_follow = 1;
             if (has_next) { na.f[1] = follow_of(c, c->dm.layer[l + 1].q_x2h, NODE_LN_RELU, c->q_x, H, H); na.n_follow = 2; }
             else if (out_v) { na.f[1] = follow_of(c, c->dm.vhead, NODE_SSP, out_v, C, C); na.n_follow = 2; v_done = true; }
-            const int n_ct = (n + 15) / 16;
             const int lin_tiles = (has_next && l + 1 < L ? 8 : 4) * NT;
             if (sf.lin_fused) {
                 na.lin_img16 = c->P(Dl.lin16_img); na.add_mol = sp.addp + (size_t)l * c->capB * 8 * H; na.mol_of = c->mol_of;
@@ -815,10 +826,7 @@ int run_score(shapemol_ctx *c, hipStream_t s, const ShapePrep &sp, const float *
             float *lin_add = sp.addp + (size_t)l * c->capB * 8 * H;
             if (sf.levels) { if (launch_node_levels<H>(c, s, na, c->P(Dl.lin6_img), lin_add, 8 * H, c->preAB, 8 * H, lin_tiles, sf.out_fused)) return 1; }
             else if (sf.xc_fused) { rec[4] = 1; if (launch_x2h_chain<H>(c, s, xea, na)) return 1; }
-            else if (c->opt.chain_bf16 && c->opt.node_f16 && c->opt.feat_f16) LAUNCH("node_chain", SMK((node_chain16_kernel<H, true>), dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
-            else if (c->opt.chain_bf16 && c->opt.node_f16) LAUNCH("node_chain", SMK(node_chain16_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain16Lds<H>::BYTES, s, na, c->status + ST_RANGE));
-            else if (c->opt.chain_bf16) LAUNCH("node_chain", SMK(node_chain6_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), Chain6Lds<H>::BYTES, s, na));
-            else LAUNCH("node_chain", SMK(node_chain_kernel<H>, dim3((n_ct + CHAIN_COLS - 1) / CHAIN_COLS), dim3(H * 4), 0, s, na));
+            else if (launch_node_chain<H>(c, s, na)) return 1;
             cur_h = dst;
             // per-node halves of the edge MLPs' first Linear: h2x of this layer | x2h of the next one
             if (!sf.lin_fused && !sf.levels && launch_linear<H>(c, s, "node_pre", cur_h, c->P(Dl.lin_img), c->P(Dl.lin6_img), c->P(Dl.lin16_img), lin_add, 8 * H,

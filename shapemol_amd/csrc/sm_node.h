@@ -1,6 +1,6 @@
 // Node kernels: every per-atom Linear / MLP of the score network.  The default path is the bf16x6 family in
-// the second half of this file (node_linear6_kernel, node_chain6_kernel, node_prologue6_kernel: exactly split
-// operands on the bf16 matrix cores, activations kept in LDS as ready-made fragments); the fp32-MFMA kernels
+// the second half of this file (node_linear6_kernel, and the Team6 kernels node_out6 / node_after6 / node_chain6 /
+// node_prologue6: exactly split operands on the bf16 matrix cores, activations kept in LDS as ready-made fragments); the fp32-MFMA kernels
 // described next are the first version, kept behind shapemol_set_option("lin_bf16" / "chain_bf16", 0).
 //
 // Reference semantics (paths relative to the reference repository):
@@ -487,11 +487,17 @@ node_chain_kernel(NodeChainArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// node_chain6_kernel: the same chain on the bf16 matrix cores with exactly split operands (the
-// gemm_bf16x6 arithmetic of sm_device.h).  Differences to node_chain_kernel:
+// The exact node family: the same MLPs on the bf16 matrix cores with exactly split operands (the gemm_bf16x6
+// arithmetic of sm_device.h).  A team of H / 16 waves owns a pair of 16-atom column tiles; its steps are
+// written once, as members of Team6, and every kernel below is a schedule of them:
+//   node_out6_pair         h' = h + MLP_out([att | h])      node_out6_kernel, node_chain6_kernel, the x2h tail (sm_edge_stream.h)
+//   node_chain6_kernel     h', then both follow-up MLPs interleaved over two pre-activation buffers
+//   node_after6_kernel     one follow-up MLP per job, beside the linear jobs (linear6_job)
+//   node_prologue6_kernel  embedding rows, the first query MLP and the per-node products of layer 0
+// Differences to node_chain_kernel:
 //   * every activation that feeds a Linear lives in LDS as ready-made B fragments (three bf16 pieces),
-//     written once by whoever produces it: the staging pass ([att | h]), the normalise pass (hidden
-//     tiles) or the producing wave itself (h': each lane owns half a fragment);
+//     written once by whoever produces it: a staging pass (put_frag), the normalise pass (hidden tiles)
+//     or the producing wave itself (put_half: each lane owns half a fragment of h');
 //   * LayerNorm + ReLU (or shifted softplus) is no longer repeated by every wave of the team: the
 //     pre-activations cross LDS in fp32 and the team's lanes normalise disjoint slices (H / 8 lanes per
 //     column, two-pass statistics over a DPP row segment) -- one more barrier per MLP, ~8x less vector work;
@@ -514,425 +520,7 @@ struct Chain6Lds {
 };
 
 template <int H>
-__global__ void __launch_bounds__(H * 4)
-node_chain6_kernel(NodeChainArgs a) {
-    using L = Chain6Lds<H>;
-    constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS, XS = L::XS;
-    constexpr int LPC = NB * 4;                            // lanes per column in the normalise pass
-    static_assert(CC == 2, "the normalise pass covers exactly 32 columns");
-    extern __shared__ __attribute__((aligned(16))) unsigned char chain6_lds[];
-    u32x4 *fin = reinterpret_cast<u32x4 *>(chain6_lds);    // [att | h] fragments (K = 2H); later the two hidden tiles
-    u32x4 *fhid0 = fin, *fhid1 = fin + L::FRAG;
-    u32x4 *fh = fin + 2 * L::FRAG;                         // fragments of the new h
-    float *pre0 = reinterpret_cast<float *>(fin + 3 * L::FRAG), *pre1 = pre0 + L::PRE;
-    const int lane = threadIdx.x & 63, ot = threadIdx.x >> 6;
-    const int n = lane & 15, g = lane >> 4;
-    const int ct0 = blockIdx.x * CC;
-    const int f0 = 16 * ot + 4 * g;
-
-    auto load_w = [&](const float *img, auto &w) {         // w[3][KB]: this wave's block of a split image
-        constexpr int KB = sizeof(w[0]) / sizeof(u32x4);
-        const u32x4 *wi = reinterpret_cast<const u32x4 *>(img) + (size_t)ot * 3 * KB * 64 + lane;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int b = 0; b < KB; ++b) w[p][b] = wi[(p * KB + b) * 64];
-    };
-    // acc[c] += W * X_c over KB k-steps; fragments at f[((piece * KB + b) * CC + c) * 64 + lane]
-    auto gemm6 = [&](const auto &w, const u32x4 *f, f32x4 (&acc)[CC]) {
-        constexpr int KB = sizeof(w[0]) / sizeof(u32x4);
-#pragma unroll
-        for (int b = 0; b < KB; ++b) {
-            u32x4 xh[CC], xm[CC], xl[CC];
-#pragma unroll
-            for (int c = 0; c < CC; ++c) {
-                xh[c] = f[((0 * KB + b) * CC + c) * 64 + frag_slot(b, lane)];
-                xm[c] = f[((1 * KB + b) * CC + c) * 64 + frag_slot(b, lane)];
-                xl[c] = f[((2 * KB + b) * CC + c) * 64 + frag_slot(b, lane)];
-            }
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[2][b], xh[c], acc[c]);      // smallest terms first
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[1][b], xm[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xl[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[1][b], xh[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xm[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xh[c], acc[c]);
-        }
-    };
-    auto store_pre = [&](float *pre, const f32x4 (&acc)[CC]) {
-#pragma unroll
-        for (int c = 0; c < CC; ++c) stg4(pre + (c * 16 + n) * XS + f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
-    };
-    // activation of a pre-activation buffer -> fragments: LPC lanes per column, 8 features per lane
-    auto normalise = [&](const float *pre, int mode, const float *gam, const float *bet, u32x4 *fo) {
-        const int col = ot * (64 / LPC) + lane / LPC, ln = lane % LPC;
-        const int b = ln >> 2, gg = ln & 3;
-        const int fa = 32 * b + 4 * gg;
-        const float4 p0 = ldg4(pre + col * XS + fa), p1 = ldg4(pre + col * XS + fa + 16);
-        float v[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-        if (mode == NODE_LN_RELU) {
-            float s = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) s += v[i];
-            const float mean = seg_sum<LPC>(s) * (1.0f / H);
-            float q = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { const float d = v[i] - mean; q += d * d; }
-            const float var = seg_sum<LPC>(q) * (1.0f / H);
-            const float rstd = 1.0f / sqrtf(var + 1e-5f);
-            const float4 g0 = ldg4(gam + fa), g1 = ldg4(gam + fa + 16), b0 = ldg4(bet + fa), b1 = ldg4(bet + fa + 16);
-            const float ga[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-            const float be[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = fmaxf((v[i] - mean) * rstd * ga[i] + be[i], 0.f);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = (v[i] > 20.f ? v[i] : log1pf(expf(v[i]))) - 0.6931471805599453f;
-        }
-        u32x4 hi, mid, lo;
-        split3_bf16(v, hi, mid, lo);
-        u32x4 *dst = fo + (b * CC + (col >> 4)) * 64 + frag_slot(b, gg * 16 + (col & 15));
-        dst[0] = hi; dst[NB * CC * 64] = mid; dst[2 * NB * CC * 64] = lo;
-    };
-    auto atom_of = [&](int c) { return min((ct0 + c) * 16 + n, a.n_atoms - 1); };
-    auto atom_ok = [&](int c) { return (ct0 + c) * 16 + n < a.n_atoms; };
-
-    SM_TICK(a.stamps, 0);
-    // ---- stage 0: weights of the output MLP; [att | h] tiles -> fragments ----------------------------
-    // The activation rows are requested BEFORE the weights: vector memory operations complete in order, and behind the 48 weight
-    // loads of a wave the staging pass waits for them too (18.96 -> 18.61 us per launch at B = 256).
-    u32x4 w1[3][2 * NB], w2[3][NB];
-    constexpr int SITER = CC * 2 * NB * 64 / (NT * 64);
-    float4 sv0[SITER], sv1[SITER];
-#pragma unroll
-    for (int it = 0; it < SITER; ++it) {
-        const int idx = threadIdx.x + it * NT * 64;
-        const int sl = idx & 63, sb = (idx >> 6) % (2 * NB), sc = idx / (64 * 2 * NB);
-        const int at = min((ct0 + sc) * 16 + (sl & 15), a.n_atoms - 1);
-        const float *src = (sb < NB ? a.att + (size_t)at * H + 32 * sb : a.h + (size_t)at * H + 32 * (sb - NB)) + 4 * (sl >> 4);
-        sv0[it] = ldg4(src); sv1[it] = ldg4(src + 16);
-    }
-    float4 hres[CC];
-#pragma unroll
-    for (int c = 0; c < CC; ++c) hres[c] = ldg4(a.h + (size_t)atom_of(c) * H + f0);    // residual
-    const float4 b1 = ldg4(a.b1 + f0), b2 = ldg4(a.b2 + f0);
-    load_w(a.w1img6, w1);
-#pragma unroll
-    for (int it = 0; it < SITER; ++it) {
-        const int idx = threadIdx.x + it * NT * 64;
-        const int sl = idx & 63, sb = (idx >> 6) % (2 * NB), sc = idx / (64 * 2 * NB);
-        const float v[8] = {sv0[it].x, sv0[it].y, sv0[it].z, sv0[it].w, sv1[it].x, sv1[it].y, sv1[it].z, sv1[it].w};
-        u32x4 hi, mid, lo;
-        split3_bf16(v, hi, mid, lo);
-        u32x4 *dst = fin + (sb * CC + sc) * 64 + frag_slot(sb, sl);
-        dst[0] = hi; dst[2 * NB * CC * 64] = mid; dst[2 * 2 * NB * CC * 64] = lo;
-    }
-    load_w(a.w2img6, w2);
-    __syncthreads();
-    SM_TICK(a.stamps, 1);
-
-    // ---- stage 1: h' = h + W2 relu(LN(W1 [att | h] + b1)) + b2 ---------------------------------------
-    {
-        f32x4 acc[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b1.x, b1.y, b1.z, b1.w};
-        gemm6(w1, fin, acc);
-        store_pre(pre0, acc);
-    }
-    u32x4 wf0[3][NB], wf1[3][NB];                                    // first Linears of the follow-up MLPs
-    if (a.n_follow > 0) load_w(a.f[0].w1img6, wf0);
-    if (a.n_follow > 1) load_w(a.f[1].w1img6, wf1);
-    __syncthreads();
-    SM_TICK(a.stamps, 2);
-    normalise(pre0, NODE_LN_RELU, a.ln_g, a.ln_b, fhid0);
-    __syncthreads();
-    SM_TICK(a.stamps, 3);
-    {
-        f32x4 acc[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b2.x, b2.y, b2.z, b2.w};
-        gemm6(w2, fhid0, acc);
-#pragma unroll
-        for (int c = 0; c < CC; ++c) {
-            const float4 hn = {acc[c][0] + hres[c].x, acc[c][1] + hres[c].y, acc[c][2] + hres[c].z, acc[c][3] + hres[c].w};
-            if (atom_ok(c)) stg4(a.h_out + (size_t)atom_of(c) * H + f0, hn);
-            // this lane's four features are half of fragment (k-step ot / 2, lane) of column tile c
-            unsigned ph[2], pm[2], pl[2];
-            split3_pair(hn.x, hn.y, ph[0], pm[0], pl[0]);
-            split3_pair(hn.z, hn.w, ph[1], pm[1], pl[1]);
-            uint2 *dst = reinterpret_cast<uint2 *>(fh + ((ot >> 1) * CC + c) * 64 + frag_slot(ot >> 1, lane)) + (ot & 1);
-            dst[0] = uint2{ph[0], ph[1]};
-            dst[NB * CC * 64 * 2] = uint2{pm[0], pm[1]};
-            dst[2 * NB * CC * 64 * 2] = uint2{pl[0], pl[1]};
-        }
-    }
-    if (a.n_follow == 0) return;
-    const bool on0 = ot < a.f[0].nt2, on1 = a.n_follow > 1 && ot < a.f[1].nt2;
-    u32x4 wg0[3][NB], wg1[3][NB];                                    // second Linears of the follow-up MLPs
-    if (on0) load_w(a.f[0].w2img6, wg0);
-    __syncthreads();
-    SM_TICK(a.stamps, 4);
-
-    // ---- stage 2: follow-up MLPs on the new h ---------------------------------------------------------
-    {
-        const float4 ba = ldg4(a.f[0].b1 + f0);
-        f32x4 acc[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) acc[c] = f32x4{ba.x, ba.y, ba.z, ba.w};
-        gemm6(wf0, fh, acc);
-        store_pre(pre0, acc);
-    }
-    if (a.n_follow > 1) {
-        const float4 bb = ldg4(a.f[1].b1 + f0);
-        f32x4 acc[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) acc[c] = f32x4{bb.x, bb.y, bb.z, bb.w};
-        gemm6(wf1, fh, acc);
-        store_pre(pre1, acc);
-    }
-    if (on1) load_w(a.f[1].w2img6, wg1);
-    __syncthreads();
-    SM_TICK(a.stamps, 5);
-    normalise(pre0, a.f[0].mode, a.f[0].ln_g, a.f[0].ln_b, fhid0);
-    if (a.n_follow > 1) normalise(pre1, a.f[1].mode, a.f[1].ln_g, a.f[1].ln_b, fhid1);
-    __syncthreads();
-    SM_TICK(a.stamps, 6);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (!(k == 0 ? on0 : on1)) continue;
-        const NodeFollow &F = a.f[k];
-        const float4 b = ldg4(F.b2 + f0);
-        f32x4 acc[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b.x, b.y, b.z, b.w};
-        if (k == 0) gemm6(wg0, fhid0, acc); else gemm6(wg1, fhid1, acc);
-#pragma unroll
-        for (int c = 0; c < CC; ++c) {
-            if (!atom_ok(c)) continue;
-            const int atom = atom_of(c);
-            if (f0 + 4 <= F.n_store && (F.ld_out & 3) == 0) {
-                stg4(F.out + (size_t)atom * F.ld_out + f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (f0 + r < F.n_store) F.out[(size_t)atom * F.ld_out + f0 + r] = acc[c][r];
-            }
-        }
-    }
-    SM_STAMP(a.stamps, 7);
-}
-
-// -------------------------------------------------------------------------------------------------
-// node_prologue6_kernel: everything on the node side that precedes the first attention of an evaluation, in
-// one launch (it replaces atom_embed_kernel + node_mlp2_kernel + node_linear6_kernel at layer 0):
-//     h0 = ligand_atom_emb([one_hot(v) | time_emb])          (molopt_score_model.py:292-301), stored and split
-//     q  = query MLP of the first x2h attention on h0         (uni_transformer.py:68)
-//     pre0 = per-node halves of that attention's edge MLPs:   h0 W^T + per-molecule term  ([N][4H])
-// plus the per-evaluation bookkeeping (latch the step counter, clear the batch-norm accumulators).
-// Same team layout and bf16x6 arithmetic as node_chain6_kernel.
-// -------------------------------------------------------------------------------------------------
-struct NodePrologueArgs {
-    const float *emb_wT, *emb_b;  // [C + D][H] (transposed: a lane's four features are one 16-byte load), [H]
-    const int64_t *v;             // [N]
-    const int *mol_of;
-    const float *ttab;            // [T][D]
-    const float *etab;            // [T][C][H] embedding of every (timestep, atom type) pair (emb_table_kernel), or nullptr
-    const int *t_mol;             // [B] timestep per molecule (score API)
-    const int *step_ptr;          // sampling: device step counter (t = t_first - step), else nullptr
-    int *step_cur;
-    double *bn_acc;               // zeroed here
-    float *h_out;                 // [N][H]
-    NodeFollow q;                 // query MLP -> q.out
-    const float *lin_img6;        // split image of [n_lin_tiles * 16][H]
-    const float *add_mol;         // [B][ld_add] per-molecule term of the linear outputs
-    float *pre_out;               // [N][ld_out]
-    int n_lin_tiles, ld_add, ld_out;
-    int n_atoms, C, D, t_first, bn_acc_len;
-    unsigned long long *stamps;   // diagnostic build only
-};
-
-template <int H>
-__global__ void __launch_bounds__(H * 4)
-node_prologue6_kernel(NodePrologueArgs a) {
-    using L = Chain6Lds<H>;
-    constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS, XS = L::XS;
-    constexpr int LPC = NB * 4;
-    static_assert(CC == 2, "the normalise pass covers exactly 32 columns");
-    extern __shared__ __attribute__((aligned(16))) unsigned char chain6_lds[];
-    u32x4 *fh = reinterpret_cast<u32x4 *>(chain6_lds);      // fragments of h0
-    u32x4 *fhid = fh + L::FRAG;                             // hidden tile of the query MLP
-    float *pre0 = reinterpret_cast<float *>(fh + 2 * L::FRAG);
-    const int lane = threadIdx.x & 63, ot = threadIdx.x >> 6;
-    const int n = lane & 15, g = lane >> 4;
-    const int ct0 = blockIdx.x * CC;
-    const int f0 = 16 * ot + 4 * g;
-
-    auto load_w = [&](const float *img, int tile, u32x4 (&w)[3][NB]) {
-        const u32x4 *wi = reinterpret_cast<const u32x4 *>(img) + (size_t)tile * 3 * NB * 64 + lane;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int b = 0; b < NB; ++b) w[p][b] = wi[(p * NB + b) * 64];
-    };
-    auto gemm6 = [&](const u32x4 (&w)[3][NB], const u32x4 *f, f32x4 (&acc)[CC]) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            u32x4 xh[CC], xm[CC], xl[CC];
-#pragma unroll
-            for (int c = 0; c < CC; ++c) {
-                xh[c] = f[((0 * NB + b) * CC + c) * 64 + frag_slot(b, lane)];
-                xm[c] = f[((1 * NB + b) * CC + c) * 64 + frag_slot(b, lane)];
-                xl[c] = f[((2 * NB + b) * CC + c) * 64 + frag_slot(b, lane)];
-            }
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[2][b], xh[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[1][b], xm[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xl[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[1][b], xh[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xm[c], acc[c]);
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[c] = mfma_bf16(w[0][b], xh[c], acc[c]);
-        }
-    };
-    auto atom_of = [&](int c) { return min((ct0 + c) * 16 + n, a.n_atoms - 1); };
-    auto atom_ok = [&](int c) { return (ct0 + c) * 16 + n < a.n_atoms; };
-
-    // ---- bookkeeping of the evaluation ------------------------------------------------------------------
-    const int step = a.step_ptr ? *a.step_ptr : 0;
-    {
-        const int gid = blockIdx.x * (H * 4) + threadIdx.x;           // (the launch uses H * 4 threads: no blockDim read)
-        if (gid == 0 && a.step_ptr) *a.step_cur = step;
-        for (int i = gid; i < a.bn_acc_len; i += gridDim.x * (H * 4)) a.bn_acc[i] = 0.0;
-    }
-    // ---- stage 0: embedding of the workgroup's atoms -> global h0 and LDS fragments ----------------------
-    u32x4 wq1[3][NB], wl[3][NB];
-    load_w(a.q.w1img6, ot, wq1);
-    for (int idx = threadIdx.x; idx < CC * NB * 64; idx += NT * 64) {
-        const int sl = idx & 63, sb = (idx >> 6) % NB, sc = idx / (64 * NB);
-        const int at_raw = (ct0 + sc) * 16 + (sl & 15);
-        const int at = min(at_raw, a.n_atoms - 1);
-        const int t = a.step_ptr ? a.t_first - step : a.t_mol[a.mol_of[at]];
-        const int vi = min(max((int)a.v[at], 0), a.C - 1);       // out-of-range types are flagged by v_check_kernel
-        const int fa = 32 * sb + 4 * (sl >> 4);
-        float vv[8];
-        {   // the precomputed row of (t, v) (emb_table_kernel, built once per context with the sum y = (b + W[:, v]) + sum_k W[:, C + k] te[k],
-            // k ascending, that the reference's Linear evaluates per atom: molopt_score_model.py:292-301)
-            const float *row = a.etab + ((size_t)t * a.C + vi) * H + fa;
-            const float4 r0 = ldg4(row), r1 = ldg4(row + 16);
-            vv[0] = r0.x; vv[1] = r0.y; vv[2] = r0.z; vv[3] = r0.w; vv[4] = r1.x; vv[5] = r1.y; vv[6] = r1.z; vv[7] = r1.w;
-        }
-        if (at_raw < a.n_atoms) {
-            stg4(a.h_out + (size_t)at * H + fa, float4{vv[0], vv[1], vv[2], vv[3]});
-            stg4(a.h_out + (size_t)at * H + fa + 16, float4{vv[4], vv[5], vv[6], vv[7]});
-        }
-        u32x4 hi, mid, lo;
-        split3_bf16(vv, hi, mid, lo);
-        u32x4 *dst = fh + (sb * CC + sc) * 64 + frag_slot(sb, sl);
-        dst[0] = hi; dst[NB * CC * 64] = mid; dst[2 * NB * CC * 64] = lo;
-    }
-    if (a.n_lin_tiles > 0) load_w(a.lin_img6, ot, wl);
-    const float4 b1 = ldg4(a.q.b1 + f0);
-    __syncthreads();
-
-    // ---- stage 1: first Linear of the query MLP; the per-node linear outputs of the edge MLPs ------------
-    {
-        f32x4 acc[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b1.x, b1.y, b1.z, b1.w};
-        gemm6(wq1, fh, acc);
-#pragma unroll
-        for (int c = 0; c < CC; ++c) stg4(pre0 + (c * 16 + n) * XS + f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
-    }
-    const bool onq = ot < a.q.nt2;
-    if (onq) load_w(a.q.w2img6, ot, wq1);                    // second Linear of the query MLP (reuses the registers)
-    // linear outputs: tiles ot, ot + NT, ... (4 per wave for the [N][4H] products); weights alternate between two
-    // register sets so that the next block is in flight during the current product
-    auto lin_tile = [&](int tile, const u32x4 (&w)[3][NB]) {
-        // the per-molecule term is added to the finished products, not accumulated onto: the rows of pre_tab (built by this kernel
-        // without the term) plus the term, as node_prologue_tab_kernel adds them, are then these very bits
-        f32x4 acc[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        gemm6(w, fh, acc);
-#pragma unroll
-        for (int c = 0; c < CC; ++c) {
-            if (!a.add_mol) continue;
-            const float4 t = ldg4(a.add_mol + (size_t)a.mol_of[atom_of(c)] * a.ld_add + 16 * tile + 4 * g);
-            acc[c][0] += t.x; acc[c][1] += t.y; acc[c][2] += t.z; acc[c][3] += t.w;
-        }
-#pragma unroll
-        for (int c = 0; c < CC; ++c)
-            if (atom_ok(c)) stg4(a.pre_out + (size_t)atom_of(c) * a.ld_out + 16 * tile + 4 * g, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
-    };
-    for (int tile = ot; tile < a.n_lin_tiles; tile += 2 * NT) {
-        u32x4 wn[3][NB];
-        const bool more1 = tile + NT < a.n_lin_tiles, more2 = tile + 2 * NT < a.n_lin_tiles;
-        if (more1) load_w(a.lin_img6, tile + NT, wn);
-        lin_tile(tile, wl);
-        if (more2) load_w(a.lin_img6, tile + 2 * NT, wl);
-        if (more1) lin_tile(tile + NT, wn);
-    }
-    __syncthreads();
-    {   // LayerNorm + ReLU of the hidden tile -> fragments (LPC lanes per column, as in node_chain6_kernel)
-        const int col = ot * (64 / LPC) + lane / LPC, ln = lane % LPC;
-        const int b = ln >> 2, gg = ln & 3;
-        const int fa = 32 * b + 4 * gg;
-        const float4 p0 = ldg4(pre0 + col * XS + fa), p1 = ldg4(pre0 + col * XS + fa + 16);
-        float v[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += v[i];
-        const float mean = seg_sum<LPC>(s) * (1.0f / H);
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const float d = v[i] - mean; q += d * d; }
-        const float var = seg_sum<LPC>(q) * (1.0f / H);
-        const float rstd = 1.0f / sqrtf(var + 1e-5f);
-        const float4 g0 = ldg4(a.q.ln_g + fa), g1 = ldg4(a.q.ln_g + fa + 16), e0 = ldg4(a.q.ln_b + fa), e1 = ldg4(a.q.ln_b + fa + 16);
-        const float ga[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-        const float be[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = fmaxf((v[i] - mean) * rstd * ga[i] + be[i], 0.f);
-        u32x4 hi, mid, lo;
-        split3_bf16(v, hi, mid, lo);
-        u32x4 *dst = fhid + (b * CC + (col >> 4)) * 64 + frag_slot(b, gg * 16 + (col & 15));
-        dst[0] = hi; dst[NB * CC * 64] = mid; dst[2 * NB * CC * 64] = lo;
-    }
-    __syncthreads();
-    if (onq) {
-        const float4 b = ldg4(a.q.b2 + f0);
-        f32x4 acc[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b.x, b.y, b.z, b.w};
-        gemm6(wq1, fhid, acc);
-#pragma unroll
-        for (int c = 0; c < CC; ++c)
-            if (atom_ok(c)) stg4(a.q.out + (size_t)atom_of(c) * a.q.ld_out + f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
-    }
-}
-
-// -------------------------------------------------------------------------------------------------
-// The node stage by dependency level (option node_levels = 1): only h' needs the x2h attention's output; the follow-up
-// MLPs and all per-node products read h' and nothing else.  Instead of node_chain6_kernel (h' and the follow-ups in series
-// on ceil(n_ct / 2) workgroups) + node_linear6_kernel:
-//   node_out6_kernel   : stages 0-1 of node_chain6_kernel -- h' = h + MLP_out([att | h]) -> h_out, nothing else;
-//   node_after6_kernel : one launch whose workgroups are either a follow-up job (one follow-up MLP on one pair of column
-//                        tiles: stage 2 of node_chain6_kernel for that MLP, h' staged from global memory) or a linear job
-//                        (linear6_job on h').
-// Team layout, fragment slots and the MFMA order per output element are those of node_chain6_kernel and node_linear6_kernel:
-// every output has the same bits in both forms (tests/test_gpu_node_levels.py).
-// -------------------------------------------------------------------------------------------------
-template <int H>
-struct Team6 {       // the steps of node_chain6_kernel's team of H / 16 waves over CHAIN_COLS column tiles
+struct Team6 {       // the steps of a team of H / 16 waves (wave ot: output features 16 ot .. 16 ot + 15) over CHAIN_COLS column tiles
     static constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS, XS = Chain6Lds<H>::XS;
     static constexpr int LPC = NB * 4;                     // lanes per column in the normalise pass
     static_assert(CC == 2, "the normalise pass covers exactly 32 columns");
@@ -940,16 +528,17 @@ struct Team6 {       // the steps of node_chain6_kernel's team of H / 16 waves o
     const int n = lane & 15, g = lane >> 4;
     const int f0 = 16 * ot + 4 * g;
 
+    // piece p of a 16-row block of a split image: the wave's own block (tile < 0), or block `tile`
     template <int KB>
-    SM_DEV void load_piece(const float *img, int p, u32x4 (&w)[3][KB]) const {      // piece p of this wave's block of a split image
-        const u32x4 *wi = reinterpret_cast<const u32x4 *>(img) + (size_t)ot * 3 * KB * 64 + lane;
+    SM_DEV void load_piece(const float *img, int p, u32x4 (&w)[3][KB], int tile = -1) const {
+        const u32x4 *wi = reinterpret_cast<const u32x4 *>(img) + (size_t)(tile < 0 ? ot : tile) * 3 * KB * 64 + lane;
 #pragma unroll
         for (int b = 0; b < KB; ++b) w[p][b] = wi[(p * KB + b) * 64];
     }
     template <int KB>
-    SM_DEV void load_w(const float *img, u32x4 (&w)[3][KB]) const {
+    SM_DEV void load_w(const float *img, u32x4 (&w)[3][KB], int tile = -1) const {
 #pragma unroll
-        for (int p = 0; p < 3; ++p) load_piece(img, p, w);
+        for (int p = 0; p < 3; ++p) load_piece(img, p, w, tile);
     }
     // load_w with one running address instead of 3 * KB precomputed ones (two VGPRs each: the blocks lie 1 KB apart, beyond the
     // immediate offset of a load), for callers with a tight register budget
@@ -999,6 +588,32 @@ struct Team6 {       // the steps of node_chain6_kernel's team of H / 16 waves o
         u32x4 *dst = fo + (sb * CC + sc) * 64 + frag_slot(sb, sl);
         dst[0] = hi; dst[KB * CC * 64] = mid; dst[2 * KB * CC * 64] = lo;
     }
+    // the wave's own four output features of column tile c -> a K = H buffer: they are half of fragment (k-step ot / 2, lane)
+    SM_DEV void put_half(u32x4 *fo, int c, const float4 &v) const {
+        unsigned ph[2], pm[2], pl[2];
+        split3_pair(v.x, v.y, ph[0], pm[0], pl[0]);
+        split3_pair(v.z, v.w, ph[1], pm[1], pl[1]);
+        uint2 *dst = reinterpret_cast<uint2 *>(fo + ((ot >> 1) * CC + c) * 64 + frag_slot(ot >> 1, lane)) + (ot & 1);
+        dst[0] = uint2{ph[0], ph[1]};
+        dst[NB * CC * 64 * 2] = uint2{pm[0], pm[1]};
+        dst[2 * NB * CC * 64 * 2] = uint2{pl[0], pl[1]};
+    }
+    // a follow-up MLP's outputs for the column tiles from atom0 on: vector stores, or the scalar tail of a row that ends inside
+    // the lane's four features or is not 16-byte aligned (the 15-class head)
+    SM_DEV void store_follow(const NodeFollow &F, int atom0, int n_atoms, const f32x4 (&acc)[CC]) const {
+#pragma unroll
+        for (int c = 0; c < CC; ++c) {
+            const int atom = atom0 + c * 16 + n;
+            if (atom >= n_atoms) continue;
+            if (f0 + 4 <= F.n_store && (F.ld_out & 3) == 0) {
+                stg4(F.out + (size_t)atom * F.ld_out + f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (f0 + r < F.n_store) F.out[(size_t)atom * F.ld_out + f0 + r] = acc[c][r];
+            }
+        }
+    }
     // activation of a pre-activation buffer -> fragments: LPC lanes per column, 8 features per lane
     SM_DEV void normalise(const float *pre, int mode, const float *gam, const float *bet, u32x4 *fo) const {
         const int col = ot * (64 / LPC) + lane / LPC, ln = lane % LPC;
@@ -1035,18 +650,27 @@ struct Out6Lds {     // one K = 2H fragment buffer (later the hidden tile) + one
 };
 
 // h' = h + MLP_out([att | h]) for the (up to) 32 atoms atom0 .. atom0 + 31 below atom_end, as two 16-atom column tiles of the
-// team's H / 16 waves: stages 0-1 of node_chain6_kernel.  lds: Out6Lds<H>::BYTES.  A column's arithmetic does not depend on
-// which column of which tile the atom sits in, so h' has the same bits for any atom0.
+// team's H / 16 waves.  lds: Out6Lds<H>::BYTES.  A column's arithmetic does not depend on which column of which tile the atom
+// sits in, so h' has the same bits for any atom0.
+//   stage 0: the output MLP's weights; [att | h] tiles -> fragments (the activation rows are requested BEFORE the weights:
+//            vector memory operations complete in order, and behind the 48 weight loads of a wave the staging pass waits for
+//            them too: 18.96 -> 18.61 us per node_chain6_kernel launch at B = 256)
+//   stage 1: h' = h + W2 relu(LN(W1 [att | h] + b1)) + b2
 // AHEAD: the second Linear's block and the residual rows are requested with the first's (node_out6_kernel: 195 VGPRs); without
 // it they are requested once the first product has freed its registers (the x2h kernel's tail, sm_edge_stream.h: 168).
+// FRAGS: h' is also left in fh as the fragments of a K = H buffer (node_chain6_kernel's follow-up MLPs read them after a
+// barrier of the caller's), and request_next() runs where the first product has freed its registers: the caller's place to
+// request the weights of what follows.
 struct NodeOutArgs {
     const float *att, *h;                                 // [N][H] each
     const float *b1, *ln_g, *ln_b, *b2, *w1img6, *w2img6; // node_output MLP (K = 2H), split bf16 images
     float *h_out;                                         // [N][H]
 };
 
-template <int H, bool AHEAD>
-SM_DEV void node_out6_pair(const NodeOutArgs &a, int atom0, int atom_end, unsigned char *lds) {
+struct NoRequest { SM_DEV void operator()() const {} };
+
+template <int H, bool AHEAD, bool FRAGS = false, class Next = NoRequest>
+SM_DEV void node_out6_pair(const NodeOutArgs &a, int atom0, int atom_end, unsigned char *lds, u32x4 *fh = nullptr, Next request_next = {}) {
     using L = Chain6Lds<H>;
     constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS;
     u32x4 *fin = reinterpret_cast<u32x4 *>(lds);           // [att | h] fragments (K = 2H); later the hidden tile
@@ -1055,8 +679,7 @@ SM_DEV void node_out6_pair(const NodeOutArgs &a, int atom0, int atom_end, unsign
     auto atom_of = [&](int c) { return min(atom0 + c * 16 + t.n, atom_end - 1); };
     auto atom_ok = [&](int c) { return atom0 + c * 16 + t.n < atom_end; };
 
-    // ---- stage 0: weights of the output MLP; [att | h] tiles -> fragments (activation rows requested before the weights,
-    // as in node_chain6_kernel) ------------------------------------------------------------------------
+    // ---- stage 0 ---------------------------------------------------------------------------------------
     u32x4 w1[3][2 * NB], w2[3][NB];
     constexpr int SITER = CC * 2 * NB * 64 / (NT * 64);
     float4 sv0[SITER], sv1[SITER];
@@ -1086,7 +709,7 @@ SM_DEV void node_out6_pair(const NodeOutArgs &a, int atom0, int atom_end, unsign
     if constexpr (AHEAD) t.load_w(a.w2img6, w2);
     __syncthreads();
 
-    // ---- stage 1: h' = h + W2 relu(LN(W1 [att | h] + b1)) + b2 ---------------------------------------
+    // ---- stage 1 ---------------------------------------------------------------------------------------
     {
         f32x4 acc[CC];
 #pragma unroll
@@ -1100,7 +723,8 @@ SM_DEV void node_out6_pair(const NodeOutArgs &a, int atom0, int atom_end, unsign
         for (int c = 0; c < CC; ++c) hres[c] = ldg4(a.h + (size_t)atom_of(c) * H + t.f0);
         b2 = ldg4(a.b2 + t.f0);
     }
-    __syncthreads();                                       // (every wave has also finished reading fin)
+    request_next();
+    __syncthreads();                                      // (every wave has also finished reading fin)
     t.normalise(pre0, NODE_LN_RELU, a.ln_g, a.ln_b, fin);
     __syncthreads();
     f32x4 acc[CC];
@@ -1111,9 +735,228 @@ SM_DEV void node_out6_pair(const NodeOutArgs &a, int atom0, int atom_end, unsign
     for (int c = 0; c < CC; ++c) {
         const float4 hn = {acc[c][0] + hres[c].x, acc[c][1] + hres[c].y, acc[c][2] + hres[c].z, acc[c][3] + hres[c].w};
         if (atom_ok(c)) stg4(a.h_out + (size_t)atom_of(c) * H + t.f0, hn);
+        if constexpr (FRAGS) t.put_half(fh, c, hn);
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// node_chain6_kernel (option node_levels = 0): h' and its follow-up MLPs in series, one launch per pair of column tiles.
+//   stages 0-1: node_out6_pair, which also leaves h' as fragments and requests the follow-ups' first Linears a stage ahead;
+//   stage 2:    the (up to) two follow-up MLPs on h', interleaved over the two pre-activation and hidden-tile buffers.
+// LDS (Chain6Lds): [fh | the pair's K = 2H buffer = the two hidden tiles | pre0 | pre1]; the pair's pre-activation buffer is pre0.
+// -------------------------------------------------------------------------------------------------
+template <int H>
+__global__ void __launch_bounds__(H * 4)
+node_chain6_kernel(NodeChainArgs a) {
+    using L = Chain6Lds<H>;
+    constexpr int NB = H / 32, CC = CHAIN_COLS;
+    static_assert(Out6Lds<H>::BYTES + (size_t)(L::FRAG * 16 + L::PRE * 4) == L::BYTES, "fh, the pair's buffers and pre1 fill Chain6Lds");
+    extern __shared__ __attribute__((aligned(16))) unsigned char chain6_lds[];
+    u32x4 *fh = reinterpret_cast<u32x4 *>(chain6_lds);     // fragments of the new h
+    u32x4 *fhid0 = fh + L::FRAG, *fhid1 = fhid0 + L::FRAG;
+    float *pre0 = reinterpret_cast<float *>(fh + 3 * L::FRAG), *pre1 = pre0 + L::PRE;
+    const Team6<H> t;
+    const int atom0 = blockIdx.x * CC * 16;
+
+    SM_TICK(a.stamps, 0);
+    u32x4 wf0[3][NB], wf1[3][NB];                                    // first Linears of the follow-up MLPs
+    const NodeOutArgs o{a.att, a.h, a.b1, a.ln_g, a.ln_b, a.b2, a.w1img6, a.w2img6, a.h_out};
+    node_out6_pair<H, true, true>(o, atom0, a.n_atoms, reinterpret_cast<unsigned char *>(fhid0), fh, [&]() {
+        if (a.n_follow > 0) t.load_w(a.f[0].w1img6, wf0);
+        if (a.n_follow > 1) t.load_w(a.f[1].w1img6, wf1);
+    });
+    if (a.n_follow == 0) return;
+    const bool on0 = t.ot < a.f[0].nt2, on1 = a.n_follow > 1 && t.ot < a.f[1].nt2;
+    u32x4 wg0[3][NB], wg1[3][NB];                                    // second Linears of the follow-up MLPs
+    if (on0) t.load_w(a.f[0].w2img6, wg0);
+    __syncthreads();
+    SM_TICK(a.stamps, 4);
+
+    // ---- stage 2: follow-up MLPs on the new h ---------------------------------------------------------
+    {
+        const float4 ba = ldg4(a.f[0].b1 + t.f0);
+        f32x4 acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{ba.x, ba.y, ba.z, ba.w};
+        t.gemm6(wf0, fh, acc);
+        t.store_pre(pre0, acc);
+    }
+    if (a.n_follow > 1) {
+        const float4 bb = ldg4(a.f[1].b1 + t.f0);
+        f32x4 acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{bb.x, bb.y, bb.z, bb.w};
+        t.gemm6(wf1, fh, acc);
+        t.store_pre(pre1, acc);
+    }
+    if (on1) t.load_w(a.f[1].w2img6, wg1);
+    __syncthreads();
+    SM_TICK(a.stamps, 5);
+    t.normalise(pre0, a.f[0].mode, a.f[0].ln_g, a.f[0].ln_b, fhid0);
+    if (a.n_follow > 1) t.normalise(pre1, a.f[1].mode, a.f[1].ln_g, a.f[1].ln_b, fhid1);
+    __syncthreads();
+    SM_TICK(a.stamps, 6);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!(k == 0 ? on0 : on1)) continue;
+        const NodeFollow &F = a.f[k];
+        const float4 b = ldg4(F.b2 + t.f0);
+        f32x4 acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b.x, b.y, b.z, b.w};
+        if (k == 0) t.gemm6(wg0, fhid0, acc); else t.gemm6(wg1, fhid1, acc);
+        t.store_follow(F, atom0, a.n_atoms, acc);
+    }
+    SM_STAMP(a.stamps, 7);
+}
+
+// -------------------------------------------------------------------------------------------------
+// node_prologue6_kernel: everything on the node side that precedes the first attention of an evaluation, in
+// one launch (it replaces atom_embed_kernel + node_mlp2_kernel + node_linear6_kernel at layer 0):
+//     h0 = ligand_atom_emb([one_hot(v) | time_emb])          (molopt_score_model.py:292-301), stored and split
+//     q  = query MLP of the first x2h attention on h0         (uni_transformer.py:68)
+//     pre0 = per-node halves of that attention's edge MLPs:   h0 W^T + per-molecule term  ([N][4H])
+// plus the per-evaluation bookkeeping (latch the step counter, clear the batch-norm accumulators).
+// The same team (Team6); besides its own block of the query MLP a wave multiplies the product blocks ot, ot + NT, ...
+// -------------------------------------------------------------------------------------------------
+struct NodePrologueArgs {
+    const float *emb_wT, *emb_b;  // [C + D][H] (transposed: a lane's four features are one 16-byte load), [H]
+    const int64_t *v;             // [N]
+    const int *mol_of;
+    const float *ttab;            // [T][D]
+    const float *etab;            // [T][C][H] embedding of every (timestep, atom type) pair (emb_table_kernel), or nullptr
+    const int *t_mol;             // [B] timestep per molecule (score API)
+    const int *step_ptr;          // sampling: device step counter (t = t_first - step), else nullptr
+    int *step_cur;
+    double *bn_acc;               // zeroed here
+    float *h_out;                 // [N][H]
+    NodeFollow q;                 // query MLP -> q.out
+    const float *lin_img6;        // split image of [n_lin_tiles * 16][H]
+    const float *add_mol;         // [B][ld_add] per-molecule term of the linear outputs
+    float *pre_out;               // [N][ld_out]
+    int n_lin_tiles, ld_add, ld_out;
+    int n_atoms, C, D, t_first, bn_acc_len;
+    unsigned long long *stamps;   // diagnostic build only
+};
+
+template <int H>
+struct Prologue6Lds {   // the fragments of h0, the query MLP's hidden tile and one pre-activation buffer
+    static constexpr size_t BYTES = (size_t)2 * Chain6Lds<H>::FRAG * 16 + (size_t)Chain6Lds<H>::PRE * 4;
+};
+
+template <int H>
+__global__ void __launch_bounds__(H * 4)
+node_prologue6_kernel(NodePrologueArgs a) {
+    using L = Chain6Lds<H>;
+    constexpr int NT = H / 16, NB = H / 32, CC = CHAIN_COLS;
+    extern __shared__ __attribute__((aligned(16))) unsigned char chain6_lds[];
+    u32x4 *fh = reinterpret_cast<u32x4 *>(chain6_lds);      // fragments of h0
+    u32x4 *fhid = fh + L::FRAG;                             // hidden tile of the query MLP
+    float *pre0 = reinterpret_cast<float *>(fh + 2 * L::FRAG);
+    const Team6<H> t;
+    const int ot = t.ot, n = t.n, g = t.g, f0 = t.f0;
+    const int ct0 = blockIdx.x * CC;
+
+    auto atom_of = [&](int c) { return min((ct0 + c) * 16 + n, a.n_atoms - 1); };
+    auto atom_ok = [&](int c) { return (ct0 + c) * 16 + n < a.n_atoms; };
+
+    // ---- bookkeeping of the evaluation ------------------------------------------------------------------
+    const int step = a.step_ptr ? *a.step_ptr : 0;
+    {
+        const int gid = blockIdx.x * (H * 4) + threadIdx.x;           // (the launch uses H * 4 threads: no blockDim read)
+        if (gid == 0 && a.step_ptr) *a.step_cur = step;
+        for (int i = gid; i < a.bn_acc_len; i += gridDim.x * (H * 4)) a.bn_acc[i] = 0.0;
+    }
+    // ---- stage 0: embedding of the workgroup's atoms -> global h0 and LDS fragments ----------------------
+    u32x4 wq1[3][NB], wl[3][NB];
+    t.load_w(a.q.w1img6, wq1);
+    for (int idx = threadIdx.x; idx < CC * NB * 64; idx += NT * 64) {
+        const int sl = idx & 63, sb = (idx >> 6) % NB, sc = idx / (64 * NB);
+        const int at_raw = (ct0 + sc) * 16 + (sl & 15);
+        const int at = min(at_raw, a.n_atoms - 1);
+        const int ts = a.step_ptr ? a.t_first - step : a.t_mol[a.mol_of[at]];
+        const int vi = min(max((int)a.v[at], 0), a.C - 1);       // out-of-range types are flagged by v_check_kernel
+        const int fa = 32 * sb + 4 * (sl >> 4);
+        float vv[8];
+        {   // the precomputed row of (t, v) (emb_table_kernel, built once per context with the sum y = (b + W[:, v]) + sum_k W[:, C + k] te[k],
+            // k ascending, that the reference's Linear evaluates per atom: molopt_score_model.py:292-301)
+            const float *row = a.etab + ((size_t)ts * a.C + vi) * H + fa;
+            const float4 r0 = ldg4(row), r1 = ldg4(row + 16);
+            vv[0] = r0.x; vv[1] = r0.y; vv[2] = r0.z; vv[3] = r0.w; vv[4] = r1.x; vv[5] = r1.y; vv[6] = r1.z; vv[7] = r1.w;
+        }
+        if (at_raw < a.n_atoms) {
+            stg4(a.h_out + (size_t)at * H + fa, float4{vv[0], vv[1], vv[2], vv[3]});
+            stg4(a.h_out + (size_t)at * H + fa + 16, float4{vv[4], vv[5], vv[6], vv[7]});
+        }
+        t.template put_frag<NB>(fh, sb, sc, sl, vv);
+    }
+    if (a.n_lin_tiles > 0) t.load_w(a.lin_img6, wl);
+    const float4 b1 = ldg4(a.q.b1 + f0);
+    __syncthreads();
+
+    // ---- stage 1: first Linear of the query MLP; the per-node linear outputs of the edge MLPs ------------
+    {
+        f32x4 acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b1.x, b1.y, b1.z, b1.w};
+        t.gemm6(wq1, fh, acc);
+        t.store_pre(pre0, acc);
+    }
+    const bool onq = ot < a.q.nt2;
+    if (onq) t.load_w(a.q.w2img6, wq1);                      // second Linear of the query MLP (reuses the registers)
+    // linear outputs: tiles ot, ot + NT, ... (4 per wave for the [N][4H] products); weights alternate between two
+    // register sets so that the next block is in flight during the current product
+    auto lin_tile = [&](int tile, const u32x4 (&w)[3][NB]) {
+        // the per-molecule term is added to the finished products, not accumulated onto: the rows of pre_tab (built by this kernel
+        // without the term) plus the term, as node_prologue_tab_kernel adds them, are then these very bits
+        f32x4 acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        t.gemm6(w, fh, acc);
+#pragma unroll
+        for (int c = 0; c < CC; ++c) {
+            if (!a.add_mol) continue;
+            const float4 term = ldg4(a.add_mol + (size_t)a.mol_of[atom_of(c)] * a.ld_add + 16 * tile + 4 * g);
+            acc[c][0] += term.x; acc[c][1] += term.y; acc[c][2] += term.z; acc[c][3] += term.w;
+        }
+#pragma unroll
+        for (int c = 0; c < CC; ++c)
+            if (atom_ok(c)) stg4(a.pre_out + (size_t)atom_of(c) * a.ld_out + 16 * tile + 4 * g, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
+    };
+    for (int tile = ot; tile < a.n_lin_tiles; tile += 2 * NT) {
+        u32x4 wn[3][NB];
+        const bool more1 = tile + NT < a.n_lin_tiles, more2 = tile + 2 * NT < a.n_lin_tiles;
+        if (more1) t.load_w(a.lin_img6, wn, tile + NT);
+        lin_tile(tile, wl);
+        if (more2) t.load_w(a.lin_img6, wl, tile + 2 * NT);
+        if (more1) lin_tile(tile + NT, wn);
+    }
+    __syncthreads();
+    t.normalise(pre0, NODE_LN_RELU, a.q.ln_g, a.q.ln_b, fhid);
+    __syncthreads();
+    if (onq) {
+        const float4 b = ldg4(a.q.b2 + f0);
+        f32x4 acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = f32x4{b.x, b.y, b.z, b.w};
+        t.gemm6(wq1, fhid, acc);
+#pragma unroll
+        for (int c = 0; c < CC; ++c)
+            if (atom_ok(c)) stg4(a.q.out + (size_t)atom_of(c) * a.q.ld_out + f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
+// The node stage by dependency level (option node_levels = 1): only h' needs the x2h attention's output; the follow-up
+// MLPs and all per-node products read h' and nothing else.  Instead of node_chain6_kernel (h' and the follow-ups in series
+// on ceil(n_ct / 2) workgroups) + node_linear6_kernel:
+//   node_out6_kernel   : node_out6_pair alone -- h' = h + MLP_out([att | h]) -> h_out, nothing else;
+//   node_after6_kernel : one launch whose workgroups are either a follow-up job (one follow-up MLP on one pair of column
+//                        tiles, h' staged from global memory, the second Linear's pieces requested in two instalments) or a
+//                        linear job (linear6_job on h').
+// Both forms call the same Team6 steps and linear6_job, so every output has the same bits in both: what differs is the
+// schedule and the LDS layout (tests/test_gpu_node_levels.py).
+// -------------------------------------------------------------------------------------------------
 template <int H>
 __global__ void __launch_bounds__(H * 4)
 node_out6_kernel(NodeChainArgs a) {
@@ -1200,16 +1043,5 @@ node_after6_kernel(NodeAfterArgs a) {
 #pragma unroll
     for (int c = 0; c < CC; ++c) acc[c] = f32x4{b.x, b.y, b.z, b.w};
     t.gemm6(w2, fh, acc);
-#pragma unroll
-    for (int c = 0; c < CC; ++c) {
-        const int atom = (ct0 + c) * 16 + t.n;
-        if (atom >= n_atoms) continue;
-        if (t.f0 + 4 <= F.n_store && (F.ld_out & 3) == 0) {
-            stg4(F.out + (size_t)atom * F.ld_out + t.f0, float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]});
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (t.f0 + r < F.n_store) F.out[(size_t)atom * F.ld_out + t.f0 + r] = acc[c][r];
-        }
-    }
+    t.store_follow(F, ct0 * 16, n_atoms, acc);
 }

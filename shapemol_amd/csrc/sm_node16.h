@@ -1,6 +1,6 @@
 // Node kernels on two-piece f16 operands: the arithmetic of sm_edge16.h (x = hi + lo, both f16 round-to-nearest, three
 // v_mfma_f32_16x16x32_f16 products per term, fp32 accumulation) in the structure of the bf16x6 node kernels of sm_node.h
-// (node_chain6_kernel / node_linear6_kernel / node_prologue6_kernel, whose comments describe the stages).  Per element the
+// (node_chain6_kernel / node_linear6_kernel / node_prologue6_kernel; Team6 and node_out6_pair describe the stages).  Per element the
 // weights take 4 bytes instead of 6 and a product three matrix instructions instead of six: these kernels stream their
 // weights from L2 once per workgroup, so both the bytes and the instruction count matter.
 // Unlike the edge MLPs' operands (LayerNorm outputs, bounded by construction), the inputs here are the residual stream h,
@@ -104,6 +104,10 @@ struct Chain16Lds {
     static constexpr int XS = H + 4;
     static constexpr int PRE = CC * 16 * XS;
     static constexpr size_t BYTES = (size_t)3 * FRAG * 16 + (size_t)2 * PRE * 4;
+};
+template <int H>
+struct Prologue16Lds {  // node_prologue16_kernel: the fragments of h0, the query MLP's hidden tile and one pre-activation buffer
+    static constexpr size_t BYTES = (size_t)2 * Chain16Lds<H>::FRAG * 16 + (size_t)Chain16Lds<H>::PRE * 4;
 };
 
 // shared device pieces of the chain / prologue kernels

@@ -2,6 +2,9 @@
 the follow-up MLPs and the per-node products side by side) against node_chain6_kernel + node_linear6_kernel (node_levels = 0)
 on the same context and inputs.  Every output element keeps its MFMA accumulation order, so everything must agree to the bit:
 h', the queries q_h and q_x, the atom-type head and the per-node products, and with them the evaluation's three outputs.
+Both forms call the same device functions (Team6 and node_out6_pair in csrc/sm_node.h), so this file no longer compares two
+independent statements of the arithmetic, only two schedules and LDS layouts of one; that the arithmetic itself is the
+reference's is what test_gpu_parity.py::test_forward_alternative_kernels_golden holds both forms to.
 Shapes are the ones where the new indexing can go wrong: a single partial tile, a full tile, odd tile counts (the last pair of
 column tiles has one tile), a pair plus one; H = 128 (8 waves per follow-up job) and the reduced H = 32 model (2 waves), in workgroups of 16:
 the other waves leave before the first barrier; molecules of mixed sizes inside a tile.

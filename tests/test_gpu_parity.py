@@ -120,9 +120,10 @@ def test_forward_b4_golden(name, mode):
 
 @pytest.mark.parametrize("opts", [{"edge_bf16": 0}, {"edge_bf16": 1}, {"lin_bf16": 0, "chain_bf16": 0}, {"edge_bf16": 3, "node_f16": 0},
                                   {"edge_bf16": 1, "node_f16": 0}, {"vn_fuse": 1}, {"vn_fuse": 0}, {"edge_bf16": 2, "node_f16": 1},
-                                  {"edge_bf16": 3, "node_f16": 1, "vn_fuse": 1}, {"edge_bf16": 3, "node_f16": 1, "vn_fuse": 0}],
+                                  {"edge_bf16": 3, "node_f16": 1, "vn_fuse": 1}, {"edge_bf16": 3, "node_f16": 1, "vn_fuse": 0},
+                                  {"node_levels": 0}, {"prologue_tab": 0}],
                          ids=["edge_fp32", "edge_bf16x6_phase", "node_fp32", "edge_f16x2_node_bf16x6", "all_exact_phase", "vn_grid_barrier", "vn_separate",
-                              "edge_stream_node_f16x2", "f16x2_vn_grid_barrier", "f16x2_vn_separate"])
+                              "edge_stream_node_f16x2", "f16x2_vn_grid_barrier", "f16x2_vn_separate", "node_chain_form", "prologue_kernel"])
 def test_forward_alternative_kernels_golden(opts):
     """The optional kernel variants behind shapemol_set_option compute the same forward (ragged batch too)."""
     m = hip_model()
@@ -141,7 +142,7 @@ def test_forward_alternative_kernels_golden(opts):
     finally:
         for k in opts:
             if k not in ("edge_bf16", "node_f16"):      # (those two are restored by _restore_modes)
-                m.set_option(k, {"lin_bf16": 1, "chain_bf16": 1, "vn_fuse": 2}[k])
+                m.set_option(k, {"lin_bf16": 1, "chain_bf16": 1, "vn_fuse": 2, "node_levels": 1, "prologue_tab": 1}[k])
 
 
 def test_forward_ragged_golden(mode):
