@@ -732,6 +732,52 @@ int shapemol_sim_align(shapemol_sim_ctx *ctx, int64_t n_mols_a, const int64_t *h
 /* Tests only: fill the context's device workspaces with `byte`. */
 int shapemol_sim_debug_fill(shapemol_sim_ctx *ctx, int32_t byte, void *stream);
 
+/* ---- bond graphs of sampled molecules: bonds, fragments, rings, bond lengths ------------------------------------------------
+ * What the reference's evaluation script needs once it knows which atoms are bonded, with the bonds
+ * decided by THIS library's rule, the thresholds of shapemol_eval_* above (a pair is a bond when its order is > 0), not by a
+ * chemistry toolkit's perception.  Inputs as for shapemol_eval_run, plus h_bl_edges (n_bl): the bond-length bin edges.
+ * Molecules of at most 64 atoms take the wave form (0), molecules of 65..256 atoms the block form (1); shapemol_graph_sizes
+ * writes up to n of (atoms of the wave form, atoms per molecule, elements, classes, edges per histogram, threads per
+ * workgroup, bits of ring_sizes) and returns 7.  Limits, refused with a message that names the molecule or argument before
+ * any kernel runs: 1..256 atoms per molecule, n_elements 1..16, n_classes 1..32, class slots inside the rule, 1..255 finite
+ * ascending edges per histogram, n_frames and n_mols 1..2^20.  The bonds of a call are counted on the device; a call with
+ * 2^31 or more is refused after the count and before anything is written.  shapemol_graph_check touches no device; it
+ * writes the form of every molecule to the optional h_forms (n_mols). */
+typedef struct shapemol_graph_ctx shapemol_graph_ctx;
+int shapemol_graph_sizes(int64_t *out, int32_t n);
+int shapemol_graph_check(int64_t n_frames, int64_t n_mols, const int64_t *h_off, int32_t n_elements, int32_t n_classes,
+                         const int32_t *h_class_slot, const double *h_cc_edges, int32_t n_cc, double cc_cut,
+                         const double *h_all_edges, int32_t n_all, double all_cut, const double *h_bl_edges, int32_t n_bl,
+                         int32_t *h_forms);
+int shapemol_graph_create(int device, shapemol_graph_ctx **out);
+void shapemol_graph_destroy(shapemol_graph_ctx *ctx);
+/* Count pass, scan, fill pass with the rings.  DEVICE outputs, all int32 and all written by the call: d_nr_bonds, d_degree,
+ * d_frag, d_ring_atom (n_frames, N) = the bond orders summed per atom (shapemol_eval_run's d_nr_bonds), the bonds per atom,
+ * the smallest atom index (within the frame) of the atom's fragment, the smallest ring through one of the atom's bonds (0:
+ * none); d_mol (n_frames, n_mols, 6) = bonds, fragments, atoms of the largest fragment, complete (one fragment), cyclomatic
+ * number bonds - atoms + fragments, ring_sizes (bit s, 3 <= s <= 30: some bond's shortest cycle has s bonds; bit 31: more).
+ * int64 counters per frame, zeroed by the call: d_hist_bl (n_frames, 2, E (E + 1) / 2, 3, n_bl + 1) bond lengths over all
+ * molecules | over complete ones, per pair of element slots a <= b (row-major upper triangle), order 1..3 and bin
+ * np.searchsorted(edges, d, 'left'); d_hist_cc, d_hist_all, d_class_counts as for shapemol_eval_run but over complete
+ * molecules only; d_frame_counts (n_frames, 33) = complete molecules, then molecules whose ring_sizes has bit 0..31.
+ * *h_total = the bonds of the call.  The bond list stays in the context until its next run: shapemol_graph_bonds copies the
+ * first n_items scalars of the offsets (which = 0, int64, n_frames * n_mols + 1), the bonds (1, int32, (total, 3) = atom i,
+ * atom j > i, order, sorted by frame, molecule, i, j; atoms indexed within the frame) or their rings (2, int32, total: bonds
+ * in the shortest cycle through the bond, 0 for a bridge) to dst, HOST or DEVICE.  The same in every run.  Both calls
+ * synchronise the stream (the run twice: the host reads the bond total between the passes).  Return 0, or 1 with a message:
+ * a refused call launches nothing; a class outside [0, n_classes) found on the device makes the outputs invalid.  Either way
+ * the context stays usable.  A context serves one stream at a time. */
+int shapemol_graph_run(shapemol_graph_ctx *ctx, int64_t n_frames, int64_t n_mols, const int64_t *h_off, const float *d_pos,
+                       const void *d_classes, int32_t classes_int64, int32_t n_elements, const double *h_thresholds,
+                       int32_t carbon_slot, int32_t n_classes, const int32_t *h_class_slot, const double *h_cc_edges,
+                       int32_t n_cc, double cc_cut, const double *h_all_edges, int32_t n_all, double all_cut,
+                       const double *h_bl_edges, int32_t n_bl, int32_t *d_nr_bonds, int32_t *d_degree, int32_t *d_frag,
+                       int32_t *d_ring_atom, int32_t *d_mol, int64_t *d_hist_bl, int64_t *d_hist_cc, int64_t *d_hist_all,
+                       int64_t *d_class_counts, int64_t *d_frame_counts, int64_t *h_total, void *stream);
+int shapemol_graph_bonds(shapemol_graph_ctx *ctx, int32_t which, void *dst, int64_t n_items, void *stream);
+/* Tests only: fill the context's device workspaces with `byte`; the last run's bond list is gone afterwards. */
+int shapemol_graph_debug_fill(shapemol_graph_ctx *ctx, int32_t byte, void *stream);
+
 /* Per-kernel launch-time accounting with HIP events on the launch stream (bench only).
  * shapemol_profile_begin() arms it for the following _score/_sample calls (forces eager launches);
  * shapemol_profile_end() synchronises and writes, for each of up to `cap` kernel classes,

@@ -17,6 +17,9 @@ eval_bond_length pair-distance profiles), for one frame or every recorded frame,
 and how well a sample matches the shape of its condition (utils/evaluation shaep_utils.get_ROCS / shape_tanimoto, espsim's Gaussian
 integrals, calculate_shaep_shape_sim with this package's own overlay in place of the ShaEP executable):
     shape_tanimoto, get_rocs, esp_similarity, align_shapes, similarity_to_condition
+and the molecular graph of a sample under the same distance rule -- bonds with orders, fragments, completeness, rings, bond-length
+profiles (the rule is this package's, not OpenBabel's perception; agreement with the reference's reconstruction is not measured):
+    GraphReport, bond_graph, bond_graph_trajectory, bond_graph_samples, atom_type_jsd, to_molblock
 plus helpers: synthetic weights/inputs (synth), schedules (diffusion), the C-ABI binding (_lib).
 """
 from .molopt_score_model import ScorePosNet3D, log_sample_categorical, pointcloud_shape_guidance, mesh_shape_guidance  # noqa: F401
@@ -28,5 +31,6 @@ from .mol_surface import get_mesh, get_mesh_batch  # noqa: F401
 from .evaluation import (StabilityRule, GeometryReport, check_stability, evaluate_geometry, evaluate_trajectory,  # noqa: F401
                          evaluate_samples)
 from .similarity import shape_tanimoto, get_rocs, esp_similarity, align_shapes, similarity_to_condition  # noqa: F401
+from .mol_graph import GraphReport, bond_graph, bond_graph_trajectory, bond_graph_samples, atom_type_jsd, to_molblock  # noqa: F401
 
 __version__ = "0.3.0"

@@ -41,6 +41,8 @@ EXPORTS = (
     "shapemol_eval_debug_fill",
     "shapemol_sim_sizes", "shapemol_sim_check", "shapemol_sim_create", "shapemol_sim_destroy", "shapemol_sim_score",
     "shapemol_sim_align", "shapemol_sim_debug_fill",
+    "shapemol_graph_sizes", "shapemol_graph_check", "shapemol_graph_create", "shapemol_graph_destroy", "shapemol_graph_run",
+    "shapemol_graph_bonds", "shapemol_graph_debug_fill",
 )
 
 
@@ -208,6 +210,15 @@ def load():
     lib.shapemol_sim_score.argtypes = [vp, i32, i32, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp]
     lib.shapemol_sim_align.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, C.c_double] + [vp] * 6
     lib.shapemol_sim_debug_fill.argtypes = [vp, i32, vp]
+    lib.shapemol_graph_sizes.argtypes = [vp, i32]
+    lib.shapemol_graph_check.argtypes = [i64, i64, vp, i32, i32, vp, vp, i32, C.c_double, vp, i32, C.c_double, vp, i32, vp]
+    lib.shapemol_graph_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.shapemol_graph_destroy.argtypes = [vp]
+    lib.shapemol_graph_destroy.restype = None
+    lib.shapemol_graph_run.argtypes = ([vp, i64, i64, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, C.c_double, vp, i32, C.c_double, vp, i32]
+                                       + [vp] * 12)
+    lib.shapemol_graph_bonds.argtypes = [vp, i32, vp, i64, vp]
+    lib.shapemol_graph_debug_fill.argtypes = [vp, i32, vp]
     lib.shapemol_profile_begin.argtypes = [vp]
     lib.shapemol_profile_end.argtypes = [vp, vp, vp, vp, C.c_int]
     if lib.shapemol_abi_version() != ABI_VERSION:

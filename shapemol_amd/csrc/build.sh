@@ -6,7 +6,7 @@ OUT=../libshapemol_hip.so
 # -fno-slp-vectorize: packed fp32 VALU (v_pk_add/mul/fma_f32) beside MFMAs is slower than the scalar forms (+1 % on the step)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -Wno-unused-value -Wno-comment -Wno-pass-failed -fno-slp-vectorize"
 # the library's translation units, in link order
-SRC="shapemol_hip.hip shape_encoder.hip shape_decoder.hip train_ops.hip shape_data.hip mol_surface.hip mol_eval.hip mol_sim.hip"
+SRC="shapemol_hip.hip shape_encoder.hip shape_decoder.hip train_ops.hip shape_data.hip mol_surface.hip mol_eval.hip mol_sim.hip mol_graph.hip"
 if [[ "${1:-}" == "--report" ]]; then
   hipcc $FLAGS -o $OUT $SRC -Rpass-analysis=kernel-resource-usage 2>&1 \
    | grep -E "Function Name|VGPRs:|AGPRs|Scratch|Occupancy|LDS Size|VGPRs Spill" | paste - - - - - - - \
