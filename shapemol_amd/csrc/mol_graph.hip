@@ -1,51 +1,22 @@
 // C ABI of the bond graphs of sampled molecules (include/shapemol_hip.h, shapemol_graph_*): bonds with orders, fragments,
-// completeness, rings and bond-length histograms for every frame of a packed batch, on the device.  The arithmetic, the
-// kernels and the host plan: sm_mol_graph.h.
+// completeness, rings and bond-length histograms for every frame of a packed batch, on the device.  The kernels: sm_mol_graph.h;
+// the arithmetic and the host plan: sm_mol_rule.h; the upload and the launch: sm_mol_upload.h.
 #include "../../include/shapemol_hip.h"
 #include "sm_mol_graph.h"
-#include "sm_devmem.h"
-#include "sm_host.h"
-
-#include <cstring>
-#include <string>
-#include <vector>
+#include "sm_mol_upload.h"
 
 struct shapemol_graph_ctx {
     int device = 0;
-    MgraphPlan plan;                      // of the last call (the upload reads its image until the call's synchronise)
-    std::vector<unsigned char> up;        // the upload's host image: rule tables, bin edges, molecules, job lists, class table
-    unsigned char *d_in = nullptr; int64_t cap_in = 0; DevList mem_in;                      // the upload, bytes
+    MolInput in{"bond graph"};            // the plan and the upload
     int *d_count = nullptr; long long *d_offset = nullptr; int64_t cap_fb = 0; DevList mem_fb;       // per (frame, molecule)
     int *d_bonds = nullptr, *d_ring = nullptr; int64_t cap_b = 0; DevList mem_b;                     // per bond
     int64_t n_fb = 0, total = -1;         // of the last run that reached its fill pass; total < 0: none
 };
 
-namespace {
-
-template <typename T> size_t put(std::vector<unsigned char> &img, const T *src, size_t count) {      // -> the offset, 8-aligned
-    const size_t o = (img.size() + 7) / 8 * 8;
-    img.resize(o + count * sizeof(T));
-    if (count) std::memcpy(img.data() + o, src, count * sizeof(T));
-    return o;
-}
-
-template <int PASS> void launch_forms(const MgraphPlan &pl, MgraphArgs a, const unsigned char *d_in, size_t o_wave, size_t o_block, int F, hipStream_t s) {
-    if (pl.wave.gx) {
-        a.jobs = reinterpret_cast<const int *>(d_in + o_wave); a.n_jobs = (int)pl.wave.jobs.size(); a.gx = pl.wave.gx; a.iters = pl.wave.iters;
-        hipLaunchKernelGGL((mgraph_kernel<64, PASS>), dim3((unsigned)((int64_t)pl.wave.gx * F)), dim3(kMgraphThreads), 0, s, a);
-    }
-    if (pl.block.gx) {
-        a.jobs = reinterpret_cast<const int *>(d_in + o_block); a.n_jobs = (int)pl.block.jobs.size(); a.gx = pl.block.gx; a.iters = pl.block.iters;
-        hipLaunchKernelGGL((mgraph_kernel<kMgraphThreads, PASS>), dim3((unsigned)((int64_t)pl.block.gx * F)), dim3(kMgraphThreads), 0, s, a);
-    }
-}
-
-}  // namespace
-
 extern "C" {
 
 int shapemol_graph_sizes(int64_t *out, int32_t n) {
-    const int64_t v[7] = {kMgraphWaveAtoms, kMgraphMaxAtoms, kMevalMaxElements, kMevalMaxClasses, kMevalMaxEdges, kMgraphThreads, kMgraphRingBits};
+    const int64_t v[7] = {kMolWaveAtoms, kMgraphMaxAtoms, kMolMaxElements, kMolMaxClasses, kMolMaxEdges, kMolThreads, kMgraphRingBits};
     for (int i = 0; i < n && i < 7; ++i) out[i] = v[i];
     return 7;
 }
@@ -53,7 +24,7 @@ int shapemol_graph_sizes(int64_t *out, int32_t n) {
 int shapemol_graph_check(int64_t n_frames, int64_t n_mols, const int64_t *h_off, int32_t n_elements, int32_t n_classes, const int32_t *h_class_slot,
                          const double *h_cc_edges, int32_t n_cc, double cc_cut, const double *h_all_edges, int32_t n_all, double all_cut,
                          const double *h_bl_edges, int32_t n_bl, int32_t *h_forms) {
-    MgraphPlan pl;
+    MolPlan pl;
     const std::string e = mgraph_plan(n_frames, n_mols, h_off, n_elements, n_classes, h_class_slot, h_cc_edges, n_cc, cc_cut, h_all_edges, n_all, all_cut,
                                       h_bl_edges, n_bl, &pl);
     if (!e.empty()) return sm_fail(e);
@@ -86,45 +57,23 @@ int shapemol_graph_run(shapemol_graph_ctx *c, int64_t n_frames, int64_t n_mols, 
     if (!d_pos || !d_classes || !h_thresholds || !d_nr_bonds || !d_degree || !d_frag || !d_ring_atom || !d_mol || !d_hist_bl || !d_hist_cc || !d_hist_all ||
         !d_class_counts || !d_frame_counts || !h_total)
         return sm_fail("shapemol_graph_run: null argument");
-    // a run before this one has synchronised its stream before it returned: the host image is free to be rewritten
     const std::string err = mgraph_plan(n_frames, n_mols, h_off, n_elements, n_classes, h_class_slot, h_cc_edges, n_cc, cc_cut, h_all_edges, n_all, all_cut,
-                                        h_bl_edges, n_bl, &c->plan);
+                                        h_bl_edges, n_bl, &c->in.plan);
     if (!err.empty()) return sm_fail(err);
-    if (carbon_slot < -1 || carbon_slot >= n_elements) return sm_fail("bond graph: the carbon slot lies outside the rule");
     SMCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const MgraphPlan &pl = c->plan;
-    const int E = n_elements, C = n_classes, B = (int)n_mols, F = (int)n_frames;
-    const int64_t n_fb = (int64_t)F * B;
+    const int64_t n_fb = n_frames * n_mols;
     c->total = -1;
-    unsigned char slot[kMevalMaxClasses];
-    for (int k = 0; k < C; ++k) slot[k] = (unsigned char)h_class_slot[k];
-    const int zero = 0;
-    std::vector<unsigned char> &img = c->up;
-    img.clear();
-    const size_t o_thr = put(img, h_thresholds, (size_t)3 * E * E);
-    const size_t o_cc = put(img, h_cc_edges, (size_t)n_cc), o_all = put(img, h_all_edges, (size_t)n_all), o_bl = put(img, h_bl_edges, (size_t)n_bl);
-    const size_t o_mol = put(img, pl.mol.data(), pl.mol.size());
-    const size_t o_wave = put(img, pl.wave.jobs.data(), pl.wave.jobs.size()), o_block = put(img, pl.block.jobs.data(), pl.block.jobs.size());
-    const size_t o_slot = put(img, slot, (size_t)C), o_bad = put(img, &zero, 1);
-    SMCHK(grow(c->mem_in, {dev_buf(&c->d_in, img.size())}, c->cap_in, (int64_t)img.size()));
-    SMCHK(grow(c->mem_fb, {dev_buf(&c->d_count, (size_t)n_fb * sizeof(int)), dev_buf(&c->d_offset, (size_t)(n_fb + 1) * sizeof(long long))}, c->cap_fb, n_fb));
-    SMCHK(hipMemcpyAsync(c->d_in, img.data(), img.size(), hipMemcpyHostToDevice, s));
     MgraphArgs a{};
-    a.pos = d_pos; a.cls = d_classes; a.cls64 = classes_int64 != 0;
-    a.N = pl.N; a.F = F; a.B = B;
-    a.mol = reinterpret_cast<const MevalMol *>(c->d_in + o_mol);
-    a.thr = reinterpret_cast<const double *>(c->d_in + o_thr);
-    a.slot = c->d_in + o_slot;
-    a.E = E; a.C = C; a.carbon = carbon_slot;
-    a.cc_edges = reinterpret_cast<const double *>(c->d_in + o_cc); a.all_edges = reinterpret_cast<const double *>(c->d_in + o_all);
-    a.bl_edges = reinterpret_cast<const double *>(c->d_in + o_bl);
-    a.n_cc = n_cc; a.n_all = n_all; a.n_bl = n_bl; a.cc_cut = cc_cut; a.all_cut = all_cut;
+    if (mol_upload(c->in, s, n_frames, n_mols, d_pos, d_classes, classes_int64, n_elements, h_thresholds, carbon_slot, n_classes, h_class_slot, h_cc_edges,
+                   n_cc, cc_cut, h_all_edges, n_all, all_cut, h_bl_edges, (size_t)n_bl, &a.bl_edges, a.b, a.r))
+        return 1;
+    SMCHK(grow(c->mem_fb, {dev_buf(&c->d_count, (size_t)n_fb * sizeof(int)), dev_buf(&c->d_offset, (size_t)(n_fb + 1) * sizeof(long long))}, c->cap_fb, n_fb));
+    a.n_bl = n_bl;
     a.count = c->d_count; a.offset = c->d_offset;
-    a.bad = reinterpret_cast<int *>(c->d_in + o_bad);
     // count, scan, and the one synchronisation that tells the host how many bonds there are
-    launch_forms<0>(pl, a, c->d_in, o_wave, o_block, F, s);
-    hipLaunchKernelGGL(mgraph_scan_kernel, dim3(1), dim3(kMgraphThreads), 0, s, c->d_count, c->d_offset, (long long)n_fb);
+    mol_launch(mgraph_kernel<64, 0>, mgraph_kernel<kMolThreads, 0>, c->in, a, s);
+    hipLaunchKernelGGL(mgraph_scan_kernel, dim3(1), dim3(kMolThreads), 0, s, c->d_count, c->d_offset, (long long)n_fb);
     SMCHK(hipGetLastError());
     long long total = 0;
     SMCHK(hipMemcpyAsync(&total, c->d_offset + n_fb, sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -132,24 +81,16 @@ int shapemol_graph_run(shapemol_graph_ctx *c, int64_t n_frames, int64_t n_mols, 
     if (total < 0 || total >= (1ll << 31)) return sm_fail("bond graph: " + std::to_string(total) + " bonds in this call; the limit is 2^31 - 1 (pass fewer frames)");
     const int64_t need_b = std::max<int64_t>(total, 1);
     SMCHK(grow(c->mem_b, {dev_buf(&c->d_bonds, (size_t)3 * need_b * sizeof(int)), dev_buf(&c->d_ring, (size_t)need_b * sizeof(int))}, c->cap_b, need_b));
-    const size_t np = (size_t)E * (E + 1) / 2;
-    SMCHK(hipMemsetAsync(d_hist_bl, 0, (size_t)F * 2 * np * 3 * (n_bl + 1) * 8, s));
-    SMCHK(hipMemsetAsync(d_hist_cc, 0, (size_t)F * (n_cc + 1) * 8, s));
-    SMCHK(hipMemsetAsync(d_hist_all, 0, (size_t)F * (n_all + 1) * 8, s));
-    SMCHK(hipMemsetAsync(d_class_counts, 0, (size_t)F * C * 8, s));
-    SMCHK(hipMemsetAsync(d_frame_counts, 0, (size_t)F * (1 + kMgraphRingBits) * 8, s));
+    const size_t np = (size_t)n_elements * (n_elements + 1) / 2;
+    SMCHK(hipMemsetAsync(d_hist_bl, 0, (size_t)n_frames * 2 * np * 3 * (n_bl + 1) * 8, s));
+    SMCHK(hipMemsetAsync(d_frame_counts, 0, (size_t)n_frames * (1 + kMgraphRingBits) * 8, s));
+    if (mol_zero_counts(a.o, d_hist_cc, d_hist_all, d_class_counts, a.b, a.r, s)) return 1;
     a.nr_bonds = d_nr_bonds; a.degree = d_degree; a.frag = d_frag; a.ring_atom = d_ring_atom; a.mol_out = d_mol;
     a.bonds = c->d_bonds; a.ring_bond = c->d_ring;
     a.hist_bl = reinterpret_cast<unsigned long long *>(d_hist_bl);
-    a.hist_cc = reinterpret_cast<unsigned long long *>(d_hist_cc); a.hist_all = reinterpret_cast<unsigned long long *>(d_hist_all);
-    a.cls_counts = reinterpret_cast<unsigned long long *>(d_class_counts);
     a.frame_counts = reinterpret_cast<unsigned long long *>(d_frame_counts);
-    launch_forms<1>(pl, a, c->d_in, o_wave, o_block, F, s);
-    SMCHK(hipGetLastError());
-    int bad = 0;
-    SMCHK(hipMemcpyAsync(&bad, c->d_in + o_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    SMCHK(hipStreamSynchronize(s));
-    if (bad) return sm_fail("bond graph: " + std::to_string(bad) + " atom(s) have a class outside the " + std::to_string(C) + " classes; the outputs are not valid");
+    mol_launch(mgraph_kernel<64, 1>, mgraph_kernel<kMolThreads, 1>, c->in, a, s);
+    if (mol_finish(c->in, n_classes, s)) return 1;
     c->n_fb = n_fb; c->total = total;
     *h_total = total;
     return 0;
@@ -171,7 +112,7 @@ int shapemol_graph_debug_fill(shapemol_graph_ctx *c, int32_t byte, void *stream)
     if (!c) return sm_fail("shapemol_graph_debug_fill: null context");
     SMCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (c->cap_in) SMCHK(hipMemsetAsync(c->d_in, byte, (size_t)c->cap_in, s));
+    if (c->in.cap_in) SMCHK(hipMemsetAsync(c->in.d_in, byte, (size_t)c->in.cap_in, s));
     if (c->cap_fb) {
         SMCHK(hipMemsetAsync(c->d_count, byte, (size_t)c->cap_fb * sizeof(int), s));
         SMCHK(hipMemsetAsync(c->d_offset, byte, (size_t)(c->cap_fb + 1) * sizeof(long long), s));

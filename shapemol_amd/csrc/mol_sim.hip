@@ -20,13 +20,6 @@ struct shapemol_sim_ctx {
 
 namespace {
 
-template <typename T> size_t put(std::vector<unsigned char> &img, const T *src, size_t count) {      // -> the offset, 8-aligned
-    const size_t o = (img.size() + 7) / 8 * 8;
-    img.resize(o + count * sizeof(T));
-    if (count) std::memcpy(img.data() + o, src, count * sizeof(T));
-    return o;
-}
-
 MsimSet set_of(int64_t n_mols, const int64_t *off, const double *u, const double *v) { return {n_mols, off, u, v}; }
 
 // the per-atom parameters of both sets and the term tables, behind each other in the image

@@ -1,13 +1,14 @@
 // Bond graphs of sampled molecules: for every (frame, molecule) of a packed batch the bonds that the
-// distance rule of sm_mol_eval.h finds (meval_kernel keeps only their sum per atom), with their orders, the fragments, whether
-// the molecule is complete (one fragment), the shortest cycle through every bond, and per frame the bond-length histograms, the
-// pair-distance histograms and class counts of the complete molecules, and how many molecules are complete or hold a ring of
-// each size.  The rule is this project's own -- the caller's thresholds -- not a chemistry toolkit's bond perception.
+// distance rule of sm_mol_rule.h finds (meval_kernel of sm_mol_eval.h keeps only their sum per atom), with their orders, the
+// fragments, whether the molecule is complete (one fragment), the shortest cycle through every bond, and per frame the
+// bond-length histograms, the pair-distance histograms and class counts of the complete molecules, and how many molecules are
+// complete or hold a ring of each size.  The rule is this project's own -- the caller's thresholds -- not a chemistry toolkit's
+// bond perception.
 //
-// Arithmetic of a pair: mg_pair below, float64, the statement order of meval_kernel's pair loop under the same pragma, so an
-// atom's orders add up to meval_kernel's nr_bonds bit for bit.  Everything after it is integer work on bit masks.
+// Arithmetic of a pair: mol_pair of sm_mol_rule.h, the function meval_kernel's pair loop calls, so an atom's orders add up to
+// meval_kernel's nr_bonds bit for bit.  Everything after it is integer work on bit masks.
 //
-// One kernel body, two launch forms (MgraphPlan): a team of 64 threads (one wave) per (frame, molecule) for molecules of at most
+// One kernel body, two launch forms (MolPlan): a team of 64 threads (one wave) per (frame, molecule) for molecules of at most
 // 64 atoms, four teams to the workgroup; a team of 256 threads (the workgroup) for molecules of 65..256 atoms.  Thread i of a
 // team owns atom i.  A team keeps the adjacency of its molecule in LDS as bit masks, W = 1 or 4 64-bit words per atom: thread i
 // forms row i in registers from its own pair loop (d(i, j) and d(j, i) are the same bits, so the matrix is symmetric without
@@ -19,39 +20,25 @@
 //
 // Every loop whose trip count depends on the data is left through __syncthreads_or, so all barriers are reached by the whole
 // workgroup in both forms.  Histograms and counters of a frame: 32-bit LDS counts added to the frame's 64-bit counters when the
-// workgroup ends, meval_kernel's scheme with its bound on iterations per workgroup -- except the bond-length histograms, whose
+// workgroup ends, sm_mol_rule.h's scheme with its bound on iterations per workgroup -- except the bond-length histograms, whose
 // table (pairs of elements x 3 orders x bins, up to 136 x 3 x 256 counts) does not fit LDS: a bond adds 1 to its 64-bit global
 // counter directly, about one atomic per atom against the pair loop's n / 2 distances.  Only integers are added, so every output
 // is the same in every run.
 #pragma once
-#include "sm_mol_eval.h"
+#include "sm_mol_rule.h"
 
 #pragma clang fp contract(off)
 
-constexpr int kMgraphThreads = 256;                      // workgroup of both forms
-constexpr int kMgraphWaveAtoms = 64;                     // wave form: lane i owns atom i, one mask word per atom
-constexpr int kMgraphMaxAtoms = 256;                     // block form: thread i owns atom i, four mask words per atom (8 KiB)
+constexpr int kMgraphMaxAtoms = 256;                     // one atom per thread; block form: four mask words per atom (8 KiB)
 constexpr int kMgraphRingBits = 32;                      // ring_sizes: bit s for a ring of s bonds, 3 <= s <= 30; bit 31: larger
 constexpr int kMgraphScanItems = 8;                      // consecutive counts per thread of the scan kernel
-// iterations of one workgroup so that its 32-bit LDS counts cannot wrap: per iteration at most 4 * 2016 pairs (wave) or 32640
-// pairs (block) enter a histogram, 256 atoms the class counts, 4 molecules a ring-size or the complete counter
-constexpr int kMgraphMaxItersWave = 65536, kMgraphMaxItersBlock = 2048;
 
 struct MgraphArgs {
-    const float *pos;                 // (F, N, 3)
-    const void *cls;                  // (F, N) int32 or int64
-    int cls64;
-    long long N;
-    int F, B;
-    const MevalMol *mol;              // (B)
-    const int *jobs;
-    int n_jobs, gx, iters;
-    const double *thr;                // (3, E, E)
-    const unsigned char *slot;        // (C)
-    int E, C, carbon;
-    const double *cc_edges, *all_edges, *bl_edges;
-    int n_cc, n_all, n_bl;
-    double cc_cut, all_cut;
+    MolBatch b;
+    MolRule r;
+    MolCounts o;                      // of the complete molecules
+    const double *bl_edges;
+    int n_bl;
     int *count;                       // (F * B) bonds per (frame, molecule): pass 0 writes, the scan reads
     const long long *offset;          // (F * B + 1): pass 1 reads
     int *nr_bonds, *degree, *frag, *ring_atom;                               // (F, N)
@@ -59,23 +46,10 @@ struct MgraphArgs {
     int *bonds;                       // (total, 3)
     int *ring_bond;                   // (total)
     unsigned long long *hist_bl;      // (F, 2, E (E + 1) / 2, 3, n_bl + 1): all molecules | complete ones
-    unsigned long long *hist_cc, *hist_all, *cls_counts;                     // complete molecules: (F, n_cc + 1), (F, n_all + 1), (F, C)
     unsigned long long *frame_counts; // (F, 1 + kMgraphRingBits): complete molecules, then molecules with a ring of bit s
-    int *bad;
 };
 
 #if defined(__HIPCC__) && !defined(SM_MOL_EVAL_HOST_ONLY)
-
-// distance and bond order of a pair: the statements of meval_kernel's pair loop
-__device__ __forceinline__ int mg_pair(double xi, double yi, double zi, double xj, double yj, double zj, const double *t1, const double *t2,
-                                       const double *t3, int ej, double &d) {
-    const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    d = sqrt((dx * dx + dy * dy) + dz * dz);
-    const double p = 100.0 * d;
-    int o = 0;
-    if (p < t1[ej]) o = p < t2[ej] ? (p < t3[ej] ? 3 : 2) : 1;
-    return o;
-}
 
 struct MgSum { __device__ int operator()(int a, int b) const { return a + b; } };
 struct MgMax { __device__ int operator()(int a, int b) const { return a > b ? a : b; } };
@@ -163,54 +137,39 @@ template <int W> __device__ __forceinline__ int mg_ring(const unsigned long long
 
 // PASS 0: the bonds of every (frame, molecule) into a.count.  PASS 1: everything else, with a.offset from the scan
 template <int TEAM, int PASS>
-__global__ __launch_bounds__(kMgraphThreads) void mgraph_kernel(MgraphArgs a) {
-    constexpr int JPB = kMgraphThreads / TEAM, CAP = TEAM, W = CAP / 64;
+__global__ __launch_bounds__(kMolThreads) void mgraph_kernel(MgraphArgs a) {
+    constexpr int JPB = kMolThreads / TEAM, CAP = TEAM, W = CAP / 64;
     __shared__ double s_x[JPB * CAP], s_y[JPB * CAP], s_z[JPB * CAP];
-    __shared__ double s_thr[3 * kMevalMaxElements * kMevalMaxElements];
-    __shared__ double s_cc[PASS ? kMevalMaxEdges + 1 : 1], s_all[PASS ? kMevalMaxEdges + 1 : 1], s_bl[PASS ? kMevalMaxEdges + 1 : 1];
+    __shared__ double s_thr[3 * kMolMaxElements * kMolMaxElements];
+    __shared__ double s_cc[PASS ? kMolMaxEdges + 1 : 1], s_all[PASS ? kMolMaxEdges + 1 : 1], s_bl[PASS ? kMolMaxEdges + 1 : 1];
     __shared__ unsigned long long s_adj[PASS ? JPB * CAP * W : 1];
     __shared__ int s_label[PASS ? JPB * CAP : 1], s_start[PASS ? JPB * CAP : 1];
-    __shared__ unsigned s_hcc[PASS ? kMevalMaxEdges + 1 : 1], s_hall[PASS ? kMevalMaxEdges + 1 : 1], s_cls[kMevalMaxClasses];
+    __shared__ unsigned s_hcc[PASS ? kMolMaxEdges + 1 : 1], s_hall[PASS ? kMolMaxEdges + 1 : 1], s_cls[kMolMaxClasses];
     __shared__ unsigned s_fc[1 + kMgraphRingBits];
     __shared__ int s_w[4];
-    __shared__ unsigned char s_e[JPB * CAP], s_slot[kMevalMaxClasses];
+    __shared__ unsigned char s_e[JPB * CAP], s_slot[kMolMaxClasses];
     const int tid = threadIdx.x, team = tid / TEAM, lane = tid % TEAM;
-    const int frame = blockIdx.x / a.gx, bx = blockIdx.x % a.gx;
-    const int E = a.E, EE = a.E * a.E;
-    for (int i = tid; i < 3 * EE; i += kMgraphThreads) s_thr[i] = a.thr[i];
-    for (int i = tid; i < a.C; i += kMgraphThreads) { s_slot[i] = a.slot[i]; s_cls[i] = 0; }
+    const int frame = blockIdx.x / a.b.gx, bx = blockIdx.x % a.b.gx;
+    const int E = a.r.E, EE = E * E;
+    mol_stage(a.r, PASS != 0, s_thr, s_slot, s_cls, s_cc, s_all, s_hcc, s_hall);
     if (PASS) {
-        for (int i = tid; i <= kMevalMaxEdges; i += kMgraphThreads) {
-            if (i < a.n_cc) s_cc[i] = a.cc_edges[i];
-            if (i < a.n_all) s_all[i] = a.all_edges[i];
-            if (i < a.n_bl) s_bl[i] = a.bl_edges[i];
-            s_hcc[i] = 0; s_hall[i] = 0;
-        }
+        for (int i = tid; i < a.n_bl; i += kMolThreads) s_bl[i] = a.bl_edges[i];
         if (tid <= kMgraphRingBits) s_fc[tid] = 0;
     }
     double *x = s_x + team * CAP, *y = s_y + team * CAP, *z = s_z + team * CAP;
     unsigned char *el = s_e + team * CAP;
     unsigned long long *adj = s_adj + (PASS ? team * CAP * W : 0);
     int *label = s_label + (PASS ? team * CAP : 0), *start = s_start + (PASS ? team * CAP : 0);
-    for (int it = 0; it < a.iters; ++it) {
-        const int job = (it * a.gx + bx) * JPB + team;
-        const bool active = job < a.n_jobs;
-        int m = 0, n = 0, moff = 0;
-        size_t base = 0;
-        if (active) { m = a.jobs[job]; n = a.mol[m].n; moff = a.mol[m].off; base = (size_t)frame * (size_t)a.N + (size_t)moff; }
-        const size_t fm = (size_t)frame * (size_t)a.B + (size_t)m;
+    for (int it = 0; it < a.b.iters; ++it) {
+        const MolJob job = mol_job<JPB>(a.b, it, bx, team, frame);
+        const bool active = job.active;
+        const int n = job.n, moff = job.off;
+        const size_t base = job.base, fm = (size_t)frame * (size_t)a.b.B + (size_t)job.m;
         __syncthreads();                  // the tables are written; the iteration before has read its molecule
         const int i = lane;
         const bool mine = i < n;
-        int cl = -1;
-        if (mine) {
-            const float *p = a.pos + 3 * (base + i);
-            x[i] = (double)p[0]; y[i] = (double)p[1]; z[i] = (double)p[2];
-            const long long c = a.cls64 ? reinterpret_cast<const long long *>(a.cls)[base + i] : (long long)reinterpret_cast<const int *>(a.cls)[base + i];
-            const bool ok = c >= 0 && c < a.C;
-            el[i] = ok ? s_slot[c] : (unsigned char)0;
-            if (ok) cl = (int)c; else if (PASS) atomicAdd(a.bad, 1);
-        }
+        // the classes are counted below, for complete molecules only; a bad one is flagged once, by the fill pass
+        const int cl = mine ? mol_load_atom(a.b, a.r, base + i, i, PASS != 0, s_slot, x, y, z, el) : -1;
         __syncthreads();
         // ---- row i of the adjacency, in registers
         unsigned long long row[W];
@@ -228,7 +187,7 @@ __global__ __launch_bounds__(kMgraphThreads) void mgraph_kernel(MgraphArgs a) {
                     const int j = w * 64 + jj;
                     if (j == i) continue;
                     double d;
-                    const int o = mg_pair(xi, yi, zi, x[j], y[j], z[j], t1, t2, t3, el[j], d);
+                    const int o = mol_pair(xi, yi, zi, x[j], y[j], z[j], t1, t2, t3, el[j], d);
                     sum += o;
                     if (o) row[w] |= 1ull << jj;
                 }
@@ -299,7 +258,7 @@ __global__ __launch_bounds__(kMgraphThreads) void mgraph_kernel(MgraphArgs a) {
                     r &= r - 1;
                     double d;
                     const int ej = el[j];
-                    const int o = mg_pair(xi, yi, zi, x[j], y[j], z[j], t1, t2, t3, ej, d);
+                    const int o = mol_pair(xi, yi, zi, x[j], y[j], z[j], t1, t2, t3, ej, d);
                     const int ring = mg_ring<W>(adj, i, j);
                     a.bonds[3 * k] = moff + i; a.bonds[3 * k + 1] = moff + j; a.bonds[3 * k + 2] = o;
                     a.ring_bond[k] = ring;
@@ -310,7 +269,7 @@ __global__ __launch_bounds__(kMgraphThreads) void mgraph_kernel(MgraphArgs a) {
                     }
                     if (o < 1) continue;  // cannot happen: the row bit came from the same statements
                     const int lo = ei < ej ? ei : ej, hi = ei < ej ? ej : ei;
-                    const size_t cell = (((size_t)(lo * E - lo * (lo - 1) / 2 + (hi - lo))) * 3 + (o - 1)) * nbin + meval_bin(s_bl, a.n_bl, d);
+                    const size_t cell = (((size_t)(lo * E - lo * (lo - 1) / 2 + (hi - lo))) * 3 + (o - 1)) * nbin + mol_bin(s_bl, a.n_bl, d);
                     unsigned long long *h = a.hist_bl + (size_t)frame * 2 * np * 3 * nbin;
                     atomicAdd(&h[cell], 1ull);
                     if (complete) atomicAdd(&h[(size_t)np * 3 * nbin + cell], 1ull);
@@ -345,13 +304,12 @@ __global__ __launch_bounds__(kMgraphThreads) void mgraph_kernel(MgraphArgs a) {
         }
         // ---- pair-distance histograms of complete molecules
         if (mine && complete) {
-            const bool ci = ei == a.carbon;
+            const bool ci = ei == a.r.carbon;
             for (int j = i + 1; j < n; ++j) {
                 double d;
                 const int ej = el[j];
-                (void)mg_pair(xi, yi, zi, x[j], y[j], z[j], t1, t2, t3, ej, d);
-                if (ci && ej == a.carbon && d < a.cc_cut) atomicAdd(&s_hcc[meval_bin(s_cc, a.n_cc, d)], 1u);
-                if (d < a.all_cut) atomicAdd(&s_hall[meval_bin(s_all, a.n_all, d)], 1u);
+                (void)mol_pair(xi, yi, zi, x[j], y[j], z[j], t1, t2, t3, ej, d);
+                mol_hist_add(a.r, ci, ej, d, s_cc, s_all, s_hcc, s_hall);
             }
         }
         if (active && lane == 0) {
@@ -364,22 +322,17 @@ __global__ __launch_bounds__(kMgraphThreads) void mgraph_kernel(MgraphArgs a) {
     }
     if (!PASS) return;
     __syncthreads();
-    for (int i = tid; i <= kMevalMaxEdges; i += kMgraphThreads) {
-        if (i <= a.n_cc && s_hcc[i]) atomicAdd(&a.hist_cc[(size_t)frame * (a.n_cc + 1) + i], (unsigned long long)s_hcc[i]);
-        if (i <= a.n_all && s_hall[i]) atomicAdd(&a.hist_all[(size_t)frame * (a.n_all + 1) + i], (unsigned long long)s_hall[i]);
-    }
-    for (int i = tid; i < a.C; i += kMgraphThreads)
-        if (s_cls[i]) atomicAdd(&a.cls_counts[(size_t)frame * a.C + i], (unsigned long long)s_cls[i]);
+    mol_flush(a.r, a.o, frame, s_hcc, s_hall, s_cls);
     if (tid <= kMgraphRingBits && s_fc[tid]) atomicAdd(&a.frame_counts[(size_t)frame * (1 + kMgraphRingBits) + tid], (unsigned long long)s_fc[tid]);
 }
 
 // One workgroup: exclusive scan of the n counts into offset (n + 1, 64-bit), kMgraphScanItems consecutive counts per thread and
 // a carry from pass to pass; offset[n] is the total
-__global__ __launch_bounds__(kMgraphThreads) void mgraph_scan_kernel(const int *count, long long *offset, long long n) {
+__global__ __launch_bounds__(kMolThreads) void mgraph_scan_kernel(const int *count, long long *offset, long long n) {
     __shared__ long long s_wave[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     long long carry = 0;
-    for (long long base = 0; base < n; base += (long long)kMgraphThreads * kMgraphScanItems) {
+    for (long long base = 0; base < n; base += (long long)kMolThreads * kMgraphScanItems) {
         const long long first = base + (long long)threadIdx.x * kMgraphScanItems;
         int c[kMgraphScanItems];
         long long v = 0;
@@ -412,52 +365,9 @@ __global__ __launch_bounds__(kMgraphThreads) void mgraph_scan_kernel(const int *
 
 #endif  // device code
 
-// ---- host plan --------------------------------------------------------------------------------------------------------------
-struct MgraphPlan {
-    std::vector<MevalMol> mol;
-    MevalForm wave, block;
-    std::vector<int> form;            // per molecule: 0 wave, 1 block
-    long long N = 0;
-};
-
-inline std::string mgraph_edges_error(const char *name, const double *edges, int n, double cut) {
-    if (n < 1 || n > kMevalMaxEdges || !edges) return std::string("bond graph: ") + name + " needs 1.." + std::to_string(kMevalMaxEdges) + " bin edges, got " + std::to_string(n);
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(edges[i]) || (i && !(edges[i - 1] <= edges[i]))) return std::string("bond graph: the ") + name + " bin edges must be finite and ascending";
-    if (std::isnan(cut)) return std::string("bond graph: the ") + name + " cut-off is NaN";
-    return "";
-}
-
 // Checks a call and lays out its two launch forms.  "" or the refusal's message; `out` may be null.
 inline std::string mgraph_plan(int64_t F, int64_t B, const int64_t *off, int E, int C, const int32_t *class_slot, const double *cc_edges, int n_cc,
-                               double cc_cut, const double *all_edges, int n_all, double all_cut, const double *bl_edges, int n_bl, MgraphPlan *out) {
-    if (F < 1 || F > kMevalMaxFrames) return "bond graph: 1.." + std::to_string(kMevalMaxFrames) + " frames, got " + std::to_string(F);
-    if (B < 1 || B > kMevalMaxMols || !off) return "bond graph: 1.." + std::to_string(kMevalMaxMols) + " molecules, got " + std::to_string(B);
-    if (E < 1 || E > kMevalMaxElements) return "bond graph: the rule has " + std::to_string(E) + " elements; the limit is " + std::to_string(kMevalMaxElements);
-    if (C < 1 || C > kMevalMaxClasses || !class_slot) return "bond graph: " + std::to_string(C) + " atom classes; the limit is " + std::to_string(kMevalMaxClasses);
-    for (int c = 0; c < C; ++c)
-        if (class_slot[c] < 0 || class_slot[c] >= E) return "bond graph: class " + std::to_string(c) + " has no element of the rule";
-    std::string e = mgraph_edges_error("C-C", cc_edges, n_cc, cc_cut);
-    if (e.empty()) e = mgraph_edges_error("all-pairs", all_edges, n_all, all_cut);
-    if (e.empty()) e = mgraph_edges_error("bond-length", bl_edges, n_bl, 0.0);
-    if (!e.empty()) return e;
-    if (off[0] != 0) return "bond graph: the offsets must start at 0";
-    MgraphPlan pl;
-    pl.mol.resize((size_t)B); pl.form.resize((size_t)B);
-    for (int64_t b = 0; b < B; ++b) {
-        const int64_t n = off[b + 1] - off[b];
-        if (n < 1) return "bond graph: molecule " + std::to_string(b) + " has no atoms";
-        if (n > kMgraphMaxAtoms) return "bond graph: molecule " + std::to_string(b) + " has " + std::to_string(n) + " atoms; the limit is " + std::to_string(kMgraphMaxAtoms);
-        if (off[b + 1] >= (1ll << 31)) return "bond graph: molecule " + std::to_string(b) + " ends past 2^31 atoms in a frame";
-        pl.mol[(size_t)b] = {(int)off[b], (int)n};
-        const int form = n > kMgraphWaveAtoms;
-        pl.form[(size_t)b] = form;
-        (form ? pl.block : pl.wave).jobs.push_back((int)b);
-    }
-    pl.N = off[B];
-    meval_form_grid(pl.wave, kMgraphThreads / 64, kMgraphMaxItersWave, F);
-    meval_form_grid(pl.block, 1, kMgraphMaxItersBlock, F);
-    if ((int64_t)pl.wave.gx * F >= (1ll << 31) || (int64_t)pl.block.gx * F >= (1ll << 31)) return "bond graph: frames x molecules exceed one launch grid";
-    if (out) *out = std::move(pl);
-    return "";
+                               double cc_cut, const double *all_edges, int n_all, double all_cut, const double *bl_edges, int n_bl, MolPlan *out) {
+    return mol_plan("bond graph", kMgraphMaxAtoms, F, B, off, E, C, class_slot,
+                    {{"C-C", cc_edges, n_cc, cc_cut}, {"all-pairs", all_edges, n_all, all_cut}, {"bond-length", bl_edges, n_bl, 0.0}}, out);
 }

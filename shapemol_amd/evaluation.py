@@ -29,7 +29,7 @@ _RULE_FIELDS = ("elements", "bonds1", "bonds2", "bonds3", "margins", "allowed_bo
 
 
 def sizes():
-    """The library's limits and block shape (shapemol_eval_sizes; the constants of csrc/sm_mol_eval.h)."""
+    """The library's limits and block shape (shapemol_eval_sizes; the constants of csrc/sm_mol_rule.h and sm_mol_eval.h)."""
     out = (C.c_int64 * 6)()
     _lib.load().shapemol_eval_sizes(out, 6)
     return Sizes(*out)
@@ -114,12 +114,8 @@ def _debug_fill(device, byte):
     _lib.check(_lib.load().shapemol_eval_debug_fill(_contexts.of(device), int(byte), stream_ptr(device)), "shapemol_eval_debug_fill")
 
 
-class GeometryReport:
-    """Device tensors of one call over F frames, N atoms and B molecules per frame: ``nr_bonds (F, N)`` int32,
-    ``n_stable_atoms (F, B)`` int32, ``mol_stable (F, B)`` bool, ``hist_cc (F, n_cc + 1)``, ``hist_all (F, n_all + 1)`` and
-    ``class_counts (F, C)`` int64; ``n_atoms (B,)`` (host) the molecules' sizes; ``cc_bins`` / ``all_bins`` the edges used;
-    ``forms`` (with ``details=True``) the launch form of every molecule, ``"wave"`` or ``"block"``.  ``evaluate_geometry``
-    drops the frame axis."""
+class _Report:
+    """The fields of one call; ``single``: the call had one frame and its tensors have no frame axis."""
 
     def __init__(self, single, **kw):
         self.single = single
@@ -128,6 +124,14 @@ class GeometryReport:
     def _frames(self, t, frame):
         t = t[None] if self.single else t
         return t if frame is None else t[frame][None] if isinstance(frame, int) else t[frame]
+
+
+class GeometryReport(_Report):
+    """Device tensors of one call over F frames, N atoms and B molecules per frame: ``nr_bonds (F, N)`` int32,
+    ``n_stable_atoms (F, B)`` int32, ``mol_stable (F, B)`` bool, ``hist_cc (F, n_cc + 1)``, ``hist_all (F, n_all + 1)`` and
+    ``class_counts (F, C)`` int64; ``n_atoms (B,)`` (host) the molecules' sizes; ``cc_bins`` / ``all_bins`` the edges used;
+    ``forms`` (with ``details=True``) the launch form of every molecule, ``"wave"`` or ``"block"``.  ``evaluate_geometry``
+    drops the frame axis."""
 
     def validity(self, frame=None):
         """``mol_stable`` and ``atm_stable`` as the script computes them: stable molecules over molecules, stable atoms over
@@ -157,8 +161,15 @@ def _as_stack(x):
     return x
 
 
-def _run(pos, classes, batch, rule, slots, single, hs, cc_bins, all_bins, details, device):
-    """``pos (F, N, 3)``, ``classes (F, N)`` indices into ``slots`` (class -> rule row), ``batch (N,)`` sorted molecule ids."""
+_Call = collections.namedtuple("_Call", "pos classes thr device F N B counts off slots cc_edges all_edges forms batch_args rule_args new")
+
+
+def _prepare(what, check, more_edges, class_range, device_msg, pos, classes, batch, rule, slots, cc_bins, all_bins, device):
+    """The front half of a call of the geometry scores and of the bond graphs (mol_graph.py), refusals prefixed with ``what``:
+    ``pos (F, N, 3)``, ``classes (F, N)`` indices into ``slots`` (class -> rule row) and ``batch (N,)`` sorted molecule ids
+    are checked, the library's ``check`` function (given the histograms' edges, ``more_edges`` after the two common ones) plans
+    the call and names the launch forms, and the inputs go to the device.  ``class_range``: refuse classes outside ``slots``
+    here, with one reduction, and not after the run."""
     E, Cn = len(rule.elements), len(slots)
     cc_edges, cc_cut = _bins(cc_bins, 2)
     all_edges, all_cut = _bins(all_bins, 12)
@@ -166,50 +177,66 @@ def _run(pos, classes, batch, rule, slots, single, hs, cc_bins, all_bins, detail
     if not tensors:
         pos, classes = torch.as_tensor(host(pos)), torch.as_tensor(host(classes))
     if pos.dim() != 3 or pos.shape[-1] != 3 or classes.shape != pos.shape[:2]:
-        raise ValueError(f"molecule evaluation: positions (F, N, 3) and classes (F, N), got {tuple(pos.shape)} and {tuple(classes.shape)}")
+        raise ValueError(f"{what}: positions (F, N, 3) and classes (F, N), got {tuple(pos.shape)} and {tuple(classes.shape)}")
     F, N = int(pos.shape[0]), int(pos.shape[1])
     b = host(batch).astype(np.int64).reshape(-1)
     if len(b) != N or N < 1:
-        raise ValueError(f"molecule evaluation: {N} atoms per frame and a batch vector of {len(b)}")
+        raise ValueError(f"{what}: {N} atoms per frame and a batch vector of {len(b)}")
     if b[0] != 0 or (np.diff(b) < 0).any():
-        raise ValueError("molecule evaluation: the batch vector must be sorted and start at 0 (a packed batch)")
+        raise ValueError(f"{what}: the batch vector must be sorted and start at 0 (a packed batch)")
     B = int(b[-1]) + 1
     counts = np.bincount(b, minlength=B)
     off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     slots = np.ascontiguousarray(slots, np.int32)
     forms = np.zeros(B, np.int32)
     lib = _lib.load()
-    if lib.shapemol_eval_check(F, B, ptr(off), E, Cn, ptr(slots), ptr(cc_edges), len(cc_edges), cc_cut, ptr(all_edges), len(all_edges), all_cut, ptr(forms)):
+    more = [x for e in more_edges for x in (ptr(e), len(e))]
+    if getattr(lib, check)(F, B, ptr(off), E, Cn, ptr(slots), ptr(cc_edges), len(cc_edges), cc_cut, ptr(all_edges), len(all_edges), all_cut, *more,
+                           ptr(forms)):
         raise ValueError(lib.shapemol_last_error().decode())
     if classes.dtype not in (torch.int32, torch.int64):
         if classes.is_floating_point() or classes.dtype == torch.bool:
-            raise TypeError(f"molecule evaluation: atom classes must be integers, got {classes.dtype}")
+            raise TypeError(f"{what}: atom classes must be integers, got {classes.dtype}")
         classes = classes.to(torch.int64)
-    lo, hi = (int(t) for t in torch.aminmax(classes))
-    if lo < 0 or hi >= Cn:
-        raise ValueError(f"molecule evaluation: atom classes {lo}..{hi} lie outside the {Cn} classes")
+    if class_range:
+        lo, hi = (int(t) for t in torch.aminmax(classes))
+        if lo < 0 or hi >= Cn:
+            raise ValueError(f"{what}: atom classes {lo}..{hi} lie outside the {Cn} classes")
     if device is None:
         device = pos.device if pos.is_cuda else "cuda" if torch.cuda.is_available() else "cpu"
-    device = hip_device(device, "molecules are evaluated on a HIP device")
+    device = hip_device(device, device_msg)
     pos = pos.to(device=device, dtype=torch.float32).contiguous()
     classes = classes.to(device).contiguous()
-    carbon = np.flatnonzero(rule.elements == 6.0)
-    thr, allowed = rule.thresholds(), np.ascontiguousarray(rule.allowed_bonds)
+    carbon, thr = np.flatnonzero(rule.elements == 6.0), rule.thresholds()
+    # what both run functions take first: the batch up to the thresholds, then the rule from the carbon slot to the histograms
+    batch_args = (F, B, ptr(off), ptr(pos), ptr(classes), int(classes.dtype == torch.int64), E, ptr(thr))
+    rule_args = (int(carbon[0]) if len(carbon) else -1, Cn, ptr(slots), ptr(cc_edges), len(cc_edges), cc_cut, ptr(all_edges), len(all_edges), all_cut)
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)  # noqa: E731
-    out = dict(nr_bonds=new((F, N), torch.int32), n_stable_atoms=new((F, B), torch.int32), mol_stable=new((F, B), torch.bool),
-               hist_cc=new((F, len(cc_edges) + 1), torch.int64), hist_all=new((F, len(all_edges) + 1), torch.int64),
-               class_counts=new((F, Cn), torch.int64))
-    with torch.cuda.device(device):
-        _lib.check(lib.shapemol_eval_run(
-            _contexts.of(device), F, B, ptr(off), ptr(pos), ptr(classes), int(classes.dtype == torch.int64), E, ptr(thr), ptr(allowed),
-            int(carbon[0]) if len(carbon) else -1, Cn, ptr(slots), ptr(cc_edges), len(cc_edges), cc_cut, ptr(all_edges), len(all_edges), all_cut,
-            int(bool(hs)), *(ptr(out[k]) for k in ("nr_bonds", "n_stable_atoms", "mol_stable", "hist_cc", "hist_all", "class_counts")),
-            stream_ptr(device)), "shapemol_eval_run")
+    return _Call(pos, classes, thr, device, F, N, B, counts, off, slots, cc_edges, all_edges, forms, batch_args, rule_args, new)
+
+
+def _finish(report, c, single, details, out, **kw):
+    """The report of a call: without the frame axis for a ``single`` frame, with the launch forms for ``details``."""
     if single:
         out = {k: t[0] for k, t in out.items()}
     if details:
-        out["forms"] = [FORMS[k] for k in forms]
-    return GeometryReport(single, n_atoms=counts, cc_bins=cc_edges, all_bins=all_edges, **out)
+        out["forms"] = [FORMS[k] for k in c.forms]
+    return report(single, n_atoms=c.counts, cc_bins=c.cc_edges, all_bins=c.all_edges, **kw, **out)
+
+
+def _run(pos, classes, batch, rule, slots, single, hs, cc_bins, all_bins, details, device):
+    """``pos (F, N, 3)``, ``classes (F, N)`` indices into ``slots`` (class -> rule row), ``batch (N,)`` sorted molecule ids."""
+    c = _prepare("molecule evaluation", "shapemol_eval_check", (), True, "molecules are evaluated on a HIP device", pos, classes, batch, rule, slots,
+                 cc_bins, all_bins, device)
+    F, N, B, new = c.F, c.N, c.B, c.new
+    allowed = np.ascontiguousarray(rule.allowed_bonds)
+    out = dict(nr_bonds=new((F, N), torch.int32), n_stable_atoms=new((F, B), torch.int32), mol_stable=new((F, B), torch.bool),
+               hist_cc=new((F, len(c.cc_edges) + 1), torch.int64), hist_all=new((F, len(c.all_edges) + 1), torch.int64),
+               class_counts=new((F, len(c.slots)), torch.int64))
+    with torch.cuda.device(c.device):
+        _lib.check(_lib.load().shapemol_eval_run(_contexts.of(c.device), *c.batch_args, ptr(allowed), *c.rule_args, int(bool(hs)),
+                                                 *(ptr(t) for t in out.values()), stream_ptr(c.device)), "shapemol_eval_run")
+    return _finish(GeometryReport, c, single, details, out)
 
 
 def evaluate_trajectory(pos_traj, v_traj, batch, rule, mode="add_aromatic", hs=False, cc_bins=None, all_bins=None, details=False, *,
@@ -235,21 +262,26 @@ def evaluate_geometry(pos, v, batch, rule, mode="add_aromatic", hs=False, cc_bin
     return _run(pos[None], v[None], batch, rule, slots, True, hs, cc_bins, all_bins, details, device)
 
 
+def _pack_samples(what, result):
+    """Per-molecule lists ``(pred_pos, pred_v, ...)`` as one packed frame: float32 positions, int64 classes, the batch vector."""
+    pred_pos, pred_v = result[0], result[1]
+    if len(pred_pos) != len(pred_v) or not len(pred_pos):
+        raise ValueError(f"{what}: one position array and one class array per molecule, at least one")
+    ns = [len(host(v).reshape(-1)) for v in pred_v]
+    if 0 in ns:
+        raise ValueError(f"{what}: molecule {ns.index(0)} has no atoms")
+    pos = np.concatenate([host(p, np.float64).reshape(-1, 3) for p in pred_pos]).astype(np.float32)
+    v = np.concatenate([host(v).reshape(-1) for v in pred_v]).astype(np.int64)
+    if len(pos) != len(v):
+        raise ValueError(f"{what}: positions and classes of a molecule differ in length")
+    return pos, v, np.repeat(np.arange(len(ns)), ns)
+
+
 def evaluate_samples(result, rule, mode="add_aromatic", hs=False, cc_bins=None, all_bins=None, details=False, *, num_classes=None, device=None):
     """The final molecules of ``sample_diffusion_ligand``: ``result`` is its tuple (``pred_pos``, ``pred_v`` first: lists with
     one ``(n, 3)`` and one ``(n,)`` array per molecule) or just that pair.  The float64 host positions are the chain's float32
     ones, so the upload as float32 loses nothing.  One frame; see :func:`evaluate_geometry`."""
-    pred_pos, pred_v = result[0], result[1]
-    if len(pred_pos) != len(pred_v) or not len(pred_pos):
-        raise ValueError("molecule evaluation: one position array and one class array per molecule, at least one")
-    ns = [len(host(v).reshape(-1)) for v in pred_v]
-    if 0 in ns:
-        raise ValueError(f"molecule evaluation: molecule {ns.index(0)} has no atoms")
-    pos = np.concatenate([host(p, np.float64).reshape(-1, 3) for p in pred_pos]).astype(np.float32)
-    v = np.concatenate([host(v).reshape(-1) for v in pred_v]).astype(np.int64)
-    batch = np.repeat(np.arange(len(ns)), ns)
-    if len(pos) != len(v):
-        raise ValueError("molecule evaluation: positions and classes of a molecule differ in length")
+    pos, v, batch = _pack_samples("molecule evaluation", result)
     return evaluate_geometry(pos, v, batch, rule, mode, hs, cc_bins, all_bins, details, num_classes=num_classes, device=device)
 
 

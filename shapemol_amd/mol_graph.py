@@ -21,10 +21,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._native import DeviceContexts, hip_device, host, ptr, stream_ptr
-from .evaluation import _as_stack, _bins, class_table
+from ._native import DeviceContexts, host, ptr, stream_ptr
+from .evaluation import FORMS  # noqa: F401  (the launch forms' names, a name of this module as well)
+from .evaluation import _as_stack, _bins, _finish, _pack_samples, _prepare, _Report, class_table
 
-FORMS = ("wave", "block")
 Sizes = collections.namedtuple("Sizes", "wave_atoms max_atoms max_elements max_classes max_edges threads ring_bits")
 MOL_FIELDS = ("n_bonds", "n_frags", "largest_frag", "complete", "n_cycles", "ring_sizes")
 # element symbols by atomic number, for the mol block
@@ -33,7 +33,7 @@ _SYMBOLS = ("* H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn 
 
 
 def sizes():
-    """The library's limits and block shape (shapemol_graph_sizes; the constants of csrc/sm_mol_graph.h)."""
+    """The library's limits and block shape (shapemol_graph_sizes; the constants of csrc/sm_mol_rule.h and sm_mol_graph.h)."""
     out = (C.c_int64 * 7)()
     _lib.load().shapemol_graph_sizes(out, 7)
     return Sizes(*out)
@@ -58,7 +58,7 @@ def bond_key(bond_type):
     return f"{int(a)}-{int(b)}|{int(o)}"
 
 
-class GraphReport:
+class GraphReport(_Report):
     """Device tensors of one call over F frames, N atoms and B molecules per frame.  Per atom ``(F, N)`` int32: ``nr_bonds``
     (the orders summed: ``evaluate_geometry``'s ``nr_bonds``), ``degree``, ``frag`` (the smallest atom index, within the frame,
     of the atom's fragment), ``ring`` (the smallest ring through one of its bonds, 0: none).  Per molecule ``(F, B)``:
@@ -70,14 +70,6 @@ class GraphReport:
     complete molecules; ``n_complete (F,)``; ``ring_counts (F, 32)`` molecules whose ``ring_sizes`` has each bit.  Host:
     ``n_atoms (B,)``, ``mol_off (B + 1,)``, the bin edges ``bl_bins``, ``cc_bins``, ``all_bins``.  ``bond_graph`` drops the
     frame axis of the per-atom, per-molecule and per-frame tensors."""
-
-    def __init__(self, single, **kw):
-        self.single = single
-        self.__dict__.update(kw)
-
-    def _frames(self, t, frame):
-        t = t[None] if self.single else t
-        return t if frame is None else t[frame][None] if isinstance(frame, int) else t[frame]
 
     def _span(self, mol, frame):
         f = 0 if frame is None else int(frame)
@@ -163,54 +155,19 @@ class GraphReport:
 
 def _run(pos, classes, batch, rule, slots, single, cc_bins, all_bins, bond_bins, details, device):
     """``pos (F, N, 3)``, ``classes (F, N)`` indices into ``slots`` (class -> rule row), ``batch (N,)`` sorted molecule ids."""
-    E, Cn = len(rule.elements), len(slots)
-    cc_edges, cc_cut = _bins(cc_bins, 2)
-    all_edges, all_cut = _bins(all_bins, 12)
     bl_edges, _ = _bins(np.linspace(0.8, 2.4, 161) if bond_bins is None else bond_bins, 0)
-    tensors = isinstance(pos, torch.Tensor) and isinstance(classes, torch.Tensor)
-    if not tensors:
-        pos, classes = torch.as_tensor(host(pos)), torch.as_tensor(host(classes))
-    if pos.dim() != 3 or pos.shape[-1] != 3 or classes.shape != pos.shape[:2]:
-        raise ValueError(f"bond graph: positions (F, N, 3) and classes (F, N), got {tuple(pos.shape)} and {tuple(classes.shape)}")
-    F, N = int(pos.shape[0]), int(pos.shape[1])
-    b = host(batch).astype(np.int64).reshape(-1)
-    if len(b) != N or N < 1:
-        raise ValueError(f"bond graph: {N} atoms per frame and a batch vector of {len(b)}")
-    if b[0] != 0 or (np.diff(b) < 0).any():
-        raise ValueError("bond graph: the batch vector must be sorted and start at 0 (a packed batch)")
-    B = int(b[-1]) + 1
-    counts = np.bincount(b, minlength=B)
-    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    slots = np.ascontiguousarray(slots, np.int32)
-    forms = np.zeros(B, np.int32)
-    lib = _lib.load()
-    if lib.shapemol_graph_check(F, B, ptr(off), E, Cn, ptr(slots), ptr(cc_edges), len(cc_edges), cc_cut, ptr(all_edges), len(all_edges), all_cut,
-                                ptr(bl_edges), len(bl_edges), ptr(forms)):
-        raise ValueError(lib.shapemol_last_error().decode())
-    if classes.dtype not in (torch.int32, torch.int64):
-        if classes.is_floating_point() or classes.dtype == torch.bool:
-            raise TypeError(f"bond graph: atom classes must be integers, got {classes.dtype}")
-        classes = classes.to(torch.int64)
-    if device is None:
-        device = pos.device if pos.is_cuda else "cuda" if torch.cuda.is_available() else "cpu"
-    device = hip_device(device, "bond graphs are built on a HIP device")
-    pos = pos.to(device=device, dtype=torch.float32).contiguous()
-    classes = classes.to(device).contiguous()
-    carbon = np.flatnonzero(rule.elements == 6.0)
-    thr = rule.thresholds()
-    P = E * (E + 1) // 2
-    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)  # noqa: E731
+    # a class outside the table is left to the device: the run's status flag, reported as a ValueError below
+    c = _prepare("bond graph", "shapemol_graph_check", (bl_edges,), False, "bond graphs are built on a HIP device", pos, classes, batch, rule, slots,
+                 cc_bins, all_bins, device)
+    F, N, B, E, new, lib = c.F, c.N, c.B, len(rule.elements), c.new, _lib.load()
     out = dict(nr_bonds=new((F, N), torch.int32), degree=new((F, N), torch.int32), frag=new((F, N), torch.int32), ring=new((F, N), torch.int32),
-               mol=new((F, B, 6), torch.int32), hist_bl=new((F, 2, P, 3, len(bl_edges) + 1), torch.int64),
-               hist_cc=new((F, len(cc_edges) + 1), torch.int64), hist_all=new((F, len(all_edges) + 1), torch.int64),
-               class_counts=new((F, Cn), torch.int64), frame_counts=new((F, 33), torch.int64))
+               mol=new((F, B, 6), torch.int32), hist_bl=new((F, 2, E * (E + 1) // 2, 3, len(bl_edges) + 1), torch.int64),
+               hist_cc=new((F, len(c.cc_edges) + 1), torch.int64), hist_all=new((F, len(c.all_edges) + 1), torch.int64),
+               class_counts=new((F, len(c.slots)), torch.int64), frame_counts=new((F, 33), torch.int64))
     total = C.c_int64(0)
-    with torch.cuda.device(device):
-        ctx, s = _contexts.of(device), stream_ptr(device)
-        # a class outside [0, Cn) is found on the device: the run's status flag, reported as a ValueError
-        if lib.shapemol_graph_run(ctx, F, B, ptr(off), ptr(pos), ptr(classes), int(classes.dtype == torch.int64), E, ptr(thr),
-                                  int(carbon[0]) if len(carbon) else -1, Cn, ptr(slots), ptr(cc_edges), len(cc_edges), cc_cut, ptr(all_edges),
-                                  len(all_edges), all_cut, ptr(bl_edges), len(bl_edges), *(ptr(t) for t in out.values()), C.byref(total), s):
+    with torch.cuda.device(c.device):
+        ctx, s = _contexts.of(c.device), stream_ptr(c.device)
+        if lib.shapemol_graph_run(ctx, *c.batch_args, *c.rule_args, ptr(bl_edges), len(bl_edges), *(ptr(t) for t in out.values()), C.byref(total), s):
             msg = lib.shapemol_last_error().decode()
             if msg.startswith("bond graph:"):
                 raise ValueError(msg)
@@ -225,13 +182,9 @@ def _run(pos, classes, batch, rule, slots, single, cc_bins, all_bins, bond_bins,
     for k, name in enumerate(MOL_FIELDS):
         out[name] = mol[..., k].contiguous() if name != "complete" else mol[..., k] != 0
     out["n_complete"], out["ring_counts"] = fc[:, 0].contiguous(), fc[:, 1:].contiguous()
-    if single:
-        out = {k: t[0] for k, t in out.items()}
-    if details:
-        out["forms"] = [FORMS[k] for k in forms]
     z = [int(e) for e in rule.elements]
-    return GraphReport(single, n_frames=F, n_atoms=counts, mol_off=off, bond_offsets=offsets, bond_list=bond_list, bond_ring=bond_ring,
-                       pairs=[(z[a], z[c]) for a in range(E) for c in range(a, E)], bl_bins=bl_edges, cc_bins=cc_edges, all_bins=all_edges, **out)
+    return _finish(GraphReport, c, single, details, out, n_frames=F, mol_off=c.off, bond_offsets=offsets, bond_list=bond_list, bond_ring=bond_ring,
+                   pairs=[(z[a], z[b]) for a in range(E) for b in range(a, E)], bl_bins=bl_edges)
 
 
 def bond_graph_trajectory(pos_traj, v_traj, batch, rule, mode="add_aromatic", hs=False, cc_bins=None, all_bins=None, bond_bins=None, details=False, *,
@@ -261,18 +214,8 @@ def bond_graph_samples(result, rule, mode="add_aromatic", hs=False, cc_bins=None
                        device=None):
     """The final molecules of ``sample_diffusion_ligand``, as ``evaluate_samples`` takes them: ``result`` is its tuple
     (``pred_pos``, ``pred_v`` first) or just that pair.  One frame; see :func:`bond_graph`."""
-    pred_pos, pred_v = result[0], result[1]
-    if len(pred_pos) != len(pred_v) or not len(pred_pos):
-        raise ValueError("bond graph: one position array and one class array per molecule, at least one")
-    ns = [len(host(v).reshape(-1)) for v in pred_v]
-    if 0 in ns:
-        raise ValueError(f"bond graph: molecule {ns.index(0)} has no atoms")
-    pos = np.concatenate([host(p, np.float64).reshape(-1, 3) for p in pred_pos]).astype(np.float32)
-    v = np.concatenate([host(v).reshape(-1) for v in pred_v]).astype(np.int64)
-    if len(pos) != len(v):
-        raise ValueError("bond graph: positions and classes of a molecule differ in length")
-    return bond_graph(pos, v, np.repeat(np.arange(len(ns)), ns), rule, mode, hs, cc_bins, all_bins, bond_bins, details, num_classes=num_classes,
-                      device=device)
+    pos, v, batch = _pack_samples("bond graph", result)
+    return bond_graph(pos, v, batch, rule, mode, hs, cc_bins, all_bins, bond_bins, details, num_classes=num_classes, device=device)
 
 
 def atom_type_jsd(counts, empirical, atomic_numbers=None):

@@ -8,7 +8,7 @@ import numpy as np
 
 import mol_eval_oracle as E
 
-WAVE_ATOMS, MAX_ATOMS, RING_BITS = 64, 256, 32
+WAVE_ATOMS, MAX_ATOMS, RING_BITS = E.WAVE_ATOMS, 256, 32
 BOND_BINS = np.linspace(0.8, 2.4, 161)
 
 

@@ -162,6 +162,34 @@ def test_consistency_with_the_geometry_scores(rule):
     assert r.validity(geometry=geo).keys() == {"mol_stable", "atm_stable", "complete"}
 
 
+def test_shared_frame_serves_both_features(rule, ragged, crafted):
+    """T3b: the pair, the histogram adds and the flush are one piece of code (csrc/sm_mol_rule.h) with two callers.  On the
+    ragged batch, both launch forms of both kernels: equal nr_bonds, and the graph's complete-only counters nowhere above the
+    scores'.  The oracle finds no frame of that batch all-complete, so the complete molecules among the crafted structures make
+    one: there the counters of both are equal."""
+    from shapemol_amd import bond_graph, bond_graph_trajectory, evaluate_geometry, evaluate_trajectory
+    counters = ("hist_cc", "hist_all", "class_counts")
+    pos, cls, batch, off, exp = ragged
+    g = bond_graph_trajectory(dev(pos), dev(cls), dev(batch), rule, mode="basic", bond_bins=EDGES, details=True)
+    s = evaluate_trajectory(dev(pos), dev(cls), dev(batch), rule, mode="basic", details=True)
+    assert g.forms == s.forms and set(g.forms) == {"wave", "block"}
+    assert torch.equal(g.nr_bonds, s.nr_bonds)
+    for k in counters:
+        a, b = getattr(g, k), getattr(s, k)
+        assert a.dtype == b.dtype and a.shape == b.shape and bool((a <= b).all()), k
+    assert not exp["complete"].all(axis=1).any() and bool((g.hist_all < s.hist_all).any())
+    names, cpos, ccls, _, coff, cexp = crafted
+    whole = np.flatnonzero(cexp["complete"][0])                                # the oracle's word, molecule by molecule
+    assert {"path64", "path256", "cycle256", "cube"} <= {names[m] for m in whole} and len(whole) < len(names)
+    pos, cls, batch, off = K.pack([(cpos[coff[m]:coff[m + 1]], ccls[coff[m]:coff[m + 1]]) for m in whole])
+    g = bond_graph(dev(pos), dev(cls), dev(batch), rule, mode="basic", bond_bins=EDGES, details=True)
+    s = evaluate_geometry(dev(pos), dev(cls), dev(batch), rule, mode="basic", details=True)
+    assert set(g.forms) == {"wave", "block"} and bool(g.complete.all()) and int(g.n_complete) == len(whole)
+    assert torch.equal(g.nr_bonds, s.nr_bonds)
+    for k in counters:
+        assert torch.equal(getattr(g, k), getattr(s, k)) and int(getattr(g, k).sum()) > 0, k
+
+
 def test_accumulations(rule, orule, crafted):
     """T4: bond-length histograms over all and over complete molecules, the complete-only pair histograms and class counts,
     the ring-size counters; a distance exactly on a bin edge; a frame without a complete molecule."""

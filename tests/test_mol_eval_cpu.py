@@ -201,8 +201,8 @@ def probe(tmp_path_factory):
                         "-fno-sanitize-recover=all", "-o", exe, os.path.join(HERE, "mol_eval_probe.cpp")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
 
-    def run(frames, sizes):
-        r = subprocess.run([exe, str(frames)] + [str(s) for s in sizes], capture_output=True, text=True)
+    def run(frames, sizes, graph=False):
+        r = subprocess.run([exe] + ["graph"] * graph + [str(frames)] + [str(s) for s in sizes], capture_output=True, text=True)
         assert r.stderr == "", r.stderr[-2000:]                       # the sanitizers report nothing
         lines = [ln.split() for ln in r.stdout.splitlines()]
         if r.returncode:
@@ -222,6 +222,16 @@ def test_plan_puts_molecules_into_the_right_form(probe):
     assert p["jobs"]["wave"] == [0, 1, 2, 5] and p["jobs"]["block"] == [3, 4, 6, 7]
     assert p["form"]["wave"] == [4, 1, 1] and p["form"]["block"] == [4, 4, 1]
     assert "limit is 1024" in probe(1, [5, 1025]) and "no atoms" in probe(1, [5, 0, 3]) and "frames" in probe(0, [5])
+
+
+def test_bond_graph_plan_is_the_same_plan_with_its_own_limit(probe):
+    sizes = [1, 64, 65, 256]
+    g = probe(3, sizes, graph=True)
+    assert g["mol"][:, 2].tolist() == sizes and g["mol"][:, 3].tolist() == [0, 0, 1, 1]
+    assert "limit is 256" in probe(3, [5, 257], graph=True) and "bond graph:" in probe(3, [5, 257], graph=True)
+    for frames, s in ((3, sizes), (1, [30] * 1000 + [100] * 3), (7, [30] * 40000 + [100] * 9), (1 << 20, [5, 200])):
+        g, e = probe(frames, s, graph=True), probe(frames, s)
+        assert g["form"] == e["form"] and g["jobs"] == e["jobs"] and np.array_equal(g["mol"], e["mol"])
 
 
 @pytest.mark.parametrize("frames, n_small, n_large", [(1, 1, 0), (1, 0, 1), (1, 1000, 3), (1000, 256, 0), (7, 40000, 9), (1 << 20, 5, 2), (3, 70000, 9000)])
